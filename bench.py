@@ -10,7 +10,9 @@ Launching: `python bench.py --gpus N ...` -- for N > 1 without a torch.distribut
 touches a GPU) starts N worker processes itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*, backend nccl = RCCL);
 under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` the workers are already there.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times exactly --steps steps in one
+region and prints the headline (`value`, `ms_per_step`, ...); --dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy.  With --full the line carries the extra objects below, and a region shorter than --min-timed-ms is repeated (median):
   roofline     -- the fused step kernel: algorithmic bytes (4022 B/env-step on flat ANYmal) x envs / mean kernel
                   duration from HIP events recorded on the launch stream around the timed graph replays themselves, against
                   the 8 TB/s HBM peak; and the second ratio SURVEY 8(d) asks for: counted fp32 FLOPs (tools/flop_count.py)
@@ -57,10 +59,12 @@ def parse_args():
     ap.add_argument("--f32-actor", action="store_true", help="wide actors (235/169-512-256-128): the f32-MFMA kernel instead of the split-bf16 one (lg_mlp_wide_set_precision(0))")
     ap.add_argument("--no-rollout", action="store_true", help="one launch per policy step (lg_step_policy) instead of one per --graph-steps steps (lg_rollout_policy): the A/B of the multi-step kernel")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one captured HIP graph per step")
-    ap.add_argument("--training-iters", type=int, default=-1, help="PPO iterations timed for the ppo_training object (0 = skip; -1 = 100 for anymal_c_flat, 20 otherwise)")
+    ap.add_argument("--training-iters", type=int, default=-1, help="PPO iterations timed for the ppo_training object of --full (0 = skip; -1 = 100 for anymal_c_flat, 20 otherwise)")
     ap.add_argument("--trimesh", action="store_true", help="keep the registered mesh_type 'trimesh' (vertical faces beyond slope_treshold) instead of BASELINE.json's height-field contact")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0, help="a timed region shorter than this is repeated and the median reported")
+    ap.add_argument("--min-timed-ms", type=float, default=50.0, help="with --full, a timed region shorter than this is repeated and the median reported")
     ap.add_argument("--event-steps", type=int, default=200, help="steps timed with HIP events for the step-kernel-only graph (tasks whose timed graph also holds the actor kernel)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated short regions, roofline, self-collision cost, PPO leg, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0's envs) as DIR/<name>.npy")
     a = ap.parse_args()
     if a.num_envs <= 0:
         a.num_envs = 8192 if a.task == "cassie" else 4096           # BASELINE.json configs 2/3 (4096) and 5 (8192)
@@ -266,9 +270,11 @@ def worker(a):
         walls, evs = [], []
         w, e = timed_region()
         walls.append(w); evs.append(e)
-        # short run (the driver's --steps 20): repeat the region, report the median.  Rank 0 decides (regions contain barriers).
-        repeats = 1 if w * 1e3 >= a.min_timed_ms else int(min(400, max(9, round(0.5 / max(w, 1e-6)))))
-        if world > 1:
+        # what the last step of the first region computed: taken before --full runs anything else, so it depends on the arguments only
+        outputs = step_outputs(env) if a.dump_outputs and rank == 0 else None
+        # --full, short run (the driver's --steps 20): repeat the region, report the median.  Rank 0 decides (regions contain barriers).
+        repeats = 1 if not a.full or w * 1e3 >= a.min_timed_ms else int(min(400, max(9, round(0.5 / max(w, 1e-6)))))
+        if world > 1 and a.full:
             flag = torch.tensor([repeats], device=coll_dev)
             dist.broadcast(flag, src=0)
             repeats = int(flag.item())
@@ -278,11 +284,11 @@ def worker(a):
 
         # step kernel alone, for tasks whose timed graph also holds the actor kernel: HIP events around replays of a graph that holds
         # ONLY k_step, KG launches back to back, directly after the timed region
-        if fused_step and not a.no_graph:
+        if a.full and fused_step and not a.no_graph:
             kern_ms_each = [1e3 * e / a.steps for e in evs]     # the timed graph IS G x k_step<..., POL>: same replays, same region
             kern_method = (f"HIP events on the launch stream around the {a.steps // G} graph replays of the timed region itself "
                            f"(median of {repeats} regions; includes the ~1 us gaps between launches" + ")")
-        else:
+        elif a.full:
             KG = 20
             fixed_actions = (policy_act(env.obs_buf) if not fused_step else fused.act(env.obs_buf)).clone()
             kernel_replay = env.make_graphed_step(lambda _obs: fixed_actions, steps_per_replay=KG)   # KG x lg_step, nothing else
@@ -297,7 +303,8 @@ def worker(a):
             kern_ms_each = [s_.elapsed_time(e_) / KG for s_, e_ in ev]
             kern_method = f"HIP events around {n_rep} replays of a HIP graph of {KG} back-to-back launches of the step kernel alone, right after the timed region (median per-launch time)"
     finite = bool(torch.isfinite(env.obs_buf).all()) and bool(torch.isfinite(env.root_states).all())
-    kern_ms = statistics.median(kern_ms_each)
+    if outputs is not None:
+        write_outputs(a.dump_outputs, outputs, a.num_envs)
     t = torch.tensor(walls, dtype=torch.float64, device=coll_dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)           # per region: the slowest rank
@@ -305,7 +312,7 @@ def worker(a):
 
     # cost of self-collision (on in the anymal_c_flat config): the same rollout with asset.self_collisions switched off
     sc_cost = None
-    if getattr(env, "self_collision_modelled", False) and world == 1 and fused_step and not a.no_graph:
+    if a.full and getattr(env, "self_collision_modelled", False) and world == 1 and fused_step and not a.no_graph:
         try:
             env_cfg2, _ = task_registry.get_cfgs(a.task)
             keep = env_cfg2.asset.self_collisions
@@ -333,27 +340,8 @@ def worker(a):
 
     out = None
     if rank == 0:
-        from tools.flop_count import flops_per_env_step
         total_envs = a.num_envs * world
         value = total_envs * a.steps / elapsed
-        bpe = BYTES_PER_ENV_STEP.get(a.task, 4022)
-        traffic, mfma_busy, pm_src = None, None, None   # PMC figures per k_step launch from the committed rocprofv3 passes (same workload only)
-        try:
-            pm = json.load(open(PMC_SUMMARY))["tasks"].get(a.task)
-            if pm and pm["envs_per_gpu"] == a.num_envs:       # counters of the same workload only; per launch of the dominant kernel, like `achieved`
-                per_step = pm["k_step"]["steps_per_launch"]
-                traffic = pm["k_step"]["traffic_bytes_per_launch"] / per_step * (G if rollout_kernel else 1)
-                mfma_busy = 100.0 * pm["k_step"]["mfma_busy_frac_of_busy_cycles"]
-                pm_src = (os.path.relpath(PMC_SUMMARY, REPO) + f" (rocprofv3 --pmc passes of `{pm['command']}`: FETCH_SIZE / WRITE_SIZE KiB per dispatch of {pm['k_step']['kernel']}, "
-                          f"2*FETCH+WRITE, {per_step} policy step(s) per dispatch; SQ_VALU_MFMA_BUSY_CYCLES / SQ_BUSY_CYCLES)")
-        except Exception:
-            pass
-        achieved = bpe * a.num_envs / (kern_ms * 1e-3) / 1e9
-        fl = flops_per_env_step(a.task, int(env.cfg.control.decimation))
-        step_flops = fl["total"] - (0 if fused_step else fl["actor_mlp"])          # what the timed kernel computes
-        tflops = step_flops * a.num_envs / (kern_ms * 1e-3) / 1e12
-        kname = {"anymal_c_flat": "k_step<AnymalTraits,NET,plane" + ((",POL,ROLL> (actor + step, %d steps per launch)" % G) if rollout_kernel else ",POL> (actor + step)" if fused_step else ">"),
-                 "cassie": "k_step<CassieTraits,PD,HF>"}.get(a.task, "k_step<AnymalTraits," + ("NET" if getattr(env.cfg.control, "use_actuator_network", False) else "PD") + ",HF>")
         wide_bf16 = (not use_torch) and (not fused_step) and capi_wide_precision() == 1
         dtype_text = "f32" if not wide_bf16 else "f32 physics + bf16x3 actor (split-bf16 products hi*hi + hi*lo + lo*hi with f32 accumulation: 16 significand bits per operand; --f32-actor times the f32-MFMA actor)"
         out = {
@@ -371,17 +359,38 @@ def worker(a):
                        "policy": "torch ops (hipBLASLt)" if use_torch else ("MFMA actor inside k_step (v_mfma_f32_16x16x4_f32, 4 waves)" if fused_step else "actor kernel lg_policy_act: k_policy_act_wide, 32 envs per workgroup, split-bf16 products (hi*hi + hi*lo + lo*hi, f32 accumulate) on v_mfma_f32_32x32x16_bf16")},
             "repeats": repeats,
             "timing": f"median of {repeats} timed regions of exactly {a.steps} steps each (a region shorter than {a.min_timed_ms:g} ms is repeated)" if repeats > 1 else f"one timed region of {a.steps} steps",
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": pm_src, "kernel": kname,
-                         "policy_steps_per_launch": G if rollout_kernel else 1,
-                         "algorithmic_bytes_per_launch": bpe * a.num_envs * (G if rollout_kernel else 1), "launch_ms": kern_ms * (G if rollout_kernel else 1),
-                         "kernel_ms": kern_ms, "kernel_ms_method": kern_method,
-                         "algorithmic_bytes_per_env_step": bpe,
-                         "flops": {"per_env_step": step_flops, "breakdown": fl, "achieved_tflops": tflops, "peak_tflops": FP32_VECTOR_PEAK_TFLOPS,
-                                   "frac": tflops / FP32_VECTOR_PEAK_TFLOPS, "mfma_busy_pct": mfma_busy,
-                                   "note": "counted fp32 flops of the timed kernel (tools/flop_count.py: ABA + contacts, actuator LSTM, actor when fused) / fp32 vector peak"},
-                         "note": "issue/latency-bound, not HBM-bound: one 512-register rigid-body wave per SIMD runs a serial chain of ~20k instructions; state is L2/MALL-resident; see DESIGN.md section 5"},
         }
+        if a.full:
+            kern_ms = statistics.median(kern_ms_each)
+            from tools.flop_count import flops_per_env_step
+            bpe = BYTES_PER_ENV_STEP.get(a.task, 4022)
+            traffic, mfma_busy, pm_src = None, None, None   # PMC figures per k_step launch from the committed rocprofv3 passes (same workload only)
+            try:
+                pm = json.load(open(PMC_SUMMARY))["tasks"].get(a.task)
+                if pm and pm["envs_per_gpu"] == a.num_envs:       # counters of the same workload only; per launch of the dominant kernel, like `achieved`
+                    per_step = pm["k_step"]["steps_per_launch"]
+                    traffic = pm["k_step"]["traffic_bytes_per_launch"] / per_step * (G if rollout_kernel else 1)
+                    mfma_busy = 100.0 * pm["k_step"]["mfma_busy_frac_of_busy_cycles"]
+                    pm_src = (os.path.relpath(PMC_SUMMARY, REPO) + f" (rocprofv3 --pmc passes of `{pm['command']}`: FETCH_SIZE / WRITE_SIZE KiB per dispatch of {pm['k_step']['kernel']}, "
+                              f"2*FETCH+WRITE, {per_step} policy step(s) per dispatch; SQ_VALU_MFMA_BUSY_CYCLES / SQ_BUSY_CYCLES)")
+            except Exception:
+                pass
+            achieved = bpe * a.num_envs / (kern_ms * 1e-3) / 1e9
+            fl = flops_per_env_step(a.task, int(env.cfg.control.decimation))
+            step_flops = fl["total"] - (0 if fused_step else fl["actor_mlp"])          # what the timed kernel computes
+            tflops = step_flops * a.num_envs / (kern_ms * 1e-3) / 1e12
+            kname = {"anymal_c_flat": "k_step<AnymalTraits,NET,plane" + ((",POL,ROLL> (actor + step, %d steps per launch)" % G) if rollout_kernel else ",POL> (actor + step)" if fused_step else ">"),
+                     "cassie": "k_step<CassieTraits,PD,HF>"}.get(a.task, "k_step<AnymalTraits," + ("NET" if getattr(env.cfg.control, "use_actuator_network", False) else "PD") + ",HF>")
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                               "traffic": traffic, "traffic_source": pm_src, "kernel": kname,
+                               "policy_steps_per_launch": G if rollout_kernel else 1,
+                               "algorithmic_bytes_per_launch": bpe * a.num_envs * (G if rollout_kernel else 1), "launch_ms": kern_ms * (G if rollout_kernel else 1),
+                               "kernel_ms": kern_ms, "kernel_ms_method": kern_method,
+                               "algorithmic_bytes_per_env_step": bpe,
+                               "flops": {"per_env_step": step_flops, "breakdown": fl, "achieved_tflops": tflops, "peak_tflops": FP32_VECTOR_PEAK_TFLOPS,
+                                         "frac": tflops / FP32_VECTOR_PEAK_TFLOPS, "mfma_busy_pct": mfma_busy,
+                                         "note": "counted fp32 flops of the timed kernel (tools/flop_count.py: ABA + contacts, actuator LSTM, actor when fused) / fp32 vector peak"},
+                               "note": "issue/latency-bound, not HBM-bound: one 512-register rigid-body wave per SIMD runs a serial chain of ~20k instructions; state is L2/MALL-resident; see DESIGN.md section 5"}
         if sc_cost is not None:
             if "ms_per_step_without_self_collision" in sc_cost:
                 sc_cost["self_collision_cost_ms_per_step"] = out["ms_per_step"] - sc_cost["ms_per_step_without_self_collision"]
@@ -399,13 +408,13 @@ def worker(a):
             return
         if training is not None:
             out["ppo_training"] = training
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a, env)
         sys.__stdout__.write(json.dumps(out) + "\n")         # (the watchdog may fire while the leg has sys.stdout redirected)
         sys.__stdout__.flush()
 
     training, broken = None, False
-    iters = a.training_iters if a.training_iters >= 0 else (100 if a.task == "anymal_c_flat" else 20)
+    iters = 0 if not a.full else a.training_iters if a.training_iters >= 0 else (100 if a.task == "anymal_c_flat" else 20)
     if iters > 0:
         limit = float(os.environ.get("LG_BENCH_PPO_TIMEOUT_S", "300"))
         finished = threading.Event()
@@ -490,6 +499,32 @@ def training_leg(a, iters, rank, local_rank, world, coll_dev, ranks_seen, backen
         out["collectives_per_iteration"] = coll
         out["host_launches_per_update"] = getattr(alg, "dp_launches", None) or {"note": "eager kernel launches (two-graph capture not used: " + str(getattr(alg, "_dp_graph_error", "torch MLP path")) + ")"}
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(env):
+    """Host copies of what a caller of the timed path holds after its last step: observations, rewards, dones, time-outs
+    (privileged observations where the task has them) and the env's root / joint state.  float64 stays float64, the rest becomes float32."""
+    import torch
+    bufs = {"obs": env.obs_buf, "privileged_obs": env.privileged_obs_buf, "rew": env.rew_buf, "dones": env.reset_buf,
+            "time_outs": env.time_out_buf, "root_states": env.root_states, "dof_state": env.dof_state}
+    return {name: t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+            for name, t in bufs.items() if t is not None}
+
+
+def write_outputs(dirpath, arrays, num_envs, limit=DUMP_LIMIT_BYTES):
+    """DIR/<name>.npy for every array (leading dimension a multiple of num_envs).  Above `limit` bytes in all, every array keeps the
+    rows of the same fixed, seeded sample of envs."""
+    import numpy as np
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        rows = np.sort(np.random.default_rng(0).choice(num_envs, size=max(1, num_envs * limit // total), replace=False))
+        arrays = {k: v.reshape(num_envs, -1)[rows].reshape((-1,) + v.shape[1:]) for k, v in arrays.items()}
+    os.makedirs(dirpath, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), v)
 
 
 def capi_wide_precision():

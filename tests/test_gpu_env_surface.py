@@ -74,10 +74,12 @@ def test_a1_and_anymal_b_tasks_stand_on_rough_terrain(task, height):
     assert float((env.base_lin_vel.norm(dim=1) < 0.5).float().mean()) > 0.7 and rel_z.isfinite().all()
 
 
-def test_bundled_runner_learns_a_few_iterations(tmp_path):
+def test_bundled_runner_learns_a_few_iterations(tmp_path, monkeypatch):
     from legged_games_gym_amd.envs import task_registry
     from legged_games_gym_amd.utils import get_args
     from legged_games_gym_amd.utils.helpers import get_load_path
+    registered = task_registry.get_cfgs("anymal_c_flat")[1].runner       # --max_iterations below writes into this shared cfg: restore it afterwards
+    monkeypatch.setattr(registered, "max_iterations", registered.max_iterations)
     args = get_args(["--task", "anymal_c_flat", "--num_envs", "128", "--headless", "--sim_device", "cuda:0", "--rl_device", "cuda:0", "--max_iterations", "2"])
     env, _ = task_registry.make_env("anymal_c_flat", args)
     runner, train_cfg = task_registry.make_alg_runner(env, "anymal_c_flat", args, log_root=str(tmp_path))
@@ -228,6 +230,8 @@ def test_train_then_headless_play_resumes_from_checkpoint(tmp_path, monkeypatch)
     from legged_games_gym_amd.utils import get_args
     from legged_games_gym_amd.scripts.play import play
     monkeypatch.setattr(tr_mod, "LEGGED_GYM_ROOT_DIR", str(tmp_path))       # logs/<experiment>/<date>_<run>/ under tmp
+    registered = task_registry.get_cfgs("anymal_c_flat")[1].runner       # --max_iterations below writes into this shared cfg: restore it afterwards
+    monkeypatch.setattr(registered, "max_iterations", registered.max_iterations)
     args = get_args(["--task", "anymal_c_flat", "--num_envs", "64", "--headless", "--sim_device", "cuda:0", "--rl_device", "cuda:0",
                      "--max_iterations", "1"])
     env, _ = task_registry.make_env("anymal_c_flat", args)
@@ -284,13 +288,15 @@ def test_reference_style_smoke_script(task, capsys):
     assert time_outs >= 10 or resets >= 10                        # every env finished at least one 1000-step episode
 
 
-def test_rough_task_trains_on_the_wide_kernels_and_critic_pass_matches_torch(tmp_path):
+def test_rough_task_trains_on_the_wide_kernels_and_critic_pass_matches_torch(tmp_path, monkeypatch):
     """anymal_c_rough through the bundled runner: the rollout's critic pass over the stored transitions runs the chain forward of the
     wide learner kernels (runner._critic_values -> lg_mlp_wide_forward) and must agree with the torch critic; two iterations of the
     update on lg_mlp_wide_* leave finite parameters and move them."""
     from legged_games_gym_amd.envs import task_registry
     from legged_games_gym_amd.utils import get_args
     from legged_games_gym_amd.rl.mlp_kernels import WideMlpTrainer
+    registered = task_registry.get_cfgs("anymal_c_rough")[1].runner       # --max_iterations below writes into this shared cfg: restore it afterwards
+    monkeypatch.setattr(registered, "max_iterations", registered.max_iterations)
     args = get_args(["--task", "anymal_c_rough", "--num_envs", "128", "--headless", "--sim_device", "cuda:0", "--rl_device", "cuda:0",
                      "--max_iterations", "2"])
     env, _ = task_registry.make_env("anymal_c_rough", args)

@@ -166,6 +166,33 @@ def test_committed_pmc_summary_has_what_bench_reads():
     assert pm["anymal_c_flat"]["k_step"]["steps_per_launch"] == 20 and "true, true>" in pm["anymal_c_flat"]["k_step"]["kernel"]     # the multi-step kernel
 
 
+def test_bench_output_dump_keeps_one_seeded_sample_of_envs_above_the_limit(tmp_path):
+    """bench.py --dump-outputs: every array whole below the size limit; above it, the same fixed seeded rows of envs from every array
+    (an env's joints stay together in the [N * dofs, 2] joint state) and the same files on every call."""
+    import importlib.util
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    N = 64
+    arrays = {"obs": np.arange(N * 48, dtype=np.float32).reshape(N, 48), "rew": np.arange(N, dtype=np.float32),
+              "dof_state": np.arange(N * 12 * 2, dtype=np.float32).reshape(N * 12, 2)}
+    bench.write_outputs(str(tmp_path / "whole"), arrays, N)
+    for k, v in arrays.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "whole" / f"{k}.npy"), v)
+    limit = sum(v.nbytes for v in arrays.values()) // 4
+    bench.write_outputs(str(tmp_path / "a"), arrays, N, limit=limit)
+    bench.write_outputs(str(tmp_path / "b"), arrays, N, limit=limit)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert sum(v.nbytes for v in got.values()) <= limit
+    rows = got["rew"].astype(int)
+    assert len(rows) == N // 4 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(got["obs"], arrays["obs"][rows])
+    np.testing.assert_array_equal(got["dof_state"], arrays["dof_state"].reshape(N, 24)[rows].reshape(-1, 2))
+    for k in arrays:
+        np.testing.assert_array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
+
+
 def test_committed_kernel_resource_table_keeps_the_headline_kernels_out_of_scratch():
     """csrc/kernel_resources.txt (written by __graft_entry__.build() from hipcc's resource remarks) is the evidence DESIGN.md quotes for
     register use.  Guard what the measurements rest on: the rollout kernel of the headline (ANYmal-C flat, actuator net, fused actor,

@@ -97,11 +97,15 @@ def test_box_points_rules():
     assert sorted((round(c.pos[0], 6), round(c.pos[1], 6)) for c in slab) == [(-0.15, -0.05), (-0.15, 0.05), (0.15, -0.05), (0.15, 0.05)]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference URDFs only exist in the build container")
 @pytest.mark.parametrize("stem,rel", [("anymal_c", "resources/robots/anymal_c/urdf/anymal_c.urdf"), ("cassie", "resources/robots/cassie/urdf/cassie.urdf"),
                                       ("anymal_b", "resources/robots/anymal_b/urdf/anymal_b.urdf"), ("a1", "resources/robots/a1/urdf/a1.urdf")])
-def test_compiled_table_is_fresh(stem, rel):
-    a, b = compile_urdf(os.path.join(REF, rel), name=stem), load_model(stem + ".urdf")
+def test_compiled_table_is_fresh(stem, rel, golden_dir):
+    """The shipped tables against the reference URDFs, stored as fixtures (tests/golden/urdf/); where the reference tree is present the
+    fixtures must still be byte-identical to it."""
+    urdf = os.path.join(golden_dir, "urdf", stem + ".urdf")
+    if os.path.isfile(os.path.join(REF, rel)):
+        assert open(os.path.join(REF, rel), "rb").read() == open(urdf, "rb").read(), f"{rel} changed: refresh tests/golden/urdf/{stem}.urdf"
+    a, b = compile_urdf(urdf, name=stem), load_model(stem + ".urdf")
     for f in ("joint_pos", "joint_rot", "joint_axis", "body_mass", "body_com", "body_inertia", "base_inertia", "base_com"):
         np.testing.assert_allclose(getattr(a, f), getattr(b, f), atol=1e-12)
     assert a.body_names == b.body_names and a.dof_names == b.dof_names

@@ -11,9 +11,9 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for task in anymal_c_rough cassie; do
     echo "[bench + kernel table] $task"
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$task" -- python3 "$ROOT/bench.py" --task $task --training-iters 0 --no-cpu-baseline > "$OUT/bench_${task}_profiled.json" 2> "$OUT/bench_$task.err" || exit 1
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_$task" -- python3 "$ROOT/bench.py" --full --task $task --training-iters 0 --no-cpu-baseline > "$OUT/bench_${task}_profiled.json" 2> "$OUT/bench_$task.err" || exit 1
     cp "$(find "$OUT/stats_$task" -name '*kernel_stats.csv' | head -1)" "$OUT/bench_${task}_kernel_stats.csv"; rm -rf "$OUT/stats_$task"
-    timeout -k 10 300 python3 "$ROOT/bench.py" --task $task > "$OUT/bench_$task.json" 2>> "$OUT/bench_$task.err" || exit 1
+    timeout -k 10 300 python3 "$ROOT/bench.py" --full --task $task > "$OUT/bench_$task.json" 2>> "$OUT/bench_$task.err" || exit 1
 done
 echo "[wide learner timeline]"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/wide" -- python3 "$ROOT/tools/wide_probe.py" 235 > "$OUT/wide_probe.txt" 2> "$OUT/wide.err" || exit 1
