@@ -60,3 +60,18 @@ def observation_noise(seed, num_envs, step, num_obs, K, L):
     if num_obs > 48:
         out[:, 48:] = lanes(seed, envs, step, NOISE_H, 0, num_obs - 48)
     return out
+
+
+def action_noise(seed, env_ids, step, num_actions):
+    """float64 [len(env_ids), num_actions]: the standard normal eps of the exploration noise ``actions = mean + std * eps``.
+    Action a takes word a % 4 of the Box-Muller pair built from Philox block (seed ^ 0x9E3779B97F4A7C15; env, step, 100 + a // 4, 0):
+    eps = [r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3, r1 sin 2 pi u3], r = sqrt(-2 log max(u, 1e-12)) of u0 / u2, in float64."""
+    env_ids = np.asarray(env_ids, np.int64).reshape(-1, 1)
+    groups = (num_actions + 3) // 4
+    key = (int(seed) ^ 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    u = uniforms(key, env_ids, step, 100 + np.arange(groups).reshape(1, -1), 0).astype(np.float64)      # [n, groups, 4]
+    r0 = np.sqrt(-2.0 * np.log(np.maximum(u[..., 0], 1e-12)))
+    r1 = np.sqrt(-2.0 * np.log(np.maximum(u[..., 2], 1e-12)))
+    eps = np.stack((r0 * np.cos(2 * np.pi * u[..., 1]), r0 * np.sin(2 * np.pi * u[..., 1]),
+                    r1 * np.cos(2 * np.pi * u[..., 3]), r1 * np.sin(2 * np.pi * u[..., 3])), axis=-1)
+    return eps.reshape(env_ids.shape[0], 4 * groups)[:, :num_actions]

@@ -75,17 +75,28 @@ def _get(d, name):
     return (t.to(torch.uint8) if t.dtype == torch.bool else t).cpu().numpy()
 
 
-def _step_parity_every_env(o, d, N, act, step, vel_tol, pos_tol, obs_tol, rew_tol, min_contact_frac):
+def _step_both(o, d, act, step):
+    """The compared policy step: the same actions and counter on both sides."""
     o.step(act.numpy(), step); d.step(act.cuda(), step)
+
+
+def _compare_every_env(o, dev, N, step, vel_tol, pos_tol, obs_tol, rew_tol, min_contact_frac, push_interval=750, same_branch_vel=None):
+    """The oracle's state after a policy step (``o.buf``) against the device's (``dev(name)`` -> numpy) on EVERY env.  Plane builds
+    have no ``measured_heights`` / ``terrain_levels``: their observation check takes every env of the bulk.  ``same_branch_vel``
+    (multi-step checks, where a contact onset or a stick / slide switch on a 1-ulp difference inside the bulk is met many times):
+    the contact forces take the rule of the joint states -- 99.9 % of the bulk within the budget, the rest an order of magnitude
+    looser -- and the envs whose joint velocities also agree within ``same_branch_vel`` must be all but 0.1 % of the bulk.
+    Returns (survivors, the bulk or, with ``same_branch_vel``, its same-branch part)."""
     # --- integer / boolean outputs: bit-equal on every env
     for k in ("reset_buf", "time_out_buf", "episode_length_buf", "terrain_levels"):
-        assert np.array_equal(o.buf[k], _get(d, k)), k
+        if k in o.buf:
+            assert np.array_equal(o.buf[k], dev(k)), k
     survivors = o.buf["reset_buf"] == 0
     # --- the contacts were real: most robots carry weight on the height field at the end of the step
-    cf_o, cf_d = o.buf["contact_forces"], _get(d, "contact_forces")
+    cf_o, cf_d = o.buf["contact_forces"], dev("contact_forces")
     assert (np.abs(cf_o[..., 2]).sum(axis=1) > 50.0).mean() > min_contact_frac
-    q_o, q_d = o.buf["dof_state"].reshape(N, 12, 2), _get(d, "dof_state").reshape(N, 12, 2)
-    r_o, r_d = o.buf["root_states"], _get(d, "root_states")
+    q_o, q_d = o.buf["dof_state"].reshape(N, 12, 2), dev("dof_state").reshape(N, 12, 2)
+    r_o, r_d = o.buf["root_states"], dev("root_states")
     e_pos = np.abs(q_o[..., 0] - q_d[..., 0]).max(axis=1)
     e_vel = np.abs(q_o[..., 1] - q_d[..., 1]).max(axis=1)
     e_root = np.abs(r_o[:, :7] - r_d[:, :7]).max(axis=1)
@@ -99,20 +110,35 @@ def _step_parity_every_env(o, d, N, act, step, vel_tol, pos_tol, obs_tol, rew_to
     assert e_pos.max() < 20 * pos_tol and e_root.max() < 20 * pos_tol and e_vel.max() < 20 * vel_tol, (e_pos.max(), e_root.max(), e_vel.max())
     # ... and the bulk two orders tighter
     assert np.median(e_pos) < pos_tol / 50 and np.median(e_vel) < vel_tol / 50, (np.median(e_pos), np.median(e_vel))
-    mh_o, mh_d = o.buf["measured_heights"], _get(d, "measured_heights")
-    assert (np.abs(mh_o - mh_d) > 1e-6).mean() < 2e-3          # a sample point within 1 ulp of a cell edge may truncate differently
     bulk = (e_pos < pos_tol) & (e_vel < vel_tol)                 # envs that took the same branches
+    if "measured_heights" in o.buf:
+        mh_o, mh_d = o.buf["measured_heights"], dev("measured_heights")
+        assert (np.abs(mh_o - mh_d) > 1e-6).mean() < 2e-3      # a sample point within 1 ulp of a cell edge may truncate differently
+        same_cells = ~(np.abs(mh_o - mh_d) > 1e-6).any(axis=1) & bulk
+    else:
+        same_cells = bulk
     assert bulk.mean() > 0.998
-    assert np.abs(o.buf["rew_buf"] - _get(d, "rew_buf"))[bulk].max() < rew_tol
-    same_cells = ~(np.abs(mh_o - mh_d) > 1e-6).any(axis=1) & bulk
-    assert np.abs(o.buf["obs_buf"][same_cells] - _get(d, "obs_buf")[same_cells]).max() < obs_tol
-    assert np.abs(o.buf["episode_sums"] - _get(d, "episode_sums"))[:, bulk].max() < rew_tol
+    assert np.abs(o.buf["rew_buf"] - dev("rew_buf"))[bulk].max() < rew_tol
+    assert np.abs(o.buf["obs_buf"][same_cells] - dev("obs_buf")[same_cells]).max() < obs_tol
+    assert np.abs(o.buf["episode_sums"] - dev("episode_sums"))[:, bulk].max() < rew_tol
     f_scale = max(1.0, float(np.abs(cf_o).max()))
-    assert np.abs(cf_o - cf_d)[bulk].max() < 2e-3 * f_scale, (np.abs(cf_o - cf_d)[bulk].max(), f_scale)
+    same = bulk
+    if same_branch_vel is None:
+        assert np.abs(cf_o - cf_d)[bulk].max() < 2e-3 * f_scale, (np.abs(cf_o - cf_d)[bulk].max(), f_scale)
+    else:
+        same = bulk & (e_vel < same_branch_vel)
+        assert (bulk & ~same).mean() < 1e-3, (bulk & ~same).sum()
+        e_f = np.abs(cf_o - cf_d).max(axis=(1, 2))[bulk]
+        assert q999(e_f) < 2e-3 * f_scale and e_f.max() < 20 * 2e-3 * f_scale, (q999(e_f), e_f.max(), f_scale)
     # push step: every surviving env got a new xy velocity within +-max_push_vel, identical on both sides (Philox key)
-    if step % 750 == 0:
+    if step % push_interval == 0:
         assert np.abs(r_o[survivors][:, 7:9]).max() <= 1.0 + 1e-6 and np.abs(r_o[:, 7:9] - r_d[:, 7:9]).max() < 1e-6
-    return survivors
+    return survivors, same
+
+
+def _step_parity_every_env(o, d, N, act, step, vel_tol, pos_tol, obs_tol, rew_tol, min_contact_frac):
+    _step_both(o, d, act, step)
+    return _compare_every_env(o, lambda k: _get(d, k), N, step, vel_tol, pos_tol, obs_tol, rew_tol, min_contact_frac)[0]
 
 
 def _invariants(d, N, robot, dm, steps, action_std, vel_limit, first_step, upright_frac):

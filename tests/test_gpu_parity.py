@@ -180,16 +180,30 @@ def test_actuator_kernel_matches_golden_and_oracle(golden_dir):
     np.testing.assert_allclose(probe.cpu().numpy()[:4], g["survey_probe_first4"], atol=1e-4)
 
 
-@pytest.mark.parametrize("task", ["anymal_c_flat", "cassie", "a1", "anymal_b"])
-def test_physics_substep_parity(task):
-    """One 5 ms rigid-body step from random states (airborne, touching and penetrating), given torques."""
+@pytest.mark.parametrize("task,terrain", [pytest.param(t, None, id=t) for t in ("anymal_c_flat", "cassie", "a1", "anymal_b")]
+                         + [pytest.param("cassie", "hf", id="cassie-heightfield")])
+def test_physics_substep_parity(task, terrain):
+    """One 5 ms rigid-body step from random states (airborne, touching and penetrating), given torques.  On the plane, and for
+    Cassie on a curriculum height field (k_physics<CassieTraits, HF>: heights above the ground under the env origin)."""
     N = 512
-    cfg, robot, p, names, o, d = pair(task, N)
-    init_both(o, d, N)
+    if terrain is None:
+        cfg, robot, p, names, o, d = pair(task, N)
+        init_both(o, d, N)
+        ground = 0.0
+    else:
+        terr = _rough_terrain(N)
+
+        def tweak(cfg):
+            cfg.terrain.mesh_type, cfg.terrain.num_rows, cfg.terrain.num_cols, cfg.terrain.border_size = "heightfield", 4, 5, 5
+        cfg, robot, p, names, o, d = pair(task, N, tweak=tweak, terrain=terr, plane=False)
+        lv = np.random.default_rng(0).integers(0, 4, N).astype(np.int32); ty = (np.arange(N) * 5 // N).astype(np.int32)
+        put(o, d, "terrain_levels", lv); put(o, d, "terrain_types", ty)
+        init_both(o, d, N, origins=terr.env_origins[lv, ty].astype(np.float32))
+        ground = o.buf["env_origins"][:, 2].copy()
     rng = np.random.default_rng(2)
     root = o.buf["root_states"].copy()
     lo, hi = {"cassie": (0.7, 1.1), "a1": (0.15, 0.45)}.get(task, (0.35, 0.75))
-    root[:, 2] = rng.uniform(lo, hi, N)
+    root[:, 2] = ground + rng.uniform(lo, hi, N)
     quat = np.array([0, 0, 0, 1.0]) + rng.normal(0, 0.15, (N, 4)); quat /= np.linalg.norm(quat, axis=1, keepdims=True)
     root[:, 3:7] = quat
     root[:, 7:13] = rng.normal(0, 0.7, (N, 6))

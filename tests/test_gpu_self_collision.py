@@ -11,18 +11,22 @@ from tests.test_oracle_physics import _crossing_pose
 pytestmark = pytest.mark.gpu
 
 
-def _pair(task, N, on=True, tweak=None):
+def _pair(task, N, on=True, tweak=None, terrain=None):
     from oracle.oracle import OracleSim
     from legged_games_gym_amd.device_sim import DeviceSim
 
     def tw(cfg):
         cfg.asset.self_collisions = 0 if on else 1
+        if terrain is not None:
+            cfg.terrain.mesh_type, cfg.terrain.num_rows, cfg.terrain.num_cols, cfg.terrain.border_size = "heightfield", 4, 5, 5
         if tweak:
             tweak(cfg)
-    cfg, robot, p, names, model, w = make_setup(task, N, tweak=tw)
+    cfg, robot, p, names, model, w = make_setup(task, N, tweak=tw, terrain=terrain, plane=False if terrain is not None else None)
     assert p.self_collision == int(on)
     o = OracleSim(p, model, robot, w, threads=8)
     d = DeviceSim(p, model, robot, torch.device("cuda:0"), w)
+    if terrain is not None:
+        o.set_terrain(terrain.heightsamples, terrain.env_origins); d.set_terrain(terrain.heightsamples, terrain.env_origins)
     return cfg, robot, p, o, d
 
 
@@ -40,21 +44,33 @@ def _get(d, name):
 from tests.test_oracle_physics import adversarial_actions as _adversarial_actions  # noqa: E402
 
 
-@pytest.mark.parametrize("task", ["anymal_c_flat", "a1"])
-def test_substep_parity_with_crossed_legs(task):
+@pytest.mark.parametrize("task,terrain", [pytest.param("anymal_c_flat", None, id="anymal_c_flat"), pytest.param("a1", None, id="a1"),
+                                          pytest.param("anymal_c_rough", "hf", id="anymal_c_rough-heightfield")])
+def test_substep_parity_with_crossed_legs(task, terrain):
     """One 5 ms sub-step from poses whose front legs overlap by up to ~2 cm (plus random base / joint velocities): the kernel's
-    pair detection, Jacobi-coupled implicit contact and force export against the oracle's, every env."""
+    pair detection, Jacobi-coupled implicit contact and force export against the oracle's, every env.  Also on a height field
+    (k_physics<AnymalTraits, HF, SC>), the robots 1.5 m above their env origins."""
     N = 256
-    cfg, robot, p, o, d = _pair(task, N)
+    terr = None
+    if terrain is not None:
+        from tests.test_gpu_parity import _rough_terrain
+        terr = _rough_terrain(N)
+    cfg, robot, p, o, d = _pair(task, N, terrain=terr)
     fr, dm = randomize_env_params(N, 3)
-    _put(o, d, "env_origins", grid_origins(N)); _put(o, d, "friction_coeffs", fr); _put(o, d, "base_mass_delta", dm)
+    if terr is not None:
+        lv = np.random.default_rng(0).integers(0, 4, N).astype(np.int32); ty = (np.arange(N) * 5 // N).astype(np.int32)
+        _put(o, d, "terrain_levels", lv); _put(o, d, "terrain_types", ty)
+        _put(o, d, "env_origins", terr.env_origins[lv, ty].astype(np.float32))
+    else:
+        _put(o, d, "env_origins", grid_origins(N))
+    _put(o, d, "friction_coeffs", fr); _put(o, d, "base_mass_delta", dm)
     ids = np.arange(N, dtype=np.int32)
     o.reset_idx(ids, 0); d.reset_idx(torch.from_numpy(ids), 0)
     q0 = np.array(list(p.default_dof_pos)[:12], np.float64)
     names = list(robot.dof_names)
     haa = [i for i, n in enumerate(names) if n.endswith("HAA") or n.endswith("hip_joint")]
     rng = np.random.default_rng(1)
-    if task == "anymal_c_flat":
+    if task != "a1":
         qx, sign, (lf, rf) = _crossing_pose(robot, q0)
     else:                                        # A1: find the inward direction of the front abduction joints the same way
         lf, rf = names.index("FL_hip_joint"), names.index("FR_hip_joint")
@@ -73,7 +89,7 @@ def test_substep_parity_with_crossed_legs(task):
     dof[:, :, 1] = rng.normal(0, 1.0, (N, 12))
     _put(o, d, "dof_state", dof.reshape(-1, 2))
     root = o.buf["root_states"].copy()
-    root[:, 2] = 1.5                             # airborne: ground contact is not the subject here
+    root[:, 2] = 1.5 + o.buf["env_origins"][:, 2]   # airborne: ground contact is not the subject here
     root[:, 7:13] = rng.normal(0, 0.3, (N, 6))
     _put(o, d, "root_states", root)
     tau = rng.normal(0, 10.0, (N, 12)).astype(np.float32)

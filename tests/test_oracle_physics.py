@@ -310,14 +310,17 @@ def test_non_finite_state_forces_a_reset(oracle_lib):
 # ------------------------------------------------------------------ self-collision (asset.self_collisions = 0: anymal_c_flat_config.py:42)
 def _crossing_pose(robot, q0):
     """Joint angles that push the left-front and right-front lower legs a centimetre INTO each other (found numerically with the
-    independent capsule model of tests/common.py: sweep both HAA joints inwards from the default pose)."""
+    independent capsule model of tests/common.py: sweep both HAA joints inwards from the default pose).  ANYmal's LF_HAA / RF_HAA,
+    or A1's FL_hip_joint / FR_hip_joint (inward sign probed at +-0.4 rad, as test_substep_parity_with_crossed_legs does)."""
     from tests.common import min_self_clearance
     names = list(robot.dof_names)
-    lf, rf = names.index("LF_HAA"), names.index("RF_HAA")
+    a1 = "FL_hip_joint" in names
+    lf, rf = (names.index("FL_hip_joint"), names.index("FR_hip_joint")) if a1 else (names.index("LF_HAA"), names.index("RF_HAA"))
+    probe = 0.4 if a1 else 0.5
     sign = {}
     for d in (lf, rf):                       # which direction swings that leg towards the other one?
         qa, qb = q0.copy(), q0.copy()
-        qa[d] += 0.5; qb[d] -= 0.5
+        qa[d] += probe; qb[d] -= probe
         sign[d] = 1.0 if min_self_clearance(robot, qa) < min_self_clearance(robot, qb) else -1.0
     lo, hi = 0.0, 1.5
     for _ in range(30):                      # bisection on the common inward angle: clearance(mid) = -1 cm
@@ -387,16 +390,25 @@ def test_self_collision_exchanges_momentum_between_the_links_only(oracle_lib):
 
 
 def adversarial_actions(robot, p, N, seed=0):
-    """All four HAA joints swing towards the body's mid-plane, the knees fold: legs are driven into each other and into the trunk."""
+    """All four HAA joints swing towards the body's mid-plane, the knees fold: legs are driven into each other and into the trunk.
+    A1 (FL_hip_joint ... RR_calf_joint, action_scale 0.25): the same joint targets, the actions scaled by 0.5 / action_scale."""
     q0 = np.array(list(p.default_dof_pos)[:12], np.float64)
     _, sign, (lf, rf) = _crossing_pose(robot, q0)
     rng = np.random.default_rng(seed)
     act = np.zeros((N, 12), np.float32)
+    if "FL_hip_joint" not in list(robot.dof_names):
+        for d, nme in enumerate(robot.dof_names):
+            if nme.endswith("HAA"):
+                act[:, d] = (sign[lf] if nme.startswith("L") else sign[rf]) * rng.uniform(1.5, 3.0, N)     # x action_scale 0.5 = 0.75 .. 1.5 rad
+            if nme.endswith("KFE"):
+                act[:, d] = np.sign(q0[d]) * rng.uniform(1.0, 3.0, N)                                      # fold the knees further
+        return act
+    k = 0.5 / float(p.action_scale)
     for d, nme in enumerate(robot.dof_names):
-        if nme.endswith("HAA"):
-            act[:, d] = (sign[lf] if nme.startswith("L") else sign[rf]) * rng.uniform(1.5, 3.0, N)     # x action_scale 0.5 = 0.75 .. 1.5 rad
-        if nme.endswith("KFE"):
-            act[:, d] = np.sign(q0[d]) * rng.uniform(1.0, 3.0, N)                                      # fold the knees further
+        if nme.endswith("hip_joint"):
+            act[:, d] = (sign[lf] if nme[1] == "L" else sign[rf]) * rng.uniform(1.5, 3.0, N) * k
+        if nme.endswith("calf_joint"):
+            act[:, d] = np.sign(q0[d]) * rng.uniform(1.0, 3.0, N) * k
     return act
 
 
