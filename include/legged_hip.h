@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LG_ABI_VERSION        21
+#define LG_ABI_VERSION        22
 
 #define LG_MAX_LIMBS          4
 #define LG_MAX_CHAIN          6
@@ -117,6 +117,19 @@ typedef struct lg_params {
     /* reset: legged_robot.py:397-436 */
     float   base_init_state[13], _padf4;
     uint64_t seed;
+    /* commands.curriculum (legged_robot.py:159-168, rule :471-483).  cmd_curriculum != 0: every command draw reads the lin_vel_x
+     * range from B.cmd_range instead of cmd_lin_vel_x, and the launches no host stands between -- lg_step / lg_step_policy on the
+     * device counter (common_step_counter = -1) and every lg_rollout_policy -- apply the rule themselves on a tick step
+     * (counter % max_episode_length == 0 with at least one reset): the mean tracking sum of the step's reset envs, as the f32
+     * episode_means entry, is compared in double precision, the range is widened in B.cmd_range and that step's reset envs
+     * re-draw their commands from it (lg_resample_reset_commands' draw).  Launches with an explicit counter leave the rule to the
+     * caller (the host rule + lg_set_params / lg_resample_reset_commands), as before. */
+    int32_t cmd_curriculum;
+    int32_t cmd_curriculum_slot;       /* row of episode_sums of tracking_lin_vel */
+    double  cmd_max_curriculum;
+    double  cmd_tracking_scale_dt;     /* reward scale of tracking_lin_vel x dt */
+    double  cmd_max_episode_length;    /* ceil(episode_length_s / dt), the rule's divisor */
+    double  cmd_episode_length_s;      /* episode_length_s: episode sum = episode_means entry x this */
 } lg_params;
 
 /* Raw device pointers to caller-owned (torch-allocated) buffers.  Layouts are
@@ -151,6 +164,7 @@ typedef struct lg_buffers {
     const int16_t *height_samples;    /* [hf_rows,hf_cols] or NULL                       T8 */
     const float   *friction_coeffs;   /* [N] per-env shape friction (legged_robot.py:261-285) */
     const float   *base_mass_delta;   /* [N] added base mass (legged_robot.py:316-327) */
+    double  *cmd_range;         /* [2] lin_vel_x range while P.cmd_curriculum is on (double: the host rule's arithmetic), else unused */
 } lg_buffers;
 
 typedef struct lg_sim lg_sim;
@@ -244,7 +258,11 @@ int  lg_step_policy(lg_sim *sim, lg_policy *p, const float *obs, float *actions,
  * obs[steps + 1][N][num_obs] (obs[0] = the input of the first step, step t writes obs[t + 1]), actions / mean[steps][N][num_actions]
  * (mean may be null), rew[steps][N], dones / time_outs[steps][N] (uint8).  The bound state buffers hold the state after the last
  * step; extras["episode"] (episode_means) is that of the last step of the segment in which an env was reset (legged_robot.py:179-183);
- * the device step counter advances by `steps`.  Compiled for the shape lg_step_policy is compiled for (48-128-64-32 actor,
+ * the device step counter advances by `steps`.  With P.cmd_curriculum on the segment is split at its curriculum ticks into a fixed
+ * 1 + ceil(steps / max_episode_length) launches of the same kernel (the workgroups never meet between steps, so no launch runs past
+ * a tick): each resumes at a device-held step, ends behind the next tick (whose rule its last workgroup applies, re-drawing the
+ * reset envs' commands and their rows of obs[t + 1]) or at the end of the segment; the ones left over exit at once, so a captured
+ * graph stays valid on every replay.  Compiled for the shape lg_step_policy is compiled for (48-128-64-32 actor,
  * quadruped actuator-net kernel on the plane, no height measurements); -4 otherwise.  The first call on a handle allocates a small
  * workspace (make it outside stream capture). */
 #define LG_MAX_ROLL_STEPS 256

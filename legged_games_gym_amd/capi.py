@@ -16,7 +16,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-LG_ABI_VERSION = 21
+LG_ABI_VERSION = 22
 LG_ADAM_SCRATCH_FLOATS = 2050
 LG_MAX_LIMBS, LG_MAX_CHAIN, LG_MAX_DOF = 4, 6, 12
 LG_MAX_LIMB_POINTS, LG_MAX_BASE_POINTS, LG_MAX_BODIES = 8, 4, 20
@@ -81,6 +81,9 @@ class lg_params(C.Structure):
         ("terrain_env_length", f32), ("max_episode_length_s", f32),
         ("base_init_state", f32 * 13), ("_padf4", f32),
         ("seed", u64),
+        # commands.curriculum on the device (legged_hip.h): on/off, tracking_lin_vel's slot, the host rule's constants in double
+        ("cmd_curriculum", i32), ("cmd_curriculum_slot", i32), ("cmd_max_curriculum", C.c_double), ("cmd_tracking_scale_dt", C.c_double),
+        ("cmd_max_episode_length", C.c_double), ("cmd_episode_length_s", C.c_double),
     ]
 
 
@@ -105,7 +108,7 @@ class lg_buffers(C.Structure):
         ("measured_heights", _PF), ("sea_hidden_state", _PF), ("sea_cell_state", _PF),
         ("episode_sums", _PF), ("episode_means", _PF), ("extras_accum", _PF), ("step_counter", _PI64), ("env_origins", _PF),
         ("terrain_levels", _PI32), ("terrain_types", _PI32), ("terrain_origins", _PF),
-        ("height_samples", _PI16), ("friction_coeffs", _PF), ("base_mass_delta", _PF),
+        ("height_samples", _PI16), ("friction_coeffs", _PF), ("base_mass_delta", _PF), ("cmd_range", C.POINTER(C.c_double)),
     ]
 
 

@@ -79,6 +79,8 @@ struct RollArgs {
     float   *rew;              // [steps][N]
     uint8_t *done, *time_outs; // [steps][N]
     float   *extras;           // [steps][LG_NUM_REWARD_TERMS + 2] episode accumulators per step (zero at launch; roll_finish publishes and re-zeroes)
+    int      sub;              // commands.curriculum: index of this launch among the segment's sub-launches (0 starts at step 0) ...
+    int     *cursor;           // ... and the device-held step the next one resumes at (written by roll_finish)
 };
 
 struct KArgs {                 // passed by value: lives in the kernarg segment -> scalar loads
@@ -105,6 +107,18 @@ struct KArgs {                 // passed by value: lives in the kernarg segment 
     int   debug_skip;             // test hook: 1 = the rigid-body wave withholds the frame hand-over flag, 2 = the helpers withhold the self-collision flags
     RollArgs roll;                // k_step<..., ROLL> only
 };
+
+// commands.curriculum: the lin_vel_x range every command draw reads (device buffer), or null = the by-value P.cmd_lin_vel_x
+LG_DEV const double *cmd_x_range(const KArgs &A) { return A.P.cmd_curriculum ? A.B.cmd_range : nullptr; }
+LG_DEV void cmd_x_range_f32(const KArgs &A, float *out) {
+    const double *xr = cmd_x_range(A);
+    out[0] = xr ? (float)xr[0] : A.P.cmd_lin_vel_x[0];
+    out[1] = xr ? (float)xr[1] : A.P.cmd_lin_vel_x[1];
+}
+// a single-step launch applies the curriculum rule itself only on the device counter (no host between its steps, lg_params.cmd_curriculum)
+LG_DEV bool curriculum_tick_step(const KArgs &A, int64_t step) {
+    return A.P.cmd_curriculum && A.step < 0 && A.P.max_episode_length > 0 && step % A.P.max_episode_length == 0;
+}
 
 // A hand-over poll that ran out must not pass silently (rc 0 with wrong physics is the worst failure this library can have): the
 // wave ORs a bit into the host-visible status word and goes on (a hung CU would be worse); every later C-ABI call on the handle
@@ -881,18 +895,23 @@ template <int L> LG_DEV void pd_torques(const lg_params &P, const float *tab, co
 }
 
 // ------------------------------------------------------------------ commands / heights / reset values
-LG_DEV void resample_commands_u(const lg_params &P, const float (&u)[4], float (&cmd)[4]) {   // :347-369, from four uniforms
-    cmd[0] = urange(P.cmd_lin_vel_x[0], P.cmd_lin_vel_x[1], u[0]);
+LG_DEV void resample_commands_x(const lg_params &P, float x0, float x1, const float (&u)[4], float (&cmd)[4]) {   // :347-369, from four uniforms
+    cmd[0] = urange(x0, x1, u[0]);
     cmd[1] = urange(P.cmd_lin_vel_y[0], P.cmd_lin_vel_y[1], u[1]);
     if (P.heading_command) cmd[3] = urange(P.cmd_heading[0], P.cmd_heading[1], u[2]);
     else cmd[2] = urange(P.cmd_ang_vel_yaw[0], P.cmd_ang_vel_yaw[1], u[2]);
     float keep = (sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]) > 0.2f) ? 1.0f : 0.0f;
     cmd[0] *= keep; cmd[1] *= keep;
 }
-LG_DEV void resample_commands(const lg_params &P, int e, int64_t step, int purpose, float (&cmd)[4]) {
+// xr: the launch's lin_vel_x range (cmd_x_range_f32: the device-held one under commands.curriculum, else P.cmd_lin_vel_x), resolved once per
+// launch -- in k_step an LDS pair, so the step loop keeps no pointer or flag of it in scalar registers
+LG_DEV void resample_commands_u(const lg_params &P, const float *xr, const float (&u)[4], float (&cmd)[4]) {
+    resample_commands_x(P, xr[0], xr[1], u, cmd);
+}
+LG_DEV void resample_commands(const lg_params &P, const float *xr, int e, int64_t step, int purpose, float (&cmd)[4]) {
     float u[4];
     rand4(P.seed, e, step, purpose, 0, u);
-    resample_commands_u(P, u, cmd);
+    resample_commands_u(P, xr, u, cmd);
 }
 LG_DEV float wrap_to_pi(float a) {                                                                       // utils/math.py:45-48
     const float two_pi = 6.2831855f, pi = 3.14159274f;
@@ -1034,7 +1053,7 @@ template <class T> struct ResetRand {
 // identically; `origin` is in/out (terrain curriculum :446-469), lane-0 writes are done by the caller.
 template <class T>
 LG_DEV void reset_values(const KArgs &A, const float *tab, int e, int k, int64_t step, float (&root)[13], float (&q)[T::L],
-                         float (&qd)[T::L], float (&cmd)[4], float (&origin)[3], int &level, bool &level_changed,
+                         float (&qd)[T::L], float (&cmd)[4], float (&origin)[3], int &level, bool &level_changed, const float *xr /* lin_vel_x range */,
                          const ResetRand<T> *rr = nullptr, int lane = 0) {
     constexpr int L = T::L;
     const lg_params &P = A.P;
@@ -1080,7 +1099,7 @@ LG_DEV void reset_values(const KArgs &A, const float *tab, int e, int k, int64_t
     root[9] = urange(-0.5f, 0.5f, v[0]); root[10] = urange(-0.5f, 0.5f, v[1]);
     root[11] = urange(-0.5f, 0.5f, v[2]); root[12] = urange(-0.5f, 0.5f, v[3]);
     uniforms(RNG_CMD_RESET, 0, ResetRand<T>::CMD, u);
-    resample_commands_u(P, u, cmd);
+    resample_commands_u(P, xr, u, cmd);
 }
 
 // ------------------------------------------------------------------ observations (legged_robot.py:212-230, :100-101)
@@ -1226,21 +1245,61 @@ LG_DEV void finish_extras(const KArgs &A, int t, int64_t step_used, bool publish
 // steps, so all their episode atomics are performed and all of them have read the step counter): extras["episode"] (legged_robot.py:179-188)
 // = the sums of the LAST step of the segment in which any env was reset (the dictionary stays stale otherwise, quirk Q4); the device step
 // counter moves to the last executed step; the per-step accumulators are left zeroed for the next segment.
-LG_DEV void roll_finish(const KArgs &A, int t, int64_t step0) {
+// With commands.curriculum a launch runs the slice [rt0, rt1) of the segment: the same for that slice, and the next launch resumes at rt1.
+LG_DEV void roll_finish(const KArgs &A, int t, int64_t step0, int rt0, int rt1) {
     const lg_params &P = A.P;
     const int R = P.num_reward_slots, stride = LG_NUM_REWARD_TERMS + 2;
     int last = -1;
-    for (int s = A.roll.steps - 1; s >= 0 && last < 0; s--)
+    for (int s = rt1 - 1; s >= rt0 && last < 0; s--)
         if (__hip_atomic_load(A.roll.extras + (size_t)s * stride + R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0.0f) last = s;
     if (last >= 0 && t < R) {
         const float v = __hip_atomic_load(A.roll.extras + (size_t)last * stride + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const float c = __hip_atomic_load(A.roll.extras + (size_t)last * stride + R, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         A.B.episode_means[t] = v / c / P.max_episode_length_s;
     }
-    if (t == 0 && A.B.step_counter) A.B.step_counter[0] = step0 + A.roll.steps - 1;
+    if (t == 0 && A.B.step_counter) A.B.step_counter[0] = step0 + rt1 - 1;
+    if (t == 0 && A.roll.cursor) A.roll.cursor[0] = rt1;
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
-    for (int i = t; i < A.roll.steps * stride; i += 64) __hip_atomic_store(A.roll.extras + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int i = rt0 * stride + t; i < rt1 * stride; i += 64) __hip_atomic_store(A.roll.extras + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ------------------------------------------------------------------ commands.curriculum on the device (lg_params.cmd_curriculum)
+// reset_idx :159-176 for the resets of a tick step: update_command_curriculum (:471-483) BEFORE _resample_commands.  The fused step has
+// already reset those envs and drawn their commands from the old range; when the rule widens it, they re-draw from the new one -- the same
+// Philox block (seed; env, step, CMD_RESET) as the in-step draw, only the range differs -- and the command slots of their observations
+// (noise scale 0, :500) follow.  This is lg_resample_reset_commands' draw (k_resample_reset) for one env.
+LG_DEV void redraw_reset_command(const KArgs &A, float x0, float x1, int e, int64_t step, float *obs_row) {
+    const lg_params &P = A.P; const lg_buffers &B = A.B;
+    float u[4], cmd[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) cmd[i] = B.commands[(size_t)e * 4 + i];
+    rand4(P.seed, e, step, RNG_CMD_RESET, 0, u);
+    resample_commands_x(P, x0, x1, u, cmd);
+#pragma unroll
+    for (int i = 0; i < 4; i++) B.commands[(size_t)e * 4 + i] = cmd[i];
+    const float c = P.clip_observations;
+    obs_row[9] = fminf(fmaxf(cmd[0] * P.obs_scale_lin_vel, -c), c); obs_row[10] = fminf(fmaxf(cmd[1] * P.obs_scale_lin_vel, -c), c);
+    obs_row[11] = fminf(fmaxf(cmd[2] * P.obs_scale_ang_vel, -c), c);
+}
+// The rule, run by EVERY thread of the finisher workgroup of a tick step (uniform branches, a barrier) once the step's extras["episode"] are
+// published and behind an agent-scope acquire: `cnt` = the number of envs the step reset (no reset: no tick, as the host rule), the mean is
+// the f32 episode_means entry the host rule reads, compared in the host rule's double arithmetic.  `resets` / `obs` are the step's reset
+// flags and observation rows: other workgroups wrote them, and released them before their tickets.
+LG_DEV void curriculum_apply(const KArgs &A, int t, int nt, int64_t step, float cnt, const uint8_t *resets, float *obs) {
+    const lg_params &P = A.P;
+    if (!(cnt > 0.0f) || P.cmd_curriculum_slot < 0) return;
+    double *xr = A.B.cmd_range;
+    const double mean_sum = (double)A.B.episode_means[P.cmd_curriculum_slot] * P.cmd_episode_length_s;
+    const double lo0 = xr[0], hi0 = xr[1];
+    if (!(mean_sum / P.cmd_max_episode_length > 0.8 * P.cmd_tracking_scale_dt)) return;
+    const double lo = fmin(fmax(lo0 - 0.5, -P.cmd_max_curriculum), 0.0), hi = fmin(fmax(hi0 + 0.5, 0.0), P.cmd_max_curriculum);
+    if (lo == lo0 && hi == hi0) return;                                    // unchanged range: the draws stand (host: new == old)
+    __syncthreads();                                                       // every thread has read the old range
+    if (t == 0) { xr[0] = lo; xr[1] = hi; }
+    const float x0 = (float)lo, x1 = (float)hi;
+    for (int e = t; e < P.num_envs; e += nt)
+        if (resets[e]) redraw_reset_command(A, x0, x1, e, step, obs + (size_t)e * P.num_obs);
 }
 
 // ------------------------------------------------------------------ THE fused policy-step kernel
@@ -1314,7 +1373,8 @@ template <class T, bool NET, bool HF, int NW, bool SC = false> struct HelperWave
     static LG_DEV void run(const KArgs &A, int wave, int lane, int e, int k, int d0, bool live, int64_t step, const float *tab,
                            float2 (*lds_x)[LG_BLOCK], float (*lds_tau)[LG_BLOCK], StepSharedT<OFF, T::L> &sh, SelfLds<T> *sc = nullptr,
                            const float *lds_tab = nullptr, ResetRand<T> *reset_rand = nullptr, int *s_last = nullptr, float4 (*hnoise)[LG_BLOCK] = nullptr,
-                           int sub0 = 0 /* sub-steps before this policy step in the launch (rollout kernel) */, float *roll_accum = nullptr /* rollout kernel: this step's episode accumulators */) {
+                           int sub0 = 0 /* sub-steps before this policy step in the launch (rollout kernel) */, float *roll_accum = nullptr /* rollout kernel: this step's episode accumulators */,
+                           bool tick_step = false /* curriculum_tick_step(A, step), decided by the caller (no 64-bit modulo in the rollout kernel's loop) */) {
         const lg_buffers &B = A.B;
         const lg_params &P = A.P;
         const int j = wave - 1;
@@ -1432,7 +1492,8 @@ template <class T, bool NET, bool HF, int NW, bool SC = false> struct HelperWave
             // atomics just issued by this wave (and terrain levels, drained by the rigid-body wave before P3), so the ticket only
             // has to follow their completion -- both round trips (drain, ticket) overlap the rigid-body wave's observations and
             // state write-back instead of standing at the end of the kernel.
-            if (A.defer) {
+            if (tick_step) { /* commands.curriculum tick: the ticket is taken behind the state write-back (k_step) */ }
+            else if (A.defer) {
                 // deferred extras: the ticket's only job left is the device step counter -- whoever takes the LAST one knows that every workgroup
                 // has read the counter and may advance it.  Nothing to drain first, and no finisher behind it.  (Taken here and not in the
                 // prologue: an atomic with a return value in front of this wave's first loads delayed the first torques of every workgroup.)
@@ -1495,6 +1556,18 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     __shared__ float4 pol_xa[POL ? 4 : 1][64], pol_xb[POL ? 8 : 1][64], pol_xy[1][64];
     __shared__ float lds_act[POL ? 16 : 1][16];                 // sampled actions [action][env in block]
     __shared__ float lds_obs[ROLL ? 16 : 1][48];                // rollout kernel: the observations a step leaves for the next step's actor
+    __shared__ float s_tick_cnt;                                // commands.curriculum tick: the finisher's count of the step's resets
+    __shared__ float s_xr[2];                                   // the launch's lin_vel_x range (cmd_x_range_f32)
+    __shared__ int s_roll[2];                                   // ROLL: this launch's slice [begin, end) of the segment
+    // ROLL with commands.curriculum: this launch runs the slice [roll_begin, roll_end) of the segment, from the step the previous launch left
+    // in roll.cursor to the next tick (see lg_rollout_policy); a launch left over after the last slice exits here.  (kernel-uniform)
+    // The bounds and the range are handed to the steps in LDS: values held in scalar registers across the step loop cost the rollout
+    // kernel spilled scalars in every step.
+    int roll_begin = 0;
+    if (ROLL && A.P.cmd_curriculum && A.roll.sub > 0) {
+        roll_begin = A.roll.cursor[0];
+        if (roll_begin >= A.roll.steps) return;
+    }
     LG_PROF_BEGIN();
     if (threadIdx.x == 0) sh.fk_ready = 0;                      // published before the first use by stage_limb_table's barrier
     if constexpr (SC) {
@@ -1512,7 +1585,18 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     if (!live) e = N - 1;
     const float *tab = lds_tab + k * Tab<T>::STRIDE;
     const int d0 = e * ND + k * L;                                // first dof of this lane
-    const int64_t step0 = A.step >= 0 ? A.step : B.step_counter[0] + 1;   // -1: self-advancing (HIP-graph replay)
+    const int64_t step0 = A.step >= 0 ? A.step : B.step_counter[0] + 1 - roll_begin;   // -1: self-advancing (HIP-graph replay)
+    if (threadIdx.x == 0) {                                       // published by the first barrier of the step (policy_forward / HeightCrew)
+        cmd_x_range_f32(A, s_xr);
+        if (ROLL) {
+            int roll_end = A.roll.steps;                          // the slice ends behind the next curriculum tick (or with the segment)
+            if (P.cmd_curriculum) {
+                const int64_t M = P.max_episode_length, first = step0 + roll_begin;
+                roll_end = min(roll_end, roll_begin + (int)((M - first % M) % M) + 1);
+            }
+            s_roll[0] = roll_begin; s_roll[1] = roll_end;
+        }
+    }
     // ROLL: `roll.steps` policy steps in this launch.  Every step is the single-step kernel's body on the same state buffers; the
     // workgroup's own stores are ordered before the next step's loads by the barrier that ends the step (workgroup-scope release /
     // acquire; all of an env's data stays inside its workgroup), per-step outputs go to the [t] slice of the rollout storage.
@@ -1548,12 +1632,13 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
             }
             pa.actions = A.roll.actions + (size_t)rt * N * ND;
             pa.mean = A.roll.mean ? A.roll.mean + (size_t)rt * N * ND : nullptr;
-            policy_forward<3, 8, 4, 2>(pa, pol_xa, pol_xb, pol_xy, blockIdx.x, wave, lane, step, lds_act, rt > 0 ? lds_obs : nullptr);
+            policy_forward<3, 8, 4, 2>(pa, pol_xa, pol_xb, pol_xy, blockIdx.x, wave, lane, step, lds_act, rt > s_roll[0] ? lds_obs : nullptr);
         } else policy_forward<3, 8, 4, 2>(A.pol, pol_xa, pol_xb, pol_xy, blockIdx.x, wave, lane, step, lds_act);
         __syncthreads();
     }
     if (wave > 0) {
-        HelperWave<T, NET, HF, NW, SC>::run(A, wave, lane, e, k, d0, live, step, tab, lds_x, lds_tau, sh, sc_store.get(), lds_tab, &reset_rand, &s_last, hnoise, sub0, roll_accum);
+        HelperWave<T, NET, HF, NW, SC>::run(A, wave, lane, e, k, d0, live, step, tab, lds_x, lds_tau, sh, sc_store.get(), lds_tab, &reset_rand, &s_last, hnoise, sub0, roll_accum,
+                                            !ROLL && curriculum_tick_step(A, step));
     } else {
     // ---- load persistent state (read once per env-step)
     float root[13], q[L], qd[L], act[L], tau[L];
@@ -1645,8 +1730,8 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     __syncthreads();                                               // P1 (also publishes the helpers' uniforms)
     // _post_physics_step_callback :329-345
     if (ep_len % P.resample_interval == 0) {
-        if (NW > 1) { float u[4]; reset_rand.get(ResetRand<T>::CMD_STEP, lane, u); resample_commands_u(P, u, cmd); }
-        else resample_commands(P, e, step, RNG_CMD_STEP, cmd);
+        if (NW > 1) { float u[4]; reset_rand.get(ResetRand<T>::CMD_STEP, lane, u); resample_commands_u(P, s_xr, u, cmd); }
+        else resample_commands(P, s_xr, e, step, RNG_CMD_STEP, cmd);
     }
     if (P.heading_command) {
         V3 fwd = quat_apply(root + 3, v3(1, 0, 0));
@@ -1780,7 +1865,7 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     if (!EARLY_POST) { origin[0] = B.env_origins[(size_t)e * 3]; origin[1] = B.env_origins[(size_t)e * 3 + 1]; origin[2] = B.env_origins[(size_t)e * 3 + 2]; }
     if (reset) {
         int level = 0; bool level_changed = false;
-        reset_values<T>(A, tab, e, k, step, root, q, qd, cmd, origin, level, level_changed, NW > 1 ? &reset_rand : nullptr, lane);
+        reset_values<T>(A, tab, e, k, step, root, q, qd, cmd, origin, level, level_changed, s_xr, NW > 1 ? &reset_rand : nullptr, lane);
         if (writer && level_changed) {
             __hip_atomic_store(B.terrain_levels + e, level, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read by the finisher
             B.env_origins[(size_t)e * 3] = origin[0]; B.env_origins[(size_t)e * 3 + 1] = origin[1]; B.env_origins[(size_t)e * 3 + 2] = origin[2];
@@ -1852,8 +1937,9 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
 #ifdef LG_PROFILE
         if (threadIdx.x == 0 && A.prof && blockIdx.x < LG_NPROF_BLOCKS) A.prof[LG_NPROF + LG_NPROF_BLOCKS * 40 + blockIdx.x] = wall_clock64();
 #endif
+        __syncthreads();                                           // s_roll / s_xr published
 #pragma unroll 1
-        for (int rt = 0; rt < A.roll.steps; rt++) {
+        for (int rt = s_roll[0]; rt < s_roll[1]; rt++) {
             one_step(rt);
             // Step boundary inside the launch.  What the next step reads of this step's GLOBAL stores it reads in the wave that stored it
             // (state, actuator rows, episode sums: same wave instruction stream, in order) -- the one cross-wave item, the observations the
@@ -1866,20 +1952,62 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
 #endif
         }
         // the segment's finisher: the workgroup that takes the last ticket (behind its waves' drained memory operations)
+        const int roll_end = s_roll[1];
+        const bool tick = P.cmd_curriculum && (step0 + roll_end - 1) % P.max_episode_length == 0;   // the slice ends in a curriculum tick
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (tick) __threadfence();                                 // the tick's finisher reads and rewrites this workgroup's rows: agent-scope release
         __syncthreads();
         if (threadIdx.x == 0) {
             const unsigned int ticket = atomicAdd(A.done_counter, 1u);
             s_last = (ticket == gridDim.x - 1);
             if (s_last) __hip_atomic_store(A.done_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (s_last && tick) s_tick_cnt = __hip_atomic_load(A.roll.extras + (size_t)(roll_end - 1) * (LG_NUM_REWARD_TERMS + 2) + P.num_reward_slots,
+                                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         __syncthreads();
-        if (s_last && threadIdx.x < LG_BLOCK) roll_finish(A, threadIdx.x, step0);
+        if (s_last) {
+            if (threadIdx.x < LG_BLOCK) roll_finish(A, threadIdx.x, step0, s_roll[0], roll_end);
+            if (tick) {                                            // the tick step's rule, from its accumulators (roll.extras[roll_end - 1])
+                __threadfence();                                   // agent-scope acquire (+ episode_means published by roll_finish)
+                __syncthreads();
+                curriculum_apply(A, threadIdx.x, blockDim.x, step0 + roll_end - 1, s_tick_cnt, A.roll.done + (size_t)(roll_end - 1) * N,
+                                 A.roll.obs + (size_t)roll_end * N * P.num_obs);
+            }
+        }
         LG_PROF_END(PF_EXTRAS, A.prof);
         return;
     } else one_step(0);
     const int64_t step = step0;
     LG_PROF(PF_POST);
+    if (curriculum_tick_step(A, step)) {                           // (kernel-uniform)
+        // commands.curriculum tick: the finisher re-draws the commands and observation rows of OTHER workgroups' reset envs, so the ticket is
+        // taken behind every wave's state write-back, released at agent scope (HelperWave leaves it to here).  A launch that defers its extras
+        // takes this in-launch finisher too: the previous step's slot first, then this step's.
+        __threadfence();
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned int ticket = atomicAdd(A.done_counter, 1u);
+            s_last = (ticket == gridDim.x - 1);
+            if (s_last) {
+                __hip_atomic_store(A.done_counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                s_tick_cnt = __hip_atomic_load(accum_slot(A, step) + P.num_reward_slots, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __syncthreads();
+        if (s_last) {
+            __threadfence();                                       // agent-scope acquire
+            if (A.defer) {
+                finish_extras(A, threadIdx.x, step, false, accum_slot(A, step - 1), NW > 1 ? level_parts_slot(A, step - 1, gridDim.x) : nullptr, gridDim.x);
+                __syncthreads();                                   // its LDS level partials are read before the next call rewrites them
+            }
+            finish_extras(A, threadIdx.x, step, true, accum_slot(A, step), NW > 1 ? level_parts_slot(A, step, gridDim.x) : nullptr, gridDim.x);
+            __threadfence();                                       // episode_means published for every thread
+            __syncthreads();
+            curriculum_apply(A, threadIdx.x, blockDim.x, step, s_tick_cnt, B.reset_buf, B.obs_buf);
+        }
+        LG_PROF_END(PF_EXTRAS, A.prof);
+        return;
+    }
     if (NW == 1 && !A.defer) {                                     // no helper wave: ticket at the end, behind this wave's own memory operations
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (threadIdx.x == 0) {
@@ -1926,7 +2054,9 @@ __global__ void __launch_bounds__(LG_BLOCK) k_reset(const KArgs A) {
 #pragma unroll
     for (int i = 0; i < 3; i++) origin[i] = B.env_origins[(size_t)e * 3 + i];
     int level = 0; bool level_changed = false;
-    reset_values<T>(A, tab, e, k, A.step, root, q, qd, cmd, origin, level, level_changed);
+    float xr[2];
+    cmd_x_range_f32(A, xr);
+    reset_values<T>(A, tab, e, k, A.step, root, q, qd, cmd, origin, level, level_changed, xr);
 #pragma unroll
     for (int j = 0; j < L; j++) {
         reinterpret_cast<float2 *>(B.dof_state)[d0 + j] = make_float2(q[j], qd[j]);
@@ -2087,17 +2217,8 @@ __global__ void __launch_bounds__(256) k_resample_reset(const KArgs A) {
     const lg_params &P = A.P; const lg_buffers &B = A.B;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= P.num_envs || !B.reset_buf[e]) return;
-    float u[4], cmd[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) cmd[i] = B.commands[(size_t)e * 4 + i];
-    rand4(P.seed, e, A.step, RNG_CMD_RESET, 0, u);
-    resample_commands_u(P, u, cmd);
-#pragma unroll
-    for (int i = 0; i < 4; i++) B.commands[(size_t)e * 4 + i] = cmd[i];
-    float *obs = B.obs_buf + (size_t)e * P.num_obs;
-    const float c = P.clip_observations;
-    obs[9] = fminf(fmaxf(cmd[0] * P.obs_scale_lin_vel, -c), c); obs[10] = fminf(fmaxf(cmd[1] * P.obs_scale_lin_vel, -c), c);
-    obs[11] = fminf(fmaxf(cmd[2] * P.obs_scale_ang_vel, -c), c);
+    const double *xr = cmd_x_range(A);
+    redraw_reset_command(A, xr ? (float)xr[0] : P.cmd_lin_vel_x[0], xr ? (float)xr[1] : P.cmd_lin_vel_x[1], e, A.step, B.obs_buf + (size_t)e * P.num_obs);
 }
 
 // ====================================================================  host side: C-ABI  ====================================================================
@@ -3082,6 +3203,8 @@ int lg_create(const lg_params *params, const lg_robot_model *model, const float 
     if (params->control_type == LG_CTRL_ACTUATOR_NET && kind != ROBOT_ANYMAL) return fail(-2, "actuator net is compiled for the ANYmal layout only");
     if (params->self_collision && kind != ROBOT_ANYMAL) return fail(-4, "self-collision (asset.self_collisions = 0) is compiled for the quadruped layouts only");
     if (params->self_collision && !check_capsules<AnymalTraits>(model)) return fail(-4, "collision points do not form the compiled-in capsule layout (self-collision)");
+    if (params->cmd_curriculum && (params->max_episode_length < 1 || params->cmd_curriculum_slot >= params->num_reward_slots))
+        return fail(-2, "commands.curriculum needs max_episode_length >= 1 and the tracking reward's slot (or -1)");
     HIP_TRY(hipSetDevice(device_id));
     lg_sim *s = new (std::nothrow) lg_sim();
     if (!s) return fail(-5, "out of host memory");
@@ -3138,6 +3261,7 @@ int lg_bind(lg_sim *s, const lg_buffers *b) {
     if (s->P.terrain_type == LG_TERRAIN_HEIGHTFIELD && (s->P.hf_rows < 2 || s->P.hf_cols < 2 || (int64_t)s->P.hf_rows * s->P.hf_cols > 0x7fffffff))
         return fail(-6, "height field must have 2 <= rows, cols and rows*cols < 2^31");
     if (s->P.terrain_curriculum && (!b->terrain_levels || !b->terrain_types || !b->terrain_origins)) return fail(-6, "terrain curriculum buffers missing");
+    if (s->P.cmd_curriculum && !b->cmd_range) return fail(-6, "commands.curriculum needs the cmd_range buffer");
     s->B = *b; s->bound = true;
     return 0;
 }
@@ -3151,6 +3275,8 @@ int lg_set_obs_buffer(lg_sim *s, float *obs_buf) {
 int lg_set_params(lg_sim *s, const lg_params *p) {
     if (!s || !p) return fail(-1, "null argument");
     if (p->num_envs != s->P.num_envs || p->control_type != s->P.control_type) return fail(-7, "num_envs / control_type cannot change after create");
+    if (p->cmd_curriculum && (p->max_episode_length < 1 || p->cmd_curriculum_slot >= p->num_reward_slots || (s->bound && !s->B.cmd_range)))
+        return fail(-2, "commands.curriculum needs max_episode_length >= 1, the tracking reward's slot (or -1) and the cmd_range buffer");
     s->P = *p;
     return upload_tables(s);
 }
@@ -3230,19 +3356,27 @@ int lg_rollout_policy(lg_sim *s, lg_policy *p, const lg_rollout_buffers *r, uint
         (void)hipStreamIsCapturing(st, &cap);
         if (cap != hipStreamCaptureStatusNone) return fail(-9, "first lg_rollout_policy call on a handle allocates its workspace: make one call outside stream capture");
         HIP_TRY(hipSetDevice(s->device));
-        if (hipMalloc(&s->d_roll_extras, sizeof(float) * LG_MAX_ROLL_STEPS * stride) != hipSuccess) return fail(-10, "hipMalloc failed");
-        HIP_TRY(hipMemset(s->d_roll_extras, 0, sizeof(float) * LG_MAX_ROLL_STEPS * stride));      // roll_finish leaves it zeroed after every segment
+        // + one int behind the accumulators: the resume step of the next sub-launch (commands.curriculum, roll_finish writes it)
+        if (hipMalloc(&s->d_roll_extras, sizeof(float) * (LG_MAX_ROLL_STEPS * stride + 1)) != hipSuccess) return fail(-10, "hipMalloc failed");
+        HIP_TRY(hipMemset(s->d_roll_extras, 0, sizeof(float) * (LG_MAX_ROLL_STEPS * stride + 1)));      // roll_finish leaves it zeroed after every segment
     }
     KArgs a; fill_args(s, a, common_step_counter); a.actions_in = nullptr; a.defer = 0;
     fill_policy_args(p, a.pol, r->obs, r->actions, r->mean, s->P.num_envs, seed, common_step_counter, s->B.step_counter, deterministic);
     a.roll.steps = r->steps; a.roll.obs = r->obs; a.roll.actions = r->actions; a.roll.mean = r->mean; a.roll.rew = r->rew;
     a.roll.done = r->dones; a.roll.time_outs = r->time_outs; a.roll.extras = s->d_roll_extras;
     a.roll.obs0 = r->obs0;
-    if (s->P.self_collision)
-        hipLaunchKernelGGL((k_step<AnymalTraits, true, false, true, 4, true, true>), dim3(grid_for<AnymalTraits>(s->P.num_envs)), dim3(LG_STEP_WAVES * LG_BLOCK), 0, st, a);
-    else
-        hipLaunchKernelGGL((k_step<AnymalTraits, true, false, true, 4, false, true>), dim3(grid_for<AnymalTraits>(s->P.num_envs)), dim3(LG_STEP_WAVES * LG_BLOCK), 0, st, a);
-    HIP_TRY(hipGetLastError());
+    a.roll.cursor = reinterpret_cast<int *>(s->d_roll_extras + LG_MAX_ROLL_STEPS * stride);
+    // commands.curriculum: the workgroups never meet between steps, so no launch may run past a curriculum tick -- a FIXED number of
+    // launches of the same kernel (a captured graph holds them all), each resuming where the previous one stopped; left-over ones exit at once
+    const int launches = s->P.cmd_curriculum ? 1 + (r->steps + s->P.max_episode_length - 1) / s->P.max_episode_length : 1;
+    for (int i = 0; i < launches; i++) {
+        a.roll.sub = i;
+        if (s->P.self_collision)
+            hipLaunchKernelGGL((k_step<AnymalTraits, true, false, true, 4, true, true>), dim3(grid_for<AnymalTraits>(s->P.num_envs)), dim3(LG_STEP_WAVES * LG_BLOCK), 0, st, a);
+        else
+            hipLaunchKernelGGL((k_step<AnymalTraits, true, false, true, 4, false, true>), dim3(grid_for<AnymalTraits>(s->P.num_envs)), dim3(LG_STEP_WAVES * LG_BLOCK), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 

@@ -17,7 +17,7 @@ import torch
 from . import capi
 from .utils import packing
 
-_TORCH_DTYPES = {"float32": torch.float32, "bool": torch.bool, "int64": torch.int64, "int32": torch.int32,
+_TORCH_DTYPES = {"float32": torch.float32, "float64": torch.float64, "bool": torch.bool, "int64": torch.int64, "int32": torch.int32,
                  "int16": torch.int16}
 
 
@@ -36,6 +36,7 @@ class DeviceSim:
         for name, (shape, dt) in packing.buffer_spec(params, robot).items():
             self.buf[name] = torch.zeros(shape, dtype=_TORCH_DTYPES[dt], device=device)
         self.buf["friction_coeffs"].fill_(1.0)
+        self.buf["cmd_range"].copy_(torch.tensor(list(params.cmd_lin_vel_x), dtype=torch.float64))   # read instead of cmd_lin_vel_x under commands.curriculum
         if height_samples is not None:
             self.set_terrain(height_samples, terrain_origins)
         elif params.terrain_type != capi.TERRAIN_HEIGHTFIELD:

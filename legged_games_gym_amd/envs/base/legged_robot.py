@@ -79,8 +79,6 @@ class LeggedRobot(BaseTask):
         """Rollout step with the actor fused in: ``actions = fused_actor(obs_buf)`` and ``step(actions)`` as ONE launch
         (``lg_step_policy``).  Returns ``(actions, mean), (obs, privileged_obs, rew, dones, extras)``.  Only for the
         compiled fused shape (flat ANYmal actor on the plane); raises RuntimeError otherwise -- use ``step``."""
-        if self.cfg.commands.curriculum and self._capturing:
-            raise NotImplementedError("commands.curriculum needs eager steps (host-side rule between steps)")
         self.common_step_counter += 1
         prev_obs = self.obs_buf
         self._obs_flip ^= 1
@@ -105,14 +103,15 @@ class LeggedRobot(BaseTask):
         """reset_idx :159-168 for resets that happen INSIDE the fused step: every ``max_episode_length`` policy steps, if envs
         were reset by this step, apply ``update_command_curriculum`` to them (host rule, one device read per 1000 steps).
         The kernel has already zeroed the episode sums of those envs; their mean is what it published in ``episode_means``
-        (= mean over the reset envs / max_episode_length_s, :179-183)."""
+        (= mean over the reset envs / max_episode_length_s, :179-183).  Captured steps run on the device counter: there the
+        finisher of the tick step applies the same rule on the device (lg_params.cmd_curriculum), nothing is left to do here."""
         if self._capturing:
-            raise NotImplementedError("commands.curriculum is a host-side rule evaluated between steps: it cannot be captured into a "
-                                      "multi-step HIP graph (use eager steps; the bundled runner falls back by itself)")
+            return
         if self.common_step_counter % self.max_episode_length != 0 or "tracking_lin_vel" not in self.episode_sums:
             return
         if not bool(self.reset_buf.any()):
             return
+        self.sync_command_ranges()                      # a graphed / rolled step may have widened the range on the device
         i = self.reward_names_all.index("tracking_lin_vel")
         mean_sum = float(self._episode_means[i]) * self.max_episode_length_s
         new = command_curriculum_update(mean_sum, self.max_episode_length, self.reward_scales["tracking_lin_vel"],
@@ -126,8 +125,7 @@ class LeggedRobot(BaseTask):
 
     def begin_graph_capture(self):
         """Prepare for capturing several step() calls into one HIP graph: the step counter moves to the device."""
-        if self.cfg.commands.curriculum:
-            raise NotImplementedError("commands.curriculum needs eager steps (host-side rule between steps)")
+        self._expose_device_command_range()
         self._sim.buf["step_counter"].fill_(self.common_step_counter)
         self._capturing = True
         self._sim.set_deferred_extras(_DEFER_EXTRAS)      # captured steps leave extras["episode"] to the next launch ...
@@ -147,8 +145,7 @@ class LeggedRobot(BaseTask):
         zero-argument callable that replays it (launch-bound inner loop -> one hipGraphLaunch).
         The step counter lives on the device while replaying (``lg_step(..., -1)``), the host copy is
         advanced alongside.  ``policy_act`` must be capturable (no host syncs) and read ``self.obs_buf``."""
-        if self.cfg.commands.curriculum:
-            raise NotImplementedError("commands.curriculum needs eager steps (host-side rule between steps)")
+        self._expose_device_command_range()
         sim = self._sim
         sim.set_obs_output(self.obs_buf)                  # single fixed buffer while replaying (the policy reads it inside the graph)
         sim.buf["step_counter"].fill_(self.common_step_counter)
@@ -180,8 +177,7 @@ class LeggedRobot(BaseTask):
     def make_graphed_policy_step(self, fused_actor, warmup=3, steps_per_replay=1):
         """Like ``make_graphed_step`` with the actor fused into the step kernel: the graph is ONE ``lg_step_policy`` launch
         (obs_buf -> actions -> next obs_buf, in place).  Raises RuntimeError when the sim / actor pair has no fused kernel."""
-        if self.cfg.commands.curriculum:
-            raise NotImplementedError("commands.curriculum needs eager steps (host-side rule between steps)")
+        self._expose_device_command_range()
         sim = self._sim
         sim.set_obs_output(self.obs_buf)
         sim.buf["step_counter"].fill_(self.common_step_counter)
@@ -216,9 +212,8 @@ class LeggedRobot(BaseTask):
         steps of its own envs without meeting the others at each step boundary.  Returns the rollout storage: ``obs`` [T+1, N, num_obs]
         (``obs[0]`` = the observations before the first step), ``actions`` / ``mean`` [T, N, num_actions], ``rew`` [T, N], bool ``dones`` /
         ``time_outs`` [T, N].  ``self.obs_buf`` becomes ``obs[T]``; ``rew_buf`` / ``reset_buf`` / ``time_out_buf`` hold the last step's
-        values as after ``step()``.  Raises RuntimeError when the sim / actor pair is not the compiled fused shape."""
-        if self.cfg.commands.curriculum:
-            raise NotImplementedError("commands.curriculum is a host-side rule evaluated between steps: use step()")
+        values as after ``step()``.  Raises RuntimeError when the sim / actor pair is not the compiled fused shape.
+        With ``commands.curriculum`` the kernel applies the rule at every tick inside the segment (lg_rollout_policy)."""
         N, T = self.num_envs, int(steps)
         if storage is None:
             dev, f32 = self.device, torch.float32
@@ -231,6 +226,7 @@ class LeggedRobot(BaseTask):
         if obs0 is not None and not (obs0.is_contiguous() and obs0.dtype == torch.float32):
             storage["obs"][0].copy_(obs0); obs0 = None
         self._sim.rollout_policy(fused_actor, storage, -1 if self._capturing else self.common_step_counter + 1, deterministic, obs0=obs0)
+        self._expose_device_command_range()
         self.common_step_counter += T
         with torch.inference_mode(False):
             self.obs_buf = storage["obs"][T]
@@ -238,9 +234,8 @@ class LeggedRobot(BaseTask):
 
     def make_graphed_rollout(self, fused_actor, steps, warmup=1):
         """``rollout_policy(fused_actor, steps)`` on a fixed storage captured into one HIP graph (ONE kernel node: the multi-step kernel starts from
-        the previous replay's ``obs[steps]``, copies it to ``obs[0]``, and its last workgroup publishes ``extras["episode"]``): returns ``(replay, storage)``."""
-        if self.cfg.commands.curriculum:
-            raise NotImplementedError("commands.curriculum needs eager steps (host-side rule between steps)")
+        the previous replay's ``obs[steps]``, copies it to ``obs[0]``, and its last workgroup publishes ``extras["episode"]``): returns ``(replay, storage)``.
+        With ``commands.curriculum`` the graph holds the fixed 1 + ceil(steps / max_episode_length) launches of lg_rollout_policy."""
         sim = self._sim
         storage = None
         side = torch.cuda.Stream(device=self.device)
@@ -268,6 +263,7 @@ class LeggedRobot(BaseTask):
         if len(env_ids) == 0:
             return
         if self.cfg.commands.curriculum and (self.common_step_counter % self.max_episode_length == 0):
+            self.sync_command_ranges()
             self.update_command_curriculum(env_ids)
         if not self.init_done and self._params.terrain_curriculum:
             # "don't change on initial reset" (:453-455)
@@ -348,6 +344,7 @@ class LeggedRobot(BaseTask):
         to = self.terrain.env_origins if self.terrain is not None else None
         self._sim = DeviceSim(self._params, self._model, rm, torch.device(self.device), weights, hs, to)
         b = self._sim.buf
+        b["cmd_range"].copy_(torch.tensor([float(v) for v in self.command_ranges["lin_vel_x"]], dtype=torch.float64))   # the host rule's doubles
 
         # body index lookups by substring (:696-702, :733-750)
         def idx(names):
@@ -534,12 +531,32 @@ class LeggedRobot(BaseTask):
             self.set_command_ranges()
 
     def set_command_ranges(self):
-        """Re-upload ``self.command_ranges`` (tooling such as play.py edits them)."""
+        """Re-upload ``self.command_ranges`` (tooling such as play.py edits them).  Under ``commands.curriculum`` the kernels read the
+        lin_vel_x range from the device buffer ``cmd_range``: it is written too."""
         capi._fill(self._params.cmd_lin_vel_x, self.command_ranges["lin_vel_x"])
         capi._fill(self._params.cmd_lin_vel_y, self.command_ranges["lin_vel_y"])
         capi._fill(self._params.cmd_ang_vel_yaw, self.command_ranges["ang_vel_yaw"])
         capi._fill(self._params.cmd_heading, self.command_ranges["heading"])
         self._sim.sim.set_params(self._params)
+        if self.cfg.commands.curriculum:
+            self._sim.buf["cmd_range"].copy_(torch.tensor([float(v) for v in self.command_ranges["lin_vel_x"]], dtype=torch.float64))
+
+    def sync_command_ranges(self):
+        """Refresh the host ``command_ranges["lin_vel_x"]`` from the device (one read): graphed steps and rolled rollouts apply
+        ``commands.curriculum`` on the device, eager ticks call this before the host rule, so the two can be mixed freely.
+        The device range holds the host rule's doubles, so a host-side range reads back unchanged."""
+        if not self.cfg.commands.curriculum:
+            return
+        lo, hi = self._sim.buf["cmd_range"].tolist()
+        r = self.command_ranges["lin_vel_x"]
+        if [lo, hi] != [float(r[0]), float(r[1])]:
+            r[0], r[1] = lo, hi
+            capi._fill(self._params.cmd_lin_vel_x, r)           # (host copy only: under the curriculum the kernels read cmd_range)
+
+    def _expose_device_command_range(self):
+        """Fast paths (graphs, rolled rollouts) tick on the device: extras["episode"]["max_command_x"] becomes a 0-dim view of the device range."""
+        if self.cfg.commands.curriculum:
+            self.extras.setdefault("episode", {})["max_command_x"] = self._sim.buf["cmd_range"][1]
 
     def set_fixed_commands(self, vx, vy, yaw):
         """Benchmark helper (BASELINE.json: "fixed command"): pin the command and disable resampling."""

@@ -109,19 +109,21 @@ class OnPolicyRunner:
         st, T = alg.storage, self.num_steps_per_env
         N, A, dev = env.num_envs, st.actions.shape[-1], self.device
         roll = getattr(self, "_roll", None)
-        if roll is None or roll["obs"].shape[0] != T + 1 or st.observations.data_ptr() != roll["obs"].data_ptr():
+        fresh = roll is None or roll["obs"].shape[0] != T + 1 or st.observations.data_ptr() != roll["obs"].data_ptr()
+        if fresh:
             with torch.inference_mode(False):         # (rollouts run under inference_mode; env.obs_buf becomes a view of this buffer and callers feed it to autograd modules)
                 obs_all = torch.empty(T + 1, N, st.observations.shape[-1], device=dev)     # [T + 1]: the kernel leaves the next observations behind the stored ones
-                st.observations = obs_all[:T]                                                # (the learner kernels read the storage through this view)
                 roll = {"obs": obs_all, "actions": st.actions, "mean": st.mu, "rew": st.rewards.view(T, N), "dones": st.dones.view(T, N),
                         "time_outs": torch.zeros(T, N, dtype=torch.uint8, device=dev)}
-            self._roll = roll
         try:
             env.rollout_policy(fused, T, storage=roll)
         except RuntimeError as exc:
             if "multi-step rollout kernel" not in str(exc):
                 raise
-            return None
+            return None                               # (the storage is untouched: the per-step rollout goes on with it)
+        if fresh:                                     # the storage's observations become a view of the kernel's buffer only once it has run
+            st.observations = roll["obs"][:T]         # (the learner kernels read the storage through this view)
+            self._roll = roll
         post = capi.lg_rollout_post()
         p = lambda x: x.data_ptr()
         post.actions, post.mean, post.rewards, post.dones, post.time_outs = p(st.actions), p(st.mu), p(st.rewards), p(st.dones), p(roll["time_outs"])

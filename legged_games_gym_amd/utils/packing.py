@@ -143,6 +143,13 @@ def build_params(cfg, model, sim_dt: float, num_envs: int, seed: int, gravity=(0
         p.reward_slot[i] = int(slot[i])
     p.num_reward_slots = len(names)
     p.only_positive_rewards = int(bool(cfg.rewards.only_positive_rewards))
+    # commands.curriculum (legged_robot.py:159-168, 471-483): the constants of the host rule, for the launches that apply it on the device
+    p.cmd_curriculum = int(bool(getattr(cfg.commands, "curriculum", False)))
+    p.cmd_curriculum_slot = int(slot[capi.REWARD_TERMS.index("tracking_lin_vel")])
+    p.cmd_max_curriculum = float(getattr(cfg.commands, "max_curriculum", 1.0))
+    p.cmd_tracking_scale_dt = float(class_to_dict(cfg.rewards.scales)["tracking_lin_vel"]) * dt if p.cmd_curriculum_slot >= 0 else 0.0   # reward_scales[...] (float64)
+    p.cmd_max_episode_length = float(np.ceil(cfg.env.episode_length_s / dt))
+    p.cmd_episode_length_s = float(cfg.env.episode_length_s)
 
     mesh = cfg.terrain.mesh_type
     if mesh in ("heightfield", "trimesh") and terrain is not None:
@@ -183,6 +190,7 @@ def buffer_spec(p, model) -> Dict[str, Tuple[Tuple[int, ...], str]]:
         "base_lin_vel": ((N, 3), "float32"), "base_ang_vel": ((N, 3), "float32"), "projected_gravity": ((N, 3), "float32"),
         "episode_sums": ((R, N), "float32"), "episode_means": ((R + 1,), "float32"), "extras_accum": ((R + 1,), "float32"), "step_counter": ((1,), "int64"),
         "env_origins": ((N, 3), "float32"), "friction_coeffs": ((N,), "float32"), "base_mass_delta": ((N,), "float32"),
+        "cmd_range": ((2,), "float64"),
     }
     if p.measure_heights:
         spec["measured_heights"] = ((N, p.num_height_points), "float32")
