@@ -316,6 +316,71 @@ EXPORTED_SYMBOLS = ["lg_create", "lg_destroy", "lg_bind", "lg_step", "lg_reset_i
                     "lg_device_status", "lg_clear_device_status", "lg_debug_handover", "lg_rollout_policy", "lg_rollout_finish", "lg_resample_reset_commands"]
 
 
+# ----------------------------------------------------------------------------- game layer (include/legged_game.h)
+LG_GAME_NUM_OBS, LG_GAME_NUM_ACTIONS = 19, 6
+
+
+class lg_game_params(C.Structure):
+    """include/legged_game.h: lg_game_params (passed by value in the kernel arguments)."""
+    _fields_ = [
+        ("num_envs", i32), ("decimation", i32), ("heading_command", i32), ("only_positive_rewards", i32),
+        ("custom_origins", i32), ("_pad0", i32), ("seed", u64),
+        ("cmd_lin_vel_x", f32 * 2), ("cmd_lin_vel_y", f32 * 2), ("predator_lin_vel_x", f32 * 2), ("predator_lin_vel_y", f32 * 2),
+        ("capture_dist", f32), ("env_radius", f32), ("half_fov", f32), ("max_rel_pos", f32),
+        ("ll_rew_weight", f32), ("scale_evasion_dt", f32), ("scale_pursuit_dt", f32), ("sim_dt", f32),
+        ("predator_z", f32), ("_pad1", f32), ("base_init_state", f32 * 13), ("_pad2", f32),
+    ]
+
+
+class lg_game_buffers(C.Structure):
+    """include/legged_game.h: lg_game_buffers (raw device pointers)."""
+    _fields_ = [
+        ("command", _PF), ("ll_root_states", _PF), ("ll_commands", _PF), ("ll_env_origins", _PF), ("ll_rew_buf", _PF),
+        ("ll_reset_buf", _PU8), ("ll_step_counter", _PI64),
+        ("predator_pos", _PF), ("obs", _PF), ("rew", _PF), ("reset_buf", _PU8), ("curr_episode_step", _PI64),
+        ("episode_length_buf", _PI64), ("episode_sums", _PF),
+    ]
+
+
+GAME_BUFFER_FIELDS = [name for name, _ in lg_game_buffers._fields_]
+GAME_SYMBOLS = ["lg_game_pre", "lg_game_post", "lg_game_sizeof"]
+
+
+def bind_game_prototypes(lib):
+    """Attach argtypes/restype for the entry points of legged_game.h and check the struct layouts."""
+    vp = C.c_void_p
+    lib.lg_game_pre.argtypes, lib.lg_game_pre.restype = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), vp], C.c_int
+    lib.lg_game_post.argtypes, lib.lg_game_post.restype = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), i64, vp], C.c_int
+    lib.lg_game_sizeof.argtypes, lib.lg_game_sizeof.restype = [C.c_int], C.c_int
+    for which, st in enumerate((lg_game_params, lg_game_buffers)):
+        if lib.lg_game_sizeof(which) != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {lib.lg_game_sizeof(which)} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def game_buffers(pointers: Dict[str, int]) -> lg_game_buffers:
+    """``lg_game_buffers`` from a name -> device address table (missing names stay null)."""
+    b = lg_game_buffers()
+    types = dict(lg_game_buffers._fields_)
+    for name in GAME_BUFFER_FIELDS:
+        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
+    return b
+
+
+def game_pre(params: lg_game_params, buffers: lg_game_buffers, stream: int = 0):
+    lib = load_library()
+    rc = lib.lg_game_pre(C.byref(params), C.byref(buffers), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_game_pre failed ({rc}): {lib.lg_last_error().decode()}")
+
+
+def game_post(params: lg_game_params, buffers: lg_game_buffers, common_step_counter: int, stream: int = 0):
+    lib = load_library()
+    rc = lib.lg_game_post(C.byref(params), C.byref(buffers), int(common_step_counter), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_game_post failed ({rc}): {lib.lg_last_error().decode()}")
+
+
 def load_library():
     """Load the HIP extension or fail loudly -- never a CPU substitute."""
     global _lib
@@ -326,7 +391,7 @@ def load_library():
         raise RuntimeError(
             f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_prototypes(C.CDLL(path), "lg_")
+    _lib = bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_"))
     if _lib.lg_abi_version() != LG_ABI_VERSION:
         raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
     return _lib

@@ -3493,3 +3493,5 @@ int lg_compute_observations_only(lg_sim *s, int64_t common_step_counter, void *s
 }
 
 }  // extern "C"
+
+#include "lg_game.h"          // predator-prey game layer: k_game_pre / k_game_post and their entry points (include/legged_game.h)

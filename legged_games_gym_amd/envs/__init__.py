@@ -1,6 +1,8 @@
-"""Task registration (reference ``legged_gym/envs/__init__.py:32-56``), in-scope tasks only.
+"""Task registration (reference ``legged_gym/envs/__init__.py:32-56``): the five locomotion tasks.
 
-The predator-prey ``a1_game`` layer (low/high-level game tasks) is out of scope.
+The predator-prey task ``high_level_game`` (``envs/a1_game``) is NOT registered by this import: the registry is a process-wide singleton
+whose locomotion surface is pinned, so ``legged_games_gym_amd.envs.a1_game.register()`` adds it on demand (``scripts/train.py`` and
+``scripts/play.py`` call it when ``--task`` names it).  ``dec_high_level_game`` and ``low_level_game`` as a task of its own are not built.
 """
 from .base.legged_robot import LeggedRobot
 from .anymal_c.anymal import Anymal

@@ -1,0 +1,25 @@
+"""The predator-prey game layer (reference ``legged_gym/envs/a1_game/``): task ``high_level_game``.
+
+Importing this package registers NOTHING: the registry is a process-wide singleton and the locomotion surface is pinned to its five tasks.
+``register()`` adds the game task; ``scripts/train.py`` / ``scripts/play.py`` call it when ``--task`` names one of ``TASKS``."""
+from legged_games_gym_amd.utils.task_registry import task_registry
+
+from .high_level_game import HighLevelGame
+from .high_level_game_flat_config import HighLevelGameFlatCfg, HighLevelGameFlatCfgPPO
+
+TASKS = ("high_level_game",)
+
+
+def register(registry=task_registry):
+    """Register ``high_level_game`` (reference ``legged_gym/envs/__init__.py``); idempotent."""
+    if "high_level_game" not in registry.task_classes:
+        registry.register("high_level_game", HighLevelGame, HighLevelGameFlatCfg(), HighLevelGameFlatCfgPPO())
+    return registry
+
+
+def unregister(registry=task_registry):
+    """Take the game task out of the registry again (its three entries)."""
+    for name in TASKS:
+        for table in (registry.task_classes, registry.env_cfgs, registry.train_cfgs):
+            table.pop(name, None)
+    return registry

@@ -1,0 +1,307 @@
+"""``HighLevelGame`` -- the predator-prey task of the reference (``legged_gym/envs/a1_game/high_level_game.py``) on the device.
+
+One env holds a *prey* (the A1 robot, driven by a frozen low-level locomotion policy) and a *predator* (a kinematic point, a single
+integrator).  One high-level policy outputs the prey's command ``(lin_vel_x, lin_vel_y, ang_vel_yaw, heading)`` and the predator's
+velocity ``(vx, vy)``; it observes four past sensed relative predator positions, four visibility flags and the prey's position relative to
+the predator (19 numbers).
+
+``step(command)`` (reference :146-241) is four launches with no host in between:
+
+    lg_game_pre  ->  low-level actor (lg_policy_act)  ->  lg_step  ->  lg_game_post
+
+(five with the high-level actor in front, which is what ``make_graphed_step`` captures).  The low-level policy acts on the observation
+buffer as the last low-level step left it, so a new command reaches its input one step late -- as in the reference (:177-178).
+
+Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G1-G7)."""
+import copy
+import os
+import types
+
+import numpy as np
+import torch
+
+from legged_games_gym_amd import LEGGED_GYM_ROOT_DIR, capi
+from legged_games_gym_amd.envs.base.base_task import parse_device_str
+from legged_games_gym_amd.utils.helpers import class_to_dict, get_load_path, parse_sim_params
+
+HALF_FOV = 1.20428 / 2.0        # :427
+LL_REW_WEIGHT = 2.0             # :364
+PREDATOR_Z = 0.3                # low_level_game.py:432
+
+
+class HighLevelGame:
+    def __init__(self, cfg, sim_params, physics_engine, sim_device, headless):
+        from legged_games_gym_amd.envs import task_registry, LeggedRobot
+        from legged_games_gym_amd.rl import ActorCritic, FusedActor
+        self.cfg = cfg
+        self.sim_params = sim_params
+        self.height_samples = None
+        self.debug_viz = False
+        self.init_done = False
+        self.physics_engine = physics_engine
+        self.sim_device = sim_device
+        sim_device_type, self.sim_device_id = parse_device_str(self.sim_device)
+        self.headless = headless
+        self.capture_dist = self.cfg.env.capture_dist
+        self.MAX_REL_POS = 100.
+        if sim_device_type in ("cuda", "gpu") and getattr(sim_params, "use_gpu_pipeline", True):
+            self.device = f"cuda:{self.sim_device_id}"
+        else:
+            self.device = "cpu"
+        self.graphics_device_id = -1 if headless else self.sim_device_id
+
+        # low-level env: a DEEP COPY of the registered a1 configs with the overrides of :70-85 (the reference mutates the registered objects)
+        ll_env_cfg, ll_train_cfg = (copy.deepcopy(c) for c in task_registry.get_cfgs(name="a1"))
+        ll_env_cfg.env.num_envs = self.cfg.env.num_envs
+        ll_env_cfg.terrain.num_rows = self.cfg.terrain.num_rows
+        ll_env_cfg.terrain.num_cols = self.cfg.terrain.num_cols
+        ll_env_cfg.terrain.curriculum = self.cfg.terrain.curriculum
+        ll_env_cfg.noise.add_noise = self.cfg.noise.add_noise
+        ll_env_cfg.domain_rand.randomize_friction = self.cfg.domain_rand.randomize_friction
+        ll_env_cfg.domain_rand.push_robots = self.cfg.domain_rand.push_robots
+        ll_env_cfg.terrain.mesh_type = self.cfg.terrain.mesh_type
+        ll_env_cfg.rewards.scales.torques = -5.        # "instantaneous control effort cost" (:83-85)
+        ll_env_cfg.seed = getattr(self.cfg, "seed", ll_env_cfg.seed)
+        ll_args = types.SimpleNamespace(use_gpu=True, subscenes=0, num_threads=0, use_gpu_pipeline=getattr(sim_params, "use_gpu_pipeline", True))
+        ll_sim_params = parse_sim_params(ll_args, {"sim": class_to_dict(ll_env_cfg.sim)})
+        self.ll_env = LeggedRobot(cfg=ll_env_cfg, sim_params=ll_sim_params, physics_engine=physics_engine, sim_device=sim_device, headless=headless)
+        ll = self.ll_env
+
+        # frozen low-level policy: the checkpoint's actor on the MFMA actor kernel
+        path = getattr(self.cfg.env, "ll_policy_path", None)
+        if path is None:
+            log_root = os.path.join(LEGGED_GYM_ROOT_DIR, "logs", ll_train_cfg.runner.experiment_name)
+            try:
+                path = get_load_path(log_root, load_run=ll_train_cfg.runner.load_run, checkpoint=ll_train_cfg.runner.checkpoint)
+            except (ValueError, IndexError, OSError) as exc:
+                raise RuntimeError(
+                    f"high_level_game needs a trained low-level policy and found no a1 checkpoint under {log_root} ({exc}). Train the a1 task first "
+                    "(python -m legged_games_gym_amd.scripts.train --task=a1 --headless) or set env.ll_policy_path to a model_*.pt file.") from exc
+        if not os.path.isfile(path):
+            raise RuntimeError(f"high_level_game: low-level checkpoint {path} does not exist. Train the a1 task first "
+                               "(python -m legged_games_gym_amd.scripts.train --task=a1 --headless) or set env.ll_policy_path to a model_*.pt file.")
+        self.ll_policy_path = path
+        num_critic_obs = ll.num_privileged_obs if ll.num_privileged_obs is not None else ll.num_obs
+        self._ll_actor_critic = ActorCritic(ll.num_obs, num_critic_obs, ll.num_actions, **class_to_dict(ll_train_cfg.policy)).to(self.device)
+        self._ll_actor_critic.load_state_dict(torch.load(path, map_location=self.device, weights_only=True)["model_state_dict"])
+        self._ll_actor_critic.eval()
+        self._ll_fused = FusedActor(self._ll_actor_critic, self.device, seed=int(getattr(ll_env_cfg, "seed", 1)))
+        self.ll_policy = self._ll_fused.act_inference
+
+        self._parse_cfg(self.cfg)
+        self.num_envs = cfg.env.num_envs
+        self.num_obs = cfg.env.num_observations
+        self.num_privileged_obs = cfg.env.num_privileged_obs
+        self.num_actions = cfg.env.num_actions
+        if (self.num_obs, self.num_actions) != (capi.LG_GAME_NUM_OBS, capi.LG_GAME_NUM_ACTIONS):
+            raise ValueError("high_level_game is compiled for 19 observations and 6 actions")
+        if self.num_privileged_obs is not None:
+            raise NotImplementedError("the reference's high_level_game has no privileged observations")
+        self.privileged_obs_buf = None
+        self.extras = {}
+        self.enable_viewer_sync = True
+        self.viewer = None
+        self._init_buffers()
+        self._prepare_reward_function()
+        self._pack()
+        self.init_done = True
+
+    # ------------------------------------------------------------------ hot path
+    def step(self, command):
+        """Apply the high-level command, run one low-level policy step, advance the predator (reference :146-241).
+        ``command`` [num_envs, 6] is clipped IN PLACE, as in the reference."""
+        ll = self.ll_env
+        # the caller may still hold the observations returned last time (PPO.act keeps them until process_env_step, and the reference
+        # builds a new tensor every step, :405): alternate between two buffers, carrying the history over
+        prev = self.obs_buf
+        self._obs_flip ^= 1
+        self.obs_buf = self._obs_pair[self._obs_flip]
+        self.obs_buf.copy_(prev)
+        B = self._bind_command(command, self.obs_buf)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.game_pre(self._P, B, stream)
+        actions = self.ll_policy(ll.obs_buf)
+        ll.step(actions)
+        capi.game_post(self._P, B, ll.common_step_counter, stream)
+        return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
+
+    def _device_step(self, command):
+        """``step`` for graph capture: the step counter is the low-level env's device counter, observations stay in one buffer."""
+        ll = self.ll_env
+        B = self._bind_command(command, self.obs_buf)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.game_pre(self._P, B, stream)
+        actions = self.ll_policy(ll.obs_buf)
+        ll._sim.step(actions, -1)
+        capi.game_post(self._P, B, -1, stream)
+
+    def make_graphed_step(self, policy_act, warmup=3, steps_per_replay=1):
+        """Capture ``step(policy_act(obs_buf))`` into one HIP graph and return a zero-argument callable that replays it: high-level actor,
+        ``lg_game_pre``, low-level actor, ``lg_step``, ``lg_game_post`` -- no host in between (same contract as
+        ``LeggedRobot.make_graphed_step``).  ``policy_act`` must be capturable and read ``self.obs_buf``."""
+        ll = self.ll_env
+        sim = ll._sim
+        sim.set_obs_output(ll.obs_buf)                       # one fixed low-level observation buffer while replaying
+        sim.buf["step_counter"].fill_(ll.common_step_counter)
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self._device_step(policy_act(self.obs_buf))
+                ll.common_step_counter += 1
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        ll.begin_graph_capture()
+        sim.set_deferred_extras(False)                       # the low-level step publishes its extras in its own launch: five launches per step
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                for _ in range(steps_per_replay):
+                    self._device_step(policy_act(self.obs_buf))
+        finally:
+            ll.end_graph_capture(0)                          # (the captured steps went through the sim, not through ll_env.step)
+        self._step_graph = graph
+
+        def replay():
+            graph.replay()
+            ll.common_step_counter += steps_per_replay
+            return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
+        return replay
+
+    def reset_idx(self, env_ids):
+        """Reset the listed envs from the host (reference :326-349): root state of the prey, predator placement, history.  Resets that
+        happen inside ``step`` are done by ``lg_game_post`` with keyed Philox draws; this entry point serves ``reset()`` and tooling and
+        draws from torch's generator, like the creation-time randomisation of the low-level env."""
+        if len(env_ids) == 0:
+            return
+        ll = self.ll_env
+        ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long)
+        n = len(ids)
+        root = ll.base_init_state.repeat(n, 1)
+        root[:, :3] += ll.env_origins[ids]
+        if ll.custom_origins:
+            root[:, :2] += 2.0 * torch.rand(n, 2, device=self.device) - 1.0
+        root[:, 7:13] = torch.rand(n, 6, device=self.device) - 0.5
+        ll.root_states[ids] = root
+        self.predator_pos[ids] = self._place_predator(root[:, :3])
+        self.obs_buf[ids, 0:12] = self.MAX_REL_POS
+        self.obs_buf[ids, 12:16] = 0
+        self.obs_buf[ids, 16:] = -self.MAX_REL_POS
+        self.episode_length_buf[ids] = 0
+        self.curr_episode_step[ids] = 0
+
+    def reset(self):
+        """Reset all envs, then one zero-command step (:351-355)."""
+        self.reset_idx(torch.arange(self.num_envs, device=self.device))
+        obs, privileged_obs, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device, requires_grad=False))
+        return obs, privileged_obs
+
+    def get_observations(self):
+        return self.obs_buf
+
+    def get_privileged_observations(self):
+        return self.privileged_obs_buf
+
+    def render(self, sync_frame_time=True):
+        return None     # headless
+
+    # ------------------------------------------------------------------ state views (reference names)
+    @property
+    def prey_states(self):
+        return self.ll_env.root_states
+
+    @property
+    def base_quat(self):
+        return self.ll_env.root_states[:, 3:7]
+
+    @property
+    def dt(self):
+        return self.ll_env.dt
+
+    # ------------------------------------------------------------------ set-up
+    def _place_predator(self, prey_pos):
+        """low_level_game.py:420-432: a common sign per env times U(1, 10) on every axis, then z = 0.3."""
+        n = prey_pos.shape[0]
+        offset = 1.0 + 9.0 * torch.rand(n, 3, device=self.device)
+        sign = torch.where(torch.rand(n, 1, device=self.device) < 0.5, -1.0, 1.0)
+        pos = prey_pos - sign * offset
+        pos[:, 2] = PREDATOR_Z
+        return pos
+
+    def _init_buffers(self):
+        N, dev = self.num_envs, self.device
+        self._obs_pair = (self.MAX_REL_POS * torch.ones(N, self.num_obs, device=dev, dtype=torch.float),
+                          self.MAX_REL_POS * torch.ones(N, self.num_obs, device=dev, dtype=torch.float))
+        self._obs_flip = 0
+        self.obs_buf = self._obs_pair[0]
+        self.rew_buf = torch.zeros(N, device=dev, dtype=torch.float)
+        self.reset_buf = torch.ones(N, device=dev, dtype=torch.bool)          # persistent bool tensor, like the low-level env's (quirk Q1)
+        self.episode_length_buf = torch.zeros(N, device=dev, dtype=torch.long)
+        self.time_out_buf = torch.zeros(N, device=dev, dtype=torch.bool)
+        self.curr_episode_step = torch.zeros(N, device=dev, dtype=torch.long)
+        self.init_predator_pos = self._place_predator(self.ll_env.root_states[:, :3])
+        self.predator_pos = self.init_predator_pos.clone()
+        self._command = torch.zeros(N, self.num_actions, device=dev, dtype=torch.float)
+
+    def _prepare_reward_function(self):
+        """Reference :537-561: zero scales dropped, the rest multiplied by the low-level dt; one episode sum per name."""
+        for key in list(self.reward_scales.keys()):
+            if self.reward_scales[key] == 0:
+                self.reward_scales.pop(key)
+            else:
+                self.reward_scales[key] *= self.ll_env.dt
+        unknown = [k for k in self.reward_scales if k not in ("evasion", "pursuit")]
+        if unknown:
+            raise AttributeError(f"'HighLevelGame' object has no attribute '_reward_{unknown[0]}'")
+        self.reward_names = list(self.reward_scales.keys())
+        self._episode_sums = torch.zeros(2, self.num_envs, device=self.device, dtype=torch.float)
+        self.episode_sums = {name: self._episode_sums[("evasion", "pursuit").index(name)] for name in self.reward_names}
+
+    def _parse_cfg(self, cfg):
+        """Reference :563-571."""
+        self.reward_scales = class_to_dict(self.cfg.rewards.scales)
+        self.command_ranges = class_to_dict(self.cfg.commands.ranges)
+        if self.cfg.terrain.mesh_type not in ["heightfield", "trimesh"]:
+            self.cfg.terrain.curriculum = False
+        self.max_episode_length_s = self.cfg.env.episode_length_s
+        self.max_episode_length = np.ceil(self.max_episode_length_s / self.ll_env.dt)
+
+    def _pack(self):
+        """``lg_game_params`` from the configs and the pointer table of ``lg_game_buffers``."""
+        ll, P = self.ll_env, capi.lg_game_params()
+        P.num_envs, P.decimation = self.num_envs, int(ll.cfg.control.decimation)
+        P.heading_command, P.only_positive_rewards = int(bool(self.cfg.commands.heading_command)), int(bool(self.cfg.rewards.only_positive_rewards))
+        P.custom_origins = int(bool(ll.custom_origins))
+        seed = getattr(self.cfg, "seed", 1)
+        P.seed = int(seed) if seed is not None and seed >= 0 else 1
+        r = self.command_ranges
+        for name, key in (("cmd_lin_vel_x", "lin_vel_x"), ("cmd_lin_vel_y", "lin_vel_y"), ("predator_lin_vel_x", "predator_lin_vel_x"),
+                          ("predator_lin_vel_y", "predator_lin_vel_y")):
+            capi._fill(getattr(P, name), r[key])
+        P.capture_dist = float(self.capture_dist)
+        P.env_radius = -1.0 if self.cfg.env.env_radius is None else float(self.cfg.env.env_radius)
+        P.half_fov, P.max_rel_pos, P.ll_rew_weight = HALF_FOV, self.MAX_REL_POS, LL_REW_WEIGHT
+        P.scale_evasion_dt = float(self.reward_scales.get("evasion", 0.0))
+        P.scale_pursuit_dt = float(self.reward_scales.get("pursuit", 0.0))
+        P.sim_dt, P.predator_z = float(ll.cfg.sim.dt), PREDATOR_Z
+        capi._fill(P.base_init_state, ll.base_init_state.cpu().numpy())
+        self._P = P
+        b = ll._sim.buf
+        self._pointers = {"ll_root_states": b["root_states"].data_ptr(), "ll_commands": b["commands"].data_ptr(), "ll_env_origins": b["env_origins"].data_ptr(),
+                          "ll_rew_buf": b["rew_buf"].data_ptr(), "ll_reset_buf": b["reset_buf"].data_ptr(), "ll_step_counter": b["step_counter"].data_ptr(),
+                          "predator_pos": self.predator_pos.data_ptr(), "rew": self.rew_buf.data_ptr(), "reset_buf": self.reset_buf.data_ptr(),
+                          "curr_episode_step": self.curr_episode_step.data_ptr(), "episode_length_buf": self.episode_length_buf.data_ptr(),
+                          "episode_sums": self._episode_sums.data_ptr()}
+
+    def set_command_ranges(self):
+        """Re-pack after ``command_ranges`` / ``capture_dist`` / ``cfg.env.env_radius`` were edited."""
+        self._pack()
+
+    def _bind_command(self, command, obs):
+        """``lg_game_buffers`` for this call: the kernels read and clip the caller's tensor where it is."""
+        if command.shape != (self.num_envs, self.num_actions):
+            raise ValueError(f"command must be [{self.num_envs},{self.num_actions}], got {tuple(command.shape)}")
+        if command.dtype != torch.float32 or not command.is_contiguous() or str(command.device) != str(self.device):
+            self._command.copy_(command)
+            command = self._command
+        self._keep = command
+        return capi.game_buffers(dict(self._pointers, command=command.detach().data_ptr(), obs=obs.data_ptr()))

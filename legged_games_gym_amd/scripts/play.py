@@ -11,11 +11,14 @@ from legged_games_gym_amd.utils.helpers import export_policy_as_jit
 from legged_games_gym_amd.utils.logger import Logger
 
 from legged_games_gym_amd.envs import *  # noqa: F401,F403
+from legged_games_gym_amd.envs import a1_game
 from legged_games_gym_amd.utils import get_args
 from legged_games_gym_amd.utils.task_registry import task_registry
 
 
 def play(args, steps=None):
+    if args.task in a1_game.TASKS:
+        a1_game.register()
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.env.num_envs = min(env_cfg.env.num_envs, 50)
     env_cfg.terrain.num_rows = 5
@@ -34,6 +37,7 @@ def play(args, steps=None):
         print("Exported policy as jit script to:", export_policy_as_jit(ppo_runner.alg.actor_critic, path))
     logger = Logger(env.dt, out_dir=os.path.join(LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name, "exported"))
     robot_index, joint_index = 0, 1                          # which robot / joint is logged (:67-68)
+    robot = getattr(env, "ll_env", env)                      # the game task logs the states of its low-level robot (the prey)
     stop_state_log = 100                                     # steps before the states are plotted
     stop_rew_log = int(env.max_episode_length) + 1           # steps before the average episode rewards are printed
     n = steps if steps is not None else 10 * int(env.max_episode_length)
@@ -44,19 +48,19 @@ def play(args, steps=None):
         tot += rews
         if i < stop_state_log:
             logger.log_states({
-                "dof_pos_target": actions[robot_index, joint_index].item() * env.cfg.control.action_scale,
-                "dof_pos": env.dof_pos[robot_index, joint_index].item(),
-                "dof_vel": env.dof_vel[robot_index, joint_index].item(),
-                "dof_torque": env.torques[robot_index, joint_index].item(),
-                "command_x": env.commands[robot_index, 0].item(), "command_y": env.commands[robot_index, 1].item(),
-                "command_yaw": env.commands[robot_index, 2].item(),
-                "base_vel_x": env.base_lin_vel[robot_index, 0].item(), "base_vel_y": env.base_lin_vel[robot_index, 1].item(),
-                "base_vel_z": env.base_lin_vel[robot_index, 2].item(), "base_vel_yaw": env.base_ang_vel[robot_index, 2].item(),
-                "contact_forces_z": env.contact_forces[robot_index, env.feet_indices, 2].cpu().numpy()})
+                "dof_pos_target": (actions if robot is env else robot.actions)[robot_index, joint_index].item() * robot.cfg.control.action_scale,
+                "dof_pos": robot.dof_pos[robot_index, joint_index].item(),
+                "dof_vel": robot.dof_vel[robot_index, joint_index].item(),
+                "dof_torque": robot.torques[robot_index, joint_index].item(),
+                "command_x": robot.commands[robot_index, 0].item(), "command_y": robot.commands[robot_index, 1].item(),
+                "command_yaw": robot.commands[robot_index, 2].item(),
+                "base_vel_x": robot.base_lin_vel[robot_index, 0].item(), "base_vel_y": robot.base_lin_vel[robot_index, 1].item(),
+                "base_vel_z": robot.base_lin_vel[robot_index, 2].item(), "base_vel_yaw": robot.base_ang_vel[robot_index, 2].item(),
+                "contact_forces_z": robot.contact_forces[robot_index, robot.feet_indices, 2].cpu().numpy()})
         elif i == stop_state_log:
             print("state plots written to:", logger.plot_states())
         if 0 < i < stop_rew_log:
-            if infos["episode"]:
+            if infos.get("episode"):                          # (the game task's extras stay empty, as in the reference)
                 num_episodes = int(torch.sum(env.reset_buf).item())
                 if num_episodes > 0:
                     logger.log_rewards(infos["episode"], num_episodes)

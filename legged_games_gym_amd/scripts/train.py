@@ -9,7 +9,8 @@ collectives of ``rl/ppo.py`` (RCCL: all-gather of returns/advantages, gradient a
 and checkpoints."""
 import os
 
-from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the tasks)
+from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
+from legged_games_gym_amd.envs import a1_game
 from legged_games_gym_amd.utils import get_args
 from legged_games_gym_amd.utils.task_registry import task_registry
 
@@ -35,6 +36,8 @@ def _init_distributed(args):
 
 
 def train(args):
+    if args.task in a1_game.TASKS:
+        a1_game.register()               # the game layer registers on demand: python -m legged_games_gym_amd.scripts.train --task=high_level_game --headless
     rank, world = _init_distributed(args)
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))

@@ -3,8 +3,9 @@
 Mirror of reference ``legged_gym/utils/task_registry.py:44-162, 224``:
 ``register`` / ``get_task_class`` / ``get_cfgs`` / ``make_env`` /
 ``make_alg_runner`` keep their signatures, defaults, printouts-free behaviour
-and error types (``ValueError`` for an unknown task or missing name).  The
-game-layer ``make_dec_alg_runner`` (:164-221) is out of scope.
+and error types (``ValueError`` for an unknown task or missing name).  The game task
+``high_level_game`` goes through the same ``make_env`` / ``make_alg_runner`` once ``envs.a1_game.register()`` has added it;
+``make_dec_alg_runner`` (:164-221, the decentralised game's two-policy runner) is not built.
 
 The PPO runner is ``rsl_rl.runners.OnPolicyRunner`` when that package is
 importable, otherwise the bundled ``legged_games_gym_amd.rl.OnPolicyRunner``
