@@ -3,9 +3,10 @@
  *
  * The game wraps a low-level locomotion env (the `a1` task, legged_hip.h) and adds a kinematic predator.  One
  * high-level step of the reference (legged_gym/envs/a1_game/high_level_game.py:146-241) is five launches with no
- * host in between:  high-level actor -> lg_game_pre -> low-level actor -> lg_step -> lg_game_post.
+ * host in between:  high-level actor -> lg_game_pre -> low-level actor -> lg_step -> lg_game_post,
+ * or three:  lg_game_act (both actors and the clip) -> lg_step -> lg_game_post.
  *
- * Both entry points are stateless: the parameters travel by value in the kernel arguments and the buffers are raw
+ * The entry points are stateless: the parameters travel by value in the kernel arguments and the buffers are raw
  * device pointers owned by the caller.  They stand in for the gym calls
  *   set_actor_root_state_tensor            high_level_game.py:263,287   (predator integration)
  *   set_actor_root_state_tensor_indexed    low_level_game.py:442-451    (root-state reset of prey and predator)
@@ -71,6 +72,22 @@ int lg_game_pre(const lg_game_params *params, const lg_game_buffers *buffers, vo
  * observation with the occlusion model (:380-482).  `common_step_counter` keys the reset draws (seed; env, step, RNG_GAME_ROOT = 16 /
  * RNG_GAME_PREDATOR = 17, block); -1 = read `ll_step_counter` as the preceding lg_step left it (graph replay). */
 int lg_game_post(const lg_game_params *params, const lg_game_buffers *buffers, int64_t common_step_counter, void *stream);
+
+/* Both actors of a high-level step and lg_game_pre in ONE launch, workgroups split by role (the low-level policy reads the observation the
+ * previous lg_step left, so nothing in it depends on the new command):
+ *   low-level role   actions = actor_ll(ll_obs), deterministic                                  = lg_policy_act(ll, ..., deterministic = 1)
+ *   high-level role  sample = actor_hl(hl_obs) + std * eps; command = clip / wrap(sample)       = lg_policy_act(hl, ...) + lg_game_pre
+ * Each role's results are bit-identical to those stand-alone launches.  `hl` / `ll` are lg_policy handles (legged_hip.h: lg_policy_create);
+ * seed / step / step_counter / deterministic as in lg_policy_act and apply to the high-level role.  Written: buffers->command [N,6],
+ * buffers->ll_commands [N,4], ll_actions [N, actions of ll], mean [N,6], and where the pointer is not NULL: sample [N,6] (the unclipped
+ * sample), sigma [N,6] (the broadcast std), log_prob [N] (log N(sample; mean, std) summed over the six actions: what PPO.act stores
+ * before the env clips the caller's tensor), obs_copy [N,19] (the observations the high-level role read).
+ * Compiled for the 19-512-256-128-6 / 235-512-256-128 pair at wide precision 1 (lg_mlp_wide_set_precision); -4 otherwise: issue
+ * lg_policy_act x 2 + lg_game_pre instead. */
+struct lg_policy;
+int lg_game_act(struct lg_policy *hl, struct lg_policy *ll, const lg_game_params *params, const lg_game_buffers *buffers,
+                const float *hl_obs, const float *ll_obs, float *ll_actions, float *mean, uint64_t seed, int64_t step,
+                const int64_t *step_counter, int32_t deterministic, float *sample, float *sigma, float *log_prob, float *obs_copy, void *stream);
 
 /* sizeof of 0: lg_game_params, 1: lg_game_buffers (layout check of the binding); -1 otherwise */
 int lg_game_sizeof(int which);

@@ -343,7 +343,7 @@ class lg_game_buffers(C.Structure):
 
 
 GAME_BUFFER_FIELDS = [name for name, _ in lg_game_buffers._fields_]
-GAME_SYMBOLS = ["lg_game_pre", "lg_game_post", "lg_game_sizeof"]
+GAME_SYMBOLS = ["lg_game_pre", "lg_game_post", "lg_game_act", "lg_game_sizeof"]
 
 
 def bind_game_prototypes(lib):
@@ -351,6 +351,8 @@ def bind_game_prototypes(lib):
     vp = C.c_void_p
     lib.lg_game_pre.argtypes, lib.lg_game_pre.restype = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), vp], C.c_int
     lib.lg_game_post.argtypes, lib.lg_game_post.restype = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), i64, vp], C.c_int
+    lib.lg_game_act.argtypes = [vp, vp, C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), vp, vp, vp, vp, u64, i64, vp, i32, vp, vp, vp, vp, vp]
+    lib.lg_game_act.restype = C.c_int
     lib.lg_game_sizeof.argtypes, lib.lg_game_sizeof.restype = [C.c_int], C.c_int
     for which, st in enumerate((lg_game_params, lg_game_buffers)):
         if lib.lg_game_sizeof(which) != C.sizeof(st):
@@ -372,6 +374,19 @@ def game_pre(params: lg_game_params, buffers: lg_game_buffers, stream: int = 0):
     rc = lib.lg_game_pre(C.byref(params), C.byref(buffers), stream)
     if rc != 0:
         raise RuntimeError(f"lg_game_pre failed ({rc}): {lib.lg_last_error().decode()}")
+
+
+def game_act(hl_policy, ll_policy, params: lg_game_params, buffers: lg_game_buffers, hl_obs: int, ll_obs: int, ll_actions: int, mean: int, seed: int,
+             step: int, step_counter: Optional[int], deterministic: bool, sample: Optional[int] = None, sigma: Optional[int] = None,
+             log_prob: Optional[int] = None, obs_copy: Optional[int] = None, stream: int = 0) -> int:
+    """``lg_game_act``: both actors of a high-level step and the command clip in one launch.  Returns 0, or -4 when the actor pair /
+    wide precision has no shared kernel (the caller then issues ``lg_policy_act`` x 2 + ``lg_game_pre``); raises on any other error."""
+    lib = load_library()
+    rc = lib.lg_game_act(hl_policy, ll_policy, C.byref(params), C.byref(buffers), hl_obs, ll_obs, ll_actions, mean, int(seed), int(step), step_counter,
+                         int(bool(deterministic)), sample, sigma, log_prob, obs_copy, stream)
+    if rc not in (0, -4):
+        raise RuntimeError(f"lg_game_act failed ({rc}): {lib.lg_last_error().decode()}")
+    return rc
 
 
 def game_post(params: lg_game_params, buffers: lg_game_buffers, common_step_counter: int, stream: int = 0):

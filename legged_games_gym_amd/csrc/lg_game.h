@@ -7,30 +7,20 @@
 // Floating point: contraction is OFF in this header, every expression rounds once per operation in the order written.  The results are then
 // bit-comparable with a NumPy float32 restatement (tests/game_twin.py) except behind sqrtf / acosf, which are 1-ulp on this build.
 //
-// Included from lg_kernels.hip after its error helpers (fail / HIP_TRY).
+// Included from lg_kernels.hip after its error helpers (fail / HIP_TRY).  The shared actor kernel behind lg_game_act, k_prey_act, lives in
+// lg_game_act.h and is compiled in a translation unit of its own (lg_game_act.hip): inside lg_kernels.hip its presence alone changes hipcc's
+// register allocation of the existing k_policy_act_wide instantiations (211 / 214 -> 216 / 212 VGPRs).  What both units share -- the
+// clip / wrap helpers, the kernel's argument struct, its launcher -- is in lg_game_common.h.
 #pragma once
-#include "../../include/legged_game.h"
+#include "lg_game_common.h"
 
 namespace lg {
+
+#pragma clang fp contract(off)
 
 enum { RNG_GAME_ROOT = 16, RNG_GAME_PREDATOR = 17 };      // Philox purposes; the step kernel's own root draw uses RNG_ROOT
 #define LG_GAME_BLOCK 256
 
-#pragma clang fp contract(off)
-
-LG_DEV float game_clip(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }      // torch.clip(x, min, max)
-LG_DEV float game_urange(float lo, float hi, float u) {                                       // torch_rand_float: (upper - lower) * rand + lower
-#pragma clang fp contract(off)
-    return (hi - lo) * u + lo;
-}
-LG_DEV float game_wrap_to_pi(float a) {                                                       // utils/math.py:45-48
-#pragma clang fp contract(off)
-    const float two_pi = 6.2831855f, pi = 3.14159274f;
-    a = fmodf(a, two_pi);
-    if (a != 0.0f && a < 0.0f) a += two_pi;                                                   // torch's remainder: sign of the divisor
-    if (a > pi) a -= two_pi;
-    return a;
-}
 
 __global__ __launch_bounds__(LG_GAME_BLOCK) void k_game_pre(lg_game_params P, lg_game_buffers B) {
 #pragma clang fp contract(off)
@@ -174,6 +164,31 @@ int lg_game_post(const lg_game_params *P, const lg_game_buffers *B, int64_t comm
     hipLaunchKernelGGL(lg::k_game_post, dim3((P->num_envs + LG_GAME_BLOCK - 1) / LG_GAME_BLOCK), dim3(LG_GAME_BLOCK), 0, (hipStream_t)stream, *P, *B,
                        common_step_counter);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int lg_game_act(lg_policy *hl, lg_policy *ll, const lg_game_params *P, const lg_game_buffers *B, const float *hl_obs, const float *ll_obs,
+                float *ll_actions, float *mean, uint64_t seed, int64_t step, const int64_t *step_counter, int32_t deterministic,
+                float *sample, float *sigma, float *log_prob, float *obs_copy, void *stream) {
+    if (int rc = game_check(P, B)) return rc;
+    if (!hl || !ll || !hl_obs || !ll_obs || !ll_actions || !mean) return fail(-1, "null argument");
+    if (!B->command || !B->ll_commands) return fail(-1, "lg_game_act needs command and ll_commands");
+    const bool hl_ok = hl->wide && hl->dims[0] == LG_GAME_NUM_OBS && hl->dims[4] == LG_GAME_NUM_ACTIONS;
+    const bool ll_ok = ll->wide && ll->tiles[0] == 15;
+    if (g_wide_precision != 1 || !hl_ok || !ll_ok)
+        return fail(-4, "the shared actor launch is compiled for the 19-512-256-128-6 / 235-512-256-128 pair at wide precision 1; use lg_policy_act x 2 + lg_game_pre");
+    lg::PreyActArgs g;
+    fill_policy_args(hl, g.hl.base, hl_obs, sample, mean, P->num_envs, seed, step, step_counter, deterministic);
+    fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed, step, step_counter, 1);
+    for (int i = 0; i < 4; i++) {
+        g.hl.wb[i] = reinterpret_cast<const lg::bf16x8g *>(hl->d_wb[i]); g.hl.bb[i] = hl->d_bb[i];
+        g.ll.wb[i] = reinterpret_cast<const lg::bf16x8g *>(ll->d_wb[i]); g.ll.bb[i] = ll->d_bb[i];
+    }
+    g.P = *P; g.command = B->command; g.ll_commands = B->ll_commands;
+    g.sigma = sigma; g.log_prob = log_prob; g.obs_copy = obs_copy;
+    const int blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;
+    g.ll_blocks = blocks;
+    HIP_TRY((hipError_t)lg::launch_prey_act(g, blocks, stream));
     return 0;
 }
 

@@ -3001,19 +3001,21 @@ int lg_policy_act(lg_policy *p, const float *obs, float *actions, float *mean, i
     dim3 g((num_envs + 15) / 16), b(64 * LG_POLICY_WAVES);
     hipStream_t st = (hipStream_t)stream;
     const int t0 = p->tiles[0], t1 = p->tiles[1], t2 = p->tiles[2], t3 = p->tiles[3];
-    if (p->wide && g_wide_precision == 1 && (t0 == 15 || t0 == 11)) {          // 32 envs per workgroup on the bf16 matrix cores
+    if (p->wide && g_wide_precision == 1 && (t0 == 15 || t0 == 11 || t0 == 2)) {          // 32 envs per workgroup on the bf16 matrix cores
         lg::PolicyWideArgs w; w.base = a;
         for (int i = 0; i < 4; i++) { w.wb[i] = reinterpret_cast<const lg::bf16x8g *>(p->d_wb[i]); w.bb[i] = p->d_bb[i]; }
         dim3 gw((num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS), bw(64 * LG_PW_WAVES);
         if (t0 == 15) hipLaunchKernelGGL((lg::k_policy_act_wide<15, 16, 8, 4>), gw, bw, 0, st, w);     // rough: 235-512-256-128
-        else hipLaunchKernelGGL((lg::k_policy_act_wide<11, 16, 8, 4>), gw, bw, 0, st, w);              // cassie: 169-512-256-128
+        else if (t0 == 11) hipLaunchKernelGGL((lg::k_policy_act_wide<11, 16, 8, 4>), gw, bw, 0, st, w);  // cassie: 169-512-256-128
+        else hipLaunchKernelGGL((lg::k_policy_act_wide<2, 16, 8, 4>), gw, bw, 0, st, w);               // game: 19-512-256-128 (17..32 inputs)
         HIP_TRY(hipGetLastError());
         return 0;
     }
     if (t0 == 3 && t1 == 8 && t2 == 4 && t3 == 2) hipLaunchKernelGGL((k_policy_act<3, 8, 4, 2>), g, b, 0, st, a);            // flat: 48-128-64-32
     else if (t0 == 15 && t1 == 32 && t2 == 16 && t3 == 8) hipLaunchKernelGGL((k_policy_act<15, 32, 16, 8>), g, b, 0, st, a);  // rough: 235-512-256-128
     else if (t0 == 11 && t1 == 32 && t2 == 16 && t3 == 8) hipLaunchKernelGGL((k_policy_act<11, 32, 16, 8>), g, b, 0, st, a);  // cassie: 169-512-256-128
-    else return fail(-4, "actor widths are not one of the compiled-in shapes (48-128-64-32, 235/169-512-256-128)");
+    else if (t0 == 2 && t1 == 32 && t2 == 16 && t3 == 8) hipLaunchKernelGGL((k_policy_act<2, 32, 16, 8>), g, b, 0, st, a);    // game: 19-512-256-128
+    else return fail(-4, "actor widths are not one of the compiled-in shapes (48-128-64-32, 235/169/19-512-256-128)");
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -596,6 +596,7 @@ LG_DEV void pack_wide_body(const float *__restrict__ Wt, const float *__restrict
         wp[((((size_t)o * KS + s) * 2 + 1) * 64 + l) * 8 + i] = lo;
     }
 }
+#ifndef LG_POLICY_BLOCKS_ONLY                                    // (a second translation unit that only reuses the building blocks above: lg_game_act.hip)
 __global__ void k_policy_pack_wide(const float *__restrict__ Wt, const float *__restrict__ bias, int in_dim, int out_dim, int KS, int OT, int first,
                                    __bf16 *__restrict__ wp, float *__restrict__ bp) {
     pack_wide_body(Wt, bias, in_dim, out_dim, KS, OT, first, wp, bp);
@@ -606,5 +607,6 @@ __global__ void k_chain_pack(const ChainPackArgs P) {
     const int l = blockIdx.y, z = blockIdx.z;
     pack_wide_body(P.W[z][l], P.b[z][l], P.in_dim[z][l], P.out_dim[z][l], P.KS[z][l], P.OT[z][l], l == 0 ? 1 : 0, P.wp[z][l], P.bp[z][l]);
 }
+#endif
 
 }  // namespace lg

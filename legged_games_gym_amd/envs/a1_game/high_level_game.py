@@ -9,10 +9,15 @@ the predator (19 numbers).
 
     lg_game_pre  ->  low-level actor (lg_policy_act)  ->  lg_step  ->  lg_game_post
 
-(five with the high-level actor in front, which is what ``make_graphed_step`` captures).  The low-level policy acts on the observation
-buffer as the last low-level step left it, so a new command reaches its input one step late -- as in the reference (:177-178).
+(five with the high-level actor in front, which is what ``make_graphed_step`` captures).  ``step_policy(fused_actor)`` runs the
+high-level actor on the device as well, in three launches:
 
-Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G1-G7)."""
+    lg_game_act (both actors + the clip)  ->  lg_step  ->  lg_game_post
+
+The low-level policy acts on the observation buffer as the last low-level step left it, so a new command reaches its input one step
+late -- as in the reference (:177-178).  That is also what lets ``lg_game_act`` run both actors side by side.
+
+Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G1-G9)."""
 import copy
 import os
 import types
@@ -166,6 +171,141 @@ class HighLevelGame:
             ll.common_step_counter += steps_per_replay
             return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
         return replay
+
+    # ------------------------------------------------------------------ hot path with the actor on the device
+    def _act(self, fused_actor, obs_in, obs_out, deterministic, sample=None, sigma=None, log_prob=None):
+        """``lg_game_act``: command = clip(actor(obs_in) + noise) into the low-level commands, the low-level actions, and ``obs_in`` copied
+        to ``obs_out`` (where ``lg_game_post`` then shifts the history in place) -- one launch.  Separate launches when the actor pair or
+        the wide precision has no shared kernel (rc -4).  Returns ``command, mean, ll_actions, buffers``."""
+        ll, n = self.ll_env, self.num_envs
+        if obs_in.shape != (n, self.num_obs) or obs_in.dtype != torch.float32 or not obs_in.is_contiguous():
+            raise ValueError(f"observations must be a contiguous float32 [{n},{self.num_obs}] tensor")
+        self._check_output("sample", sample, n * self.num_actions)
+        self._check_output("sigma", sigma, n * self.num_actions)
+        self._check_output("log_prob", log_prob, n)
+        command, mean = fused_actor.output_buffers(n)
+        ll_actions = self._ll_fused.output_buffers(n)[0]
+        B = self._bind_command(command, obs_out)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()
+        copy = obs_out is not obs_in
+        step, ctr = fused_actor.peek_step()
+        rc = capi.game_act(fused_actor.handle, self._ll_fused.handle, self._P, B, obs_in.data_ptr(), ll.obs_buf.data_ptr(), ll_actions.data_ptr(),
+                           mean.data_ptr(), fused_actor.seed, step, ctr, deterministic, ptr(sample), ptr(sigma), ptr(log_prob),
+                           obs_out.data_ptr() if copy else None, stream)
+        if rc == 0:
+            fused_actor.next_step()                            # the launch used this step of the actor's noise stream
+            return command, mean, ll_actions, B
+        # rc -4, nothing was launched: lg_policy_act x 2 + lg_game_pre (decided per call: lg_mlp_wide_set_precision may change between
+        # calls), each actor into its own FusedActor's buffers as above
+        command, mean = fused_actor.act_with_mean(obs_in, deterministic)
+        if sample is not None:
+            sample.view(n, -1).copy_(command)
+        if sigma is not None or log_prob is not None:
+            std = fused_actor.ac.std.detach()
+            if sigma is not None:
+                sigma.view(n, -1).copy_(std.expand(n, -1))
+            if log_prob is not None:
+                log_prob.view(n).copy_(torch.distributions.Normal(mean, std).log_prob(command).sum(-1))
+        if copy:
+            obs_out.copy_(obs_in)
+        capi.game_pre(self._P, B, stream)
+        ll_actions = self.ll_policy(ll.obs_buf)
+        return command, mean, ll_actions, B
+
+    def _check_output(self, name, t, numel):
+        """An optional output of ``_act``: None, or a contiguous float32 tensor on this device with ``numel`` elements."""
+        if t is None:
+            return
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or str(t.device) != str(self.device):
+            raise ValueError(f"{name} must be a contiguous float32 tensor with {numel} elements on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    def step_policy(self, fused_actor, deterministic=False, sample=None, sigma=None, log_prob=None):
+        """Rollout step with the high-level actor on the device: ``lg_game_act`` -> ``lg_step`` -> ``lg_game_post``, three launches.
+        Returns ``(command, mean), (obs, privileged_obs, rew, dones, extras)``: ``command`` is the clipped command (what ``step`` leaves in the
+        caller's tensor), ``mean`` the actor's output; both are ``fused_actor``'s buffers.  Optional float32 outputs: ``sample`` [N,6] (the
+        unclipped sample), ``sigma`` [N,6] and ``log_prob`` [N] of that sample (what ``PPO.act`` stores).  The observations the actor read
+        stay in the tensor returned by the previous call, as with ``step``."""
+        ll = self.ll_env
+        prev = self.obs_buf
+        self._obs_flip ^= 1
+        self.obs_buf = self._obs_pair[self._obs_flip]
+        try:
+            command, mean, ll_actions, B = self._act(fused_actor, prev, self.obs_buf, deterministic, sample, sigma, log_prob)
+        except Exception:
+            self._obs_flip ^= 1
+            self.obs_buf = prev
+            raise
+        ll.step(ll_actions)
+        capi.game_post(self._P, B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
+        return (command, mean), (self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras)
+
+    def make_graphed_policy_step(self, fused_actor, warmup=3, steps_per_replay=1):
+        """``make_graphed_step`` with the actor on the device: the graph is ``lg_game_act`` -> ``lg_step`` -> ``lg_game_post`` per step, the
+        observations stay in one buffer.  ``fused_actor`` must draw its noise stream from the low-level sim's device step counter
+        (``FusedActor(..., step_counter=env.ll_env._sim.buf["step_counter"])``).  Returns a zero-argument callable that replays the graph;
+        ``fused_actor.output_buffers(num_envs)`` then hold the command and the mean of the last step."""
+        ll = self.ll_env
+        sim = ll._sim
+        if fused_actor.step_counter is None or fused_actor.step_counter.data_ptr() != sim.buf["step_counter"].data_ptr():
+            raise ValueError("make_graphed_policy_step needs a FusedActor on the low-level sim's device step counter")
+        sim.set_obs_output(ll.obs_buf)
+        sim.buf["step_counter"].fill_(ll.common_step_counter)
+
+        def device_step():
+            _, _, ll_actions, B = self._act(fused_actor, self.obs_buf, self.obs_buf, False)
+            sim.step(ll_actions, -1)
+            capi.game_post(self._P, B, -1, torch.cuda.current_stream(self.device).cuda_stream)
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                device_step()
+                ll.common_step_counter += 1
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        ll.begin_graph_capture()
+        sim.set_deferred_extras(False)
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                for _ in range(steps_per_replay):
+                    device_step()
+        finally:
+            ll.end_graph_capture(0)
+        self._policy_step_graph = graph
+
+        def replay():
+            graph.replay()
+            ll.common_step_counter += steps_per_replay
+            return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
+        return replay
+
+    # ------------------------------------------------------------------ capture hooks of the runner's device rollout
+    @property
+    def _capturing(self):
+        return self.ll_env._capturing
+
+    @_capturing.setter
+    def _capturing(self, value):
+        self.ll_env._capturing = value
+
+    @property
+    def common_step_counter(self):
+        return self.ll_env.common_step_counter
+
+    @common_step_counter.setter
+    def common_step_counter(self, value):
+        self.ll_env.common_step_counter = value
+
+    def begin_graph_capture(self):
+        """Several ``step_policy`` calls are about to be captured into one HIP graph: the step counter moves to the device."""
+        self.ll_env.begin_graph_capture()
+
+    def capture_extras_flush(self):
+        self.ll_env.capture_extras_flush()
+
+    def end_graph_capture(self, steps_captured: int):
+        self.ll_env.end_graph_capture(steps_captured)
 
     def reset_idx(self, env_ids):
         """Reset the listed envs from the host (reference :326-349): root state of the prey, predator placement, history.  Resets that

@@ -71,15 +71,25 @@ class FusedActor:
             self._out = (torch.empty(n, self.num_actions, device=self.device), torch.empty(n, self.num_actions, device=self.device))
         return self._out
 
+    def peek_step(self):
+        """``(step, step_counter)`` the next launch will use, without counting it: the shared device counter (step = -1), or this actor's
+        own host count.  A caller whose launch may be refused peeks, and calls ``next_step`` once the launch was accepted."""
+        if self.step_counter is not None:
+            return -1, self.step_counter.data_ptr()
+        return self._host_step + 1, None
+
+    def next_step(self):
+        """``peek_step`` and count the launch."""
+        step, ctr = self.peek_step()
+        if ctr is None:
+            self._host_step = step
+        return step, ctr
+
     def _call(self, obs, deterministic, want_mean):
         obs = obs if (obs.dtype == torch.float32 and obs.is_contiguous()) else obs.float().contiguous()
         n = obs.shape[0]
         actions, mean = self.output_buffers(n)
-        if self.step_counter is not None:
-            step, ctr = -1, self.step_counter.data_ptr()
-        else:
-            self._host_step += 1
-            step, ctr = self._host_step, None
+        step, ctr = self.next_step()
         rc = self.lib.lg_policy_act(self.handle, obs.data_ptr(), actions.data_ptr(), mean.data_ptr() if want_mean else None, n,
                                     self.seed, step, ctr, int(deterministic), torch.cuda.current_stream(self.device).cuda_stream)
         if rc != 0:
@@ -90,8 +100,8 @@ class FusedActor:
         """Sampled actions (ActorCritic.act)."""
         return self._call(obs, False, False)[0]
 
-    def act_with_mean(self, obs):
-        return self._call(obs, False, True)
+    def act_with_mean(self, obs, deterministic=False):
+        return self._call(obs, deterministic, True)
 
     def act_inference(self, obs):
         return self._call(obs, True, False)[0]

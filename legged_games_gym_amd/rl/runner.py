@@ -38,6 +38,20 @@ class OnPolicyRunner:
         """Rollouts with the MFMA actor (and, for the flat task, the actor fused into the step kernel) instead of torch ops;
         the critic, log-probs and the time-out bootstrap are then evaluated once per rollout on all T x N transitions."""
         env = self.env
+        self._game_rollout = False
+        if (self.cfg.get("device_rollout", False) and str(self.device).startswith("cuda") and hasattr(env, "ll_env")
+                and hasattr(env, "step_policy") and env.num_privileged_obs is None):
+            # high_level_game, opt-in: the high-level actor on the noise stream of the low-level sim's device step counter
+            from .fused_actor import FusedActor
+            try:
+                fused = FusedActor(self.alg.actor_critic, self.device, seed=int(getattr(env.cfg, "seed", 1)) + 7919,
+                                   step_counter=env.ll_env._sim.buf["step_counter"])
+                fused.act_inference(env.get_observations())   # a shape lg_policy_act refuses (rc -4) shows here, not in the first rollout
+            except Exception as exc:
+                print(f"[runner] device rollout unavailable ({type(exc).__name__}: {exc}); generic VecEnv loop")
+                return None
+            self._game_rollout = True
+            return fused
         if not (str(self.device).startswith("cuda") and self.cfg.get("fused_rollout", True) and hasattr(env, "_sim")
                 and env.num_privileged_obs is None):
             return None
@@ -174,9 +188,41 @@ class OnPolicyRunner:
         st.rewards.add_(alg.gamma * st.values * self._time_outs)                               # bootstrap on time-outs (PPO.process_env_step)
         return obs, obs
 
+    def _rollout_steps_game(self, stats):
+        """Device rollout of ``high_level_game``: per step ``env.step_policy`` (lg_game_act -> lg_step -> lg_game_post) and one
+        ``lg_rollout_record``; the critic once per rollout.  Storage semantics of the generic path: the reference clips the command in the
+        caller's tensor after ``PPO.act`` took the log-prob, so ``actions[t]`` is the clipped command while ``actions_log_prob[t]`` (and
+        ``sigma[t]``, both written by the actor launch straight into the storage) belong to the unclipped sample.  The game sends no
+        time-outs: nothing is bootstrapped."""
+        env, alg, fused = self.env, self.alg, self._fused
+        st, T = alg.storage, self.num_steps_per_env
+        obs = env.get_observations()
+        lib, step = fused.lib, capi.lg_rollout_step()
+        p = lambda x: x.data_ptr()
+        step.num_envs, step.num_obs, step.num_actions = env.num_envs, st.observations.shape[-1], st.actions.shape[-1]
+        step.cur_return, step.cur_length, step.sums = p(stats["cur_rew"]), p(stats["cur_len"]), p(stats["_sums"])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        step.std, step.time_outs, step.storage_time_outs = None, None, None
+        for t in range(T):
+            prev_obs = obs
+            (command, mean), (obs, _, rewards, dones, _) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t])
+            step.obs, step.actions, step.mean, step.rewards, step.dones = p(prev_obs), p(command), p(mean), p(rewards), p(dones)
+            step.storage_obs, step.storage_actions, step.storage_mu = p(st.observations[t]), p(st.actions[t]), p(st.mu[t])
+            step.storage_rewards, step.storage_dones = p(st.rewards[t]), p(st.dones[t])
+            step.storage_sigma, step.storage_log_prob = None, None
+            assert dones.element_size() == 1 and rewards.is_contiguous()
+            rc = lib.lg_rollout_record(step, stream)
+            if rc != 0:
+                raise RuntimeError(f"lg_rollout_record failed ({rc}): {lib.lg_last_error().decode()}")
+        st.step = T
+        st.values.copy_(self._critic_values(st).view(T, -1, 1))
+        return obs, obs
+
     # ------------------------------------------------------------------ graphed rollout
     def _rollout_steps(self, stats):
         """num_steps_per_env x (act -> env.step -> store); episode statistics as tensor ops (no host sync)."""
+        if self._fused is not None and self._game_rollout:
+            return self._rollout_steps_game(stats)
         if self._fused is not None:
             return self._rollout_steps_fused(stats)
         env, alg = self.env, self.alg
@@ -204,10 +250,11 @@ class OnPolicyRunner:
         and an even number of steps so the observation buffers line up between replays."""
         env = self.env
         ok = (str(self.device).startswith("cuda") and hasattr(env, "begin_graph_capture") and self.num_steps_per_env % 2 == 0
-              and self.cfg.get("graphed_rollout", True))
+              and self.cfg.get("graphed_rollout", True) and (hasattr(env, "_sim") or getattr(self, "_game_rollout", False)))
         if not ok:
             return None
         flip0, counter0 = getattr(env, "_obs_flip", 0), env.common_step_counter
+        ll_flip0 = getattr(getattr(env, "ll_env", None), "_obs_flip", 0)
         captured = False
         try:
             N, dev = env.num_envs, self.device
@@ -221,6 +268,7 @@ class OnPolicyRunner:
                     v.zero_()
                 torch.cuda.synchronize()
                 flip0, counter0 = env._obs_flip, env.common_step_counter
+                ll_flip0 = getattr(getattr(env, "ll_env", None), "_obs_flip", 0)
                 env.begin_graph_capture()
                 captured = True
                 graph = torch.cuda.CUDAGraph()
@@ -237,13 +285,19 @@ class OnPolicyRunner:
             print(f"[runner] graphed rollout unavailable ({type(exc).__name__}: {exc}); using eager steps")
             if hasattr(env, "_capturing"):
                 env._capturing = False
-                env._sim.set_deferred_extras(False)
+                getattr(env, "ll_env", env)._sim.set_deferred_extras(False)
             if captured:
                 # steps issued during a capture that failed part-way were counted but never executed: put the observation
                 # ping-pong and the step counter (push / resample / RNG phase) back where they were
                 env._obs_flip = flip0
                 env.obs_buf = env._obs_pair[flip0]
-                env._sim.set_obs_output(env.obs_buf)
+                if hasattr(env, "_sim"):
+                    env._sim.set_obs_output(env.obs_buf)
+                else:                                     # the game: its low-level env stepped (and flipped) along with it
+                    ll = env.ll_env
+                    ll._obs_flip = ll_flip0
+                    ll.obs_buf = ll._obs_pair[ll_flip0]
+                    ll._sim.set_obs_output(ll.obs_buf)
                 env.common_step_counter = counter0
             self.alg.storage.clear()
             return None
@@ -260,15 +314,22 @@ class OnPolicyRunner:
         cur_rew = torch.zeros(self.env.num_envs, dtype=torch.float, device=self.device)
         cur_len = torch.zeros(self.env.num_envs, dtype=torch.float, device=self.device)
         graphed = self._try_build_graphed_rollout()
+        if graphed is None and self._fused is not None and self._game_rollout:
+            # the game's device rollout without a graph (graphed_rollout = False, odd step count, failed capture): the same launches, eagerly
+            sums = torch.zeros(3, device=self.device)
+            graphed = (None, {"cur_rew": cur_rew, "cur_len": cur_len, "sum_rew": sums[0], "sum_len": sums[1], "count": sums[2], "_sums": sums}, obs, cobs)
         last = self.current_learning_iteration + num_learning_iterations
         for it in range(self.current_learning_iteration, last):
             t0 = time.time()
             if graphed is not None:
                 graph, stats, obs, cobs = graphed
                 with torch.inference_mode():
-                    graph.replay()
-                    self.env.common_step_counter += self.num_steps_per_env
-                    self.alg.storage.step = self.num_steps_per_env
+                    if graph is not None:
+                        graph.replay()
+                        self.env.common_step_counter += self.num_steps_per_env
+                        self.alg.storage.step = self.num_steps_per_env
+                    else:
+                        obs, cobs = self._rollout_steps(stats)
                     if self.log_dir is not None:
                         s_rew, s_len, cnt = (float(v) for v in torch.stack((stats["sum_rew"], stats["sum_len"], stats["count"])).cpu())
                         if cnt > 0:

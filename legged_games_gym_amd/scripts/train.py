@@ -6,7 +6,10 @@ Multi-GPU (new, the reference is single-process): launch one process per GPU,
 --task=anymal_c_rough --headless``.  Every rank owns its own ``num_envs`` environments on ``cuda:LOCAL_RANK`` (env seed
 = registered seed + rank), the policy is replicated (rank 0's initial weights are broadcast) and kept identical by the
 collectives of ``rl/ppo.py`` (RCCL: all-gather of returns/advantages, gradient and mean-KL all-reduce); only rank 0 writes logs
-and checkpoints."""
+and checkpoints.
+
+``--task=high_level_game --device_rollout`` trains the game on its device path: the high-level actor on the matrix cores, three launches
+per step, the whole rollout one graph replay (off by default: the generic VecEnv loop)."""
 import os
 
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
@@ -39,6 +42,8 @@ def train(args):
     if args.task in a1_game.TASKS:
         a1_game.register()               # the game layer registers on demand: python -m legged_games_gym_amd.scripts.train --task=high_level_game --headless
     rank, world = _init_distributed(args)
+    if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
+        task_registry.get_cfgs(args.task)[1].runner.device_rollout = True
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)

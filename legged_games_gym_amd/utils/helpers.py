@@ -164,6 +164,9 @@ def get_args(argv=None):
     p.add_argument("--num_envs", type=int)
     p.add_argument("--seed", type=int)
     p.add_argument("--max_iterations", type=int)
+    p.add_argument("--device_rollout", action="store_true", default=False,
+                   help="high_level_game: train on the device rollout (runner key of the same name: MFMA high-level actor, three launches per step, one graph "
+                        "replay per rollout); an actor shape the kernels refuse falls back to the generic loop with a message")
     # flags gymutil.parse_arguments contributes
     p.add_argument("--sim_device", type=str, default="cuda:0")
     p.add_argument("--pipeline", type=str, default="gpu")

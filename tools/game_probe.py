@@ -9,6 +9,15 @@ Times, with device events around >= 2000 replays after warm-up, alternating in o
 Writes profiles/game_step.json (or --out): the three times per repeat, their spread over the repeats, the overhead (a) - (b) and the
 env-steps/s of (a).  ``--trace`` runs a short replay loop only, for ``rocprofv3 --kernel-trace --stats -- python tools/game_probe.py --trace``.
 
+``--policy-step`` times the device path of the high-level actor instead and writes profiles/game_policy_step.json (game_step.json is left alone):
+  (p) the three-launch graph (``make_graphed_policy_step``): lg_game_act, k_step, k_game_post;
+  (a) the graphed step with the torch actor, as above;
+  (s) the five-launch graph with both actors on lg_policy_act: ``make_graphed_step(fused.act)``: lg_policy_act, k_game_pre, lg_policy_act, k_step, k_game_post;
+then the step as the runner's device rollout captures it (two ``step_policy`` calls per graph, the observations alternating between two buffers),
+per step, with the copy of the observations written by the actor launch and with an ``obs_buf.copy_`` kernel in front of it;
+and, unless ``--train-iterations 0``, PPO training of the registered task with the runner's ``device_rollout`` on and off (env-steps/s including the
+update, same seed and size).  With ``--trace`` it replays (p) only.
+
 The low-level policy is a seeded random-init checkpoint written to a temporary directory: the kernels' cost does not depend on the weights."""
 import argparse
 import json
@@ -21,6 +30,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
 sys.path.insert(0, REPO)
 
 import torch  # noqa: E402
+
+
+DEFAULT_OUT = os.path.join(REPO, "profiles", "game_step.json")
 
 
 def make_env(n, mesh, tmp):
@@ -77,6 +89,127 @@ def graph_low_level_only(env, warmup=3):
     return replay
 
 
+def fused_high_level_actor(env):
+    """The probe's random-init 19-512-256-128-6 actor on the MFMA kernels, its noise keyed by the low-level sim's device step counter."""
+    from legged_games_gym_amd.rl import ActorCritic, FusedActor
+    torch.manual_seed(1)
+    hl = ActorCritic(env.num_obs, env.num_obs, env.num_actions, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128]).to("cuda:0").eval()
+    return FusedActor(hl, "cuda:0", seed=7, step_counter=env.ll_env._sim.buf["step_counter"])
+
+
+def graph_rollout_steps(env, fused, steps, separate_copy):
+    """``steps`` (even) ``step_policy`` calls captured the way the runner's device rollout captures them: the observations alternate
+    between the two buffers, the actor launch carrying them over.  ``separate_copy``: ``obs_out.copy_(obs_in)`` in front of an actor launch
+    that reads and writes ``obs_out`` instead -- what the in-launch copy replaces.  Returns a callable that replays the ``steps`` steps."""
+    if separate_copy:
+        act = env._act
+
+        def copy_then_act(fa, obs_in, obs_out, *a, **k):
+            if obs_out is not obs_in:
+                obs_out.copy_(obs_in)
+            return act(fa, obs_out, obs_out, *a, **k)
+        env._act = copy_then_act
+    try:
+        for _ in range(steps):
+            env.step_policy(fused)
+        torch.cuda.synchronize()
+        env.begin_graph_capture()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            for _ in range(steps):
+                env.step_policy(fused)
+            env.capture_extras_flush()
+        env.end_graph_capture(steps)
+    finally:
+        if separate_copy:
+            del env._act
+
+    def replay():
+        graph.replay()
+        env.common_step_counter += steps
+    return replay
+
+
+def train_steps_per_s(n, mesh, tmp, device_rollout, iterations, warm=2):
+    """env-steps/s of ``OnPolicyRunner.learn`` on high_level_game (rollout + update), after ``warm`` iterations that build graphs and workspaces."""
+    import time
+    from legged_games_gym_amd.envs import a1_game, task_registry
+    from legged_games_gym_amd.utils import get_args
+    a1_game.register()
+    try:
+        env_cfg, train_cfg = task_registry.get_cfgs("high_level_game")
+        env_cfg.env.ll_policy_path, env_cfg.terrain.mesh_type = os.path.join(tmp, "model_0.pt"), mesh
+        if device_rollout:
+            train_cfg.runner.device_rollout = True
+        args = get_args(["--task", "high_level_game", "--num_envs", str(n), "--headless", "--sim_device", "cuda:0", "--rl_device", "cuda:0", "--seed", "1"])
+        env, _ = task_registry.make_env("high_level_game", args)
+        torch.manual_seed(1)
+        runner, _ = task_registry.make_alg_runner(env, "high_level_game", args, log_root=None)
+        runner.learn(num_learning_iterations=warm)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        runner.learn(num_learning_iterations=iterations)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        assert (runner._fused is not None) == bool(device_rollout)
+        return iterations * runner.num_steps_per_env * n / dt
+    finally:
+        a1_game.unregister()
+
+
+def policy_step_main(args):
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.replays, "repeats": args.repeats, "envs": {}, "training": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            env, policy = make_env(n, args.mesh, tmp)
+            fused = fused_high_level_actor(env)
+            shared = env.make_graphed_policy_step(fused)
+            if args.trace:
+                for _ in range(200):
+                    shared()
+                torch.cuda.synchronize()
+                continue
+            torch_actor = env.make_graphed_step(policy)
+            separate = env.make_graphed_step(fused.act)
+            for fn in (shared, torch_actor, separate):
+                timed(fn, 200)
+            p, a, s = [], [], []
+            for _ in range(args.repeats):              # alternating: other work shares the machine
+                p.append(timed(shared, args.replays))
+                a.append(timed(torch_actor, args.replays))
+                s.append(timed(separate, args.replays))
+            result["envs"][str(n)] = {"graphed_policy_step": spread(p), "graphed_step_torch_actor": spread(a), "graphed_step_separate_actor_launches": spread(s),
+                                      "env_steps_per_s_graphed_policy_step": n / (statistics.median(p) * 1e-6)}
+            assert torch.isfinite(env.obs_buf).all() and torch.isfinite(env.ll_env.root_states).all()
+            print(f"{n} envs: three launches {statistics.median(p):.1f} us, torch actor "
+                  f"{statistics.median(a):.1f} us, separate actor launches {statistics.median(s):.1f} us", flush=True)
+            # the rollout's form of the step (observations ping-pong): the copy inside the actor launch against a copy kernel in front of it
+            in_launch, copy_kernel = graph_rollout_steps(env, fused, 2, False), graph_rollout_steps(env, fused, 2, True)
+            for fn in (in_launch, copy_kernel):
+                timed(fn, 100)
+            ci, ck = [], []
+            for _ in range(args.repeats):
+                ci.append(timed(in_launch, args.replays // 2) / 2)
+                ck.append(timed(copy_kernel, args.replays // 2) / 2)
+            result["envs"][str(n)]["rollout_step_copy_in_actor_launch"] = spread(ci)
+            result["envs"][str(n)]["rollout_step_separate_copy_kernel"] = spread(ck)
+            assert torch.isfinite(env.obs_buf).all() and torch.isfinite(env.ll_env.root_states).all()
+            print(f"{n} envs, per step of a captured two-step rollout: copy in the actor launch {statistics.median(ci):.1f} us, "
+                  f"copy kernel + actor launch {statistics.median(ck):.1f} us", flush=True)
+        if not args.trace and args.train_iterations > 0:
+            n = args.envs[0]
+            for key, on in (("device_rollout_off", False), ("device_rollout_on", True)):
+                result["training"][key] = {"envs": n, "iterations": args.train_iterations,
+                                           "env_steps_per_s": train_steps_per_s(n, args.mesh, tmp, on, args.train_iterations)}
+                print(f"training, {n} envs, {key}: {result['training'][key]['env_steps_per_s']:.0f} env-steps/s", flush=True)
+    if not args.trace:
+        out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "game_policy_step.json")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        with open(out, "w") as fh:
+            json.dump(result, fh, indent=1)
+        print("wrote", out)
+
+
 def timed(fn, count):
     """Mean microseconds per call of ``fn`` over ``count`` calls, device events around the whole window."""
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -99,11 +232,15 @@ def main():
     ap.add_argument("--replays", type=int, default=2000)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--mesh", default="trimesh", help="terrain of the low-level env (the registered task: trimesh)")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "game_step.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--policy-step", action="store_true", help="time the device path of the high-level actor; writes profiles/game_policy_step.json")
+    ap.add_argument("--train-iterations", type=int, default=10, help="--policy-step: timed PPO iterations per setting of the runner switch (0: skip)")
     ap.add_argument("--trace", action="store_true", help="a short loop of graph replays only (for a kernel trace)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("game_probe needs an AMD GPU: there is nothing to time on the CPU")
+    if args.policy_step:
+        return policy_step_main(args)
     result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.replays, "repeats": args.repeats, "envs": {}}
     with tempfile.TemporaryDirectory() as tmp:
         for n in args.envs:
