@@ -395,6 +395,95 @@ def game_post(params: lg_game_params, buffers: lg_game_buffers, common_step_coun
     if rc != 0:
         raise RuntimeError(f"lg_game_post failed ({rc}): {lib.lg_last_error().decode()}")
 
+# ----------------------------------------------------------------------------- decentralised game (include/legged_dec_game.h)
+LG_DEC_NUM_OBS_PREY, LG_DEC_NUM_OBS_PRED, LG_DEC_NUM_ACTIONS_PREY, LG_DEC_NUM_ACTIONS_PRED, LG_DEC_NUM_SUMS = 16, 3, 4, 2, 3
+_PU32 = C.POINTER(u32)
+
+
+class lg_dec_game_params(C.Structure):
+    """include/legged_dec_game.h: lg_dec_game_params (passed by value in the kernel arguments)."""
+    _fields_ = [
+        ("num_envs", i32), ("decimation", i32), ("heading_command", i32), ("custom_origins", i32),
+        ("only_positive_rewards_prey", i32), ("only_positive_rewards_pred", i32), ("max_episode_length", i32), ("_pad0", i32), ("seed", u64),
+        ("cmd_lin_vel_x", f32 * 2), ("cmd_lin_vel_y", f32 * 2), ("predator_lin_vel_x", f32 * 2), ("predator_lin_vel_y", f32 * 2),
+        ("capture_dist", f32), ("half_fov", f32), ("max_rel_pos", f32), ("ll_rew_weight", f32),
+        ("scale_evasion_dt", f32), ("scale_pursuit_dt", f32), ("scale_termination_prey_dt", f32), ("sim_dt", f32),
+        ("predator_z", f32), ("max_episode_length_s", f32), ("base_init_state", f32 * 13), ("_pad1", f32), ("default_dof_pos", f32 * LG_MAX_DOF),
+    ]
+
+
+class lg_dec_game_buffers(C.Structure):
+    """include/legged_dec_game.h: lg_dec_game_buffers (raw device pointers)."""
+    _fields_ = [
+        ("command_prey", _PF), ("command_pred", _PF), ("ll_root_states", _PF), ("ll_dof_state", _PF), ("ll_commands", _PF), ("ll_env_origins", _PF),
+        ("ll_rew_buf", _PF), ("ll_reset_buf", _PU8), ("ll_step_counter", _PI64),
+        ("predator_pos", _PF), ("obs_prey", _PF), ("obs_pred", _PF), ("rew_prey", _PF), ("rew_pred", _PF), ("reset_buf", _PU8), ("time_out_buf", _PU8),
+        ("curr_episode_step", _PI64), ("episode_length_buf", _PI64), ("episode_sums", _PF), ("episode_means", _PF), ("extras_accum", _PF),
+        ("extras_ticket", _PU32),
+    ]
+
+
+DEC_GAME_BUFFER_FIELDS = [name for name, _ in lg_dec_game_buffers._fields_]
+DEC_GAME_SYMBOLS = ["lg_dec_game_pre", "lg_dec_game_post", "lg_dec_game_act", "lg_dec_game_sizeof"]
+
+
+class lg_dec_act_outputs(C.Structure):
+    """include/legged_dec_game.h: lg_dec_act_outputs (optional per-agent outputs of lg_dec_game_act; device addresses or None)."""
+    _fields_ = [("sample", C.c_void_p), ("sigma", C.c_void_p), ("log_prob", C.c_void_p), ("obs_copy", C.c_void_p)]
+
+
+def bind_dec_game_prototypes(lib):
+    """Attach argtypes/restype for the entry points of legged_dec_game.h and check the struct layouts."""
+    vp = C.c_void_p
+    lib.lg_dec_game_pre.argtypes, lib.lg_dec_game_pre.restype = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), vp], C.c_int
+    lib.lg_dec_game_post.argtypes, lib.lg_dec_game_post.restype = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), i64, vp], C.c_int
+    lib.lg_dec_game_act.argtypes = [vp, vp, vp, C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), vp, vp, vp, vp, vp, vp, u64, u64, i64, vp, i32, i32,
+                                    C.POINTER(lg_dec_act_outputs), C.POINTER(lg_dec_act_outputs), vp]
+    lib.lg_dec_game_act.restype = C.c_int
+    lib.lg_dec_game_sizeof.argtypes, lib.lg_dec_game_sizeof.restype = [C.c_int], C.c_int
+    for which, st in enumerate((lg_dec_game_params, lg_dec_game_buffers, lg_dec_act_outputs)):
+        if lib.lg_dec_game_sizeof(which) != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {lib.lg_dec_game_sizeof(which)} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def dec_game_buffers(pointers: Dict[str, int]) -> lg_dec_game_buffers:
+    """``lg_dec_game_buffers`` from a name -> device address table (missing names stay null)."""
+    b = lg_dec_game_buffers()
+    types = dict(lg_dec_game_buffers._fields_)
+    for name in DEC_GAME_BUFFER_FIELDS:
+        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
+    return b
+
+
+def dec_game_pre(params: lg_dec_game_params, buffers: lg_dec_game_buffers, stream: int = 0):
+    lib = load_library()
+    rc = lib.lg_dec_game_pre(C.byref(params), C.byref(buffers), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_game_pre failed ({rc}): {lib.lg_last_error().decode()}")
+
+
+def dec_game_act(pred_policy, prey_policy, ll_policy, params: lg_dec_game_params, buffers: lg_dec_game_buffers, pred_obs: int, prey_obs: int, ll_obs: int,
+                 ll_actions: int, mean_pred: int, mean_prey: int, seed_pred: int, seed_prey: int, step: int, step_counter: Optional[int],
+                 deterministic_pred: bool, deterministic_prey: bool, out_pred: Optional[lg_dec_act_outputs] = None,
+                 out_prey: Optional[lg_dec_act_outputs] = None, stream: int = 0) -> int:
+    """``lg_dec_game_act``: the three actors of a step and the command clips in one launch.  Returns 0, or -4 when the actor triple / wide
+    precision has no shared kernel (the caller then issues ``lg_policy_act`` x 3 + ``lg_dec_game_pre``); raises on any other error."""
+    lib = load_library()
+    rc = lib.lg_dec_game_act(pred_policy, prey_policy, ll_policy, C.byref(params), C.byref(buffers), pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey,
+                             int(seed_pred), int(seed_prey), int(step), step_counter, int(bool(deterministic_pred)), int(bool(deterministic_prey)),
+                             C.byref(out_pred) if out_pred is not None else None, C.byref(out_prey) if out_prey is not None else None, stream)
+    if rc not in (0, -4):
+        raise RuntimeError(f"lg_dec_game_act failed ({rc}): {lib.lg_last_error().decode()}")
+    return rc
+
+
+def dec_game_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, common_step_counter: int, stream: int = 0):
+    lib = load_library()
+    rc = lib.lg_dec_game_post(C.byref(params), C.byref(buffers), int(common_step_counter), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_game_post failed ({rc}): {lib.lg_last_error().decode()}")
+
 
 def load_library():
     """Load the HIP extension or fail loudly -- never a CPU substitute."""
@@ -406,7 +495,7 @@ def load_library():
         raise RuntimeError(
             f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_"))
+    _lib = bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_")))
     if _lib.lg_abi_version() != LG_ABI_VERSION:
         raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
     return _lib

@@ -1,0 +1,75 @@
+// lg_dec_game.h -- C entry points of the decentralised predator-prey game (include/legged_dec_game.h).  Host code only: the kernels live in
+// lg_dec_game.hip behind the launchers of lg_dec_game_common.h.  Included from lg_kernels.hip after its error helpers (fail / HIP_TRY).
+#pragma once
+#include "lg_dec_game_common.h"
+
+extern "C" {
+
+static int dec_game_check(const lg_dec_game_params *P, const lg_dec_game_buffers *B) {
+    if (!P || !B) return fail(-1, "null argument");
+    if (P->num_envs < 1 || P->decimation < 0) return fail(-2, "lg_dec_game_params: num_envs must be >= 1 and decimation >= 0");
+    return 0;
+}
+
+int lg_dec_game_pre(const lg_dec_game_params *P, const lg_dec_game_buffers *B, void *stream) {
+    if (int rc = dec_game_check(P, B)) return rc;
+    if (!B->command_prey || !B->command_pred || !B->ll_commands) return fail(-1, "lg_dec_game_pre needs command_prey, command_pred and ll_commands");
+    HIP_TRY((hipError_t)lg::launch_dec_pre(*P, *B, stream));
+    return 0;
+}
+
+int lg_dec_game_post(const lg_dec_game_params *P, const lg_dec_game_buffers *B, int64_t common_step_counter, void *stream) {
+    if (int rc = dec_game_check(P, B)) return rc;
+    if (!B->command_pred || !B->ll_root_states || !B->ll_dof_state || !B->ll_env_origins || !B->ll_rew_buf || !B->ll_reset_buf || !B->predator_pos ||
+        !B->obs_prey || !B->obs_pred || !B->rew_prey || !B->rew_pred || !B->reset_buf || !B->time_out_buf || !B->curr_episode_step ||
+        !B->episode_length_buf || !B->episode_sums || !B->episode_means || !B->extras_accum || !B->extras_ticket)
+        return fail(-1, "lg_dec_game_post: a buffer pointer is null");
+    if (!(P->max_episode_length_s > 0.0f)) return fail(-2, "lg_dec_game_params: max_episode_length_s must be positive");
+    if (common_step_counter < 0 && !B->ll_step_counter) return fail(-9, "common_step_counter = -1 needs the low-level step_counter buffer");
+    HIP_TRY((hipError_t)lg::launch_dec_post(*P, *B, common_step_counter, stream));
+    return 0;
+}
+
+int lg_dec_game_act(lg_policy *pred, lg_policy *prey, lg_policy *ll, const lg_dec_game_params *P, const lg_dec_game_buffers *B, const float *pred_obs,
+                    const float *prey_obs, const float *ll_obs, float *ll_actions, float *mean_pred, float *mean_prey, uint64_t seed_pred, uint64_t seed_prey,
+                    int64_t step, const int64_t *step_counter, int32_t deterministic_pred, int32_t deterministic_prey, const lg_dec_act_outputs *out_pred,
+                    const lg_dec_act_outputs *out_prey, void *stream) {
+    if (int rc = dec_game_check(P, B)) return rc;
+    if (!pred || !prey || !ll || !pred_obs || !prey_obs || !ll_obs || !ll_actions || !mean_pred || !mean_prey) return fail(-1, "null argument");
+    if (!B->command_prey || !B->command_pred || !B->ll_commands) return fail(-1, "lg_dec_game_act needs command_prey, command_pred and ll_commands");
+    const bool prey_ok = prey->wide && prey->dims[0] == LG_DEC_NUM_OBS_PREY && prey->dims[4] == LG_DEC_NUM_ACTIONS_PREY;
+    const bool pred_ok = pred->wide && pred->dims[0] == LG_DEC_NUM_OBS_PRED && pred->dims[4] == LG_DEC_NUM_ACTIONS_PRED;
+    const bool ll_ok = ll->wide && ll->tiles[0] == 15;
+    if (g_wide_precision != 1 || !prey_ok || !pred_ok || !ll_ok)
+        return fail(-4, "the shared actor launch is compiled for the 3-512-256-128-2 / 16-512-256-128-4 / 235-512-256-128 triple at wide precision 1; use lg_policy_act x 3 + lg_dec_game_pre");
+    if (seed_pred == seed_prey) return fail(-2, "lg_dec_game_act: seed_pred and seed_prey must differ (the sampled roles share their noise purposes)");
+    const lg_dec_act_outputs none = {nullptr, nullptr, nullptr, nullptr};
+    const lg_dec_act_outputs &op = out_pred ? *out_pred : none, &oy = out_prey ? *out_prey : none;
+    lg::DecActArgs g;
+    fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed_prey, step, step_counter, 1);
+    fill_policy_args(prey, g.prey.base, prey_obs, oy.sample, mean_prey, P->num_envs, seed_prey, step, step_counter, deterministic_prey);
+    fill_policy_args(pred, g.pred.base, pred_obs, op.sample, mean_pred, P->num_envs, seed_pred, step, step_counter, deterministic_pred);
+    for (int i = 0; i < 4; i++) {
+        g.ll.wb[i] = reinterpret_cast<const lg::bf16x8g *>(ll->d_wb[i]); g.ll.bb[i] = ll->d_bb[i];
+        g.prey.wb[i] = reinterpret_cast<const lg::bf16x8g *>(prey->d_wb[i]); g.prey.bb[i] = prey->d_bb[i];
+        g.pred.wb[i] = reinterpret_cast<const lg::bf16x8g *>(pred->d_wb[i]); g.pred.bb[i] = pred->d_bb[i];
+    }
+    g.P = *P;
+    g.a_prey = {B->command_prey, oy.sigma, oy.log_prob, oy.obs_copy};
+    g.a_pred = {B->command_pred, op.sigma, op.log_prob, op.obs_copy};
+    g.ll_commands = B->ll_commands;
+    g.blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;
+    HIP_TRY((hipError_t)lg::launch_dec_act(g, stream));
+    return 0;
+}
+
+int lg_dec_game_sizeof(int which) {
+    switch (which) {
+        case 0: return (int)sizeof(lg_dec_game_params);
+        case 1: return (int)sizeof(lg_dec_game_buffers);
+        case 2: return (int)sizeof(lg_dec_act_outputs);
+        default: return -1;
+    }
+}
+
+}  // extern "C"

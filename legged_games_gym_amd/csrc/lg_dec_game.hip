@@ -1,0 +1,371 @@
+// lg_dec_game.hip -- the kernels of the decentralised predator-prey game (include/legged_dec_game.h): k_dec_pre / k_dec_post, and the
+// lg_policy_act instantiations for actors with one input tile (the 16-input prey actor, the 3-input predator actor).  A translation unit of
+// its own, reached through the launchers of lg_dec_game_common.h, so that the code hipcc generates for the kernels of lg_kernels.hip does
+// not depend on it (see lg_game.h).  The C entry points are in lg_dec_game.h (lg_kernels.hip).
+//
+// Floating point: contraction is OFF in k_dec_pre / k_dec_post, every expression rounds once per operation in the order written, so the
+// results are bit-comparable with the NumPy float32 restatement (tests/dec_game_twin.py) except behind sqrtf / acosf (1 ulp on this build)
+// and in the episode means, whose summation order over workgroups is not fixed.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define LG_POLICY_BLOCKS_ONLY      // lg_policy.h without its two non-template pack kernels (they belong to lg_kernels.hip)
+#include "lg_device.h"
+#include "lg_policy.h"
+#include "lg_game_common.h"
+#include "lg_dec_game_common.h"
+
+namespace lg {
+
+enum { RNG_DEC_ROOT = 16, RNG_DEC_PREDATOR = 17, RNG_GAME_DOF = 18 };      // Philox purposes: root and predator as k_game_post (lg_game.h), the joints new
+#define LG_DEC_BLOCK 256
+
+__global__ __launch_bounds__(LG_DEC_BLOCK) void k_dec_pre(lg_dec_game_params P, lg_dec_game_buffers B) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * LG_DEC_BLOCK + threadIdx.x;
+    if (e >= P.num_envs) return;
+    float *c = B.command_prey + (size_t)e * LG_DEC_NUM_ACTIONS_PREY;
+    const float c0 = game_clip(c[0], P.cmd_lin_vel_x[0], P.cmd_lin_vel_x[1]);                 // (:182-183)
+    const float c1 = game_clip(c[1], P.cmd_lin_vel_y[0], P.cmd_lin_vel_y[1]);
+    const float c2 = P.heading_command ? game_wrap_to_pi(c[2]) : c[2];                        // (:185) column 2, as the reference
+    const float c3 = c[3];
+    c[0] = c0; c[1] = c1; c[2] = c2;
+    float *ll = B.ll_commands + (size_t)e * 4;                                                // (:195)
+    ll[0] = c0; ll[1] = c1; ll[2] = c2; ll[3] = c3;
+    float *d = B.command_pred + (size_t)e * LG_DEC_NUM_ACTIONS_PRED;                          // (:188-189)
+    const float d0 = game_clip(d[0], P.predator_lin_vel_x[0], P.predator_lin_vel_x[1]);
+    const float d1 = game_clip(d[1], P.predator_lin_vel_y[0], P.predator_lin_vel_y[1]);
+    d[0] = d0; d[1] = d1;
+}
+
+// One env of post_physics_step (:236-258).  red = (1, evasion sum, pursuit sum, termination sum) of a done env as the sums stood before
+// zeroing (:301-305), untouched otherwise.
+LG_DEV void dec_post_env(const lg_dec_game_params &P, const lg_dec_game_buffers &B, const int e, const int64_t step, float (&red)[4]) {
+#pragma clang fp contract(off)
+    const size_t N = (size_t)P.num_envs;
+    float *root = B.ll_root_states + (size_t)e * 13;
+    float *pp = B.predator_pos + (size_t)e * 3;
+    float *obs = B.obs_prey + (size_t)e * LG_DEC_NUM_OBS_PREY;
+    const float *org = B.ll_env_origins + (size_t)e * 3;
+
+    int64_t ep_len = B.episode_length_buf[e] + 1;                                             // (:243)
+    int64_t ep_step = B.curr_episode_step[e] + 1;                                             // (:244)
+
+    // step_predator_single_integrator (:228-230)
+    float px = pp[0], py = pp[1], pz = pp[2];
+    const float vx = B.command_pred[(size_t)e * LG_DEC_NUM_ACTIONS_PRED], vy = B.command_pred[(size_t)e * LG_DEC_NUM_ACTIONS_PRED + 1];
+    const float dx = P.sim_dt * vx, dy = P.sim_dt * vy;
+    for (int i = 0; i < P.decimation; i++) { px = px + dx; py = py + dy; }
+
+    float qx = root[0], qy = root[1], qz = root[2];                                           // prey_states[:, :3]
+    float quat_z = root[5], quat_w = root[6];
+
+    // check_termination (:263-269)
+    const float ax = qx - px, ay = qy - py;
+    const bool capture = sqrtf(ax * ax + ay * ay) < P.capture_dist;
+    const bool time_out = ep_len > (int64_t)P.max_episode_length;
+    bool done = capture || time_out;
+
+    // compute_reward_prey (:321-341), compute_reward_pred (:344-361)
+    float sum_ev = B.episode_sums[e], sum_pu = B.episode_sums[N + e], sum_te = B.episode_sums[2 * N + e];
+    {
+        const float rx = px - qx, ry = py - qy, rz = pz - qz;
+        const float d = sqrtf((rx * rx + ry * ry) + rz * rz);
+        const float ev = d * P.scale_evasion_dt, pu = (-d) * P.scale_pursuit_dt;
+        float rew = P.ll_rew_weight * B.ll_rew_buf[e];
+        rew = rew + ev;
+        sum_ev = sum_ev + ev;
+        if (P.only_positive_rewards_prey) rew = fmaxf(rew, 0.0f);
+        if (P.scale_termination_prey_dt != 0.0f) {                                            // after the clip; reset_buf * ~time_out_buf BEFORE the low-level resets join
+            const float te = ((done && !time_out) ? 1.0f : 0.0f) * P.scale_termination_prey_dt;
+            rew = rew + te;
+            sum_te = sum_te + te;
+        }
+        B.rew_prey[e] = rew;
+        float rp = 0.0f + pu;
+        sum_pu = sum_pu + pu;
+        if (P.only_positive_rewards_pred) rp = fmaxf(rp, 0.0f);
+        B.rew_pred[e] = rp;
+    }
+    done = done || B.ll_reset_buf[e] != 0;                                                    // (:252)
+
+    float o9 = obs[9], o10 = obs[10], o11 = obs[11];                                           // newest sensed position
+    float h[6] = {obs[3], obs[4], obs[5], obs[6], obs[7], obs[8]};
+    float f13 = obs[13], f14 = obs[14], f15 = obs[15];
+    if (done) {
+        red[0] = 1.0f; red[1] = sum_ev; red[2] = sum_pu; red[3] = sum_te;                     // (:300-305)
+        sum_ev = 0.0f; sum_pu = 0.0f; sum_te = 0.0f;
+        // LowLevelGame._reset_dofs (low_level_game.py:391-392): joint j draws lane j & 3 of block j >> 2
+        float2 *ds = reinterpret_cast<float2 *>(B.ll_dof_state) + (size_t)e * LG_DEC_NUM_DOF;
+#pragma unroll
+        for (int b = 0; b < LG_DEC_NUM_DOF / 4; b++) {
+            float uj[4];
+            rand4(P.seed, e, step, RNG_GAME_DOF, b, uj);
+#pragma unroll
+            for (int l = 0; l < 4; l++) ds[4 * b + l] = make_float2(P.default_dof_pos[4 * b + l] * game_urange(0.5f, 1.5f, uj[l]), 0.0f);
+        }
+        // LowLevelGame._reset_root_states (low_level_game.py:409-432), as k_game_post
+        float u[4], v[4], w[4];
+        rand4(P.seed, e, step, RNG_DEC_ROOT, 0, u);
+        rand4(P.seed, e, step, RNG_DEC_ROOT, 1, v);
+        rand4(P.seed, e, step, RNG_DEC_PREDATOR, 0, w);
+        float r[13];
+#pragma unroll
+        for (int i = 0; i < 13; i++) r[i] = P.base_init_state[i];
+        r[0] = r[0] + org[0]; r[1] = r[1] + org[1]; r[2] = r[2] + org[2];
+        if (P.custom_origins) { r[0] = r[0] + game_urange(-1.0f, 1.0f, u[0]); r[1] = r[1] + game_urange(-1.0f, 1.0f, u[1]); }
+        r[7] = game_urange(-0.5f, 0.5f, u[2]); r[8] = game_urange(-0.5f, 0.5f, u[3]);
+        r[9] = game_urange(-0.5f, 0.5f, v[0]); r[10] = game_urange(-0.5f, 0.5f, v[1]);
+        r[11] = game_urange(-0.5f, 0.5f, v[2]); r[12] = game_urange(-0.5f, 0.5f, v[3]);
+#pragma unroll
+        for (int i = 0; i < 13; i++) root[i] = r[i];
+        qx = r[0]; qy = r[1]; qz = r[2]; quat_z = r[5]; quat_w = r[6];
+        const float sgn = w[3] < 0.5f ? -1.0f : 1.0f;                                          // (:422-424)
+        px = qx - sgn * game_urange(1.0f, 10.0f, w[0]);
+        py = qy - sgn * game_urange(1.0f, 10.0f, w[1]);
+        pz = P.predator_z;                                                                    // (:432); the z offset w[2] is drawn and overwritten
+        // DecHighLevelGame.reset_idx (:291-296)
+        o9 = o10 = o11 = P.max_rel_pos;
+#pragma unroll
+        for (int i = 0; i < 6; i++) h[i] = P.max_rel_pos;
+        f13 = f14 = f15 = 0.0f;
+        ep_len = 0;
+        ep_step = 0;
+    }
+    B.episode_length_buf[e] = ep_len;
+    B.curr_episode_step[e] = ep_step;
+    B.reset_buf[e] = done ? 1 : 0;
+    B.time_out_buf[e] = time_out ? 1 : 0;
+    B.episode_sums[e] = sum_ev; B.episode_sums[N + e] = sum_pu; B.episode_sums[2 * N + e] = sum_te;
+    pp[0] = px; pp[1] = py; pp[2] = pz;
+
+    // compute_observations_pred (:389-391), prey_sense_predator (:417-448) + compute_observations_prey (:374-380); the occlusion test as k_game_post
+    float *op = B.obs_pred + (size_t)e * LG_DEC_NUM_OBS_PRED;
+    op[0] = qx - px; op[1] = qy - py; op[2] = qz - pz;
+    const float rx = px - qx, ry = py - qy, rz = pz - qz;
+    const float qn = fmaxf(sqrtf(quat_z * quat_z + quat_w * quat_w), 1e-9f);                  // quat_apply_yaw: normalize((0, 0, z, w))
+    const float yz = quat_z / qn, yw = quat_w / qn;
+    const float tz = yz * 2.0f;                                                               // quat_apply(q_yaw, (1, 0, 0))
+    const float fx = 1.0f - yz * tz, fy = yw * tz;
+    const float dotv = fx * rx + fy * ry;
+    const float denom = sqrtf(fx * fx + fy * fy) * sqrtf((rx * rx + ry * ry) + rz * rz);
+    const float angle = game_wrap_to_pi(acosf(dotv / denom));
+    const bool visible = fabsf(angle) <= P.half_fov;                                          // NaN (0/0) compares false: occluded
+    obs[0] = h[0]; obs[1] = h[1]; obs[2] = h[2]; obs[3] = h[3]; obs[4] = h[4]; obs[5] = h[5];
+    obs[6] = o9; obs[7] = o10; obs[8] = o11;
+    obs[9] = visible ? rx : o9; obs[10] = visible ? ry : o10; obs[11] = visible ? rz : o11;
+    obs[12] = f13; obs[13] = f14; obs[14] = f15; obs[15] = visible ? 1.0f : 0.0f;
+}
+
+__global__ __launch_bounds__(LG_DEC_BLOCK) void k_dec_post(lg_dec_game_params P, lg_dec_game_buffers B, int64_t step_arg) {
+#pragma clang fp contract(off)
+    __shared__ float s_part[LG_DEC_BLOCK / 64][4];
+    const int e = blockIdx.x * LG_DEC_BLOCK + threadIdx.x;
+    float red[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (e < P.num_envs) dec_post_env(P, B, e, step_arg >= 0 ? step_arg : B.ll_step_counter[0], red);
+    // extras["episode"] (:298-305): count and episode sums of this workgroup's done envs -> one atomic per value -> the workgroup with the
+    // last ticket publishes the means and leaves accumulator and ticket zeroed for the next launch
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) red[i] += __shfl_xor(red[i], o);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) s_part[threadIdx.x >> 6][i] = red[i];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    float tot[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { tot[i] = s_part[0][i]; for (int w = 1; w < LG_DEC_BLOCK / 64; w++) tot[i] += s_part[w][i]; }
+    if (tot[0] > 0.0f) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) atomicAdd(B.extras_accum + i, tot[i]);
+    }
+    __threadfence();                                               // this workgroup's atomics are performed before its ticket is seen
+    const unsigned int ticket = atomicAdd(B.extras_ticket, 1u);
+    if (ticket != gridDim.x - 1) return;
+    __threadfence();                                               // agent-scope acquire
+    // the accumulators were updated with device-scope atomics by other workgroups: read them past the L1
+    const float cnt = __hip_atomic_load(B.extras_accum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int i = 0; i < LG_DEC_NUM_SUMS; i++) {
+        const float v = __hip_atomic_load(B.extras_accum + 1 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cnt > 0.0f) B.episode_means[i] = v / cnt / P.max_episode_length_s;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) __hip_atomic_store(B.extras_accum + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(B.extras_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+int launch_dec_pre(const lg_dec_game_params &P, const lg_dec_game_buffers &B, void *stream) {
+    hipLaunchKernelGGL(k_dec_pre, dim3((P.num_envs + LG_DEC_BLOCK - 1) / LG_DEC_BLOCK), dim3(LG_DEC_BLOCK), 0, (hipStream_t)stream, P, B);
+    return (int)hipGetLastError();
+}
+
+int launch_dec_post(const lg_dec_game_params &P, const lg_dec_game_buffers &B, int64_t step, void *stream) {
+    hipLaunchKernelGGL(k_dec_post, dim3((P.num_envs + LG_DEC_BLOCK - 1) / LG_DEC_BLOCK), dim3(LG_DEC_BLOCK), 0, (hipStream_t)stream, P, B, step);
+    return (int)hipGetLastError();
+}
+
+// the actor kernels are compiled with the default contraction, as in lg_kernels.hip: the pragmas above are function-local
+int launch_policy_act_one_tile(const PolicyArgs &A, void *stream) {
+    hipLaunchKernelGGL((k_policy_act<1, 32, 16, 8>), dim3((A.num_envs + 15) / 16), dim3(64 * LG_POLICY_WAVES), 0, (hipStream_t)stream, A);
+    return (int)hipGetLastError();
+}
+
+int launch_policy_act_wide_one_tile(const PolicyWideArgs &W, void *stream) {
+    hipLaunchKernelGGL((k_policy_act_wide<1, 16, 8, 4>), dim3((W.base.num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS), dim3(64 * LG_PW_WAVES), 0, (hipStream_t)stream, W);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------ k_dec_act (lg_dec_game_act)
+// Epilogue of a sampled role (wave 0).  All NA <= 4 actions of the agent sit in registers 0..3 of the lanes with h == 0: the stores of
+// lg_policy_act, then exactly the agent's half of k_dec_pre on the sample -- same expressions, contraction off -- and the optional sigma /
+// log-prob of the UNCLIPPED sample (what PPO.act stores before the env clips the caller's tensor, reference :182-189).
+template <bool PREY>
+LG_DEV void dec_command_epilogue(const PolicyArgs &A, const DecActAgent &O, const lg_dec_game_params &P, float *ll_commands, int env,
+                                 const float (&m)[4], const float (&v)[4]) {
+#pragma clang fp contract(off)
+    constexpr int NA = PREY ? LG_DEC_NUM_ACTIONS_PREY : LG_DEC_NUM_ACTIONS_PRED;
+    const size_t row = (size_t)env * NA;
+    float lp = 0.0f;
+#pragma unroll
+    for (int r = 0; r < NA; r++) {
+        const float sg = A.std[r];
+        const float z = (v[r] - m[r]) / sg;
+        lp += -0.5f * z * z - __logf(sg) - 0.918938533f;
+        A.mean[row + r] = m[r];
+        if (A.actions) A.actions[row + r] = v[r];
+        if (O.sigma) O.sigma[row + r] = sg;
+    }
+    if (O.log_prob) O.log_prob[env] = lp;
+    float *c = O.command + row;
+    if constexpr (PREY) {
+        const float c0 = game_clip(v[0], P.cmd_lin_vel_x[0], P.cmd_lin_vel_x[1]);
+        const float c1 = game_clip(v[1], P.cmd_lin_vel_y[0], P.cmd_lin_vel_y[1]);
+        const float c2 = P.heading_command ? game_wrap_to_pi(v[2]) : v[2];
+        const float c3 = v[3];
+        c[0] = c0; c[1] = c1; c[2] = c2; c[3] = c3;
+        float *ll = ll_commands + (size_t)env * 4;
+        ll[0] = c0; ll[1] = c1; ll[2] = c2; ll[3] = c3;
+    } else {
+        c[0] = game_clip(v[0], P.predator_lin_vel_x[0], P.predator_lin_vel_x[1]);
+        c[1] = game_clip(v[1], P.predator_lin_vel_y[0], P.predator_lin_vel_y[1]);
+    }
+}
+
+// ROLE 0: low-level actor (deterministic, stores as k_policy_act_wide), 1: prey, 2: predator.  The body of k_policy_act_wide<K0S,16,8,4>.
+template <int K0S, int ROLE>
+LG_DEV void dec_actor_role(const PolicyWideArgs &W, const DecActArgs &G, const int blk, bf16x8g (*xa)[2][64], bf16x8g (*xb)[2][64]) {
+    const PolicyArgs &A = W.base;
+    constexpr int NW = LG_PW_WAVES, H1T = 16, H2T = 8, H3T = 4;
+    constexpr int T1 = H1T / NW, T2 = H2T / NW, T3 = 1;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5;
+    const int wv = (wave + blk) % NW;
+    const int r0 = (blk * 5) % K0S, r1 = (blk * 5) % (2 * H1T), r2 = (blk * 5) % (2 * H2T);
+    const bool on2 = wv * T2 < H2T, on3 = wv * T3 < H3T;
+    const int64_t step = A.step >= 0 ? A.step : (A.step_counter ? A.step_counter[0] + 1 : 0);
+    int env = blk * LG_PW_ENVS + (lane & 31);
+    const bool live = env < A.num_envs;
+    if (!live) env = A.num_envs - 1;
+    const float *o = A.obs + (size_t)env * A.num_obs;
+    float *obs_copy = ROLE == 1 ? G.a_prey.obs_copy : (ROLE == 2 ? G.a_pred.obs_copy : nullptr);
+    WideStream<K0S, T1> s1;
+    s1.prime(W.wb[0], wv * T1, r0, lane);
+    for (int s = wave; s < K0S; s += NW) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const int k = 16 * s + 8 * h + i; v[i] = k < A.num_obs ? o[k] : 0.0f; }
+        if (ROLE != 0 && obs_copy && live) {                       // the rollout storage's / the other ping-pong buffer's copy of what was read
+#pragma unroll
+            for (int i = 0; i < 8; i++) { const int k = 16 * s + 8 * h + i; if (k < A.num_obs) obs_copy[(size_t)env * A.num_obs + k] = v[i]; }
+        }
+        bf16x8g hi, lo;
+        split8(v, hi, lo);
+        xa[s][0][lane] = hi; xa[s][1][lane] = lo;
+    }
+    float ns[2][4], by[2][4];                                      // std * eps (0 when deterministic), output bias: the noise block of k_policy_act_wide
+    if (wave == 0) {
+#pragma unroll
+        for (int ii = 0; ii < 2; ii++) {
+            const int g = 2 * ii + h;
+#pragma unroll
+            for (int r = 0; r < 4; r++) { ns[ii][r] = 0.0f; by[ii][r] = 0.0f; }
+            if (4 * g >= A.num_actions) continue;
+            float u[4];
+            rand4(A.seed ^ 0x9E3779B97F4A7C15ull, env, step, 100 + g, 0, u);
+            const float rad0 = sqrtf(-2.0f * __logf(fmaxf(u[0], 1e-12f))), rad1 = sqrtf(-2.0f * __logf(fmaxf(u[2], 1e-12f)));
+            float s0, c0, sn1, c1;
+            __sincosf(6.2831853f * u[1], &s0, &c0);
+            __sincosf(6.2831853f * u[3], &sn1, &c1);
+            const float eps[4] = {rad0 * c0, rad0 * s0, rad1 * c1, rad1 * sn1};
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int a = 4 * g + r;
+                if (a < A.num_actions) { by[ii][r] = W.bb[3][a]; ns[ii][r] = A.deterministic ? 0.0f : A.std[a] * eps[r]; }
+            }
+        }
+    }
+    __syncthreads();
+    f32x16p a1[T1];
+    s1.run(W.wb[0], xa, wv * T1, r0, lane, a1);
+    WideStream<2 * H1T, T2> s2;
+    if (on2) s2.prime(W.wb[1], wv * T2, r1, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    wide_epilogue<T1>(a1, W.bb[0], xb, wv * T1, lane);
+    __syncthreads();
+    f32x16p a2[T2];
+    WideStream<2 * H2T, T3> s3;
+    if (on2) s2.run(W.wb[1], xb, wv * T2, r1, lane, a2);
+    if (on3) s3.prime(W.wb[2], wv * T3, r2, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    if (on2) wide_epilogue<T2>(a2, W.bb[1], xa, wv * T2, lane);
+    __syncthreads();
+    f32x16p a3[T3];
+    WideStream<2 * H3T, 1> s4;
+    if (on3) s3.run(W.wb[2], xa, wv * T3, r2, lane, a3);
+    if (wave == 0) s4.prime(W.wb[3], 0, 0, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    if (on3) wide_epilogue<T3>(a3, W.bb[2], xb, wv * T3, lane);
+    __syncthreads();
+    if (wave != 0) return;
+    f32x16p y[1];
+    s4.run(W.wb[3], xb, 0, 0, lane, y);
+    if constexpr (ROLE != 0) {                                     // at most four actions: registers 0..3 of the lanes with h == 0
+        if (h != 0 || !live) return;
+        float m[4], v[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) { m[r] = y[0][r] + by[0][r]; v[r] = m[r] + ns[0][r]; }
+        dec_command_epilogue<ROLE == 1>(A, ROLE == 1 ? G.a_prey : G.a_pred, G.P, G.ll_commands, env, m, v);
+    } else {
+#pragma unroll
+        for (int ii = 0; ii < 2; ii++) {
+            const int g = 2 * ii + h;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int a = 4 * g + r;
+                if (a < A.num_actions && live) {
+                    const float mm = y[0][4 * ii + r] + by[ii][r];
+                    if (A.mean) A.mean[(size_t)env * A.num_actions + a] = mm;
+                    A.actions[(size_t)env * A.num_actions + a] = mm + ns[ii][r];
+                }
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64 * LG_PW_WAVES) k_dec_act(const DecActArgs G) {
+    __shared__ bf16x8g xa[16][2][64], xb[32][2][64];               // as k_policy_act_wide: obs / x2 in xa, x1 / x3 in xb (96 KB), the same for all roles
+    const int role = (int)blockIdx.x / G.blocks, blk = (int)blockIdx.x - role * G.blocks;      // every role has `blocks` workgroups, the low-level role the first
+    if (role == 0) dec_actor_role<15, 0>(G.ll, G, blk, xa, xb);
+    else if (role == 1) dec_actor_role<1, 1>(G.prey, G, blk, xa, xb);
+    else dec_actor_role<1, 2>(G.pred, G, blk, xa, xb);
+}
+
+int launch_dec_act(const DecActArgs &G, void *stream) {
+    hipLaunchKernelGGL(k_dec_act, dim3(3 * G.blocks), dim3(64 * LG_PW_WAVES), 0, (hipStream_t)stream, G);
+    return (int)hipGetLastError();
+}
+
+}  // namespace lg

@@ -18,6 +18,7 @@
 
 #include "lg_device.h"
 #include "lg_policy.h"
+#include "lg_dec_game_common.h"      // launchers of lg_dec_game.hip (declarations only)
 #include "lg_train.h"
 #include "lg_gemm.h"
 
@@ -3001,9 +3002,10 @@ int lg_policy_act(lg_policy *p, const float *obs, float *actions, float *mean, i
     dim3 g((num_envs + 15) / 16), b(64 * LG_POLICY_WAVES);
     hipStream_t st = (hipStream_t)stream;
     const int t0 = p->tiles[0], t1 = p->tiles[1], t2 = p->tiles[2], t3 = p->tiles[3];
-    if (p->wide && g_wide_precision == 1 && (t0 == 15 || t0 == 11 || t0 == 2)) {          // 32 envs per workgroup on the bf16 matrix cores
+    if (p->wide && g_wide_precision == 1 && (t0 == 15 || t0 == 11 || t0 == 2 || t0 == 1)) {          // 32 envs per workgroup on the bf16 matrix cores
         lg::PolicyWideArgs w; w.base = a;
         for (int i = 0; i < 4; i++) { w.wb[i] = reinterpret_cast<const lg::bf16x8g *>(p->d_wb[i]); w.bb[i] = p->d_bb[i]; }
+        if (t0 == 1) { HIP_TRY((hipError_t)lg::launch_policy_act_wide_one_tile(w, st)); return 0; }   // dec game: 16 / 3-512-256-128 (1..16 inputs), lg_dec_game.hip
         dim3 gw((num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS), bw(64 * LG_PW_WAVES);
         if (t0 == 15) hipLaunchKernelGGL((lg::k_policy_act_wide<15, 16, 8, 4>), gw, bw, 0, st, w);     // rough: 235-512-256-128
         else if (t0 == 11) hipLaunchKernelGGL((lg::k_policy_act_wide<11, 16, 8, 4>), gw, bw, 0, st, w);  // cassie: 169-512-256-128
@@ -3015,7 +3017,8 @@ int lg_policy_act(lg_policy *p, const float *obs, float *actions, float *mean, i
     else if (t0 == 15 && t1 == 32 && t2 == 16 && t3 == 8) hipLaunchKernelGGL((k_policy_act<15, 32, 16, 8>), g, b, 0, st, a);  // rough: 235-512-256-128
     else if (t0 == 11 && t1 == 32 && t2 == 16 && t3 == 8) hipLaunchKernelGGL((k_policy_act<11, 32, 16, 8>), g, b, 0, st, a);  // cassie: 169-512-256-128
     else if (t0 == 2 && t1 == 32 && t2 == 16 && t3 == 8) hipLaunchKernelGGL((k_policy_act<2, 32, 16, 8>), g, b, 0, st, a);    // game: 19-512-256-128
-    else return fail(-4, "actor widths are not one of the compiled-in shapes (48-128-64-32, 235/169/19-512-256-128)");
+    else if (t0 == 1 && t1 == 32 && t2 == 16 && t3 == 8) { HIP_TRY((hipError_t)lg::launch_policy_act_one_tile(a, st)); return 0; }   // dec game: 16 / 3-512-256-128, lg_dec_game.hip
+    else return fail(-4, "actor widths are not one of the compiled-in shapes (48-128-64-32, 235/169/19/16/3-512-256-128)");
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -3497,3 +3500,4 @@ int lg_compute_observations_only(lg_sim *s, int64_t common_step_counter, void *s
 }  // extern "C"
 
 #include "lg_game.h"          // predator-prey game layer: k_game_pre / k_game_post and their entry points (include/legged_game.h)
+#include "lg_dec_game.h"      // decentralised game: entry points of include/legged_dec_game.h (kernels: lg_dec_game.hip)

@@ -1,13 +1,17 @@
-"""The predator-prey game layer (reference ``legged_gym/envs/a1_game/``): task ``high_level_game``.
+"""The predator-prey game layer (reference ``legged_gym/envs/a1_game/``): tasks ``high_level_game`` and ``dec_high_level_game``.
 
 Importing this package registers NOTHING: the registry is a process-wide singleton and the locomotion surface is pinned to its five tasks.
-``register()`` adds the game task; ``scripts/train.py`` / ``scripts/play.py`` call it when ``--task`` names one of ``TASKS``."""
+``register()`` adds the game task; ``scripts/train.py`` / ``scripts/play.py`` call it when ``--task`` names one of ``TASKS``.
+``register_dec()`` adds the decentralised two-policy game (``DEC_TASKS``); ``scripts/train_dec_game.py`` / ``scripts/play_dec_game.py`` call it."""
 from legged_games_gym_amd.utils.task_registry import task_registry
 
+from .dec_high_level_game import DecHighLevelGame
+from .dec_high_level_game_config import DecHighLevelGameCfg, DecHighLevelGameCfgPPO
 from .high_level_game import HighLevelGame
 from .high_level_game_flat_config import HighLevelGameFlatCfg, HighLevelGameFlatCfgPPO
 
 TASKS = ("high_level_game",)
+DEC_TASKS = ("dec_high_level_game",)
 
 
 def register(registry=task_registry):
@@ -20,6 +24,21 @@ def register(registry=task_registry):
 def unregister(registry=task_registry):
     """Take the game task out of the registry again (its three entries)."""
     for name in TASKS:
+        for table in (registry.task_classes, registry.env_cfgs, registry.train_cfgs):
+            table.pop(name, None)
+    return registry
+
+
+def register_dec(registry=task_registry):
+    """Register ``dec_high_level_game`` (reference ``legged_gym/envs/__init__.py``); idempotent."""
+    if "dec_high_level_game" not in registry.task_classes:
+        registry.register("dec_high_level_game", DecHighLevelGame, DecHighLevelGameCfg(), DecHighLevelGameCfgPPO())
+    return registry
+
+
+def unregister_dec(registry=task_registry):
+    """Take the decentralised game out of the registry again (its three entries)."""
+    for name in DEC_TASKS:
         for table in (registry.task_classes, registry.env_cfgs, registry.train_cfgs):
             table.pop(name, None)
     return registry

@@ -1,0 +1,486 @@
+"""``DecHighLevelGame`` -- the decentralised predator-prey task of the reference (``legged_gym/envs/a1_game/dec_high_level_game.py``) on the
+device.
+
+One env holds a *prey* (the A1 robot, driven by a frozen low-level locomotion policy) and a *predator* (a kinematic point, a single
+integrator).  Unlike ``HighLevelGame`` the two are separate agents: the prey policy maps 16 observations (four past sensed relative predator
+positions, four visibility flags) to its command ``(lin_vel_x, lin_vel_y, ang_vel_yaw, heading)``, the predator policy maps 3 observations
+(the prey's position relative to it) to its velocity ``(vx, vy)``, and each has its own reward.
+
+``step(command_pred, command_prey)`` (reference :169-258) is four launches with no host in between:
+
+    lg_dec_game_pre  ->  low-level actor (lg_policy_act)  ->  lg_step  ->  lg_dec_game_post
+
+``step_policy(fused_pred, fused_prey)`` runs both agents' actors on the device as well, in three launches:
+
+    lg_dec_game_act (three actors + the clips)  ->  lg_step  ->  lg_dec_game_post
+
+``agent_view(agent, opponent)`` gives one agent's single-agent surface (what ``rl.OnPolicyRunner`` drives) with the other agent acting
+inside every step.  Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G10 onward)."""
+import numpy as np
+import torch
+
+from legged_games_gym_amd import LEGGED_GYM_ROOT_DIR, capi
+from legged_games_gym_amd.utils.helpers import class_to_dict
+
+from .game_base import HALF_FOV, LL_REW_WEIGHT, PREDATOR_Z, GameBase
+
+SEED_OFFSET_PREY = 7919                      # noise seeds of the two sampled actors: cfg.seed + these (they share the purposes 100 + g, so they must differ)
+SEED_OFFSET_PRED = 7919 + 104729
+SUMS = ("evasion", "pursuit", "termination")     # rows of the device episode sums / entries of episode_means (include/legged_dec_game.h)
+AGENTS = ("pred", "prey")
+
+
+class DecHighLevelGame(GameBase):
+    TASK = "dec_high_level_game"
+
+    def __init__(self, cfg, sim_params, physics_engine, sim_device, headless):
+        self._init_low_level(cfg, sim_params, physics_engine, sim_device, headless, LEGGED_GYM_ROOT_DIR)
+        self._parse_cfg(self.cfg)
+        self.num_envs = cfg.env.num_envs
+        self.num_obs_prey = cfg.env.num_observations_prey
+        self.num_privileged_obs_prey = cfg.env.num_privileged_obs_prey
+        self.num_actions_prey = cfg.env.num_actions_prey
+        self.num_obs_pred = cfg.env.num_observations_predator
+        self.num_privileged_obs_pred = cfg.env.num_privileged_obs_predator
+        self.num_actions_pred = cfg.env.num_actions_predator
+        sizes = (self.num_obs_prey, self.num_actions_prey, self.num_obs_pred, self.num_actions_pred)
+        if sizes != (capi.LG_DEC_NUM_OBS_PREY, capi.LG_DEC_NUM_ACTIONS_PREY, capi.LG_DEC_NUM_OBS_PRED, capi.LG_DEC_NUM_ACTIONS_PRED):
+            raise ValueError(f"dec_high_level_game is compiled for 16 / 4 prey and 3 / 2 predator observations / actions, got {sizes}")
+        if self.num_privileged_obs_prey is not None or self.num_privileged_obs_pred is not None:
+            raise NotImplementedError("the reference's dec_high_level_game has no privileged observations")
+        if self.ll_env.num_dof != capi.LG_MAX_DOF:
+            raise ValueError("dec_high_level_game resets the 12 joints of the low-level robot")
+        self.privileged_obs_buf_prey = self.privileged_obs_buf_pred = None
+        self.extras = {}
+        self.enable_viewer_sync = True
+        self.viewer = None
+        self._init_buffers()
+        self._prepare_reward_functions()
+        self._pack()
+        self.init_done = True
+
+    # ------------------------------------------------------------------ hot path
+    def _flip_observations(self, carry):
+        """The caller may still hold the observations returned last time (PPO.act keeps them until process_env_step, and the reference builds
+        new tensors every step, :377, :391): alternate between two buffers per agent, carrying the prey's history over when ``carry``."""
+        prev = self.obs_buf_prey
+        self._obs_flip ^= 1
+        self.obs_buf_prey = self._obs_pair_prey[self._obs_flip]
+        self.obs_buf_pred = self._obs_pair_pred[self._obs_flip]
+        if carry:
+            self.obs_buf_prey.copy_(prev)
+        return prev
+
+    def _unflip_observations(self):
+        self._obs_flip ^= 1
+        self.obs_buf_prey = self._obs_pair_prey[self._obs_flip]
+        self.obs_buf_pred = self._obs_pair_pred[self._obs_flip]
+
+    def step(self, command_pred, command_prey):
+        """Apply both agents' commands, run one low-level policy step, advance the predator (reference :169-210).  ``command_pred`` [num_envs, 2]
+        and ``command_prey`` [num_envs, 4] are clipped IN PLACE, as in the reference."""
+        ll = self.ll_env
+        self._flip_observations(carry=True)
+        B = self._bind(command_pred, command_prey, self.obs_buf_pred, self.obs_buf_prey)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.dec_game_pre(self._P, B, stream)
+        actions = self.ll_policy(ll.obs_buf)
+        ll.step(actions)
+        capi.dec_game_post(self._P, B, ll.common_step_counter, stream)
+        return self._step_result()
+
+    def _step_result(self):
+        return (self.obs_buf_pred, self.obs_buf_prey, self.privileged_obs_buf_pred, self.privileged_obs_buf_prey, self.rew_buf_pred, self.rew_buf_prey,
+                self.reset_buf, self.extras)
+
+    def _device_step(self, command_pred, command_prey):
+        """``step`` for graph capture: the step counter is the low-level env's device counter, observations stay in one buffer per agent."""
+        ll = self.ll_env
+        B = self._bind(command_pred, command_prey, self.obs_buf_pred, self.obs_buf_prey)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        capi.dec_game_pre(self._P, B, stream)
+        actions = self.ll_policy(ll.obs_buf)
+        ll._sim.step(actions, -1)
+        capi.dec_game_post(self._P, B, -1, stream)
+
+    def make_graphed_step(self, policy_pred, policy_prey, warmup=3, steps_per_replay=1):
+        """Capture ``step(policy_pred(obs_buf_pred), policy_prey(obs_buf_prey))`` into one HIP graph and return a zero-argument callable that
+        replays it: both policies, ``lg_dec_game_pre``, low-level actor, ``lg_step``, ``lg_dec_game_post`` -- no host in between.  The
+        policies must be capturable and read ``self.obs_buf_pred`` / ``self.obs_buf_prey``."""
+        self._step_graph, replay = self._capture(lambda: self._device_step(policy_pred(self.obs_buf_pred), policy_prey(self.obs_buf_prey)), warmup, steps_per_replay, self._step_result)
+        return replay
+
+    # ------------------------------------------------------------------ hot path with both actors on the device
+    def _act(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_pred_out, obs_prey_out, deterministic_pred, deterministic_prey, out_pred=None, out_prey=None):
+        """``lg_dec_game_act``: both commands = clip(actor(obs) + noise), the prey's into the low-level commands, the low-level actions, and
+        the prey's observations copied to ``obs_prey_out`` (where ``lg_dec_game_post`` then shifts the history in place) -- one launch.
+        Separate launches when the actor triple or the wide precision has no shared kernel (rc -4).  ``out_*``: dicts of optional float32
+        outputs ``sample`` / ``sigma`` / ``log_prob`` / ``obs_copy`` (the rollout storage's copy of the observations read).
+        Returns ``(command_pred, mean_pred), (command_prey, mean_prey), ll_actions, buffers``."""
+        ll, n = self.ll_env, self.num_envs
+        for name, t, width in (("predator", obs_pred_in, self.num_obs_pred), ("prey", obs_prey_in, self.num_obs_prey)):
+            if t.shape != (n, width) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} observations must be a contiguous float32 [{n},{width}] tensor")
+        out_pred, out_prey = dict(out_pred or {}), dict(out_prey or {})
+        for out, na, no in ((out_pred, self.num_actions_pred, self.num_obs_pred), (out_prey, self.num_actions_prey, self.num_obs_prey)):
+            unknown = set(out) - {"sample", "sigma", "log_prob", "obs_copy"}
+            if unknown:
+                raise ValueError(f"unknown optional outputs {sorted(unknown)}")
+            self._check_output("sample", out.get("sample"), n * na)
+            self._check_output("sigma", out.get("sigma"), n * na)
+            self._check_output("log_prob", out.get("log_prob"), n)
+            self._check_output("obs_copy", out.get("obs_copy"), n * no)
+        command_pred, mean_pred = fused_pred.output_buffers(n)
+        command_prey, mean_prey = fused_prey.output_buffers(n)
+        ll_actions = self._ll_fused.output_buffers(n)[0]
+        B = self._bind(command_pred, command_prey, obs_pred_out, obs_prey_out)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()
+        carry = obs_prey_out is not obs_prey_in
+
+        def outputs(out, extra_copy):
+            o = capi.lg_dec_act_outputs()
+            o.sample, o.sigma, o.log_prob = ptr(out.get("sample")), ptr(out.get("sigma")), ptr(out.get("log_prob"))
+            o.obs_copy = ptr(out.get("obs_copy")) if out.get("obs_copy") is not None else extra_copy
+            return o
+        # the kernel has one observation copy per agent: the prey's goes to the other ping-pong buffer (history carry) unless the caller asks
+        # for its own copy, in which case the carry is a separate copy below
+        want_prey_copy = out_prey.get("obs_copy") is not None
+        (step_y, ctr_y), (step_p, ctr_p) = fused_prey.peek_step(), fused_pred.peek_step()
+        if (step_y, ctr_y) != (step_p, ctr_p):
+            raise ValueError("the two FusedActors must count their noise steps alike (both on the low-level sim's device step counter, or both on the host)")
+        if fused_pred.seed == fused_prey.seed:
+            raise ValueError("the two FusedActors need different seeds: they draw their noise under the same purposes")
+        rc = capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, obs_pred_in.data_ptr(), obs_prey_in.data_ptr(),
+                               ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed,
+                               step_y, ctr_y, deterministic_pred, deterministic_prey, outputs(out_pred, None),
+                               outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
+        self.last_act_rc = rc                                  # 0: the shared launch ran; -4: the separate launches below
+        if rc == 0:
+            fused_pred.next_step(); fused_prey.next_step()     # the launch used this step of both noise streams
+            if carry and want_prey_copy:
+                obs_prey_out.copy_(obs_prey_in)
+            return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
+        # rc -4, nothing was launched: lg_policy_act x 3 + lg_dec_game_pre (decided per call: lg_mlp_wide_set_precision may change between calls)
+        for fused, obs_in, det, out in ((fused_pred, obs_pred_in, deterministic_pred, out_pred), (fused_prey, obs_prey_in, deterministic_prey, out_prey)):
+            command, mean = fused.act_with_mean(obs_in, det)
+            if out.get("sample") is not None:
+                out["sample"].view(n, -1).copy_(command)
+            if out.get("sigma") is not None or out.get("log_prob") is not None:
+                std = fused.ac.std.detach()
+                if out.get("sigma") is not None:
+                    out["sigma"].view(n, -1).copy_(std.expand(n, -1))
+                if out.get("log_prob") is not None:
+                    out["log_prob"].view(n).copy_(torch.distributions.Normal(mean, std).log_prob(command).sum(-1))
+            if out.get("obs_copy") is not None:
+                out["obs_copy"].view(n, -1).copy_(obs_in)
+        if carry:
+            obs_prey_out.copy_(obs_prey_in)
+        capi.dec_game_pre(self._P, B, stream)
+        ll_actions = self.ll_policy(ll.obs_buf)
+        return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
+
+    def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None):
+        """Rollout step with both agents' actors on the device: ``lg_dec_game_act`` -> ``lg_step`` -> ``lg_dec_game_post``, three launches.
+        Returns ``(command_pred, mean_pred), (command_prey, mean_prey), step result``: the clipped commands (what ``step`` leaves in the
+        caller's tensors) and the actors' outputs, all in the ``FusedActor`` buffers.  ``out_pred`` / ``out_prey``: dicts of optional float32
+        outputs -- ``sample`` (the unclipped sample), ``sigma``, ``log_prob`` of that sample (what ``PPO.act`` stores), ``obs_copy`` (the
+        observations the actor read).  The observations the actors read stay in the tensors returned by the previous call, as with ``step``."""
+        ll = self.ll_env
+        prev_pred = self.obs_buf_pred
+        prev_prey = self._flip_observations(carry=False)
+        try:
+            pred, prey, ll_actions, B = self._act(fused_pred, fused_prey, prev_pred, prev_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
+                                                  deterministic_prey, out_pred, out_prey)
+        except Exception:
+            self._unflip_observations()
+            raise
+        ll.step(ll_actions)
+        capi.dec_game_post(self._P, B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
+        return pred, prey, self._step_result()
+
+    def make_graphed_policy_step(self, fused_pred, fused_prey, warmup=3, steps_per_replay=1):
+        """``make_graphed_step`` with both actors on the device: the graph is ``lg_dec_game_act`` -> ``lg_step`` -> ``lg_dec_game_post`` per
+        step, the observations stay in one buffer per agent.  Both ``FusedActor`` s must draw their noise stream from the low-level sim's
+        device step counter (``FusedActor(..., step_counter=env.ll_env._sim.buf["step_counter"])``).  Returns a zero-argument callable that
+        replays the graph; the actors' ``output_buffers(num_envs)`` then hold the commands and the means of the last step."""
+        sim = self.ll_env._sim
+        for fused in (fused_pred, fused_prey):
+            if fused.step_counter is None or fused.step_counter.data_ptr() != sim.buf["step_counter"].data_ptr():
+                raise ValueError("make_graphed_policy_step needs FusedActors on the low-level sim's device step counter")
+
+        def device_step():
+            _, _, ll_actions, B = self._act(fused_pred, fused_prey, self.obs_buf_pred, self.obs_buf_prey, self.obs_buf_pred, self.obs_buf_prey, False, False)
+            sim.step(ll_actions, -1)
+            capi.dec_game_post(self._P, B, -1, torch.cuda.current_stream(self.device).cuda_stream)
+        self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)
+        return replay
+
+    # ------------------------------------------------------------------ resets and observations
+    def reset_idx(self, env_ids):
+        """Reset the listed envs from the host (reference :271-311): joints and root state of the prey, predator placement, history, counters,
+        episode sums.  Resets that happen inside ``step`` are done by ``lg_dec_game_post`` with keyed Philox draws; this entry point serves
+        ``reset()`` and tooling and draws from torch's generator, like the creation-time randomisation of the low-level env."""
+        if len(env_ids) == 0:
+            return
+        ll = self.ll_env
+        ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long)
+        n = len(ids)
+        ll.dof_pos[ids] = ll.default_dof_pos * (0.5 + torch.rand(n, ll.num_dof, device=self.device))     # low_level_game.py:391-392
+        ll.dof_vel[ids] = 0.
+        root = ll.base_init_state.repeat(n, 1)
+        root[:, :3] += ll.env_origins[ids]
+        if ll.custom_origins:
+            root[:, :2] += 2.0 * torch.rand(n, 2, device=self.device) - 1.0
+        root[:, 7:13] = torch.rand(n, 6, device=self.device) - 0.5
+        ll.root_states[ids] = root
+        self.predator_pos[ids] = self._place_predator(root[:, :3])
+        self.obs_buf_prey[ids, 0:12] = self.MAX_REL_POS
+        self.obs_buf_prey[ids, 12:16] = 0
+        self.obs_buf_pred[ids] = -self.MAX_REL_POS
+        self.episode_length_buf[ids] = 0
+        self.reset_buf[ids] = True
+        self.curr_episode_step[ids] = 0
+        means = self._episode_sums[:, ids].mean(dim=1) / self.max_episode_length_s                        # (:298-305)
+        self._episode_means.copy_(means)
+        self._episode_sums[:, ids] = 0.
+
+    def reset(self):
+        """Reset all envs, then one zero-command step (:313-319)."""
+        self.reset_idx(torch.arange(self.num_envs, device=self.device))
+        actions_pred = torch.zeros(self.num_envs, self.num_actions_pred, device=self.device, requires_grad=False)
+        actions_prey = torch.zeros(self.num_envs, self.num_actions_prey, device=self.device, requires_grad=False)
+        obs_pred, obs_prey, privileged_obs_pred, privileged_obs_prey, _, _, _, _ = self.step(actions_pred, actions_prey)
+        return obs_pred, obs_prey, privileged_obs_pred, privileged_obs_prey
+
+    def get_observations_pred(self):
+        return self.obs_buf_pred
+
+    def get_observations_prey(self):
+        return self.obs_buf_prey
+
+    def get_privileged_observations_pred(self):
+        return self.privileged_obs_buf_pred
+
+    def get_privileged_observations_prey(self):
+        return self.privileged_obs_buf_prey
+
+    def agent_view(self, agent, opponent):
+        """The single-agent surface of ``agent`` ("pred" or "prey") with ``opponent`` -- a ``FusedActor`` (device path) or a torch policy
+        ``obs -> sampled actions`` (generic path) -- acting for the other agent inside every step."""
+        return AgentView(self, agent, opponent)
+
+    # ------------------------------------------------------------------ set-up
+    def _init_buffers(self):
+        N, dev = self.num_envs, self.device
+
+        def prey_obs():
+            t = self.MAX_REL_POS * torch.ones(N, self.num_obs_prey, device=dev, dtype=torch.float)
+            t[:, 12:16] = 0                                                    # (:127-128)
+            return t
+        self._obs_pair_prey = (prey_obs(), prey_obs())
+        self._obs_pair_pred = (self.MAX_REL_POS * torch.ones(N, self.num_obs_pred, device=dev, dtype=torch.float),
+                               self.MAX_REL_POS * torch.ones(N, self.num_obs_pred, device=dev, dtype=torch.float))
+        self._obs_flip = 0
+        self.obs_buf_prey, self.obs_buf_pred = self._obs_pair_prey[0], self._obs_pair_pred[0]
+        self.rew_buf_prey = torch.zeros(N, device=dev, dtype=torch.float)
+        self.rew_buf_pred = torch.zeros(N, device=dev, dtype=torch.float)
+        self.reset_buf = torch.ones(N, device=dev, dtype=torch.bool)          # persistent bool tensors, like the low-level env's (quirk Q1)
+        self.time_out_buf = torch.zeros(N, device=dev, dtype=torch.bool)
+        self.episode_length_buf = torch.zeros(N, device=dev, dtype=torch.long)
+        self.curr_episode_step = torch.zeros(N, device=dev, dtype=torch.long)
+        self.init_predator_pos = self._place_predator(self.ll_env.root_states[:, :3])
+        self.predator_pos = self.init_predator_pos.clone()
+        self._command_pred = torch.zeros(N, self.num_actions_pred, device=dev, dtype=torch.float)
+        self._command_prey = torch.zeros(N, self.num_actions_prey, device=dev, dtype=torch.float)
+        self._episode_sums = torch.zeros(len(SUMS), N, device=dev, dtype=torch.float)
+        self._episode_means = torch.zeros(len(SUMS), device=dev, dtype=torch.float)
+        self._extras_accum = torch.zeros(4, device=dev, dtype=torch.float)
+        self._extras_ticket = torch.zeros(1, device=dev, dtype=torch.int32)
+        if getattr(self.cfg.env, "send_timeouts", True):
+            self.extras["time_outs"] = self.time_out_buf                      # this step's time-outs, refreshed by every lg_dec_game_post
+
+    def _prepare_reward_functions(self):
+        """Reference :527-579: zero scales dropped, the rest multiplied by the low-level dt; one episode sum per name, and
+        ``extras["episode"]`` as views of the device episode means."""
+        for scales in (self.reward_scales_prey, self.reward_scales_pred):
+            for key in list(scales.keys()):
+                if scales[key] == 0:
+                    scales.pop(key)
+                else:
+                    scales[key] *= self.ll_env.dt
+        if "termination" in self.reward_scales_pred:
+            raise ValueError("rewards_predator.scales.termination is not supported: the reference reads a non-existent self.reward_scales for it "
+                             "(dec_high_level_game.py:359) and raises at the first step")
+        for who, scales, known in (("prey", self.reward_scales_prey, ("evasion", "termination")), ("pred", self.reward_scales_pred, ("pursuit",))):
+            unknown = [k for k in scales if k not in known]
+            if unknown:
+                raise AttributeError(f"'DecHighLevelGame' object has no attribute '_reward_{unknown[0]}' ({who})")
+        self.reward_names_prey = [k for k in self.reward_scales_prey if k != "termination"]
+        self.reward_names_pred = list(self.reward_scales_pred)
+        self.episode_sums_prey = {name: self._episode_sums[SUMS.index(name)] for name in self.reward_scales_prey}
+        self.episode_sums_pred = {name: self._episode_sums[SUMS.index(name)] for name in self.reward_scales_pred}
+        episode = {f"rew_pred_{name}": self._episode_means[SUMS.index(name)] for name in self.reward_scales_pred}
+        episode.update({f"rew_prey_{name}": self._episode_means[SUMS.index(name)] for name in self.reward_scales_prey})
+        self.extras["episode"] = episode
+
+    def _parse_cfg(self, cfg):
+        """Reference :581-590."""
+        self.reward_scales_prey = class_to_dict(self.cfg.rewards_prey.scales)
+        self.reward_scales_pred = class_to_dict(self.cfg.rewards_predator.scales)
+        self.command_ranges = class_to_dict(self.cfg.commands.ranges)
+        if self.cfg.terrain.mesh_type not in ["heightfield", "trimesh"]:
+            self.cfg.terrain.curriculum = False
+        self.max_episode_length_s = self.cfg.env.episode_length_s
+        self.max_episode_length = np.ceil(self.max_episode_length_s / self.ll_env.dt)
+
+    def _pack(self):
+        """``lg_dec_game_params`` from the configs and the pointer table of ``lg_dec_game_buffers``."""
+        ll, P = self.ll_env, capi.lg_dec_game_params()
+        P.num_envs, P.decimation = self.num_envs, int(ll.cfg.control.decimation)
+        P.heading_command, P.custom_origins = int(bool(self.cfg.commands.heading_command)), int(bool(ll.custom_origins))
+        P.only_positive_rewards_prey = int(bool(self.cfg.rewards_prey.only_positive_rewards))
+        P.only_positive_rewards_pred = int(bool(self.cfg.rewards_predator.only_positive_rewards))
+        P.max_episode_length = int(self.max_episode_length)
+        seed = getattr(self.cfg, "seed", 1)
+        P.seed = int(seed) if seed is not None and seed >= 0 else 1
+        r = self.command_ranges
+        for name, key in (("cmd_lin_vel_x", "lin_vel_x"), ("cmd_lin_vel_y", "lin_vel_y"), ("predator_lin_vel_x", "predator_lin_vel_x"),
+                          ("predator_lin_vel_y", "predator_lin_vel_y")):
+            capi._fill(getattr(P, name), r[key])
+        P.capture_dist = float(self.capture_dist)
+        P.half_fov, P.max_rel_pos, P.ll_rew_weight = HALF_FOV, self.MAX_REL_POS, LL_REW_WEIGHT
+        P.scale_evasion_dt = float(self.reward_scales_prey.get("evasion", 0.0))
+        P.scale_pursuit_dt = float(self.reward_scales_pred.get("pursuit", 0.0))
+        P.scale_termination_prey_dt = float(self.reward_scales_prey.get("termination", 0.0))
+        P.sim_dt, P.predator_z, P.max_episode_length_s = float(ll.cfg.sim.dt), PREDATOR_Z, float(self.max_episode_length_s)
+        capi._fill(P.base_init_state, ll.base_init_state.cpu().numpy())
+        capi._fill(P.default_dof_pos, ll.default_dof_pos.cpu().numpy())        # the joint order of the low-level dof_state buffer
+        self._P = P
+        b = ll._sim.buf
+        self._pointers = {"ll_root_states": b["root_states"].data_ptr(), "ll_dof_state": b["dof_state"].data_ptr(), "ll_commands": b["commands"].data_ptr(),
+                          "ll_env_origins": b["env_origins"].data_ptr(), "ll_rew_buf": b["rew_buf"].data_ptr(), "ll_reset_buf": b["reset_buf"].data_ptr(),
+                          "ll_step_counter": b["step_counter"].data_ptr(), "predator_pos": self.predator_pos.data_ptr(), "rew_prey": self.rew_buf_prey.data_ptr(),
+                          "rew_pred": self.rew_buf_pred.data_ptr(), "reset_buf": self.reset_buf.data_ptr(), "time_out_buf": self.time_out_buf.data_ptr(),
+                          "curr_episode_step": self.curr_episode_step.data_ptr(), "episode_length_buf": self.episode_length_buf.data_ptr(),
+                          "episode_sums": self._episode_sums.data_ptr(), "episode_means": self._episode_means.data_ptr(),
+                          "extras_accum": self._extras_accum.data_ptr(), "extras_ticket": self._extras_ticket.data_ptr()}
+
+    def set_command_ranges(self):
+        """Re-pack after ``command_ranges`` / ``capture_dist`` were edited."""
+        self._pack()
+
+    def _own(self, command, width, scratch, name):
+        if command.shape != (self.num_envs, width):
+            raise ValueError(f"{name} must be [{self.num_envs},{width}], got {tuple(command.shape)}")
+        if command.dtype != torch.float32 or not command.is_contiguous() or str(command.device) != str(self.device):
+            scratch.copy_(command)
+            command = scratch
+        return command
+
+    def _bind(self, command_pred, command_prey, obs_pred, obs_prey):
+        """``lg_dec_game_buffers`` for this call: the kernels read and clip the callers' tensors where they are."""
+        command_pred = self._own(command_pred, self.num_actions_pred, self._command_pred, "command_pred")
+        command_prey = self._own(command_prey, self.num_actions_prey, self._command_prey, "command_prey")
+        self._keep = (command_pred, command_prey)
+        return capi.dec_game_buffers(dict(self._pointers, command_pred=command_pred.detach().data_ptr(), command_prey=command_prey.detach().data_ptr(),
+                                          obs_pred=obs_pred.data_ptr(), obs_prey=obs_prey.data_ptr()))
+
+
+class AgentView:
+    """One agent of a ``DecHighLevelGame`` as a single-agent env: the surface ``rl.OnPolicyRunner`` drives for ``high_level_game``
+    (``step`` on the generic path, ``step_policy`` on the device path).  The opponent produces the other agent's command inside every step
+    and SAMPLES, like the learner; only this agent's transition is returned.  Both views of an env drive the same env."""
+    dec_agent_view = True          # what the runner's time-out bootstrap of the device game rollout is guarded on
+
+    def __init__(self, env, agent, opponent):
+        if agent not in AGENTS:
+            raise ValueError(f"agent must be one of {AGENTS}, got {agent!r}")
+        self.env, self.agent, self.opponent = env, agent, opponent
+        self.other = "prey" if agent == "pred" else "pred"
+        self.num_envs, self.cfg, self.device, self.ll_env = env.num_envs, env.cfg, env.device, env.ll_env
+        self.num_obs = getattr(env, f"num_obs_{agent}")
+        self.num_actions = getattr(env, f"num_actions_{agent}")
+        self.num_privileged_obs = None
+        self.max_episode_length = env.max_episode_length
+        self.fused_seed_offset = SEED_OFFSET_PRED if agent == "pred" else SEED_OFFSET_PREY     # noise seed of this agent's FusedActor: cfg.seed + this
+
+    # buffers are looked up at every access: the env alternates between two observation buffers per agent
+    obs_buf = property(lambda self: getattr(self.env, f"obs_buf_{self.agent}"))
+    rew_buf = property(lambda self: getattr(self.env, f"rew_buf_{self.agent}"))
+    reset_buf = property(lambda self: self.env.reset_buf)
+    extras = property(lambda self: self.env.extras)
+    episode_length_buf = property(lambda self: self.env.episode_length_buf)
+    dt = property(lambda self: self.env.dt)
+    _obs_pair = property(lambda self: getattr(self.env, f"_obs_pair_{self.agent}"))
+
+    @property
+    def _obs_flip(self):
+        return self.env._obs_flip
+
+    @_obs_flip.setter
+    def _obs_flip(self, value):          # (the runner puts the ping-pong back after a capture that failed part-way)
+        self.env._obs_flip = value
+        self.env.obs_buf_prey, self.env.obs_buf_pred = self.env._obs_pair_prey[value], self.env._obs_pair_pred[value]
+
+    @obs_buf.setter
+    def obs_buf(self, value):            # (same path, after the _obs_flip setter: only the current buffer of the pair can be "assigned")
+        if value is not self.obs_buf:
+            raise ValueError("an agent view's obs_buf is the env's current buffer of its observation pair; set _obs_flip to choose it")
+
+    @property
+    def _capturing(self):
+        return self.env._capturing
+
+    @_capturing.setter
+    def _capturing(self, value):
+        self.env._capturing = value
+
+    @property
+    def common_step_counter(self):
+        return self.env.common_step_counter
+
+    @common_step_counter.setter
+    def common_step_counter(self, value):
+        self.env.common_step_counter = value
+
+    def begin_graph_capture(self):
+        self.env.begin_graph_capture()
+
+    def capture_extras_flush(self):
+        self.env.capture_extras_flush()
+
+    def end_graph_capture(self, steps_captured):
+        self.env.end_graph_capture(steps_captured)
+
+    def reset(self):
+        obs_pred, obs_prey, _, _ = self.env.reset()
+        return (obs_pred if self.agent == "pred" else obs_prey), None
+
+    def get_observations(self):
+        return self.obs_buf
+
+    def get_privileged_observations(self):
+        return None
+
+    def _result(self, out):
+        obs_pred, obs_prey, _, _, rew_pred, rew_prey, dones, extras = out
+        return (obs_pred, None, rew_pred, dones, extras) if self.agent == "pred" else (obs_prey, None, rew_prey, dones, extras)
+
+    def step(self, actions):
+        """Generic path: ``opponent`` is a torch policy ``obs -> sampled actions``.  ``actions`` is clipped in place, as by ``env.step``."""
+        with torch.no_grad():
+            other = self.opponent(getattr(self.env, f"obs_buf_{self.other}")).detach().clone()
+        if self.agent == "pred":
+            return self._result(self.env.step(actions, other))
+        return self._result(self.env.step(other, actions))
+
+    def step_policy(self, fused, deterministic=False, sample=None, sigma=None, log_prob=None, obs_copy=None):
+        """Device path: ``opponent`` is a ``FusedActor``.  Returns ``(command, mean), (obs, None, rew, dones, extras)`` of this agent, the
+        contract of ``HighLevelGame.step_policy``."""
+        mine = {k: v for k, v in (("sample", sample), ("sigma", sigma), ("log_prob", log_prob), ("obs_copy", obs_copy)) if v is not None}
+        if self.agent == "pred":
+            pred, _, out = self.env.step_policy(fused, self.opponent, deterministic_pred=deterministic, out_pred=mine)
+            return pred, self._result(out)
+        _, prey, out = self.env.step_policy(self.opponent, fused, deterministic_prey=deterministic, out_prey=mine)
+        return prey, self._result(out)

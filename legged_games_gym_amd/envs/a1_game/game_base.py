@@ -1,0 +1,169 @@
+"""What ``HighLevelGame`` and ``DecHighLevelGame`` share: the device choice, the low-level ``a1`` env with its frozen locomotion policy,
+predator placement, the reference-named state views and the capture hooks the runner's device rollout touches."""
+import copy
+import os
+import types
+
+import torch
+
+from legged_games_gym_amd.envs.base.base_task import parse_device_str
+from legged_games_gym_amd.utils.helpers import class_to_dict, get_load_path, parse_sim_params
+
+HALF_FOV = 1.20428 / 2.0        # high_level_game.py:427, dec_high_level_game.py:417
+LL_REW_WEIGHT = 2.0             # high_level_game.py:364, dec_high_level_game.py:328
+PREDATOR_Z = 0.3                # low_level_game.py:432
+
+
+class GameBase:
+    TASK = "high_level_game"    # the task's name in error messages
+
+    def _init_low_level(self, cfg, sim_params, physics_engine, sim_device, headless, root_dir):
+        """The reference constructor up to and including the low-level policy (high_level_game.py:41-103, dec_high_level_game.py:41-103).
+        ``root_dir`` is where ``logs/<a1 experiment>`` is searched for the low-level checkpoint when ``env.ll_policy_path`` is None."""
+        from legged_games_gym_amd.envs import task_registry, LeggedRobot
+        from legged_games_gym_amd.rl import ActorCritic, FusedActor
+        self.cfg = cfg
+        self.sim_params = sim_params
+        self.height_samples = None
+        self.debug_viz = False
+        self.init_done = False
+        self.physics_engine = physics_engine
+        self.sim_device = sim_device
+        sim_device_type, self.sim_device_id = parse_device_str(self.sim_device)
+        self.headless = headless
+        self.capture_dist = self.cfg.env.capture_dist
+        self.MAX_REL_POS = 100.
+        if sim_device_type in ("cuda", "gpu") and getattr(sim_params, "use_gpu_pipeline", True):
+            self.device = f"cuda:{self.sim_device_id}"
+        else:
+            self.device = "cpu"
+        self.graphics_device_id = -1 if headless else self.sim_device_id
+
+        # low-level env: a DEEP COPY of the registered a1 configs with the overrides of :70-85 (the reference mutates the registered objects)
+        ll_env_cfg, ll_train_cfg = (copy.deepcopy(c) for c in task_registry.get_cfgs(name="a1"))
+        ll_env_cfg.env.num_envs = self.cfg.env.num_envs
+        ll_env_cfg.terrain.num_rows = self.cfg.terrain.num_rows
+        ll_env_cfg.terrain.num_cols = self.cfg.terrain.num_cols
+        ll_env_cfg.terrain.curriculum = self.cfg.terrain.curriculum
+        ll_env_cfg.noise.add_noise = self.cfg.noise.add_noise
+        ll_env_cfg.domain_rand.randomize_friction = self.cfg.domain_rand.randomize_friction
+        ll_env_cfg.domain_rand.push_robots = self.cfg.domain_rand.push_robots
+        ll_env_cfg.terrain.mesh_type = self.cfg.terrain.mesh_type
+        ll_env_cfg.rewards.scales.torques = -5.        # "instantaneous control effort cost" (:83-85)
+        ll_env_cfg.seed = getattr(self.cfg, "seed", ll_env_cfg.seed)
+        ll_args = types.SimpleNamespace(use_gpu=True, subscenes=0, num_threads=0, use_gpu_pipeline=getattr(sim_params, "use_gpu_pipeline", True))
+        ll_sim_params = parse_sim_params(ll_args, {"sim": class_to_dict(ll_env_cfg.sim)})
+        self.ll_env = LeggedRobot(cfg=ll_env_cfg, sim_params=ll_sim_params, physics_engine=physics_engine, sim_device=sim_device, headless=headless)
+        ll = self.ll_env
+
+        # frozen low-level policy: the checkpoint's actor on the MFMA actor kernel
+        path = getattr(self.cfg.env, "ll_policy_path", None)
+        if path is None:
+            log_root = os.path.join(root_dir, "logs", ll_train_cfg.runner.experiment_name)
+            try:
+                path = get_load_path(log_root, load_run=ll_train_cfg.runner.load_run, checkpoint=ll_train_cfg.runner.checkpoint)
+            except (ValueError, IndexError, OSError) as exc:
+                raise RuntimeError(
+                    f"{self.TASK} needs a trained low-level policy and found no a1 checkpoint under {log_root} ({exc}). Train the a1 task first "
+                    "(python -m legged_games_gym_amd.scripts.train --task=a1 --headless) or set env.ll_policy_path to a model_*.pt file.") from exc
+        if not os.path.isfile(path):
+            raise RuntimeError(f"{self.TASK}: low-level checkpoint {path} does not exist. Train the a1 task first "
+                               "(python -m legged_games_gym_amd.scripts.train --task=a1 --headless) or set env.ll_policy_path to a model_*.pt file.")
+        self.ll_policy_path = path
+        num_critic_obs = ll.num_privileged_obs if ll.num_privileged_obs is not None else ll.num_obs
+        self._ll_actor_critic = ActorCritic(ll.num_obs, num_critic_obs, ll.num_actions, **class_to_dict(ll_train_cfg.policy)).to(self.device)
+        self._ll_actor_critic.load_state_dict(torch.load(path, map_location=self.device, weights_only=True)["model_state_dict"])
+        self._ll_actor_critic.eval()
+        self._ll_fused = FusedActor(self._ll_actor_critic, self.device, seed=int(getattr(ll_env_cfg, "seed", 1)))
+        self.ll_policy = self._ll_fused.act_inference
+
+    def _check_output(self, name, t, numel):
+        """An optional output of ``_act``: None, or a contiguous float32 tensor on this device with ``numel`` elements."""
+        if t is None:
+            return
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or str(t.device) != str(self.device):
+            raise ValueError(f"{name} must be a contiguous float32 tensor with {numel} elements on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    # ------------------------------------------------------------------ graph capture of a step
+    def _capture(self, device_step, warmup, steps_per_replay, result):
+        """Warm up on a side stream, capture ``steps_per_replay`` x ``device_step`` into one HIP graph, return the replay callable
+        returning ``result()`` -- no host between the launches (same contract as ``LeggedRobot.make_graphed_step``)."""
+        ll = self.ll_env
+        sim = ll._sim
+        sim.set_obs_output(ll.obs_buf)                       # one fixed low-level observation buffer while replaying
+        sim.buf["step_counter"].fill_(ll.common_step_counter)
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                device_step()
+                ll.common_step_counter += 1
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        ll.begin_graph_capture()
+        sim.set_deferred_extras(False)                       # the low-level step publishes its extras in its own launch
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                for _ in range(steps_per_replay):
+                    device_step()
+        finally:
+            ll.end_graph_capture(0)                          # (the captured steps went through the sim, not through ll_env.step)
+
+        def replay():
+            graph.replay()
+            ll.common_step_counter += steps_per_replay
+            return result()
+        return graph, replay
+
+    # ------------------------------------------------------------------ capture hooks of the runner's device rollout
+    @property
+    def _capturing(self):
+        return self.ll_env._capturing
+
+    @_capturing.setter
+    def _capturing(self, value):
+        self.ll_env._capturing = value
+
+    @property
+    def common_step_counter(self):
+        return self.ll_env.common_step_counter
+
+    @common_step_counter.setter
+    def common_step_counter(self, value):
+        self.ll_env.common_step_counter = value
+
+    def begin_graph_capture(self):
+        """Several ``step_policy`` calls are about to be captured into one HIP graph: the step counter moves to the device."""
+        self.ll_env.begin_graph_capture()
+
+    def capture_extras_flush(self):
+        self.ll_env.capture_extras_flush()
+
+    def end_graph_capture(self, steps_captured: int):
+        self.ll_env.end_graph_capture(steps_captured)
+
+    def render(self, sync_frame_time=True):
+        return None     # headless
+
+    # ------------------------------------------------------------------ state views (reference names)
+    @property
+    def prey_states(self):
+        return self.ll_env.root_states
+
+    @property
+    def base_quat(self):
+        return self.ll_env.root_states[:, 3:7]
+
+    @property
+    def dt(self):
+        return self.ll_env.dt
+
+    # ------------------------------------------------------------------ set-up
+    def _place_predator(self, prey_pos):
+        """low_level_game.py:420-432: a common sign per env times U(1, 10) on every axis, then z = 0.3."""
+        n = prey_pos.shape[0]
+        offset = 1.0 + 9.0 * torch.rand(n, 3, device=self.device)
+        sign = torch.where(torch.rand(n, 1, device=self.device) < 0.5, -1.0, 1.0)
+        pos = prey_pos - sign * offset
+        pos[:, 2] = PREDATOR_Z
+        return pos

@@ -13,6 +13,7 @@ adaptive learning rate stays identical on every rank.
 from .actor_critic import ActorCritic
 from .ppo import PPO, RolloutStorage
 from .runner import OnPolicyRunner
+from .dec_runner import DecGamePolicyRunner
 
 
 
@@ -22,4 +23,4 @@ def FusedActor(*args, **kwargs):
     return _F(*args, **kwargs)
 
 
-__all__ = ["ActorCritic", "PPO", "RolloutStorage", "OnPolicyRunner", "FusedActor"]
+__all__ = ["ActorCritic", "PPO", "RolloutStorage", "OnPolicyRunner", "DecGamePolicyRunner", "FusedActor"]

@@ -1,0 +1,135 @@
+"""``DecGamePolicyRunner``: predator and prey of ``dec_high_level_game`` trained in alternating "evolutions" (the reference calls
+``make_dec_alg_runner(...).learn(max_num_evolutions=, num_learning_iterations=, init_at_random_ep_len=True)``,
+``legged_gym/scripts/train_dec_game.py``; its runner lives in a fork of rsl_rl that is not public, so the schedule is defined here).
+
+Two ``OnPolicyRunner`` s, one per agent view of the same env (``DecHighLevelGame.agent_view``), each with its own ``ActorCritic``, ``PPO`` and
+storage -- the learner kernels and the device rollout come with them.  Evolution ``e`` trains the PREDATOR when ``e`` is even and the PREY when
+odd (the argument order of the reference's ``step``) for ``num_learning_iterations`` PPO iterations; the other agent acts with its current
+policy, sampling, and is not updated.  The combined ``model_<it>.pt`` and ``progress.csv`` follow the training agent's runner (``runner.save_interval``,
+every logged iteration).  ``OnPolicyRunner.learn`` captures its rollout graph when it is called, i.e. at the start of every
+evolution, so a graph never outlives an update of the opponent it replays; the opponent's ``FusedActor`` is repacked in place besides."""
+import os
+import re
+
+import torch
+
+from .runner import OnPolicyRunner
+
+AGENTS = ("pred", "prey")
+
+
+class DecGamePolicyRunner:
+    def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
+        self.env, self.cfg, self.device, self.log_dir = env, train_cfg["runner"], device, log_dir
+        self.views = {a: env.agent_view(a, None) for a in AGENTS}
+        self.runners = {}
+        for a in AGENTS:
+            cfg = dict(train_cfg, runner=dict(train_cfg["runner"]))
+            self.runners[a] = OnPolicyRunner(self.views[a], cfg, os.path.join(log_dir, a) if log_dir is not None else None, device=device)
+        fused = {a: self.runners[a]._fused for a in AGENTS}
+        device_path = all(f is not None and self.runners[a]._game_rollout for a, f in fused.items())
+        for a in AGENTS:
+            other = "prey" if a == "pred" else "pred"
+            if device_path:
+                self.views[a].opponent = fused[other]
+            else:                                         # generic path for both: a view cannot mix a device learner with a torch opponent
+                self.runners[a]._fused, self.runners[a]._game_rollout = None, False
+                self.views[a].opponent = self._sampling_policy(other)
+        self.device_path = device_path
+        self.current_evolution = 0
+        if log_dir is not None:
+            for a in AGENTS:
+                self._follow(a)
+
+    def _follow(self, agent):
+        """Keep the combined files current while ``agent`` 's runner trains: whenever it saves ``model_<it>.pt`` (``runner.save_interval`` and the end
+        of ``learn``) the combined checkpoint is written as well, and every iteration it logs adds a row to ``<log_dir>/progress.csv``."""
+        runner, other = self.runners[agent], self.runners["prey" if agent == "pred" else "pred"]
+        save, log = runner.save, runner._log_scalars
+
+        def save_both(path, infos=None):
+            save(path, infos)
+            m = re.search(r"model_(\d+)\.pt$", path)
+            if m:
+                it = int(m.group(1))
+                self.save(os.path.join(self.log_dir, f"model_{it + other.current_learning_iteration}.pt"), iters={agent: it})
+
+        def log_both(it, *args, **kw):
+            row = log(it, *args, **kw)
+            self._log_row(it + other.current_learning_iteration, agent, it)
+            return row
+        runner.save, runner._log_scalars = save_both, log_both
+
+    def _sampling_policy(self, agent):
+        ac = self.runners[agent].alg.actor_critic
+
+        def act(obs):
+            with torch.no_grad():
+                return ac.act(obs)
+        return act
+
+    @staticmethod
+    def agent_of(evolution):
+        """The agent trained in evolution ``evolution``: the predator when even, the prey when odd."""
+        return AGENTS[evolution % 2]
+
+    @property
+    def current_learning_iteration(self):
+        return sum(r.current_learning_iteration for r in self.runners.values())
+
+    def learn(self, max_num_evolutions, num_learning_iterations, init_at_random_ep_len=False):
+        if init_at_random_ep_len:                          # once, before the first evolution
+            self.env.episode_length_buf[:] = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
+        for e in range(self.current_evolution, self.current_evolution + max_num_evolutions):
+            agent = self.agent_of(e)
+            runner = self.runners[agent]
+            runner.learn(num_learning_iterations=num_learning_iterations, init_at_random_ep_len=False)
+            if runner._fused is not None:
+                runner._fused.sync_device()                # the other view's opponent: this agent's new weights, repacked in place
+            self.current_evolution = e + 1
+            if self.log_dir is not None:
+                self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+
+    def _log_row(self, iteration, agent, agent_iteration):
+        """``<log_dir>/progress.csv``: one row per iteration with an ``agent`` column (the per-agent runners write the full scalar tables under
+        ``<log_dir>/pred`` and ``<log_dir>/prey``)."""
+        os.makedirs(self.log_dir, exist_ok=True)
+        path = os.path.join(self.log_dir, "progress.csv")
+        new = not os.path.isfile(path)
+        with open(path, "a") as fh:
+            if new:
+                fh.write("iteration,evolution,agent,agent_iteration\n")
+            fh.write(f"{iteration},{self.current_evolution},{agent},{agent_iteration}\n")
+
+    def _half(self, agent, it=None):
+        r = self.runners[agent]
+        return {"model_state_dict": r.alg.actor_critic.state_dict(), "optimizer_state_dict": r.alg.optimizer.state_dict(),
+                "iter": r.current_learning_iteration if it is None else it, "infos": None}
+
+    def save(self, path, iters=None):
+        """``iters``: agent -> iteration to record for it (a save in the middle of that agent's ``learn``, whose own count moves at the end)."""
+        iters = iters or {}
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        halves = {a: self._half(a, iters.get(a)) for a in AGENTS}
+        torch.save({"pred": halves["pred"], "prey": halves["prey"], "evolution": self.current_evolution,
+                    "iter": halves["pred"]["iter"] + halves["prey"]["iter"]}, path)
+
+    def load(self, path, load_optimizer=True):
+        d = torch.load(path, map_location=self.device, weights_only=True)
+        for a in AGENTS:
+            r, half = self.runners[a], d[a]
+            r.alg.actor_critic.load_state_dict(half["model_state_dict"])
+            if load_optimizer:
+                r.alg.optimizer.load_state_dict(half["optimizer_state_dict"])
+                if hasattr(r.alg, "after_optimizer_load"):
+                    r.alg.after_optimizer_load()
+            if r._fused is not None:
+                r._fused.sync_device()
+            r.current_learning_iteration = half["iter"]
+        self.current_evolution = d["evolution"]
+        return None
+
+    def get_inference_policy(self, agent, device=None):
+        if agent not in AGENTS:
+            raise ValueError(f"agent must be one of {AGENTS}, got {agent!r}")
+        return self.runners[agent].get_inference_policy(device=device)

@@ -44,8 +44,8 @@ class OnPolicyRunner:
             # high_level_game, opt-in: the high-level actor on the noise stream of the low-level sim's device step counter
             from .fused_actor import FusedActor
             try:
-                fused = FusedActor(self.alg.actor_critic, self.device, seed=int(getattr(env.cfg, "seed", 1)) + 7919,
-                                   step_counter=env.ll_env._sim.buf["step_counter"])
+                fused = FusedActor(self.alg.actor_critic, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
+                                   step_counter=env.ll_env._sim.buf["step_counter"])      # (an agent view of dec_high_level_game names its agent's offset)
                 fused.act_inference(env.get_observations())   # a shape lg_policy_act refuses (rc -4) shows here, not in the first rollout
             except Exception as exc:
                 print(f"[runner] device rollout unavailable ({type(exc).__name__}: {exc}); generic VecEnv loop")
@@ -193,9 +193,13 @@ class OnPolicyRunner:
         ``lg_rollout_record``; the critic once per rollout.  Storage semantics of the generic path: the reference clips the command in the
         caller's tensor after ``PPO.act`` took the log-prob, so ``actions[t]`` is the clipped command while ``actions_log_prob[t]`` (and
         ``sigma[t]``, both written by the actor launch straight into the storage) belong to the unclipped sample.  The game sends no
-        time-outs: nothing is bootstrapped."""
+        time-outs: nothing is bootstrapped.  An agent view of ``dec_high_level_game`` does send them (``dec_agent_view``): they are recorded
+        per step and bootstrapped as ``_rollout_steps_fused`` does."""
         env, alg, fused = self.env, self.alg, self._fused
         st, T = alg.storage, self.num_steps_per_env
+        dec = getattr(env, "dec_agent_view", False)
+        if dec and getattr(self, "_time_outs", None) is None:
+            self._time_outs = torch.zeros(T, env.num_envs, 1, device=self.device)
         obs = env.get_observations()
         lib, step = fused.lib, capi.lg_rollout_step()
         p = lambda x: x.data_ptr()
@@ -205,8 +209,11 @@ class OnPolicyRunner:
         step.std, step.time_outs, step.storage_time_outs = None, None, None
         for t in range(T):
             prev_obs = obs
-            (command, mean), (obs, _, rewards, dones, _) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t])
+            (command, mean), (obs, _, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t])
             step.obs, step.actions, step.mean, step.rewards, step.dones = p(prev_obs), p(command), p(mean), p(rewards), p(dones)
+            touts = infos.get("time_outs") if dec else None
+            if touts is not None:                                 # (absent with env.send_timeouts = False: nothing is bootstrapped then)
+                step.time_outs, step.storage_time_outs = p(touts), p(self._time_outs[t])
             step.storage_obs, step.storage_actions, step.storage_mu = p(st.observations[t]), p(st.actions[t]), p(st.mu[t])
             step.storage_rewards, step.storage_dones = p(st.rewards[t]), p(st.dones[t])
             step.storage_sigma, step.storage_log_prob = None, None
@@ -216,6 +223,8 @@ class OnPolicyRunner:
                 raise RuntimeError(f"lg_rollout_record failed ({rc}): {lib.lg_last_error().decode()}")
         st.step = T
         st.values.copy_(self._critic_values(st).view(T, -1, 1))
+        if dec:
+            st.rewards.add_(alg.gamma * st.values * self._time_outs)                           # bootstrap on time-outs (PPO.process_env_step)
         return obs, obs
 
     # ------------------------------------------------------------------ graphed rollout

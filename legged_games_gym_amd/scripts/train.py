@@ -39,6 +39,8 @@ def _init_distributed(args):
 
 
 def train(args):
+    if args.task in a1_game.DEC_TASKS:
+        raise SystemExit(f"--task={args.task} trains two policies in alternation: use python -m legged_games_gym_amd.scripts.train_dec_game --task={args.task}")
     if args.task in a1_game.TASKS:
         a1_game.register()               # the game layer registers on demand: python -m legged_games_gym_amd.scripts.train --task=high_level_game --headless
     rank, world = _init_distributed(args)

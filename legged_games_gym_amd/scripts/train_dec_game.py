@@ -1,0 +1,37 @@
+"""CLI entry point of the decentralised predator-prey game (reference ``legged_gym/scripts/train_dec_game.py``):
+``python -m legged_games_gym_amd.scripts.train_dec_game --task=dec_high_level_game --headless``
+
+Predator and prey are trained in alternating evolutions (``rl.DecGamePolicyRunner``): ``--max_evolutions`` evolutions of
+``--max_iterations`` PPO iterations each (defaults: the registered train cfg's ``runner.max_evolutions`` / ``runner.max_iterations``).
+``--device_rollout`` trains on the device path: both agents' actors on the matrix cores, three launches per step, every rollout one graph
+replay (off by default: the generic VecEnv loop).  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
+from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
+from legged_games_gym_amd.envs import a1_game
+from legged_games_gym_amd.utils import get_args
+from legged_games_gym_amd.utils.task_registry import task_registry
+
+DEFAULT_TASK = "dec_high_level_game"
+
+
+def train(args):
+    if args.task not in a1_game.DEC_TASKS:
+        raise SystemExit(f"train_dec_game trains {a1_game.DEC_TASKS}; use scripts.train for --task={args.task}")
+    a1_game.register_dec()
+    if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
+        task_registry.get_cfgs(args.task)[1].runner.device_rollout = True
+    env, env_cfg = task_registry.make_env(name=args.task, args=args)
+    runner, train_cfg = task_registry.make_dec_alg_runner(env=env, name=args.task, args=args)
+    runner.learn(max_num_evolutions=train_cfg.runner.max_evolutions, num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)
+    return runner
+
+
+def _args(argv=None):
+    import sys
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if not any(a == "--task" or a.startswith("--task=") for a in argv):
+        argv += ["--task", DEFAULT_TASK]
+    return get_args(argv)
+
+
+if __name__ == "__main__":
+    train(_args())

@@ -127,6 +127,8 @@ def update_cfg_from_args(env_cfg, cfg_train, args):
             cfg_train.seed = args.seed
         if args.max_iterations is not None:
             cfg_train.runner.max_iterations = args.max_iterations
+        if getattr(args, "max_evolutions", None) is not None:
+            cfg_train.runner.max_evolutions = args.max_evolutions
         if args.resume:
             cfg_train.runner.resume = args.resume
         for name in ("experiment_name", "run_name", "load_run", "checkpoint"):
@@ -167,6 +169,7 @@ def get_args(argv=None):
     p.add_argument("--device_rollout", action="store_true", default=False,
                    help="high_level_game: train on the device rollout (runner key of the same name: MFMA high-level actor, three launches per step, one graph "
                         "replay per rollout); an actor shape the kernels refuse falls back to the generic loop with a message")
+    p.add_argument("--max_evolutions", type=int, help="dec_high_level_game: how often predator and prey alternate (scripts/train_dec_game.py)")
     # flags gymutil.parse_arguments contributes
     p.add_argument("--sim_device", type=str, default="cuda:0")
     p.add_argument("--pipeline", type=str, default="gpu")

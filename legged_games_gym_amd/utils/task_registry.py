@@ -5,7 +5,8 @@ Mirror of reference ``legged_gym/utils/task_registry.py:44-162, 224``:
 ``make_alg_runner`` keep their signatures, defaults, printouts-free behaviour
 and error types (``ValueError`` for an unknown task or missing name).  The game task
 ``high_level_game`` goes through the same ``make_env`` / ``make_alg_runner`` once ``envs.a1_game.register()`` has added it;
-``make_dec_alg_runner`` (:164-221, the decentralised game's two-policy runner) is not built.
+``make_dec_alg_runner`` (:164-221) builds the decentralised game's two-policy runner, ``rl.DecGamePolicyRunner``, for
+``dec_high_level_game`` (``envs.a1_game.register_dec()``).
 
 The PPO runner is ``rsl_rl.runners.OnPolicyRunner`` when that package is
 importable, otherwise the bundled ``legged_games_gym_amd.rl.OnPolicyRunner``
@@ -67,7 +68,8 @@ class TaskRegistry:
                          sim_device=args.sim_device, headless=args.headless)
         return env, env_cfg
 
-    def make_alg_runner(self, env, name=None, args=None, train_cfg=None, log_root="default"):
+    def _runner_setup(self, name, args, train_cfg, log_root):
+        """What ``make_alg_runner`` and ``make_dec_alg_runner`` share: (args, train cfg with the CLI overrides, log root a resume searches, this run's log dir or None)."""
         if args is None:
             args = get_args()
         if train_cfg is None:
@@ -88,14 +90,27 @@ class TaskRegistry:
             log_root = default_root          # ... but a resume still finds the checkpoint where rank 0 saved it
         else:
             log_dir = os.path.join(log_root, stamp)
+        return args, train_cfg, log_root, log_dir
 
-        runner = _runner_class()(env, class_to_dict(train_cfg), log_dir, device=args.rl_device)
+    def _resume(self, runner, log_root, train_cfg):
         if train_cfg.runner.resume:
             resume_path = self._resume_path(log_root, train_cfg)
             print(f"Loading model from: {resume_path}")
             runner.load(resume_path)             # every rank loads the same file: replicas (weights + Adam state) start identical
+
+    def make_alg_runner(self, env, name=None, args=None, train_cfg=None, log_root="default"):
+        args, train_cfg, log_root, log_dir = self._runner_setup(name, args, train_cfg, log_root)
+        runner = _runner_class()(env, class_to_dict(train_cfg), log_dir, device=args.rl_device)
+        self._resume(runner, log_root, train_cfg)
         return runner, train_cfg
 
+    def make_dec_alg_runner(self, env, name=None, args=None, train_cfg=None, log_root="default"):
+        """``make_alg_runner`` for the decentralised game (reference :164-221): the bundled ``DecGamePolicyRunner`` on both agents of ``env``."""
+        from legged_games_gym_amd.rl import DecGamePolicyRunner
+        args, train_cfg, log_root, log_dir = self._runner_setup(name, args, train_cfg, log_root)
+        runner = DecGamePolicyRunner(env, class_to_dict(train_cfg), log_dir, device=args.rl_device)
+        self._resume(runner, log_root, train_cfg)
+        return runner, train_cfg
 
     @staticmethod
     def _resume_path(log_root, train_cfg):

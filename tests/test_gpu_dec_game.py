@@ -1,0 +1,693 @@
+"""-m gpu: the decentralised predator-prey game -- the one-tile ``lg_policy_act`` shapes against torch, ``lg_dec_game_pre`` / ``lg_dec_game_post``
+against the NumPy twin and the reference's recorded step, ``lg_dec_game_act`` against the separate launches it replaces, ``DecHighLevelGame``
+against its parts, the captured step against eager steps, and the agent views under ``DecGamePolicyRunner``.  Nothing here reads the
+reference tree: what is needed lies in tests/golden/."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import dec_game_twin as dt
+from tests.dec_game_fixtures import call_inputs, check_call, dec_registered, fixture_params, initial_state, load, synthetic_state  # noqa: F401
+from tests.test_gpu_game import place_ahead, write_ll_checkpoint
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+DEV = "cuda:0"
+HIDDEN = [512, 256, 128]
+INT_KEYS = ("num_envs", "decimation", "heading_command", "custom_origins", "only_positive_rewards_prey", "only_positive_rewards_pred", "max_episode_length", "seed")
+VEC_KEYS = ("cmd_lin_vel_x", "cmd_lin_vel_y", "predator_lin_vel_x", "predator_lin_vel_y", "base_init_state", "default_dof_pos")
+FLOAT_KEYS = ("capture_dist", "half_fov", "max_rel_pos", "ll_rew_weight", "scale_evasion_dt", "scale_pursuit_dt", "scale_termination_prey_dt", "sim_dt", "predator_z",
+              "max_episode_length_s")
+
+
+def pack_params(p):
+    from legged_games_gym_amd import capi
+    P = capi.lg_dec_game_params()
+    for k in INT_KEYS:
+        setattr(P, k, int(p[k]))
+    for k in VEC_KEYS:
+        capi._fill(getattr(P, k), p[k])
+    for k in FLOAT_KEYS:
+        setattr(P, k, float(p[k]))
+    return P
+
+
+def unpack_params(P):
+    p = {k: int(getattr(P, k)) for k in INT_KEYS}
+    p.update({k: tuple(float(v) for v in getattr(P, k)) for k in VEC_KEYS})
+    p.update({k: float(getattr(P, k)) for k in FLOAT_KEYS})
+    return dict(p, env_radius=-1.0)
+
+
+def agent_actor(agent, seed=3, std=None, bias=None):
+    from legged_games_gym_amd.rl import ActorCritic
+    no, na = (16, 4) if agent == "prey" else (3, 2)
+    torch.manual_seed(seed)
+    ac = ActorCritic(no, no, na, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV)
+    with torch.no_grad():
+        if std is not None:
+            ac.std.copy_(torch.as_tensor(std))
+        if bias is not None:
+            ac.actor[-1].bias.copy_(torch.as_tensor(bias))
+    return ac
+
+
+# ----------------------------------------------------------------------------- 1. the one-tile lg_policy_act shapes
+@pytest.mark.parametrize("agent", ["prey", "pred"])
+@pytest.mark.parametrize("precision", [1, 0])
+def test_one_tile_actor_shapes_match_torch_forward(precision, agent):
+    """The checks of tests/test_gpu_game_policy.py on the 16-512-256-128-4 and 3-512-256-128-2 actors (``tiles[0] == 1``, refused with -4
+    before): 1e-4 of the output scale at wide precision 1 (split-bf16 products), 2e-5 at precision 0 (f32 MFMA); N = 1000 leaves a ragged last
+    workgroup at both."""
+    from legged_games_gym_amd import capi
+    from legged_games_gym_amd.rl import FusedActor
+    lib = capi.load_library()
+    tol = 2e-5 if precision == 0 else 1e-4
+    old = lib.lg_mlp_wide_set_precision(precision)
+    try:
+        na = 4 if agent == "prey" else 2
+        ac = agent_actor(agent, std=torch.linspace(0.3, 1.4, na))
+        fa = FusedActor(ac, DEV, seed=5)
+        obs = torch.randn(1000, 16 if agent == "prey" else 3, device=DEV) * 2.0
+        with torch.no_grad():
+            want = ac.actor(obs)
+        actions, mean = fa.act_with_mean(obs)
+        actions, mean = actions.clone(), mean.clone()
+        torch.cuda.synchronize()
+        scale = float(want.abs().max())
+        print(f"{agent} precision {precision}: max |mean - torch| = {float((mean - want).abs().max()):.3e}, scale {scale:.3f}")
+        assert float((mean - want).abs().max()) < tol * max(1.0, scale)
+        z = ((actions - mean) / ac.std.detach()).flatten()
+        assert abs(float(z.mean())) < 0.06 and abs(float(z.std()) - 1.0) < 0.06 and float(z.abs().max()) < 6.0      # (2000 / 4000 samples: 4 sigma of the mean is 0.09 / 0.06)
+        assert not torch.equal(fa.act(obs).clone(), actions)                       # fresh noise per call
+        assert torch.allclose(fa.act_inference(obs), want, atol=tol * max(1.0, scale))
+        with torch.no_grad():                                                      # sync_device() follows changed weights on the device
+            for prm in ac.actor.parameters():
+                prm.add_(0.05 * torch.randn_like(prm))
+        fa.sync_device()
+        want3 = ac.act_inference(obs).detach()
+        got3 = fa.act_inference(obs).clone()
+        assert float((got3 - want3).abs().max()) < tol * max(1.0, float(want3.abs().max()))
+        assert torch.equal(FusedActor(ac, DEV, seed=5).act_inference(obs), got3)   # = a fresh host-side pack
+        for n in (1, 33):                                                          # one lane of one workgroup; one env in the second workgroup
+            assert torch.allclose(fa.act_inference(obs[:n].contiguous()), want3[:n], atol=tol * max(1.0, float(want3.abs().max())))
+    finally:
+        lib.lg_mlp_wide_set_precision(old)
+
+
+# ----------------------------------------------------------------------------- 2. kernels without an env
+def device_pre(p, command_prey, command_pred):
+    from legged_games_gym_amd import capi
+    n = command_prey.shape[0]
+    cy = torch.from_numpy(np.ascontiguousarray(command_prey, F)).to(DEV)
+    cp = torch.from_numpy(np.ascontiguousarray(command_pred, F)).to(DEV)
+    ll = torch.full((n, 4), 7.0, device=DEV)
+    B = capi.dec_game_buffers({"command_prey": cy.data_ptr(), "command_pred": cp.data_ptr(), "ll_commands": ll.data_ptr()})
+    capi.dec_game_pre(pack_params(dict(p, num_envs=n)), B, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return cy.cpu().numpy(), cp.cpu().numpy(), ll.cpu().numpy()
+
+
+def device_post(p, s, step, counter_on_device=False, launches=1):
+    """``lg_dec_game_post`` on the arrays of a twin state dict, uploaded as they are -> the same dict layout as ``dec_game_twin.post`` returns.
+    ``launches`` > 1 repeats the launch on a fresh upload with the SAME accumulator and ticket buffers: every launch must leave them zero."""
+    from legged_games_gym_amd import capi
+    n = s["root_states"].shape[0]
+    accum, ticket = torch.zeros(4, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV)
+    for _ in range(launches):
+        t = {k: torch.from_numpy(np.ascontiguousarray(s[k])).to(DEV) for k in ("command_pred", "root_states", "env_origins", "ll_rew", "predator_pos", "obs_prey",
+                                                                               "curr_episode_step", "episode_length_buf", "episode_sums", "episode_means")}
+        dof = torch.from_numpy(np.ascontiguousarray(np.stack((s["dof_pos"], s["dof_vel"]), axis=-1), F)).to(DEV)
+        t["ll_reset"] = torch.from_numpy(np.ascontiguousarray(s["ll_reset"]).astype(bool)).to(DEV)
+        t["obs_pred"], t["rew_prey"], t["rew_pred"] = torch.full((n, 3), -3.0, device=DEV), torch.full((n,), -3.0, device=DEV), torch.full((n,), -3.0, device=DEV)
+        t["reset_buf"], t["time_out_buf"] = torch.zeros(n, dtype=torch.bool, device=DEV), torch.ones(n, dtype=torch.bool, device=DEV)
+        t["counter"] = torch.tensor([step], dtype=torch.int64, device=DEV)
+        for k in ("command_pred", "root_states", "env_origins", "ll_rew", "predator_pos", "obs_prey", "episode_sums", "episode_means"):
+            assert t[k].dtype == torch.float32
+        B = capi.dec_game_buffers({"command_pred": t["command_pred"].data_ptr(), "ll_root_states": t["root_states"].data_ptr(), "ll_dof_state": dof.data_ptr(),
+                                   "ll_env_origins": t["env_origins"].data_ptr(), "ll_rew_buf": t["ll_rew"].data_ptr(), "ll_reset_buf": t["ll_reset"].data_ptr(),
+                                   "ll_step_counter": t["counter"].data_ptr(), "predator_pos": t["predator_pos"].data_ptr(), "obs_prey": t["obs_prey"].data_ptr(),
+                                   "obs_pred": t["obs_pred"].data_ptr(), "rew_prey": t["rew_prey"].data_ptr(), "rew_pred": t["rew_pred"].data_ptr(),
+                                   "reset_buf": t["reset_buf"].data_ptr(), "time_out_buf": t["time_out_buf"].data_ptr(),
+                                   "curr_episode_step": t["curr_episode_step"].data_ptr(), "episode_length_buf": t["episode_length_buf"].data_ptr(),
+                                   "episode_sums": t["episode_sums"].data_ptr(), "episode_means": t["episode_means"].data_ptr(),
+                                   "extras_accum": accum.data_ptr(), "extras_ticket": ticket.data_ptr()})
+        capi.dec_game_post(pack_params(dict(p, num_envs=n)), B, -1 if counter_on_device else step, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert float(accum.abs().max()) == 0.0 and int(ticket[0]) == 0                # left zero for the next launch
+    out = {k: t[k].cpu().numpy() for k in ("root_states", "predator_pos", "obs_prey", "obs_pred", "rew_prey", "rew_pred", "reset_buf", "time_out_buf",
+                                           "curr_episode_step", "episode_length_buf", "episode_sums", "episode_means")}
+    out["dof_pos"], out["dof_vel"] = dof[..., 0].cpu().numpy(), dof[..., 1].cpu().numpy()
+    assert int(t["counter"][0]) == step and np.array_equal(t["command_pred"].cpu().numpy(), s["command_pred"])      # inputs are left alone
+    return out
+
+
+@pytest.mark.parametrize("tag", ["a", "t"])
+def test_kernels_reproduce_the_recorded_reference_step(golden_dir, tag):
+    """dec_game_step.npz through the DEVICE: the state is carried by the device's own outputs; same comparison as tests/test_dec_game_reference.py,
+    with 2 more ulp on the floats behind the device's 1-ulp sqrt."""
+    g = load(golden_dir)
+    p = fixture_params(g, tag)
+    state, carried = initial_state(g, tag), None
+    for k in range(g[f"{tag}_step"].shape[0]):
+        c_prey, c_pred, ll_cmd = device_pre(p, g[f"{tag}_in_command_prey"][k], g[f"{tag}_in_command_pred"][k])
+        for have, key in ((c_prey, "command_prey"), (c_pred, "command_pred"), (ll_cmd, "ll_commands")):
+            np.testing.assert_array_equal(have.view(np.uint32), g[f"{tag}_{key}"][k].view(np.uint32), err_msg=key)
+        s, _ = call_inputs(g, tag, k, p, state)
+        _, info = dt.post(p, s, u_root=g[f"{tag}_u_root"][k], u_pred=g[f"{tag}_u_pred"][k], u_dof=g[f"{tag}_u_dof"][k])
+        dt.assert_margins(p, info)
+        out = device_post(p, s, int(g[f"{tag}_step"][k]), counter_on_device=bool(k % 2))
+        want = {n: g[f"{tag}_{n}"][k] for n in ("predator_pos", "root_states", "dof_pos", "dof_vel", "obs_prey", "obs_pred", "rew_prey", "rew_pred", "reset_buf",
+                                                "time_out_buf", "curr_episode_step", "episode_length_buf", "episode_sums", "episode_means")}
+        print(f"{tag} call {k}: means device {out['episode_means']} reference {want['episode_means']}")
+        carried = check_call(p, s, out, info, want, extra_ulp=2, carried=carried, carry_sums=True)
+        np.testing.assert_array_equal(out["obs_prey"][:, 15] != 0, g[f"{tag}_sense_flag"][k] != 0)
+        state = dict(state, **{n: out[n] for n in ("predator_pos", "obs_prey", "dof_pos", "dof_vel", "curr_episode_step", "episode_length_buf", "episode_sums",
+                                                   "episode_means")})
+
+
+@pytest.mark.parametrize("n,termination", [(1, 0.0), (63, -0.5), (257, 0.0), (4097, -0.5)])
+def test_kernels_match_the_twin_on_ragged_sizes(n, termination):
+    """Seeded state through the twin at sizes with a ragged last workgroup (256 threads per workgroup): one workgroup, two, seventeen -- the
+    ticket and the cross-workgroup accumulation of the episode means -- each launched twice on the same accumulator."""
+    p = dt.params(num_envs=n, seed=1234 + n, custom_origins=n % 2, scale_termination_prey_dt=termination, only_positive_rewards_pred=int(n == 257))
+    step = 40 + n
+    s = synthetic_state(p, n, seed=n, step=step)
+    rng = np.random.default_rng(n)
+    raw_prey, raw_pred = rng.uniform(-4, 4, (n, 4)).astype(F), rng.uniform(-4, 4, (n, 2)).astype(F)
+    got = device_pre(p, raw_prey, raw_pred)
+    for have, want in zip(got, dt.pre(p, raw_prey, raw_pred)):
+        np.testing.assert_array_equal(have.view(np.uint32), want.view(np.uint32))
+    want, info = dt.post(p, s, step=step)
+    dt.assert_margins(p, info)
+    out = device_post(p, s, step, counter_on_device=True, launches=2)
+    check_call(p, s, out, info, want, extra_ulp=2)
+    if not want["reset_buf"].any():
+        np.testing.assert_array_equal(out["episode_means"], s["episode_means"])       # untouched when no env was done
+    if n >= 63:
+        assert want["reset_buf"].any() and not want["reset_buf"].all() and info["visible"].any() and not info["visible"].all()
+        assert info["time_out"].any() and info["capture"].any()
+    if n == 257:
+        assert (out["rew_pred"] == 0).all()                                          # only_positive_rewards on a pursuit reward that is never positive
+
+
+# ----------------------------------------------------------------------------- 3. lg_dec_game_act = the separate launches
+# last-layer biases and stds that put every clipped column on both sides of its range and the prey's column 2 on both sides of +pi
+BIAS_PREY, STD_PREY = (0.7, -0.7, 2.2, 0.0), (0.6, 0.6, 1.0, 1.0)
+BIAS_PRED, STD_PRED = (1.5, -1.5), (1.0, 1.0)
+
+
+def three_actors():
+    from legged_games_gym_amd.rl import ActorCritic, FusedActor
+    prey_ac, pred_ac = agent_actor("prey", 3, STD_PREY, BIAS_PREY), agent_actor("pred", 5, STD_PRED, BIAS_PRED)
+    torch.manual_seed(4)
+    ll_ac = ActorCritic(235, 235, 12, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV)
+    return (prey_ac, pred_ac, ll_ac), (FusedActor(prey_ac, DEV, seed=11), FusedActor(pred_ac, DEV, seed=12), FusedActor(ll_ac, DEV, seed=1))
+
+
+def outputs_struct(**tensors):
+    from legged_games_gym_amd import capi
+    o = capi.lg_dec_act_outputs()
+    for k, v in tensors.items():
+        setattr(o, k, v.data_ptr())
+    return o
+
+
+@pytest.mark.parametrize("counter_on_device", [False, True])
+@pytest.mark.parametrize("n,heading", [(1, 1), (33, 0), (1000, 1), (2000, 0), (4096, 1)])
+def test_shared_actor_launch_is_bit_identical_to_the_separate_launches(n, heading, counter_on_device):
+    from legged_games_gym_amd import capi
+    lib = capi.load_library()
+    assert lib.lg_mlp_wide_set_precision(1) == 1                                   # the default
+    (prey_ac, pred_ac, _), (prey, pred, ll) = three_actors()
+    gen = torch.Generator().manual_seed(100 + n)
+    prey_obs, pred_obs = (torch.randn(n, 16, generator=gen) * 3.0).to(DEV), (torch.randn(n, 3, generator=gen) * 3.0).to(DEV)
+    ll_obs = (torch.randn(n, 235, generator=gen) * 1.5).to(DEV)
+    P = pack_params(dt.params(num_envs=n, heading_command=heading))
+    stream = torch.cuda.current_stream().cuda_stream
+    step_value = 77 + n
+    counter = torch.tensor([step_value - 1], dtype=torch.int64, device=DEV)        # the kernels read counter + 1
+    step, ctr = (-1, counter.data_ptr()) if counter_on_device else (step_value, None)
+    seed_prey, seed_pred = 4242 + 7919, 4242 + 7919 + 104729
+    f = lambda *s: torch.full(s, -9.0, device=DEV)
+
+    # the separate launches
+    sy_w, my_w, sp_w, mp_w, act_w = f(n, 4), f(n, 4), f(n, 2), f(n, 2), f(n, 12)
+    assert lib.lg_policy_act(prey.handle, prey_obs.data_ptr(), sy_w.data_ptr(), my_w.data_ptr(), n, seed_prey, step, ctr, 0, stream) == 0
+    assert lib.lg_policy_act(pred.handle, pred_obs.data_ptr(), sp_w.data_ptr(), mp_w.data_ptr(), n, seed_pred, step, ctr, 0, stream) == 0
+    assert lib.lg_policy_act(ll.handle, ll_obs.data_ptr(), act_w.data_ptr(), None, n, seed_prey, step, ctr, 1, stream) == 0
+    cy_w, cp_w, llc_w = sy_w.clone(), sp_w.clone(), f(n, 4)
+    capi.dec_game_pre(P, capi.dec_game_buffers({"command_prey": cy_w.data_ptr(), "command_pred": cp_w.data_ptr(), "ll_commands": llc_w.data_ptr()}), stream)
+
+    # one launch
+    cy, cp, llc, act, my, mp = f(n, 4), f(n, 2), f(n, 4), f(n, 12), f(n, 4), f(n, 2)
+    sy, gy, ly, oy, sp, gp, lp, op = f(n, 4), f(n, 4), f(n), f(n, 16), f(n, 2), f(n, 2), f(n), f(n, 3)
+    B = capi.dec_game_buffers({"command_prey": cy.data_ptr(), "command_pred": cp.data_ptr(), "ll_commands": llc.data_ptr()})
+    call = lambda out_pred, out_prey, det_pred=False, det_prey=False: capi.dec_game_act(
+        pred.handle, prey.handle, ll.handle, P, B, pred_obs.data_ptr(), prey_obs.data_ptr(), ll_obs.data_ptr(), act.data_ptr(), mp.data_ptr(), my.data_ptr(),
+        seed_pred, seed_prey, step, ctr, det_pred, det_prey, out_pred, out_prey, stream)
+    assert call(outputs_struct(sample=sp, sigma=gp, log_prob=lp, obs_copy=op), outputs_struct(sample=sy, sigma=gy, log_prob=ly, obs_copy=oy)) == 0
+    torch.cuda.synchronize()
+    for name, got, want in (("command_prey", cy, cy_w), ("command_pred", cp, cp_w), ("ll_commands", llc, llc_w), ("mean_prey", my, my_w), ("mean_pred", mp, mp_w),
+                            ("sample_prey", sy, sy_w), ("sample_pred", sp, sp_w), ("ll_actions", act, act_w), ("obs_copy_prey", oy, prey_obs),
+                            ("obs_copy_pred", op, pred_obs), ("ll_commands = command_prey", llc, cy)):
+        assert torch.equal(got, want), (name, float((got - want).abs().max()))
+    assert int(counter[0]) == step_value - 1
+    for ac, sigma, logp, mean, sample, who in ((prey_ac, gy, ly, my, sy, "prey"), (pred_ac, gp, lp, mp, sp, "pred")):
+        std = ac.std.detach()
+        assert torch.equal(sigma, std.expand_as(sigma))
+        err = float((logp - torch.distributions.Normal(mean, std.expand_as(mean)).log_prob(sample).sum(-1)).abs().max())
+        print(f"n {n} heading {heading} {who}: max |log_prob - torch| = {err:.3e}")
+        assert err < 2e-5                                                            # the bound tests/test_gpu_game_policy.py keeps for the f32 log-prob
+    if n >= 1000:
+        # the two sampled roles draw DIFFERENT noise: same purposes, different seeds
+        zy, zp = (sy - my) / prey_ac.std.detach(), (sp - mp) / pred_ac.std.detach()
+        assert not torch.equal(zy[:, :2], zp) and float((zy[:, :2] - zp).abs().mean()) > 0.5
+        for col, hi, c, s_ in ((0, 1.0, cy, sy), (1, 1.0, cy, sy), (0, 2.0, cp, sp), (1, 2.0, cp, sp)):            # both sides of every range
+            out = s_[:, col].abs() > hi
+            assert bool(out.any()) and bool((~out).any())
+            assert bool((c[out][:, col].abs() == hi).all()) and torch.equal(c[~out][:, col], s_[~out][:, col])
+        beyond = sy[:, 2].abs() > math.pi
+        assert bool(beyond.any()) and bool((~beyond).any())
+        if heading:
+            assert bool((cy[beyond][:, 2].abs() <= math.pi).all()) and not torch.equal(cy[:, 2], sy[:, 2])
+        else:
+            assert torch.equal(cy[:, 2], sy[:, 2])
+    assert torch.equal(cy[:, 3], sy[:, 3])
+
+    # the optional outputs are optional; deterministic per agent: that agent's command is its clipped mean, the other still samples
+    keep = [x.clone() for x in (cy, cp, llc, act, my, mp)]
+    assert call(None, None) == 0
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(keep, (cy, cp, llc, act, my, mp)))
+    assert call(None, None, det_pred=True) == 0
+    det_y, det_p, scratch = my.clone(), mp.clone(), f(n, 4)
+    capi.dec_game_pre(P, capi.dec_game_buffers({"command_prey": det_y.data_ptr(), "command_pred": det_p.data_ptr(), "ll_commands": scratch.data_ptr()}), stream)
+    torch.cuda.synchronize()
+    assert torch.equal(cp, det_p) and torch.equal(cy, keep[0]) and torch.equal(mp, keep[5])
+    assert call(None, None, det_prey=True) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(cy, det_y) and torch.equal(llc, det_y) and torch.equal(cp, keep[1])
+
+
+def test_shared_actor_launch_refuses_precision_0_other_shapes_and_equal_seeds():
+    from legged_games_gym_amd import capi
+    from legged_games_gym_amd.rl import ActorCritic, FusedActor
+    lib = capi.load_library()
+    n = 64
+    _, (prey, pred, ll) = three_actors()
+    hl = FusedActor(ActorCritic(19, 19, 6, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV), DEV, seed=1)
+    t = {k: torch.zeros(n, w, device=DEV) for k, w in (("cy", 4), ("cp", 2), ("llc", 4), ("act", 12), ("my", 4), ("mp", 2), ("oy", 16), ("op", 3), ("ll_obs", 235))}
+    P = pack_params(dt.params(num_envs=n))
+    B = capi.dec_game_buffers({"command_prey": t["cy"].data_ptr(), "command_pred": t["cp"].data_ptr(), "ll_commands": t["llc"].data_ptr()})
+    call = lambda a, b, c, s1=1, s2=2: capi.dec_game_act(a.handle, b.handle, c.handle, P, B, t["op"].data_ptr(), t["oy"].data_ptr(), t["ll_obs"].data_ptr(),
+                                                         t["act"].data_ptr(), t["mp"].data_ptr(), t["my"].data_ptr(), s1, s2, 1, None, False, False,
+                                                         stream=torch.cuda.current_stream().cuda_stream)
+    assert call(pred, prey, ll) == 0
+    assert call(prey, pred, ll) == -4 and call(pred, prey, prey) == -4 and call(pred, hl, ll) == -4 and call(hl, prey, ll) == -4
+    with pytest.raises(RuntimeError, match="must differ"):
+        call(pred, prey, ll, 5, 5)
+    old = lib.lg_mlp_wide_set_precision(0)
+    try:
+        assert call(pred, prey, ll) == -4
+    finally:
+        lib.lg_mlp_wide_set_precision(old)
+    torch.cuda.synchronize()
+
+
+# ----------------------------------------------------------------------------- 4. the env
+def make_dec(ckpt, n=512, seed=1, noise=True, tweak=None):
+    from legged_games_gym_amd.envs.a1_game import DecHighLevelGame, DecHighLevelGameCfg
+    from legged_games_gym_amd.utils import get_args, set_seed
+    from legged_games_gym_amd.utils.helpers import class_to_dict, parse_sim_params
+    cfg = DecHighLevelGameCfg()
+    cfg.env.num_envs, cfg.env.ll_policy_path = n, ckpt
+    cfg.noise.add_noise, cfg.seed = noise, seed
+    if tweak:
+        tweak(cfg)
+    args = get_args(["--headless", "--sim_device", DEV, "--rl_device", DEV])
+    set_seed(seed)
+    return DecHighLevelGame(cfg, parse_sim_params(args, {"sim": class_to_dict(cfg.sim)}), args.physics_engine, DEV, True)
+
+
+def snapshot(env, command_pred):
+    """The inputs of ``lg_dec_game_post`` as the twin takes them."""
+    ll = env.ll_env
+    c = lambda x: x.detach().cpu().numpy().copy()
+    return dict(command_pred=c(command_pred), root_states=c(ll.root_states), dof_pos=c(ll.dof_pos), dof_vel=c(ll.dof_vel), env_origins=c(ll.env_origins),
+                ll_rew=c(ll.rew_buf), ll_reset=c(ll.reset_buf), predator_pos=c(env.predator_pos), obs_prey=c(env.obs_buf_prey), curr_episode_step=c(env.curr_episode_step),
+                episode_length_buf=c(env.episode_length_buf), episode_sums=c(env._episode_sums), episode_means=c(env._episode_means))
+
+
+def outputs(env):
+    c = lambda x: x.detach().cpu().numpy().copy()
+    ll = env.ll_env
+    return dict(root_states=c(ll.root_states), dof_pos=c(ll.dof_pos), dof_vel=c(ll.dof_vel), predator_pos=c(env.predator_pos), obs_prey=c(env.obs_buf_prey),
+                obs_pred=c(env.obs_buf_pred), rew_prey=c(env.rew_buf_prey), rew_pred=c(env.rew_buf_pred), reset_buf=c(env.reset_buf), time_out_buf=c(env.time_out_buf),
+                curr_episode_step=c(env.curr_episode_step), episode_length_buf=c(env.episode_length_buf), episode_sums=c(env._episode_sums),
+                episode_means=c(env._episode_means))
+
+
+def two_envs(tmp_path, seed, reset_seed, n=512):
+    ckpt = write_ll_checkpoint(str(tmp_path / "ll" / "model_0.pt"), seed=3)
+    A, B = make_dec(ckpt, n, seed=seed), make_dec(ckpt, n, seed=seed)
+    for env in (A, B):
+        torch.manual_seed(reset_seed)             # reset_idx from the host draws from torch's generator
+        env.reset()
+        place_ahead(env, torch.arange(32, 64, device=DEV), 0.8)                          # captured within a few steps
+        env.ll_env.episode_length_buf[torch.arange(0, 32, device=DEV)] = int(env.ll_env.max_episode_length) - 12      # low-level time-outs
+        env.episode_length_buf[torch.arange(64, 96, device=DEV)] = int(env.max_episode_length) - 6                    # the game's own time-outs
+    return A, B
+
+
+STATE = ("obs_buf_prey", "obs_buf_pred", "rew_buf_prey", "rew_buf_pred", "reset_buf", "time_out_buf", "predator_pos", "curr_episode_step", "episode_length_buf",
+         "_episode_sums", "_episode_means")
+
+
+def assert_same_state(A, B, k):
+    for name in STATE:
+        assert torch.equal(getattr(A, name), getattr(B, name)), (k, name)
+    for name in ("root_states", "dof_state", "obs_buf", "commands"):
+        assert torch.equal(getattr(A.ll_env, name), getattr(B.ll_env, name)), (k, name)
+
+
+GUARD = 0.15          # rad: predators whose bearing comes this close to the edge of the field of view are put back straight ahead
+
+
+def test_env_surface_and_step_equals_its_parts_and_the_twin(tmp_path):
+    """Two identically seeded envs: A calls ``step``; on B the test calls pre -> act_inference -> ll_env.step -> post by hand and checks post against the
+    twin from a snapshot of its inputs (the method of tests/test_gpu_game.py).  A and B must agree bit for bit at every step."""
+    from legged_games_gym_amd import capi
+    N = 512
+    A, B = two_envs(tmp_path, seed=7, reset_seed=70, n=N)
+    assert (A.num_envs, A.num_obs_prey, A.num_actions_prey, A.num_obs_pred, A.num_actions_pred) == (N, 16, 4, 3, 2) and not hasattr(A, "_sim")
+    assert A.num_privileged_obs_prey is None and A.num_privileged_obs_pred is None and A.get_privileged_observations_pred() is None
+    assert A.max_episode_length == 1000 and set(A.extras["episode"]) == {"rew_pred_pursuit", "rew_prey_evasion"} and A.extras["time_outs"] is A.time_out_buf
+    assert A.get_observations_pred() is A.obs_buf_pred and A.get_observations_prey() is A.obs_buf_prey
+    assert A.prey_states is A.ll_env.root_states and set(A.episode_sums_prey) == {"evasion"} and set(A.episode_sums_pred) == {"pursuit"}
+    assert_same_state(A, B, -1)
+    p = unpack_params(B._P)
+    assert p["default_dof_pos"] == tuple(float(v) for v in B.ll_env.default_dof_pos[0]) and p["max_episode_length"] == 1000
+    gen = torch.Generator().manual_seed(5)
+    stream = torch.cuda.current_stream().cuda_stream
+    seen = {"capture": 0, "time_out": 0, "ll_only": 0, "clipped": 0}
+    for k in range(24):
+        s0 = snapshot(A, torch.zeros(N, 2))
+        _, _, angle, _, _ = dt.sense(p, s0["predator_pos"], s0["root_states"][:, :3], s0["root_states"][:, 3:7], s0["obs_prey"][:, 9:12])
+        near = torch.from_numpy(np.nonzero(np.abs(np.abs(angle) - F(p["half_fov"])) < GUARD)[0]).to(DEV)
+        if len(near):
+            for env in (A, B):
+                rel = env.predator_pos[near, :2] - env.ll_env.root_states[near, :2]
+                place_ahead(env, near, rel.norm(dim=1))
+        cmd_prey = (3.0 * torch.randn(N, 4, generator=gen)).to(DEV)                  # well outside the ranges: the clips are exercised
+        cmd_pred = (0.3 * torch.randn(N, 2, generator=gen)).to(DEV)                  # the predators drift slowly ...
+        cmd_pred[:8] = 30.0                                                          # ... but for eight that are clipped ...
+        chase = torch.arange(32, 64, device=DEV)                                     # ... and 32 that home in at 2 m/s from 0.8 m: 0.04 m per step
+        to_prey = A.ll_env.root_states[chase, :2] - A.predator_pos[chase, :2]
+        cmd_pred[chase] = 2.0 * to_prey / to_prey.norm(dim=1, keepdim=True)
+        seen["clipped"] += int((cmd_prey[:, :2].abs() > 1.0).sum()) + int((cmd_pred.abs() > 2.0).sum())
+        pa, ya, pb, yb = cmd_pred.clone(), cmd_prey.clone(), cmd_pred.clone(), cmd_prey.clone()
+        prev_prey = A.obs_buf_prey
+        res = A.step(pa, ya)
+        assert res[1] is A.obs_buf_prey and res[1] is not prev_prey and res[0] is A.obs_buf_pred and res[6] is A.reset_buf and res[7] is A.extras
+        # B, by hand
+        ll = B.ll_env
+        B._flip_observations(carry=True)
+        bufs = B._bind(pb, yb, B.obs_buf_pred, B.obs_buf_prey)
+        capi.dec_game_pre(B._P, bufs, stream)
+        actions = B.ll_policy(ll.obs_buf)
+        ll.step(actions)
+        torch.cuda.synchronize()
+        s = snapshot(B, pb)
+        capi.dec_game_post(B._P, bufs, ll.common_step_counter, stream)
+        torch.cuda.synchronize()
+        want, info = dt.post(p, s, step=ll.common_step_counter)
+        dt.assert_margins(p, info)
+        check_call(p, s, outputs(B), info, want, extra_ulp=2)
+        assert torch.equal(pa, pb) and torch.equal(ya, yb) and float(pa.abs().max()) <= 2.0 and float(ya[:, :2].abs().max()) <= 1.0
+        assert_same_state(A, B, k)
+        seen["capture"] += int(info["capture"].sum()); seen["time_out"] += int(info["time_out"].sum())
+        seen["ll_only"] += int(((s["ll_reset"] != 0) & ~info["capture"] & ~info["time_out"]).sum())
+    assert seen["capture"] >= 8 and seen["time_out"] >= 16 and seen["ll_only"] >= 8 and seen["clipped"] > 0, seen
+    # a reset from the host re-draws the joints as well
+    ids = torch.arange(0, N, 2, device=DEV)
+    A.reset_idx(ids)
+    ratio = A.ll_env.dof_pos[ids] / A.ll_env.default_dof_pos
+    assert bool(((ratio >= 0.5) & (ratio <= 1.5)).all()) and bool((A.ll_env.dof_vel[ids] == 0).all()) and bool((A.episode_length_buf[ids] == 0).all())
+    assert bool((A._episode_sums[:, ids] == 0).all()) and bool((A.obs_buf_prey[ids, :12] == 100).all())
+
+
+def test_construction_refuses_what_the_reference_cannot_run(tmp_path):
+    ckpt = write_ll_checkpoint(str(tmp_path / "ll" / "model_0.pt"), seed=3)
+
+    def pred_termination(cfg):
+        cfg.rewards_predator.scales.termination = -1.0
+    with pytest.raises(ValueError, match="rewards_predator.scales.termination"):
+        make_dec(ckpt, 16, tweak=pred_termination)
+
+    def sizes(cfg):
+        cfg.env.num_observations_prey = 19
+    with pytest.raises(ValueError, match="16 / 4"):
+        make_dec(ckpt, 16, tweak=sizes)
+
+    def prey_termination(cfg):
+        cfg.rewards_prey.scales.termination = -25.0
+    env = make_dec(ckpt, 16, tweak=prey_termination)
+    assert set(env.extras["episode"]) == {"rew_pred_pursuit", "rew_prey_evasion", "rew_prey_termination"} and env._P.scale_termination_prey_dt == pytest.approx(-0.5)
+
+
+def test_missing_low_level_checkpoint_says_to_train_a1(tmp_path, monkeypatch):
+    import legged_games_gym_amd.envs.a1_game.dec_high_level_game as mod
+    monkeypatch.setattr(mod, "LEGGED_GYM_ROOT_DIR", str(tmp_path))
+    with pytest.raises(RuntimeError, match="dec_high_level_game needs a trained low-level policy.*Train the a1 task first"):
+        make_dec(None, 16)
+
+
+def fused_pair(env_or_none=None, seeds=(21 + 104729, 21)):
+    from legged_games_gym_amd.rl import FusedActor
+    ctr = None if env_or_none is None else env_or_none.ll_env._sim.buf["step_counter"]
+    return (FusedActor(agent_actor("pred", 6, STD_PRED, BIAS_PRED), DEV, seed=seeds[0], step_counter=ctr),
+            FusedActor(agent_actor("prey", 8, STD_PREY, BIAS_PREY), DEV, seed=seeds[1], step_counter=ctr))
+
+
+@pytest.mark.parametrize("precision", [1, 0])
+def test_step_policy_equals_actors_then_step(tmp_path, precision):
+    """A: ``step_policy(fused_pred, fused_prey)``.  B, identically seeded: both ``act_with_mean`` then ``step``.  Same actor seeds and step counts.
+    At wide precision 0 ``step_policy`` takes the separate launches (rc -4) and must agree as well."""
+    from legged_games_gym_amd import capi
+    lib = capi.load_library()
+    old = lib.lg_mlp_wide_set_precision(precision)
+    try:
+        A, B = two_envs(tmp_path, seed=9, reset_seed=90)
+        (pa, ya), (pb, yb) = fused_pair(), fused_pair()
+        n = A.num_envs
+        sample_y, sample_p, ocopy = torch.empty(n, 4, device=DEV), torch.empty(n, 2, device=DEV), torch.empty(n, 16, device=DEV)
+        resets, clipped = 0, 0
+        for k in range(16):
+            prev_prey, prev_pred = A.obs_buf_prey, A.obs_buf_pred
+            read = prev_prey.clone()
+            (cpa, mpa), (cya, mya), res = A.step_policy(pa, ya, out_pred={"sample": sample_p}, out_prey={"sample": sample_y, "obs_copy": ocopy} if k % 2 else {"sample": sample_y})
+            act_p, mpb = pb.act_with_mean(B.obs_buf_pred)
+            act_y, myb = yb.act_with_mean(B.obs_buf_prey)
+            raw_p, raw_y = act_p.clone(), act_y.clone()
+            B.step(act_p, act_y)                                                       # clips where they are
+            torch.cuda.synchronize()
+            assert A.last_act_rc == (0 if precision == 1 else -4), k                  # one shared launch, or the announced separate launches
+            assert torch.equal(cpa, act_p) and torch.equal(cya, act_y) and torch.equal(mpa, mpb) and torch.equal(mya, myb), k
+            assert torch.equal(sample_p, raw_p) and torch.equal(sample_y, raw_y), k
+            assert res[1] is A.obs_buf_prey and res[1] is not prev_prey and res[0] is not prev_pred and torch.equal(prev_prey, read), k
+            if k % 2:
+                assert torch.equal(ocopy, read)
+            assert_same_state(A, B, k)
+            assert A.ll_env.common_step_counter == B.ll_env.common_step_counter and A._obs_flip == B._obs_flip
+            resets += int(A.reset_buf.sum()); clipped += int((raw_p != cpa).sum()) + int((raw_y != cya).sum())
+        assert resets >= 64 and clipped > 0, (resets, clipped)
+    finally:
+        lib.lg_mlp_wide_set_precision(old)
+
+
+def test_graphed_steps_equal_eager_steps(tmp_path):
+    """``make_graphed_policy_step`` (3 warm-up steps, then 12 replays of the three captured launches) equals 15 eager ``step_policy`` calls; then
+    ``make_graphed_step`` with two torch policies equals eager ``step`` calls from there.  The episode means travel inside the captured launch."""
+    A, B = two_envs(tmp_path, seed=9, reset_seed=90)
+    pa, ya = fused_pair(A)
+    pb, yb = fused_pair(B)
+    with pytest.raises(ValueError):
+        A.make_graphed_policy_step(*fused_pair())                                  # host-counted noise streams cannot be replayed
+    replay = A.make_graphed_policy_step(pa, ya, warmup=3)
+    assert A.last_act_rc == 0                                                  # the captured step is the shared launch, not the fallback
+    for _ in range(3):
+        B.step_policy(pb, yb)
+        assert B.last_act_rc == 0
+    resets, means = 0, set()
+    for k in range(12):
+        replay()
+        B.step_policy(pb, yb)
+        torch.cuda.synchronize()
+        for fa, fb in ((pa, pb), (ya, yb)):
+            assert all(torch.equal(a, b) for a, b in zip(fa.output_buffers(A.num_envs), fb.output_buffers(B.num_envs))), k
+        assert_same_state(A, B, k)
+        for env in (A, B):
+            assert int(env.ll_env._sim.buf["step_counter"][0]) == env.ll_env.common_step_counter
+        resets += int(A.reset_buf.sum()); means.add(float(A.extras["episode"]["rew_pred_pursuit"]))
+    assert resets >= 64 and len(means) >= 2 and A.ll_env.common_step_counter == B.ll_env.common_step_counter
+    torch.manual_seed(11)
+    net_p = torch.nn.Sequential(torch.nn.Linear(3, 32), torch.nn.ELU(), torch.nn.Linear(32, 2)).to(DEV)
+    net_y = torch.nn.Sequential(torch.nn.Linear(16, 32), torch.nn.ELU(), torch.nn.Linear(32, 4)).to(DEV)
+
+    def policy(net):
+        def act(obs):
+            with torch.no_grad():
+                return 2.0 * torch.tanh(net(obs * 0.05))
+        return act
+    replay = A.make_graphed_step(policy(net_p), policy(net_y), warmup=2)
+    for _ in range(2):
+        B._device_step(policy(net_p)(B.obs_buf_pred), policy(net_y)(B.obs_buf_prey))
+        B.ll_env.common_step_counter += 1
+    for k in range(6):
+        replay()
+        B._device_step(policy(net_p)(B.obs_buf_pred), policy(net_y)(B.obs_buf_prey))
+        B.ll_env.common_step_counter += 1
+        torch.cuda.synchronize()
+        assert_same_state(A, B, 100 + k)
+
+
+# ----------------------------------------------------------------------------- 5. agent views and the runner
+def dec_runner(reg, tmp_path, monkeypatch, ckpt, n, device_rollout=True, log=True, **runner_keys):
+    import legged_games_gym_amd.utils.task_registry as tr_mod
+    from legged_games_gym_amd.utils import get_args
+    monkeypatch.setattr(tr_mod, "LEGGED_GYM_ROOT_DIR", str(tmp_path))
+    env_cfg, train_cfg = reg.get_cfgs("dec_high_level_game")
+    env_cfg.env.ll_policy_path = ckpt
+    for key in ("device_rollout", "graphed_rollout"):
+        if hasattr(train_cfg.runner, key):
+            delattr(train_cfg.runner, key)
+    if device_rollout:
+        train_cfg.runner.device_rollout = True                          # a runner key, not a config field: set on this registration only
+    for key, value in runner_keys.items():
+        setattr(train_cfg.runner, key, value)
+    args = get_args(["--task", "dec_high_level_game", "--num_envs", str(n), "--headless", "--sim_device", DEV, "--rl_device", DEV])
+    env, _ = reg.make_env("dec_high_level_game", args)
+    torch.manual_seed(1234)                                              # the same initial actors / critics on every runner
+    runner, _ = reg.make_dec_alg_runner(env, "dec_high_level_game", args, **({} if log else {"log_root": None}))
+    return env, runner
+
+
+def perturb(runner, agent, seed):
+    """Stand-in for an optimiser step on ``agent``'s actor: the same seeded change on every runner, then the in-place repack."""
+    r = runner.runners[agent]
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    with torch.no_grad():
+        for prm in r.alg.actor_critic.actor.parameters():
+            prm.add_(0.05 * torch.randn(prm.shape, generator=g, device=DEV))
+    r._fused.sync_device()
+
+
+def test_view_rollout_graph_equals_eager_launches_after_the_opponent_was_updated(tmp_path, monkeypatch, dec_registered):
+    """The prey view's captured rollout against the same launches issued eagerly: captured after a first update of the predator (its opponent),
+    replayed, and replayed AGAIN after a second update of the predator -- the graph reads the opponent's weights where ``sync_device`` repacks
+    them.  Storage (observations, clipped commands, mean, sigma, log-prob, rewards with the time-out bootstrap, dones, values) bit for bit."""
+    reg = dec_registered
+    ckpt = write_ll_checkpoint(str(tmp_path / "ll" / "model_0.pt"), seed=3)
+    N = 256
+    env_g, run_g = dec_runner(reg, tmp_path, monkeypatch, ckpt, N, log=False)
+    env_e, run_e = dec_runner(reg, tmp_path, monkeypatch, ckpt, N, log=False, graphed_rollout=False)
+    assert run_g.device_path and run_e.device_path and run_g.views["prey"].opponent is run_g.runners["pred"]._fused
+    assert run_g.runners["prey"]._fused.seed == 1 + 7919 and run_g.runners["pred"]._fused.seed == 1 + 7919 + 104729
+    for env in (env_g, env_e):
+        env.episode_length_buf[torch.arange(0, 64, device=DEV)] = int(env.max_episode_length) - 30      # time-outs inside the rollouts: the bootstrap
+    for run in (run_g, run_e):
+        perturb(run, "pred", 1)
+    prey_g, prey_e = run_g.runners["prey"], run_e.runners["prey"]
+    T = prey_g.num_steps_per_env
+    graphed = prey_g._try_build_graphed_rollout()                       # one eager warm-up rollout (discarded), then the capture
+    assert graphed is not None and prey_e._try_build_graphed_rollout() is None
+    graph, _, obs_g, _ = graphed
+    sums = torch.zeros(3, device=DEV)
+    stats = {"cur_rew": torch.zeros(N, device=DEV), "cur_len": torch.zeros(N, device=DEV), "sum_rew": sums[0], "sum_len": sums[1], "count": sums[2], "_sums": sums}
+    with torch.inference_mode():
+        prey_e._rollout_steps(stats)                                    # the warm-up's twin
+    for round_ in range(2):
+        with torch.inference_mode():
+            graph.replay()
+            env_g.common_step_counter += T
+            prey_g.alg.storage.step = T
+            prey_e.alg.storage.clear()
+            obs_e, _ = prey_e._rollout_steps(stats)
+        torch.cuda.synchronize()
+        sg, se = prey_g.alg.storage, prey_e.alg.storage
+        print(f"round {round_}: dones graph {int(sg.dones.sum())} eager {int(se.dones.sum())}, time-outs recorded {int(prey_g._time_outs.sum())} / {int(prey_e._time_outs.sum())}, "
+              f"episode lengths {env_g.episode_length_buf[:6].tolist()} / {env_e.episode_length_buf[:6].tolist()}, step counter {env_g.common_step_counter}")
+        for name in ("observations", "actions", "mu", "sigma", "actions_log_prob", "rewards", "dones", "values"):
+            assert torch.equal(getattr(sg, name), getattr(se, name)), (round_, name)
+        assert torch.equal(obs_g, obs_e) and env_g.common_step_counter == env_e.common_step_counter
+        assert_same_state(env_g, env_e, round_)
+        assert torch.isfinite(sg.values).all()
+        assert float(sg.actions[..., :2].abs().max()) <= 1.0 and sg.observations.shape[-1] == 16 and sg.actions.shape[-1] == 4
+        if round_ == 0:
+            assert int(sg.dones.sum()) >= 64 and bool(prey_g._time_outs.any())      # the 64 time-outs were recorded: rewards carry gamma * value there
+            for run in (run_g, run_e):
+                perturb(run, "pred", 2)                                 # the opponent is updated AFTER the capture
+            prey_g.alg.storage.clear()
+
+
+def test_runner_alternates_saves_loads_and_plays(tmp_path, monkeypatch, dec_registered):
+    from legged_games_gym_amd.scripts.play_dec_game import play
+    from legged_games_gym_amd.utils import get_args
+    from legged_games_gym_amd.utils.helpers import get_load_path
+    reg = dec_registered
+    ckpt = write_ll_checkpoint(str(tmp_path / "ll" / "model_0.pt"), seed=3)
+    env, runner = dec_runner(reg, tmp_path, monkeypatch, ckpt, 256)
+    order = []
+    for a in ("pred", "prey"):
+        r = runner.runners[a]
+        r.alg.update = (lambda upd, who: lambda *x, **k: order.append(who) or upd(*x, **k))(r.alg.update, a)
+    weights = lambda a: [p.detach().clone() for p in runner.runners[a].alg.actor_critic.actor.parameters()]
+    before = {a: weights(a) for a in ("pred", "prey")}
+    runner.learn(max_num_evolutions=1, num_learning_iterations=2, init_at_random_ep_len=True)
+    assert order == ["pred", "pred"] and all(torch.equal(x, y) for x, y in zip(before["prey"], weights("prey")))       # the prey is not updated in evolution 0
+    assert any(not torch.equal(x, y) for x, y in zip(before["pred"], weights("pred")))
+    mid = weights("pred")
+    runner.learn(max_num_evolutions=2, num_learning_iterations=1)
+    torch.cuda.synchronize()
+    assert order == ["pred", "pred", "prey", "pred"] and runner.current_evolution == 3 and runner.current_learning_iteration == 4
+    assert any(not torch.equal(x, y) for x, y in zip(before["prey"], weights("prey"))) and any(not torch.equal(x, y) for x, y in zip(mid, weights("pred")))
+    for a in ("pred", "prey"):                                           # the device actors followed the optimisers
+        obs = getattr(env, f"obs_buf_{a}")
+        want = runner.runners[a].alg.actor_critic.act_inference(obs).detach()
+        got = runner.runners[a]._fused.act_inference(obs)
+        assert float((got - want).abs().max()) < 1e-4 * max(1.0, float(want.abs().max()))
+    assert torch.isfinite(env.obs_buf_prey).all() and torch.isfinite(env.rew_buf_prey).all() and torch.isfinite(env.rew_buf_pred).all()
+    path = get_load_path(str(tmp_path / "logs" / "dec_high_level_game"))
+    assert path.endswith("model_4.pt")
+    first = torch.load(os.path.join(os.path.dirname(path), "model_0.pt"), map_location="cpu", weights_only=True)       # written by save_interval INSIDE evolution 0
+    assert first["evolution"] == 0 and first["iter"] == 0 and set(first) == {"pred", "prey", "evolution", "iter"}
+    d = torch.load(path, map_location="cpu", weights_only=True)
+    assert set(d) == {"pred", "prey", "evolution", "iter"} and d["evolution"] == 3 and d["iter"] == 4
+    assert set(d["pred"]) == {"model_state_dict", "optimizer_state_dict", "iter", "infos"} and d["pred"]["iter"] == 3 and d["prey"]["iter"] == 1
+    rows = open(os.path.join(os.path.dirname(path), "progress.csv")).read().strip().splitlines()
+    assert rows[0].split(",")[:3] == ["iteration", "evolution", "agent"] and [r.split(",")[2] for r in rows[1:]] == ["pred", "pred", "prey", "pred"]
+    runner.load(path)
+    pol = runner.get_inference_policy("prey", device=env.device)
+    assert pol(env.obs_buf_prey).shape == (256, 4)
+    env2 = play(get_args(["--task", "dec_high_level_game", "--headless", "--sim_device", DEV, "--rl_device", DEV]), steps=5)
+    assert env2.num_envs == 50 and torch.isfinite(env2.obs_buf_prey).all() and torch.isfinite(env2.obs_buf_pred).all()
+
+
+def test_generic_path_trains_both_agents_through_their_views(tmp_path, monkeypatch, dec_registered):
+    reg = dec_registered
+    ckpt = write_ll_checkpoint(str(tmp_path / "ll" / "model_0.pt"), seed=3)
+    env, runner = dec_runner(reg, tmp_path, monkeypatch, ckpt, 64, device_rollout=False, log=False)
+    assert not runner.device_path and all(r._fused is None for r in runner.runners.values())
+    calls = []
+    step_policy = env.step_policy
+    env.step_policy = lambda *a, **k: calls.append(1) or step_policy(*a, **k)
+    view = runner.views["pred"]
+    assert (view.num_obs, view.num_actions, view.num_privileged_obs, view.num_envs) == (3, 2, None, 64) and view.ll_env is env.ll_env
+    obs, _, rew, dones, infos = view.step(torch.full((64, 2), 9.0, device=DEV))
+    assert obs is env.obs_buf_pred and rew is env.rew_buf_pred and dones is env.reset_buf and infos["time_outs"] is env.time_out_buf
+    runner.learn(max_num_evolutions=2, num_learning_iterations=1)
+    assert not calls and runner.current_evolution == 2 and torch.isfinite(env.obs_buf_prey).all()

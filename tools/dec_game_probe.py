@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""dec_high_level_game: the actor stage of a step, ``lg_dec_game_act`` (the three actors and both command clips in ONE launch) against the
+four launches it replaces (``lg_policy_act`` x 3 + ``lg_dec_game_pre``) -> profiles/dec_game_act.json.
+
+Each variant is captured into a HIP graph of ``--graph-steps`` actor stages on the device step counter; the two graphs are replayed in
+alternating pairs (``--replays`` replays per timing, HIP events around them), the first ``--discard`` pairs are dropped, and the median,
+minimum and maximum time per actor stage are reported per env count.  Actors are seeded random-init networks of the task's shapes
+(3-512-256-128-2, 16-512-256-128-4, 235-512-256-128-12): the time does not depend on the weights.
+
+    python tools/dec_game_probe.py [--envs 2000 4096] [--out profiles/dec_game_act.json]"""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
+sys.path.insert(0, REPO)
+
+import torch  # noqa: E402
+
+from legged_games_gym_amd import capi  # noqa: E402
+from legged_games_gym_amd.envs.a1_game.dec_high_level_game_config import DecHighLevelGameCfg  # noqa: E402
+from legged_games_gym_amd.rl import ActorCritic, FusedActor  # noqa: E402
+
+DEV = "cuda:0"
+HIDDEN = [512, 256, 128]
+
+
+def actor(num_obs, num_actions, seed):
+    torch.manual_seed(seed)
+    return FusedActor(ActorCritic(num_obs, num_obs, num_actions, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV), DEV, seed=seed)
+
+
+def params(n):
+    """The clip ranges of the registered task: all the actor stage reads of ``lg_dec_game_params``."""
+    r = DecHighLevelGameCfg().commands.ranges
+    P = capi.lg_dec_game_params()
+    P.num_envs, P.decimation, P.heading_command = n, 4, 1
+    for name, key in (("cmd_lin_vel_x", "lin_vel_x"), ("cmd_lin_vel_y", "lin_vel_y"), ("predator_lin_vel_x", "predator_lin_vel_x"),
+                      ("predator_lin_vel_y", "predator_lin_vel_y")):
+        capi._fill(getattr(P, name), getattr(r, key))
+    return P
+
+
+def measure(n, graph_steps, replays, pairs, discard):
+    lib = capi.load_library()
+    pred, prey, ll = actor(3, 2, 5), actor(16, 4, 3), actor(235, 12, 4)
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    prey_obs, pred_obs, ll_obs = torch.randn(n, 16, device=DEV), torch.randn(n, 3, device=DEV), torch.randn(n, 235, device=DEV)
+    cy, cp, llc, act, my, mp = z(n, 4), z(n, 2), z(n, 4), z(n, 12), z(n, 4), z(n, 2)
+    P = params(n)
+    B = capi.dec_game_buffers({"command_prey": cy.data_ptr(), "command_pred": cp.data_ptr(), "ll_commands": llc.data_ptr()})
+    counter = torch.zeros(1, dtype=torch.int64, device=DEV)
+    seed_prey, seed_pred = 1 + 7919, 1 + 7919 + 104729
+
+    def one_launch():
+        st = torch.cuda.current_stream().cuda_stream
+        rc = capi.dec_game_act(pred.handle, prey.handle, ll.handle, P, B, pred_obs.data_ptr(), prey_obs.data_ptr(), ll_obs.data_ptr(), act.data_ptr(),
+                               mp.data_ptr(), my.data_ptr(), seed_pred, seed_prey, -1, counter.data_ptr(), False, False, None, None, st)
+        if rc != 0:
+            raise RuntimeError("lg_dec_game_act refused the actor triple (rc -4)")
+
+    def four_launches():
+        st = torch.cuda.current_stream().cuda_stream
+        for handle, obs, out, mean, seed, det in ((prey.handle, prey_obs, cy, my, seed_prey, 0), (pred.handle, pred_obs, cp, mp, seed_pred, 0)):
+            if lib.lg_policy_act(handle, obs.data_ptr(), out.data_ptr(), mean.data_ptr(), n, seed, -1, counter.data_ptr(), det, st) != 0:
+                raise RuntimeError(lib.lg_last_error().decode())
+        capi.dec_game_pre(P, B, st)
+        if lib.lg_policy_act(ll.handle, ll_obs.data_ptr(), act.data_ptr(), None, n, seed_prey, -1, counter.data_ptr(), 1, st) != 0:
+            raise RuntimeError(lib.lg_last_error().decode())
+
+    graphs = {}
+    for name, fn in (("one_launch", one_launch), ("four_launches", four_launches)):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(5):
+                fn()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(graph_steps):
+                fn()
+        graphs[name] = g
+    times = {k: [] for k in graphs}
+    for pair in range(pairs + discard):
+        for name, g in graphs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(replays):
+                g.replay()
+            b.record()
+            torch.cuda.synchronize()
+            if pair >= discard:
+                times[name].append(a.elapsed_time(b) * 1000.0 / (replays * graph_steps))
+    return {k: {"median_us": sorted(v)[len(v) // 2], "min_us": min(v), "max_us": max(v), "repeats_us": v} for k, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--envs", type=int, nargs="+", default=[2000, 4096])
+    ap.add_argument("--graph-steps", type=int, default=50)
+    ap.add_argument("--replays", type=int, default=2)
+    ap.add_argument("--pairs", type=int, default=10)
+    ap.add_argument("--discard", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "dec_game_act.json"))
+    args = ap.parse_args()
+    out = {"device": torch.cuda.get_device_name(0), "graph_steps": args.graph_steps, "replays": args.replays, "pairs": args.pairs, "discarded_pairs": args.discard,
+           "unit": "us per actor stage of one step", "role_order": "low-level, prey, predator (the other orders are not timed)",
+           "envs": {str(n): measure(n, args.graph_steps, args.replays, args.pairs, args.discard) for n in args.envs}}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print(json.dumps({n: {k: round(v["median_us"], 2) for k, v in r.items()} for n, r in out["envs"].items()}))
+
+
+if __name__ == "__main__":
+    main()
