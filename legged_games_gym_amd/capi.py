@@ -485,6 +485,35 @@ def dec_game_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, comm
         raise RuntimeError(f"lg_dec_game_post failed ({rc}): {lib.lg_last_error().decode()}")
 
 
+# ----------------------------------------------------------------------------- scripted pursuer (include/legged_pursuer_game.h)
+class lg_pursuer_params(C.Structure):
+    """include/legged_pursuer_game.h: lg_pursuer_params (passed by value in the kernel arguments)."""
+    _fields_ = [("max_lin_vel", f32), ("min_lin_vel", f32), ("gain", f32), ("max_episode_length", i32)]
+
+
+PURSUER_SYMBOLS = ["lg_pursuer_post", "lg_pursuer_sizeof"]
+
+
+def bind_pursuer_prototypes(lib):
+    """Attach argtypes/restype for the entry points of legged_pursuer_game.h and check the struct layout."""
+    vp = C.c_void_p
+    lib.lg_pursuer_post.argtypes = [C.POINTER(lg_game_params), C.POINTER(lg_pursuer_params), C.POINTER(lg_game_buffers), vp, i64, vp]
+    lib.lg_pursuer_post.restype = C.c_int
+    lib.lg_pursuer_sizeof.argtypes, lib.lg_pursuer_sizeof.restype = [C.c_int], C.c_int
+    if lib.lg_pursuer_sizeof(0) != C.sizeof(lg_pursuer_params):
+        raise RuntimeError(f"struct layout mismatch for lg_pursuer_params: C {lib.lg_pursuer_sizeof(0)} vs ctypes {C.sizeof(lg_pursuer_params)}")
+    return lib
+
+
+def pursuer_post(params: lg_game_params, pursuer: lg_pursuer_params, buffers: lg_game_buffers, predator_command: Optional[int],
+                 common_step_counter: int, stream: int = 0):
+    """``lg_pursuer_post``: ``lg_game_post`` with the scripted pursuer's velocity, which it writes to ``predator_command`` [N,2] (or None)."""
+    lib = load_library()
+    rc = lib.lg_pursuer_post(C.byref(params), C.byref(pursuer), C.byref(buffers), predator_command, int(common_step_counter), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_pursuer_post failed ({rc}): {lib.lg_last_error().decode()}")
+
+
 def load_library():
     """Load the HIP extension or fail loudly -- never a CPU substitute."""
     global _lib
@@ -495,7 +524,7 @@ def load_library():
         raise RuntimeError(
             f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_")))
+    _lib = bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_"))))
     if _lib.lg_abi_version() != LG_ABI_VERSION:
         raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
     return _lib

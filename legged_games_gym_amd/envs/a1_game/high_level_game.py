@@ -65,7 +65,7 @@ class HighLevelGame(GameBase):
         capi.game_pre(self._P, B, stream)
         actions = self.ll_policy(ll.obs_buf)
         ll.step(actions)
-        capi.game_post(self._P, B, ll.common_step_counter, stream)
+        self._post(B, ll.common_step_counter, stream)
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
     def _device_step(self, command):
@@ -76,7 +76,7 @@ class HighLevelGame(GameBase):
         capi.game_pre(self._P, B, stream)
         actions = self.ll_policy(ll.obs_buf)
         ll._sim.step(actions, -1)
-        capi.game_post(self._P, B, -1, stream)
+        self._post(B, -1, stream)
 
     def make_graphed_step(self, policy_act, warmup=3, steps_per_replay=1):
         """Capture ``step(policy_act(obs_buf))`` into one HIP graph and return a zero-argument callable that replays it: high-level actor,
@@ -84,6 +84,10 @@ class HighLevelGame(GameBase):
         ``LeggedRobot.make_graphed_step``).  ``policy_act`` must be capturable and read ``self.obs_buf``."""
         self._step_graph, replay = self._capture(lambda: self._device_step(policy_act(self.obs_buf)), warmup, steps_per_replay, self._step_result)
         return replay
+
+    def _post(self, B, common_step_counter, stream):
+        """The last launch of every step path: ``lg_game_post`` (a subclass with another predator issues its own kernel here)."""
+        capi.game_post(self._P, B, common_step_counter, stream)
 
     def _step_result(self):
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
@@ -146,7 +150,7 @@ class HighLevelGame(GameBase):
             self.obs_buf = prev
             raise
         ll.step(ll_actions)
-        capi.game_post(self._P, B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
+        self._post(B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
         return (command, mean), (self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras)
 
     def make_graphed_policy_step(self, fused_actor, warmup=3, steps_per_replay=1):
@@ -162,7 +166,7 @@ class HighLevelGame(GameBase):
         def device_step():
             _, _, ll_actions, B = self._act(fused_actor, self.obs_buf, self.obs_buf, False)
             sim.step(ll_actions, -1)
-            capi.game_post(self._P, B, -1, torch.cuda.current_stream(self.device).cuda_stream)
+            self._post(B, -1, torch.cuda.current_stream(self.device).cuda_stream)
         self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)
         return replay
 

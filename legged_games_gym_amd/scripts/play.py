@@ -19,6 +19,8 @@ from legged_games_gym_amd.utils.task_registry import task_registry
 def play(args, steps=None):
     if args.task in a1_game.TASKS:
         a1_game.register()
+    if args.task in a1_game.SCRIPTED_TASKS:
+        a1_game.register_scripted()
     env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
     env_cfg.env.num_envs = min(env_cfg.env.num_envs, 50)
     env_cfg.terrain.num_rows = 5

@@ -9,7 +9,8 @@ collectives of ``rl/ppo.py`` (RCCL: all-gather of returns/advantages, gradient a
 and checkpoints.
 
 ``--task=high_level_game --device_rollout`` trains the game on its device path: the high-level actor on the matrix cores, three launches
-per step, the whole rollout one graph replay (off by default: the generic VecEnv loop)."""
+per step, the whole rollout one graph replay (off by default: the generic VecEnv loop).  ``--task=scripted_predator_game`` trains the prey
+alone against the reference's scripted pursuer, on either path."""
 import os
 
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
@@ -43,6 +44,8 @@ def train(args):
         raise SystemExit(f"--task={args.task} trains two policies in alternation: use python -m legged_games_gym_amd.scripts.train_dec_game --task={args.task}")
     if args.task in a1_game.TASKS:
         a1_game.register()               # the game layer registers on demand: python -m legged_games_gym_amd.scripts.train --task=high_level_game --headless
+    if args.task in a1_game.SCRIPTED_TASKS:
+        a1_game.register_scripted()      # python -m legged_games_gym_amd.scripts.train --task=scripted_predator_game --headless [--device_rollout]
     rank, world = _init_distributed(args)
     if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
         task_registry.get_cfgs(args.task)[1].runner.device_rollout = True

@@ -18,6 +18,9 @@ per step, with the copy of the observations written by the actor launch and with
 and, unless ``--train-iterations 0``, PPO training of the registered task with the runner's ``device_rollout`` on and off (env-steps/s including the
 update, same seed and size).  With ``--trace`` it replays (p) only.
 
+``--scripted`` builds ``scripted_predator_game`` beside ``high_level_game`` in one process and times the graphed three-launch policy step of both
+(lg_game_act, k_step, then k_pursuer_post against k_game_post), alternating; writes profiles/pursuer_step.json.
+
 The low-level policy is a seeded random-init checkpoint written to a temporary directory: the kernels' cost does not depend on the weights."""
 import argparse
 import json
@@ -35,9 +38,9 @@ import torch  # noqa: E402
 DEFAULT_OUT = os.path.join(REPO, "profiles", "game_step.json")
 
 
-def make_env(n, mesh, tmp):
+def make_env(n, mesh, tmp, scripted=False):
     from legged_games_gym_amd.envs import task_registry
-    from legged_games_gym_amd.envs.a1_game import HighLevelGame, HighLevelGameFlatCfg
+    from legged_games_gym_amd.envs.a1_game import HighLevelGame, HighLevelGameFlatCfg, ScriptedPredatorGame, ScriptedPredatorGameCfg
     from legged_games_gym_amd.rl import ActorCritic
     from legged_games_gym_amd.utils import get_args, set_seed
     from legged_games_gym_amd.utils.helpers import class_to_dict, parse_sim_params
@@ -46,11 +49,11 @@ def make_env(n, mesh, tmp):
     ac = ActorCritic(a1_cfg.env.num_observations, a1_cfg.env.num_observations, a1_cfg.env.num_actions, **class_to_dict(a1_train.policy))
     ckpt = os.path.join(tmp, "model_0.pt")
     torch.save({"model_state_dict": ac.state_dict(), "optimizer_state_dict": {}, "iter": 0, "infos": None}, ckpt)
-    cfg = HighLevelGameFlatCfg()
+    cfg = ScriptedPredatorGameCfg() if scripted else HighLevelGameFlatCfg()
     cfg.env.num_envs, cfg.env.ll_policy_path, cfg.terrain.mesh_type, cfg.seed = n, ckpt, mesh, 1
     args = get_args(["--headless", "--sim_device", "cuda:0", "--rl_device", "cuda:0"])
     set_seed(1)
-    env = HighLevelGame(cfg, parse_sim_params(args, {"sim": class_to_dict(cfg.sim)}), args.physics_engine, "cuda:0", True)
+    env = (ScriptedPredatorGame if scripted else HighLevelGame)(cfg, parse_sim_params(args, {"sim": class_to_dict(cfg.sim)}), args.physics_engine, "cuda:0", True)
     torch.manual_seed(1)
     hl = ActorCritic(env.num_obs, env.num_obs, env.num_actions, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128]).to("cuda:0").eval()
 
@@ -210,6 +213,38 @@ def policy_step_main(args):
         print("wrote", out)
 
 
+def scripted_main(args):
+    """The graphed three-launch policy step of scripted_predator_game against high_level_game's, same process, same sizes, alternating repeats."""
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.replays, "repeats": args.repeats, "envs": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            parent, _ = make_env(n, args.mesh, tmp)
+            scripted, _ = make_env(n, args.mesh, tmp, scripted=True)
+            step_parent = parent.make_graphed_policy_step(fused_high_level_actor(parent))
+            step_scripted = scripted.make_graphed_policy_step(fused_high_level_actor(scripted))
+            for fn in (step_parent, step_scripted):
+                timed(fn, 200)
+            a, b = [], []
+            for _ in range(args.repeats):              # alternating: other work shares the machine
+                a.append(timed(step_parent, args.replays))
+                b.append(timed(step_scripted, args.replays))
+            diff = [y - x for x, y in zip(a, b)]
+            result["envs"][str(n)] = {"high_level_game_policy_step": spread(a), "scripted_predator_game_policy_step": spread(b),
+                                      "scripted_minus_high_level_game": spread(diff),
+                                      "env_steps_per_s_scripted_predator_game": n / (statistics.median(b) * 1e-6)}
+            for env in (parent, scripted):
+                assert torch.isfinite(env.obs_buf).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            assert float(scripted.predator_command.abs().max()) > 0
+            print(f"{n} envs, graphed three-launch policy step: high_level_game {statistics.median(a):.1f} us ({min(a):.1f} .. {max(a):.1f}), "
+                  f"scripted_predator_game {statistics.median(b):.1f} us ({min(b):.1f} .. {max(b):.1f}), difference {statistics.median(diff):+.2f} us "
+                  f"({min(diff):+.2f} .. {max(diff):+.2f})", flush=True)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "pursuer_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 def timed(fn, count):
     """Mean microseconds per call of ``fn`` over ``count`` calls, device events around the whole window."""
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -235,10 +270,13 @@ def main():
     ap.add_argument("--out", default=DEFAULT_OUT)
     ap.add_argument("--policy-step", action="store_true", help="time the device path of the high-level actor; writes profiles/game_policy_step.json")
     ap.add_argument("--train-iterations", type=int, default=10, help="--policy-step: timed PPO iterations per setting of the runner switch (0: skip)")
+    ap.add_argument("--scripted", action="store_true", help="time scripted_predator_game's graphed policy step beside high_level_game's; writes profiles/pursuer_step.json")
     ap.add_argument("--trace", action="store_true", help="a short loop of graph replays only (for a kernel trace)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("game_probe needs an AMD GPU: there is nothing to time on the CPU")
+    if args.scripted:
+        return scripted_main(args)
     if args.policy_step:
         return policy_step_main(args)
     result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.replays, "repeats": args.repeats, "envs": {}}
