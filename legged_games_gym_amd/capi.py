@@ -514,6 +514,62 @@ def pursuer_post(params: lg_game_params, pursuer: lg_pursuer_params, buffers: lg
         raise RuntimeError(f"lg_pursuer_post failed ({rc}): {lib.lg_last_error().decode()}")
 
 
+# ----------------------------------------------------------------------------- game outcome statistics (include/legged_game_outcome.h)
+LG_OUTCOME_NUM_COUNTS, LG_OUTCOME_NUM_MEANS = 7, 6
+OUTCOME_COUNTS = ("episodes", "captured", "prey_out", "predator_out", "fell", "survived", "steps")     # the order of accum / totals
+OUTCOME_MEANS = OUTCOME_COUNTS[1:]                                                                    # the order of means: five rates, mean steps
+
+
+class lg_outcome_buffers(C.Structure):
+    """include/legged_game_outcome.h: lg_outcome_buffers (raw device pointers)."""
+    _fields_ = [("ll_time_out_buf", _PU8), ("accum", C.POINTER(u64)), ("ticket", C.POINTER(C.c_uint32)), ("means", _PF), ("totals", C.POINTER(u64))]
+
+
+OUTCOME_BUFFER_FIELDS = [name for name, _ in lg_outcome_buffers._fields_]
+OUTCOME_SYMBOLS = ["lg_outcome_post", "lg_outcome_pursuer_post", "lg_outcome_sizeof"]
+
+
+def bind_outcome_prototypes(lib):
+    """Attach argtypes/restype for the entry points of legged_game_outcome.h and check the struct layout."""
+    vp = C.c_void_p
+    lib.lg_outcome_post.argtypes = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), C.POINTER(lg_outcome_buffers), i64, vp]
+    lib.lg_outcome_post.restype = C.c_int
+    lib.lg_outcome_pursuer_post.argtypes = [C.POINTER(lg_game_params), C.POINTER(lg_pursuer_params), C.POINTER(lg_game_buffers),
+                                            C.POINTER(lg_outcome_buffers), vp, i64, vp]
+    lib.lg_outcome_pursuer_post.restype = C.c_int
+    lib.lg_outcome_sizeof.argtypes, lib.lg_outcome_sizeof.restype = [C.c_int], C.c_int
+    if lib.lg_outcome_sizeof(0) != C.sizeof(lg_outcome_buffers):
+        raise RuntimeError(f"struct layout mismatch for lg_outcome_buffers: C {lib.lg_outcome_sizeof(0)} vs ctypes {C.sizeof(lg_outcome_buffers)}")
+    return lib
+
+
+def outcome_buffers(pointers: Dict[str, int]) -> lg_outcome_buffers:
+    """``lg_outcome_buffers`` from a name -> device address table (missing names stay null)."""
+    b = lg_outcome_buffers()
+    types = dict(lg_outcome_buffers._fields_)
+    for name in OUTCOME_BUFFER_FIELDS:
+        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
+    return b
+
+
+def outcome_post(params: lg_game_params, buffers: lg_game_buffers, outcome: lg_outcome_buffers, common_step_counter: int, stream: int = 0):
+    """``lg_outcome_post``: ``lg_game_post`` that also counts why the done envs' episodes ended."""
+    lib = load_library()
+    rc = lib.lg_outcome_post(C.byref(params), C.byref(buffers), C.byref(outcome), int(common_step_counter), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_outcome_post failed ({rc}): {lib.lg_last_error().decode()}")
+
+
+def outcome_pursuer_post(params: lg_game_params, pursuer: lg_pursuer_params, buffers: lg_game_buffers, outcome: lg_outcome_buffers,
+                         predator_command: Optional[int], common_step_counter: int, stream: int = 0):
+    """``lg_outcome_pursuer_post``: ``lg_pursuer_post`` that also counts why the done envs' episodes ended."""
+    lib = load_library()
+    rc = lib.lg_outcome_pursuer_post(C.byref(params), C.byref(pursuer), C.byref(buffers), C.byref(outcome), predator_command,
+                                     int(common_step_counter), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_outcome_pursuer_post failed ({rc}): {lib.lg_last_error().decode()}")
+
+
 def load_library():
     """Load the HIP extension or fail loudly -- never a CPU substitute."""
     global _lib
@@ -524,7 +580,7 @@ def load_library():
         raise RuntimeError(
             f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_"))))
+    _lib = bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_")))))
     if _lib.lg_abi_version() != LG_ABI_VERSION:
         raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
     return _lib

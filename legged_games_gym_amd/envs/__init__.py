@@ -2,7 +2,9 @@
 
 The predator-prey task ``high_level_game`` (``envs/a1_game``) is NOT registered by this import: the registry is a process-wide singleton
 whose locomotion surface is pinned, so ``legged_games_gym_amd.envs.a1_game.register()`` adds it on demand (``scripts/train.py`` and
-``scripts/play.py`` call it when ``--task`` names it).  ``dec_high_level_game`` and ``low_level_game`` as a task of its own are not built.
+``scripts/play.py`` call it when ``--task`` names it).  ``dec_high_level_game`` (``register_dec()``, ``scripts/train_dec_game.py``) and
+``scripted_predator_game`` (``register_scripted()``) are built and registered on demand in the same way; ``low_level_game`` as a task of
+its own is not built.
 """
 from .base.legged_robot import LeggedRobot
 from .anymal_c.anymal import Anymal

@@ -17,6 +17,12 @@ high-level actor on the device as well, in three launches:
 The low-level policy acts on the observation buffer as the last low-level step left it, so a new command reaches its input one step
 late -- as in the reference (:177-178).  That is also what lets ``lg_game_act`` run both actors side by side.
 
+Outcome statistics (off by default; ``env.outcome_stats = True`` on the config object or ``enable_outcome_stats()``): the last launch of
+every step path becomes ``lg_outcome_post`` (include/legged_game_outcome.h), which writes what ``lg_game_post`` writes, bit for bit, and
+also counts inside the launch why the done envs' episodes ended.  ``extras["episode"]`` then holds six device scalars ``outcome_*`` -- the
+rates of the step's done envs that were captured / left the arena (prey, predator) / fell / survived, and their mean length in steps -- and
+``outcome_totals()`` the running integer sums.  A step is still three launches and a rollout still one graph replay.
+
 Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G1-G9)."""
 import numpy as np
 import torch
@@ -47,6 +53,9 @@ class HighLevelGame(GameBase):
         self._init_buffers()
         self._prepare_reward_function()
         self._pack()
+        self._outcome = None
+        if getattr(cfg.env, "outcome_stats", False):           # no field of the registered config classes: they stay value for value the reference's
+            self.enable_outcome_stats()
         self.init_done = True
 
     # ------------------------------------------------------------------ hot path
@@ -86,8 +95,50 @@ class HighLevelGame(GameBase):
         return replay
 
     def _post(self, B, common_step_counter, stream):
-        """The last launch of every step path: ``lg_game_post`` (a subclass with another predator issues its own kernel here)."""
-        capi.game_post(self._P, B, common_step_counter, stream)
+        """The last launch of every step path: ``lg_game_post``, or ``lg_outcome_post`` with the outcome statistics on (a subclass with
+        another predator issues its own pair here)."""
+        if self._outcome is None:
+            capi.game_post(self._P, B, common_step_counter, stream)
+        else:
+            capi.outcome_post(self._P, B, self._outcome, common_step_counter, stream)
+
+    # ------------------------------------------------------------------ outcome statistics
+    def enable_outcome_stats(self, on=True):
+        """Switch the outcome statistics on or off.  On: ``_post`` issues the outcome entry point of the task on every step path and
+        ``extras["episode"]`` holds 0-dim views ``outcome_captured``, ``outcome_prey_out``, ``outcome_predator_out``, ``outcome_fell``,
+        ``outcome_survived`` (shares of the done envs of the last step in which an env was done; an env may raise several) and
+        ``outcome_steps`` (their mean episode length in high-level steps).  Off: the launches of the plain task and ``extras == {}``.
+        The totals are kept across a switch; ``reset_outcome_totals()`` zeroes them.
+
+        A graph captures the launch that the switch selected at capture time: flip the switch BEFORE ``make_graphed_step``,
+        ``make_graphed_policy_step`` or the runner's device rollout capture; a graph captured earlier keeps replaying what it captured."""
+        if not on:
+            self._outcome = None
+            self.extras.pop("episode", None)
+            return
+        if getattr(self, "_outcome_accum", None) is None:
+            dev = self.device
+            self._outcome_accum = torch.zeros(capi.LG_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
+            self._outcome_ticket = torch.zeros(1, device=dev, dtype=torch.int32)
+            self._outcome_means = torch.zeros(capi.LG_OUTCOME_NUM_MEANS, device=dev, dtype=torch.float)
+            self._outcome_totals = torch.zeros(capi.LG_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
+        self._outcome = capi.outcome_buffers({"ll_time_out_buf": self.ll_env._sim.buf["time_out_buf"].data_ptr(), "accum": self._outcome_accum.data_ptr(),
+                                              "ticket": self._outcome_ticket.data_ptr(), "means": self._outcome_means.data_ptr(),
+                                              "totals": self._outcome_totals.data_ptr()})
+        self.extras["episode"] = {f"outcome_{name}": self._outcome_means[i] for i, name in enumerate(capi.OUTCOME_MEANS)}
+
+    def outcome_totals(self):
+        """Running sums since construction or the last ``reset_outcome_totals()``, as Python ints after ONE synchronising copy:
+        ``episodes, captured, prey_out, predator_out, fell, survived, steps``.  Episodes still running are not in them."""
+        if getattr(self, "_outcome_totals", None) is None:
+            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
+        return dict(zip(capi.OUTCOME_COUNTS, (int(v) for v in self._outcome_totals.cpu().tolist())))
+
+    def reset_outcome_totals(self):
+        """Zero the totals on the current stream (no synchronisation)."""
+        if getattr(self, "_outcome_totals", None) is None:
+            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
+        self._outcome_totals.zero_()
 
     def _step_result(self):
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
@@ -153,9 +204,23 @@ class HighLevelGame(GameBase):
         self._post(B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
         return (command, mean), (self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras)
 
-    def make_graphed_policy_step(self, fused_actor, warmup=3, steps_per_replay=1):
+    def shared_actor_launch(self, fused_actor):
+        """Whether ``lg_game_act`` has a kernel for ``fused_actor`` next to the low-level actor at the current wide precision (rc 0, not -4).
+        Issues that launch once, deterministically, on the current observations when it has: command, mean, low-level commands and actions
+        are overwritten (every step path rewrites them before reading them) and the actor's noise stream is not advanced."""
+        n = self.num_envs
+        command, mean = fused_actor.output_buffers(n)
+        ll_actions = self._ll_fused.output_buffers(n)[0]
+        B = self._bind_command(command, self.obs_buf)
+        step, ctr = fused_actor.peek_step()
+        return capi.game_act(fused_actor.handle, self._ll_fused.handle, self._P, B, self.obs_buf.data_ptr(), self.ll_env.obs_buf.data_ptr(),
+                             ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step, ctr, True, None, None, None, None,
+                             torch.cuda.current_stream(self.device).cuda_stream) == 0
+
+    def make_graphed_policy_step(self, fused_actor, warmup=3, steps_per_replay=1, deterministic=False):
         """``make_graphed_step`` with the actor on the device: the graph is ``lg_game_act`` -> ``lg_step`` -> ``lg_game_post`` per step, the
-        observations stay in one buffer.  ``fused_actor`` must draw its noise stream from the low-level sim's device step counter
+        observations stay in one buffer.  ``deterministic`` captures the actor's mean instead of a sample (evaluation).
+        ``fused_actor`` must draw its noise stream from the low-level sim's device step counter
         (``FusedActor(..., step_counter=env.ll_env._sim.buf["step_counter"])``).  Returns a zero-argument callable that replays the graph;
         ``fused_actor.output_buffers(num_envs)`` then hold the command and the mean of the last step."""
         ll = self.ll_env
@@ -164,7 +229,7 @@ class HighLevelGame(GameBase):
             raise ValueError("make_graphed_policy_step needs a FusedActor on the low-level sim's device step counter")
 
         def device_step():
-            _, _, ll_actions, B = self._act(fused_actor, self.obs_buf, self.obs_buf, False)
+            _, _, ll_actions, B = self._act(fused_actor, self.obs_buf, self.obs_buf, deterministic)
             sim.step(ll_actions, -1)
             self._post(B, -1, torch.cuda.current_stream(self.device).cuda_stream)
         self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)

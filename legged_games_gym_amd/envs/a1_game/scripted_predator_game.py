@@ -49,4 +49,7 @@ class ScriptedPredatorGame(HighLevelGame):
         self._Q = Q
 
     def _post(self, B, common_step_counter, stream):
-        capi.pursuer_post(self._P, self._Q, B, self.predator_command.data_ptr(), common_step_counter, stream)
+        if self._outcome is None:
+            capi.pursuer_post(self._P, self._Q, B, self.predator_command.data_ptr(), common_step_counter, stream)
+        else:                                       # outcome statistics on (HighLevelGame.enable_outcome_stats): same outputs, plus the counts
+            capi.outcome_pursuer_post(self._P, self._Q, B, self._outcome, self.predator_command.data_ptr(), common_step_counter, stream)

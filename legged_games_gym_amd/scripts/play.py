@@ -29,6 +29,8 @@ def play(args, steps=None):
     env_cfg.noise.add_noise = False
     env_cfg.domain_rand.randomize_friction = False
     env_cfg.domain_rand.push_robots = False
+    if getattr(args, "outcome_stats", False) and args.task in a1_game.TASKS + a1_game.SCRIPTED_TASKS:
+        env_cfg.env.outcome_stats = True                     # read with getattr(): no field of the registered config classes
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     obs = env.get_observations()
     train_cfg.runner.resume = True

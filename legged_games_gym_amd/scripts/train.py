@@ -10,7 +10,9 @@ and checkpoints.
 
 ``--task=high_level_game --device_rollout`` trains the game on its device path: the high-level actor on the matrix cores, three launches
 per step, the whole rollout one graph replay (off by default: the generic VecEnv loop).  ``--task=scripted_predator_game`` trains the prey
-alone against the reference's scripted pursuer, on either path."""
+alone against the reference's scripted pursuer, on either path.  ``--outcome_stats`` (both game tasks, either path) logs who wins: the
+shares of finished episodes that ended in a capture, outside the arena, with a fallen robot or with the prey surviving, and their mean
+length, as ``Episode/outcome_*``."""
 import os
 
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
@@ -49,6 +51,10 @@ def train(args):
     rank, world = _init_distributed(args)
     if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
         task_registry.get_cfgs(args.task)[1].runner.device_rollout = True
+    if args.outcome_stats:                   # read with getattr() by the game tasks: no field of the registered config classes
+        if args.task not in a1_game.TASKS + a1_game.SCRIPTED_TASKS:
+            raise SystemExit(f"--outcome_stats is for {', '.join(a1_game.TASKS + a1_game.SCRIPTED_TASKS)}, not --task={args.task}")
+        task_registry.get_cfgs(args.task)[0].env.outcome_stats = True
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     ppo_runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, **({} if rank == 0 else {"log_root": None}))
     ppo_runner.learn(num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)

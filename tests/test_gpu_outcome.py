@@ -1,0 +1,345 @@
+"""-m gpu: the outcome statistics -- ``lg_outcome_post`` / ``lg_outcome_pursuer_post`` (include/legged_game_outcome.h) write what
+``lg_game_post`` / ``lg_pursuer_post`` write, bit for bit, and count exactly what the NumPy twin counts (tests/outcome_twin.py); the state and
+the totals carried over consecutive launches and graph replays; every step path of the two envs with the switch off and on; the runner's
+log; ``scripts/play_game.py``.  Nothing here reads outside the tree."""
+import csv
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import game_twin as tw
+from tests import outcome_fixtures as of
+from tests import outcome_twin as ot
+from tests import pursuer_twin as pt
+from tests.test_gpu_game import device_post, make_game, pack_params, write_ll_checkpoint
+from tests.test_gpu_game_policy import high_level_actor
+from tests.test_gpu_pursuer_game import STATE, device_pursuer_post, make_scripted, pack_pursuer, policy_net, scripted_registered  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+DEV = "cuda:0"
+CARRIED = ("root_states", "predator_pos", "obs", "curr_episode_step", "episode_length_buf", "episode_sums")
+KEYS = tuple(f"outcome_{k}" for k in ot.MEANS)
+
+
+# ----------------------------------------------------------------------------- the kernel without an env
+class Launcher:
+    """Device buffers of ``calls`` consecutive outcome launches on ``n`` envs: ONE set of state buffers, rewritten in place by every launch
+    (as in an env), and per-call inputs (command, low-level reward / resets / time-outs, step counter), so that the launches can also be
+    captured into a graph."""
+
+    def __init__(self, state, calls, scripted):
+        from legged_games_gym_amd import capi
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+        self.scripted, self.calls, self.n = scripted, calls, state["root_states"].shape[0]
+        n = self.n
+        self.t = {k: up(state[k]) for k in CARRIED + ("env_origins",)}
+        assert self.t["curr_episode_step"].dtype == torch.int64 and self.t["obs"].shape == (n, 19) and self.t["episode_sums"].shape == (2, n)
+        self.t["rew"], self.t["reset_buf"] = torch.full((n,), -3.0, device=DEV), torch.zeros(n, dtype=torch.bool, device=DEV)
+        self.t["predator_command"] = torch.full((n, 2), float("nan"), device=DEV)
+        self.accum, self.totals = torch.zeros(7, dtype=torch.int64, device=DEV), torch.zeros(7, dtype=torch.int64, device=DEV)
+        self.ticket, self.means = torch.zeros(1, dtype=torch.int32, device=DEV), torch.zeros(6, device=DEV)
+        self.per_call = []
+        for c in calls:
+            d = dict(command=up(c["command"]), ll_rew=up(c["ll_rew"]), ll_reset=up(np.asarray(c["ll_reset"], bool)), ll_time_out=up(np.asarray(c["ll_time_out"], bool)),
+                     counter=torch.tensor([c["step"]], dtype=torch.int64, device=DEV))
+            assert d["ll_reset"].element_size() == 1 and d["ll_time_out"].element_size() == 1 and d["command"].dtype == torch.float32
+            t = self.t
+            d["B"] = capi.game_buffers({"command": d["command"].data_ptr(), "ll_root_states": t["root_states"].data_ptr(), "ll_env_origins": t["env_origins"].data_ptr(),
+                                        "ll_rew_buf": d["ll_rew"].data_ptr(), "ll_reset_buf": d["ll_reset"].data_ptr(), "ll_step_counter": d["counter"].data_ptr(),
+                                        "predator_pos": t["predator_pos"].data_ptr(), "obs": t["obs"].data_ptr(), "rew": t["rew"].data_ptr(),
+                                        "reset_buf": t["reset_buf"].data_ptr(), "curr_episode_step": t["curr_episode_step"].data_ptr(),
+                                        "episode_length_buf": t["episode_length_buf"].data_ptr(), "episode_sums": t["episode_sums"].data_ptr()})
+            d["O"] = capi.outcome_buffers({"ll_time_out_buf": d["ll_time_out"].data_ptr(), "accum": self.accum.data_ptr(), "ticket": self.ticket.data_ptr(),
+                                           "means": self.means.data_ptr(), "totals": self.totals.data_ptr()})
+            d["P"], d["Q"] = pack_params(dict(c["p"], num_envs=n)), pack_pursuer(c["q"])
+            self.per_call.append(d)
+
+    def launch(self, k, counter_on_device):
+        from legged_games_gym_amd import capi
+        d, step = self.per_call[k], -1 if counter_on_device else self.calls[k]["step"]
+        stream = torch.cuda.current_stream().cuda_stream
+        if self.scripted:
+            capi.outcome_pursuer_post(d["P"], d["Q"], d["B"], d["O"], self.t["predator_command"].data_ptr(), step, stream)
+        else:
+            capi.outcome_post(d["P"], d["B"], d["O"], step, stream)
+
+    def state(self):
+        """The carried state as NumPy arrays (synchronises)."""
+        torch.cuda.synchronize()
+        return {k: self.t[k].cpu().numpy() for k in CARRIED}
+
+    def outputs(self):
+        torch.cuda.synchronize()
+        out = {k: self.t[k].cpu().numpy() for k in STATE}
+        out["predator_command"] = self.t["predator_command"].cpu().numpy()
+        return out
+
+    def stats(self):
+        torch.cuda.synchronize()
+        return self.accum.cpu().numpy(), int(self.ticket[0]), self.means.cpu().numpy(), self.totals.cpu().numpy()
+
+    def restore(self, state):
+        for k in CARRIED:
+            self.t[k].copy_(torch.from_numpy(np.ascontiguousarray(state[k])))
+
+
+def ulps(a, b):
+    """Distance of two float32 arrays in units in the last place of ``b``."""
+    return np.abs(a.astype(np.float64) - b.astype(np.float64)) / np.spacing(np.maximum(np.abs(b), np.finfo(F).tiny).astype(F)).astype(np.float64)
+
+
+def test_the_seeded_cases_cover_every_flag_on_the_twin():
+    """On the twin alone, over the whole parametrisation below: every flag occurs, some env raises two at once, every done env raises one."""
+    occurs, double, bare = of.coverage()
+    assert all(v > 0 for v in occurs.values()), occurs
+    assert double > 0 and bare == 0
+    assert int(of.case(1, -1.0)["counts"][0]) == 0 and int(of.case(1, 2.5)["counts"][0]) == 1          # a launch without, and with one, done env
+
+
+@pytest.mark.parametrize("scripted", [False, True])
+@pytest.mark.parametrize("radius", of.RADII)
+@pytest.mark.parametrize("n", of.SIZES)
+def test_same_step_bit_for_bit_and_exact_counts(n, radius, scripted):
+    """One launch of the outcome entry point against one of the plain entry point on the same inputs: every array either writes, and the
+    pursuer's velocity, as uint32 views.  Then the statistics of that launch against the twin: the seven integers exactly, accumulator and
+    ticket back at zero, the means within 3 ulp of the twin's float32 quotient (the library's division is the 2.5-ulp one, DESIGN.md section 5
+    "The division"; the kernel does not divide correctly rounded here; on the MI355X the largest distance over these cases was 1 ulp).  A launch
+    without a done env leaves means and totals at zero."""
+    c = of.case(n, radius)
+    s = c["s"] if scripted else c["s_plain"]
+    odd = bool(n % 2)
+    plain = device_pursuer_post(c["p"], c["q"], s, c["step"], counter_on_device=odd) if scripted else device_post(c["p"], s, c["step"], counter_on_device=odd)
+    call = dict(p=c["p"], q=c["q"], step=c["step"], command=s["command"], ll_rew=s["ll_rew"], ll_reset=s["ll_reset"], ll_time_out=c["ll_time_out"])
+    L = Launcher(s, [call], scripted)
+    L.launch(0, counter_on_device=odd)
+    got = L.outputs()
+    for k in STATE + (("predator_command",) if scripted else ()):
+        a, b = got[k], plain[k]
+        assert a.dtype == b.dtype and a.shape == b.shape, k
+        np.testing.assert_array_equal(a.view(np.uint8) if a.dtype == bool else a.view(np.uint32 if a.itemsize == 4 else np.uint64),
+                                      b.view(np.uint8) if b.dtype == bool else b.view(np.uint32 if b.itemsize == 4 else np.uint64), err_msg=k)
+    assert np.array_equal(L.per_call[0]["command"].cpu().numpy(), s["command"]) and int(L.per_call[0]["counter"][0]) == c["step"]      # inputs are left alone
+    np.testing.assert_array_equal(got["reset_buf"].astype(bool), c["flags"]["done"])
+    accum, ticket, means, totals = L.stats()
+    np.testing.assert_array_equal(totals, c["counts"])
+    assert not accum.any() and ticket == 0
+    worst = float(ulps(means, c["means"]).max())
+    print(f"n {n} radius {radius} scripted {scripted}: counts {totals.tolist()}, means off by at most {worst:.2f} ulp")
+    if int(c["counts"][0]) == 0:
+        assert not means.any() and not totals.any()
+    assert worst <= 3.0, (means.tolist(), c["means"].tolist())
+
+
+@pytest.mark.parametrize("scripted", [False, True])
+def test_state_and_totals_carried_over_four_launches_and_graph_replays(scripted):
+    """Four consecutive launches at 257 envs on one set of buffers, the twin fed the state the device left: ``totals`` adds up call by call,
+    the call without a done env leaves ``means`` and ``totals`` bit-identical, accumulator and ticket read zero after every call.  The step
+    counter is passed by value on even calls and read from the device on odd ones.  Then the same four launches captured into one graph
+    and replayed twice from the restored inputs: twice the totals, the same final state."""
+    p, q, state0, calls = of.sequence_inputs(scripted)
+    calls = [dict(c, q=q) for c in calls]
+    L = Launcher(state0, calls, scripted)
+    running, prev_means, per_call = np.zeros(7, np.int64), np.zeros(6, F), []
+    for k, c in enumerate(calls):
+        before = L.state()
+        s = dict(before, env_origins=state0["env_origins"], command=c["command"], ll_rew=c["ll_rew"], ll_reset=c["ll_reset"])
+        _, info = pt.post(c["p"], q, s, step=c["step"]) if scripted else tw.post(c["p"], s, step=c["step"])
+        assert float(np.min(np.abs(info["dist_xy"] - F(c["p"]["capture_dist"])))) >= 1e-4          # no env near the one threshold the counts depend on
+        f, cnt, want_means = ot.outcome(c["p"], info, c["ll_reset"], c["ll_time_out"], before["curr_episode_step"], prev_means)
+        L.launch(k, counter_on_device=bool(k % 2))
+        accum, ticket, means, totals = L.stats()
+        running = running + cnt
+        np.testing.assert_array_equal(totals, running, err_msg=f"call {k}")
+        assert not accum.any() and ticket == 0, k
+        np.testing.assert_array_equal(L.t["reset_buf"].cpu().numpy().astype(bool), f["done"])
+        if k == of.SEQ_QUIET:
+            assert int(cnt[0]) == 0 and not f["done"].any()
+            np.testing.assert_array_equal(means.view(np.uint32), prev_means.view(np.uint32))
+        else:
+            assert int(cnt[0]) > 0
+            assert float(ulps(means, want_means).max()) <= 3.0, (k, means.tolist(), want_means.tolist())
+        prev_means = means
+        per_call.append(cnt)
+    assert running[0] == sum(int(c[0]) for c in per_call) > 50                          # (radius off: no env leaves the arena)
+    assert running[1] > 0 and running[4] > 0 and running[5] > 0 and running[2] == running[3] == 0
+    final, final_means = L.state(), L.stats()[2]
+
+    L.restore(state0)
+    L.totals.zero_()
+    L.means.zero_()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for k in range(len(calls)):
+            L.launch(k, counter_on_device=bool(k % 2))
+    for rep in range(2):
+        L.restore(state0)
+        graph.replay()
+        accum, ticket, means, totals = L.stats()
+        np.testing.assert_array_equal(totals, (rep + 1) * running, err_msg=f"replay {rep}")
+        assert not accum.any() and ticket == 0
+        np.testing.assert_array_equal(means.view(np.uint32), final_means.view(np.uint32))
+        now = L.state()
+        for key in CARRIED:
+            np.testing.assert_array_equal(now[key], final[key], err_msg=f"replay {rep}: {key}")
+
+
+# ----------------------------------------------------------------------------- the env, every path
+def two_envs(tmp_path, task, seed, reset_seed, n=64):
+    """Two identically seeded envs of ``task``, the second with the outcome statistics on; spread episode steps and 8 low-level time-outs ahead
+    (as tests/test_gpu_pursuer_game.py: two_scripted).  The capture distance is raised from the registered 0.5 m to 2.5 m in both envs (the
+    predator is placed 1 .. 10 m away on each axis), so that episodes also end in captures within the 40 steps, not in the time-outs alone."""
+    ckpt = write_ll_checkpoint(str(tmp_path / "ll" / "model_0.pt"), seed=3)
+    make = make_scripted if task == "scripted_predator_game" else (lambda ckpt, n, seed: make_game(ckpt, n, seed=seed))
+    A, B = make(ckpt, n, seed=seed), make(ckpt, n, seed=seed)
+    B.enable_outcome_stats()
+    for env in (A, B):
+        env.capture_dist = 2.5
+        env.set_command_ranges()                  # re-packs lg_game_params
+        torch.manual_seed(reset_seed)             # reset_idx from the host draws from torch's generator
+        env.reset()
+        env.curr_episode_step[:] = torch.arange(n, device=DEV) * (1300 // n)
+        env.ll_env.episode_length_buf[:8] = int(env.ll_env.max_episode_length) - 6
+    B.reset_outcome_totals()
+    assert torch.equal(A.ll_env.root_states, B.ll_env.root_states) and torch.equal(A.predator_pos, B.predator_pos) and torch.equal(A.obs_buf, B.obs_buf)
+    assert A.extras == {} and tuple(B.extras) == ("episode",) and tuple(B.extras["episode"]) == KEYS
+    return A, B
+
+
+def assert_same(A, B, k):
+    for name in ("obs_buf", "rew_buf", "reset_buf", "predator_pos", "curr_episode_step"):
+        assert torch.equal(getattr(A, name), getattr(B, name)), (k, name)
+    assert torch.equal(A.ll_env.root_states, B.ll_env.root_states), k
+    if hasattr(A, "predator_command"):
+        assert torch.equal(A.predator_command, B.predator_command), k
+
+
+@pytest.mark.parametrize("path", ["step", "graphed_step", "step_policy", "graphed_policy_step"])
+@pytest.mark.parametrize("task", ["scripted_predator_game", "high_level_game"])
+def test_env_paths_are_unchanged_by_the_switch_and_count_every_episode(tmp_path, task, path):
+    """40 steps on one step path of two identically seeded envs, statistics off (A) and on (B): observations, rewards, resets, predator and
+    root states bit-equal at every step; A's extras stay empty, B's hold the six device scalars; B's totals equal the summed ``reset_buf``
+    and the summed (pre-step ``curr_episode_step`` + 1) of the done envs, and their fell / survived counts the low-level env's own
+    ``reset_buf`` / ``time_out_buf`` summed over the steps."""
+    from legged_games_gym_amd.rl import FusedActor
+    A, B = two_envs(tmp_path, task, seed=9, reset_seed=90)
+    if path in ("step", "graphed_step"):
+        policy = policy_net()
+        if path == "step":
+            step_a, step_b = (lambda: A.step(policy(A.obs_buf))), (lambda: B.step(policy(B.obs_buf)))
+        else:
+            step_a, step_b = A.make_graphed_step(policy, warmup=3), B.make_graphed_step(policy, warmup=3)
+    else:
+        ac = high_level_actor(seed=6)
+        fa = FusedActor(ac, DEV, seed=21, step_counter=A.ll_env._sim.buf["step_counter"] if path == "graphed_policy_step" else None)
+        fb = FusedActor(ac, DEV, seed=21, step_counter=B.ll_env._sim.buf["step_counter"] if path == "graphed_policy_step" else None)
+        if path == "step_policy":
+            step_a, step_b = (lambda: A.step_policy(fa)[1]), (lambda: B.step_policy(fb)[1])
+        else:
+            step_a, step_b = A.make_graphed_policy_step(fa, warmup=3), B.make_graphed_policy_step(fb, warmup=3)
+    B.reset_outcome_totals()                                   # (the warm-up steps of a capture were counted too)
+    episodes = torch.zeros((), dtype=torch.int64, device=DEV)
+    steps, fell, survived = torch.zeros_like(episodes), torch.zeros_like(episodes), torch.zeros_like(episodes)
+    ll_reset, ll_time_out = B.ll_env._sim.buf["reset_buf"], B.ll_env._sim.buf["time_out_buf"]
+    for k in range(40):
+        before = B.curr_episode_step.clone()
+        out_a, out_b = step_a(), step_b()
+        assert_same(A, B, k)
+        assert out_a[4] == {} and A.extras == {}
+        assert out_b[4] is B.extras and tuple(B.extras["episode"]) == KEYS
+        episodes += B.reset_buf.sum()
+        steps += ((before + 1) * B.reset_buf).sum()
+        fell += (ll_reset.bool() & ~ll_time_out.bool()).sum()
+        survived += (ll_reset.bool() & ll_time_out.bool()).sum()
+        assert bool((B.reset_buf | ~ll_reset.bool()).all())                 # a low-level reset ends the game's episode
+    torch.cuda.synchronize()
+    totals = B.outcome_totals()
+    assert tuple(totals) == ot.COUNTS and all(isinstance(v, int) for v in totals.values())
+    assert totals["episodes"] == int(episodes) and totals["steps"] == int(steps)
+    assert totals["fell"] == int(fell) and totals["survived"] == int(survived)
+    print(f"{task} {path}: {totals}")
+    assert totals["episodes"] >= 8 and totals["fell"] + totals["survived"] + totals["captured"] >= totals["episodes"]
+    assert totals["captured"] > 0 and totals["survived"] > 0
+    assert totals["prey_out"] == totals["predator_out"] == 0                        # env_radius is None
+    for key in KEYS:
+        v = B.extras["episode"][key]
+        assert v.dim() == 0 and v.is_cuda and math.isfinite(float(v)) and (key == "outcome_steps" or 0.0 <= float(v) <= 1.0)
+    assert int(B._outcome_accum.abs().sum()) == 0 and int(B._outcome_ticket[0]) == 0
+    with pytest.raises(RuntimeError, match="never switched on"):
+        A.outcome_totals()
+    # switching off returns to the plain launch and empty extras; the totals stay
+    B.enable_outcome_stats(False)
+    assert B.extras == {} and B.outcome_totals() == totals
+
+
+# ----------------------------------------------------------------------------- the runner and play_game
+def _train(tmp_path, monkeypatch, reg, iterations, outcome_stats, device_rollout):
+    import legged_games_gym_amd.utils.task_registry as tr_mod
+    from legged_games_gym_amd.utils import get_args
+    ckpt = write_ll_checkpoint(str(tmp_path / "ll" / "model_0.pt"), seed=3)
+    monkeypatch.setattr(tr_mod, "LEGGED_GYM_ROOT_DIR", str(tmp_path))
+    env_cfg, train_cfg = reg.get_cfgs("scripted_predator_game")
+    env_cfg.terrain.mesh_type, env_cfg.env.ll_policy_path = "plane", ckpt
+    if device_rollout:
+        train_cfg.runner.device_rollout = True                          # a runner key, set on this registration only
+    if outcome_stats:
+        env_cfg.env.outcome_stats = True                                # an attribute the env reads with getattr(), set on this registration only
+    args = get_args(["--task", "scripted_predator_game", "--num_envs", "64", "--headless", "--sim_device", DEV, "--rl_device", DEV])
+    env, _ = reg.make_env("scripted_predator_game", args)
+    runner, _ = reg.make_alg_runner(env, "scripted_predator_game", args)
+    runner.learn(num_learning_iterations=iterations, init_at_random_ep_len=True)
+    torch.cuda.synchronize()
+    return env, runner, ckpt
+
+
+@pytest.mark.parametrize("outcome_stats", [True, False])
+def test_runner_logs_the_outcome_columns_only_when_switched_on(tmp_path, monkeypatch, scripted_registered, outcome_stats):
+    """Two PPO iterations of ``scripted_predator_game`` at 64 envs on the captured device rollout: with the statistics on, ``progress.csv``
+    has the six ``Episode/outcome_*`` columns with finite values; with them off it has none."""
+    env, runner, _ = _train(tmp_path, monkeypatch, scripted_registered, 2, outcome_stats, device_rollout=True)
+    assert runner._game_rollout and (env._outcome is not None) == outcome_stats
+    rows = list(csv.DictReader(open(os.path.join(runner.log_dir, "progress.csv"))))
+    assert len(rows) == 2
+    cols = [c for c in rows[0] if c.startswith("Episode/outcome_")]
+    if not outcome_stats:
+        assert cols == [] and env.extras == {}
+        return
+    assert sorted(cols) == sorted(f"Episode/{k}" for k in KEYS)
+    for row in rows:
+        for c in cols:
+            assert math.isfinite(float(row[c])), (c, row[c])
+    totals = env.outcome_totals()
+    assert totals["episodes"] > 0 and totals["steps"] >= totals["episodes"]
+    assert float(rows[-1]["Episode/outcome_steps"]) >= 1.0
+
+
+def test_play_game_reports_the_totals_of_its_rollout(tmp_path, monkeypatch, scripted_registered, capsys):
+    """``play_game`` in process on a one-iteration checkpoint, 30 steps at 16 envs: the JSON next to the checkpoint has the keys, and its
+    counts are the env's totals."""
+    from legged_games_gym_amd.scripts import play_game as pg
+    _, runner, _ = _train(tmp_path, monkeypatch, scripted_registered, 1, outcome_stats=False, device_rollout=False)
+    run_dir = runner.log_dir
+    assert os.path.isfile(os.path.join(run_dir, "model_1.pt"))
+    args = pg._args(["--task", "scripted_predator_game", "--num_envs", "16", "--steps", "30", "--headless", "--sim_device", DEV, "--rl_device", DEV])
+    assert args.steps == 30
+    env, result, path = pg.play_game(args, steps=args.steps)
+    assert path == os.path.join(run_dir, "outcomes_1.json") and os.path.isfile(path)
+    data = json.load(open(path))
+    assert data == json.loads(json.dumps(result))
+    assert set(data) == {"totals", "rates", "mean_steps", "num_envs", "steps", "task", "iteration", "path"}
+    assert tuple(data["totals"]) == ot.COUNTS and set(data["rates"]) == {f"{k}_rate" for k in ot.FLAGS}
+    totals = env.outcome_totals()
+    assert data["num_envs"] == env.num_envs == 16 and data["steps"] == 30 and data["iteration"] == 1
+    assert data["totals"] == totals and data["totals"]["episodes"] == totals["episodes"]
+    assert data["path"] == "graphed policy step"                    # the registered 19-512-256-128-6 actor has the shared actor launch
+    rates = pg.outcome_rates(totals)
+    for k, v in rates.items():
+        got = data["mean_steps"] if k == "mean_steps" else data["rates"][k]
+        assert (got is None and math.isnan(v)) or got == v
+    text = capsys.readouterr().out
+    assert "not counted" in text and "captured" in text and "survived" in text

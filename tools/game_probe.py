@@ -21,6 +21,10 @@ update, same seed and size).  With ``--trace`` it replays (p) only.
 ``--scripted`` builds ``scripted_predator_game`` beside ``high_level_game`` in one process and times the graphed three-launch policy step of both
 (lg_game_act, k_step, then k_pursuer_post against k_game_post), alternating; writes profiles/pursuer_step.json.
 
+``--outcome`` builds both tasks with the outcome statistics off and on (four envs per size, one process) and times their graphed three-launch
+policy step, alternating: k_outcome_post<false> against k_game_post and k_outcome_post<true> against k_pursuer_post in the same run; writes
+profiles/game_outcome_step.json.
+
 The low-level policy is a seeded random-init checkpoint written to a temporary directory: the kernels' cost does not depend on the weights."""
 import argparse
 import json
@@ -245,6 +249,49 @@ def scripted_main(args):
     print("wrote", out)
 
 
+def outcome_main(args):
+    """The graphed three-launch policy step of both game tasks with the outcome statistics off (the parent's post kernels) and on
+    (k_outcome_post), same process, same sizes, alternating repeats; the difference on - off repeat by repeat."""
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.replays, "repeats": args.repeats, "envs": {}}
+    names = ("high_level_game", "high_level_game_outcome", "scripted_predator_game", "scripted_predator_game_outcome")
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            envs, steps = [], []
+            for scripted in (False, True):
+                for on in (False, True):
+                    env, _ = make_env(n, args.mesh, tmp, scripted=scripted)
+                    if on:
+                        env.enable_outcome_stats()           # before the capture: the graph keeps the launch the switch selected
+                    envs.append(env)
+                    steps.append(env.make_graphed_policy_step(fused_high_level_actor(env)))
+            for fn in steps:
+                timed(fn, 200)
+            t = [[] for _ in steps]
+            for _ in range(args.repeats):              # alternating: other work shares the machine
+                for i, fn in enumerate(steps):
+                    t[i].append(timed(fn, args.replays))
+            row = {f"{name}_policy_step": spread(x) for name, x in zip(names, t)}
+            for task, off, on in (("high_level_game", 0, 1), ("scripted_predator_game", 2, 3)):
+                row[f"{task}_outcome_minus_plain"] = spread([y - x for x, y in zip(t[off], t[on])])
+            for env in envs:
+                assert torch.isfinite(env.obs_buf).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            for i in (1, 3):
+                totals = envs[i].outcome_totals()
+                assert totals["episodes"] > 0 and envs[i - 1].extras == {}
+                row[f"{names[i]}_totals"] = totals
+            result["envs"][str(n)] = row
+            print(f"{n} envs, graphed three-launch policy step: " + "; ".join(
+                f"{name} {statistics.median(x):.1f} us ({min(x):.1f} .. {max(x):.1f})" for name, x in zip(names, t)), flush=True)
+            for task in ("high_level_game", "scripted_predator_game"):
+                d = row[f"{task}_outcome_minus_plain"]
+                print(f"  {task}: statistics on - off {d['median_us']:+.2f} us ({d['min_us']:+.2f} .. {d['max_us']:+.2f})", flush=True)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "game_outcome_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 def timed(fn, count):
     """Mean microseconds per call of ``fn`` over ``count`` calls, device events around the whole window."""
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -271,10 +318,13 @@ def main():
     ap.add_argument("--policy-step", action="store_true", help="time the device path of the high-level actor; writes profiles/game_policy_step.json")
     ap.add_argument("--train-iterations", type=int, default=10, help="--policy-step: timed PPO iterations per setting of the runner switch (0: skip)")
     ap.add_argument("--scripted", action="store_true", help="time scripted_predator_game's graphed policy step beside high_level_game's; writes profiles/pursuer_step.json")
+    ap.add_argument("--outcome", action="store_true", help="time the graphed policy step of both tasks with the outcome statistics off and on; writes profiles/game_outcome_step.json")
     ap.add_argument("--trace", action="store_true", help="a short loop of graph replays only (for a kernel trace)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("game_probe needs an AMD GPU: there is nothing to time on the CPU")
+    if args.outcome:
+        return outcome_main(args)
     if args.scripted:
         return scripted_main(args)
     if args.policy_step:
