@@ -12,12 +12,12 @@
 #define LG_POLICY_BLOCKS_ONLY      // lg_policy.h without its two non-template pack kernels (they belong to lg_kernels.hip)
 #include "lg_device.h"
 #include "lg_policy.h"
-#include "lg_game_common.h"
+#include "lg_game_post.h"      // the integrator, the root reset and the observation writer of the post stage
 #include "lg_dec_game_common.h"
 
 namespace lg {
 
-enum { RNG_DEC_ROOT = 16, RNG_DEC_PREDATOR = 17, RNG_GAME_DOF = 18 };      // Philox purposes: root and predator as k_game_post (lg_game.h), the joints new
+enum { RNG_GAME_DOF = 18 };      // Philox purpose of the joint reset; root and predator: RNG_GAME_ROOT / RNG_GAME_PREDATOR (lg_game_post.h)
 #define LG_DEC_BLOCK 256
 
 __global__ __launch_bounds__(LG_DEC_BLOCK) void k_dec_pre(lg_dec_game_params P, lg_dec_game_buffers B) {
@@ -52,16 +52,12 @@ LG_DEV void dec_post_env(const lg_dec_game_params &P, const lg_dec_game_buffers 
     int64_t ep_step = B.curr_episode_step[e] + 1;                                             // (:244)
 
     // step_predator_single_integrator (:228-230)
-    float px = pp[0], py = pp[1], pz = pp[2];
-    const float vx = B.command_pred[(size_t)e * LG_DEC_NUM_ACTIONS_PRED], vy = B.command_pred[(size_t)e * LG_DEC_NUM_ACTIONS_PRED + 1];
-    const float dx = P.sim_dt * vx, dy = P.sim_dt * vy;
-    for (int i = 0; i < P.decimation; i++) { px = px + dx; py = py + dy; }
-
-    float qx = root[0], qy = root[1], qz = root[2];                                           // prey_states[:, :3]
-    float quat_z = root[5], quat_w = root[6];
+    GamePose s = game_load_pose(pp, root);
+    game_integrate_predator(P.sim_dt, P.decimation, B.command_pred[(size_t)e * LG_DEC_NUM_ACTIONS_PRED],
+                            B.command_pred[(size_t)e * LG_DEC_NUM_ACTIONS_PRED + 1], s);
 
     // check_termination (:263-269)
-    const float ax = qx - px, ay = qy - py;
+    const float ax = s.qx - s.px, ay = s.qy - s.py;
     const bool capture = sqrtf(ax * ax + ay * ay) < P.capture_dist;
     const bool time_out = ep_len > (int64_t)P.max_episode_length;
     bool done = capture || time_out;
@@ -69,7 +65,7 @@ LG_DEV void dec_post_env(const lg_dec_game_params &P, const lg_dec_game_buffers 
     // compute_reward_prey (:321-341), compute_reward_pred (:344-361)
     float sum_ev = B.episode_sums[e], sum_pu = B.episode_sums[N + e], sum_te = B.episode_sums[2 * N + e];
     {
-        const float rx = px - qx, ry = py - qy, rz = pz - qz;
+        const float rx = s.px - s.qx, ry = s.py - s.qy, rz = s.pz - s.qz;
         const float d = sqrtf((rx * rx + ry * ry) + rz * rz);
         const float ev = d * P.scale_evasion_dt, pu = (-d) * P.scale_pursuit_dt;
         float rew = P.ll_rew_weight * B.ll_rew_buf[e];
@@ -89,9 +85,8 @@ LG_DEV void dec_post_env(const lg_dec_game_params &P, const lg_dec_game_buffers 
     }
     done = done || B.ll_reset_buf[e] != 0;                                                    // (:252)
 
-    float o9 = obs[9], o10 = obs[10], o11 = obs[11];                                           // newest sensed position
-    float h[6] = {obs[3], obs[4], obs[5], obs[6], obs[7], obs[8]};
-    float f13 = obs[13], f14 = obs[14], f15 = obs[15];
+    GameHistory k;
+    k.load(obs);
     if (done) {
         red[0] = 1.0f; red[1] = sum_ev; red[2] = sum_pu; red[3] = sum_te;                     // (:300-305)
         sum_ev = 0.0f; sum_pu = 0.0f; sum_te = 0.0f;
@@ -104,31 +99,8 @@ LG_DEV void dec_post_env(const lg_dec_game_params &P, const lg_dec_game_buffers 
 #pragma unroll
             for (int l = 0; l < 4; l++) ds[4 * b + l] = make_float2(P.default_dof_pos[4 * b + l] * game_urange(0.5f, 1.5f, uj[l]), 0.0f);
         }
-        // LowLevelGame._reset_root_states (low_level_game.py:409-432), as k_game_post
-        float u[4], v[4], w[4];
-        rand4(P.seed, e, step, RNG_DEC_ROOT, 0, u);
-        rand4(P.seed, e, step, RNG_DEC_ROOT, 1, v);
-        rand4(P.seed, e, step, RNG_DEC_PREDATOR, 0, w);
-        float r[13];
-#pragma unroll
-        for (int i = 0; i < 13; i++) r[i] = P.base_init_state[i];
-        r[0] = r[0] + org[0]; r[1] = r[1] + org[1]; r[2] = r[2] + org[2];
-        if (P.custom_origins) { r[0] = r[0] + game_urange(-1.0f, 1.0f, u[0]); r[1] = r[1] + game_urange(-1.0f, 1.0f, u[1]); }
-        r[7] = game_urange(-0.5f, 0.5f, u[2]); r[8] = game_urange(-0.5f, 0.5f, u[3]);
-        r[9] = game_urange(-0.5f, 0.5f, v[0]); r[10] = game_urange(-0.5f, 0.5f, v[1]);
-        r[11] = game_urange(-0.5f, 0.5f, v[2]); r[12] = game_urange(-0.5f, 0.5f, v[3]);
-#pragma unroll
-        for (int i = 0; i < 13; i++) root[i] = r[i];
-        qx = r[0]; qy = r[1]; qz = r[2]; quat_z = r[5]; quat_w = r[6];
-        const float sgn = w[3] < 0.5f ? -1.0f : 1.0f;                                          // (:422-424)
-        px = qx - sgn * game_urange(1.0f, 10.0f, w[0]);
-        py = qy - sgn * game_urange(1.0f, 10.0f, w[1]);
-        pz = P.predator_z;                                                                    // (:432); the z offset w[2] is drawn and overwritten
-        // DecHighLevelGame.reset_idx (:291-296)
-        o9 = o10 = o11 = P.max_rel_pos;
-#pragma unroll
-        for (int i = 0; i < 6; i++) h[i] = P.max_rel_pos;
-        f13 = f14 = f15 = 0.0f;
+        game_reset_root(P, e, step, org, root, s);
+        k.clear(P.max_rel_pos);                                                               // DecHighLevelGame.reset_idx (:291-296)
         ep_len = 0;
         ep_step = 0;
     }
@@ -137,24 +109,12 @@ LG_DEV void dec_post_env(const lg_dec_game_params &P, const lg_dec_game_buffers 
     B.reset_buf[e] = done ? 1 : 0;
     B.time_out_buf[e] = time_out ? 1 : 0;
     B.episode_sums[e] = sum_ev; B.episode_sums[N + e] = sum_pu; B.episode_sums[2 * N + e] = sum_te;
-    pp[0] = px; pp[1] = py; pp[2] = pz;
+    pp[0] = s.px; pp[1] = s.py; pp[2] = s.pz;
 
-    // compute_observations_pred (:389-391), prey_sense_predator (:417-448) + compute_observations_prey (:374-380); the occlusion test as k_game_post
+    // compute_observations_pred (:389-391), prey_sense_predator (:417-448) + compute_observations_prey (:374-380)
     float *op = B.obs_pred + (size_t)e * LG_DEC_NUM_OBS_PRED;
-    op[0] = qx - px; op[1] = qy - py; op[2] = qz - pz;
-    const float rx = px - qx, ry = py - qy, rz = pz - qz;
-    const float qn = fmaxf(sqrtf(quat_z * quat_z + quat_w * quat_w), 1e-9f);                  // quat_apply_yaw: normalize((0, 0, z, w))
-    const float yz = quat_z / qn, yw = quat_w / qn;
-    const float tz = yz * 2.0f;                                                               // quat_apply(q_yaw, (1, 0, 0))
-    const float fx = 1.0f - yz * tz, fy = yw * tz;
-    const float dotv = fx * rx + fy * ry;
-    const float denom = sqrtf(fx * fx + fy * fy) * sqrtf((rx * rx + ry * ry) + rz * rz);
-    const float angle = game_wrap_to_pi(acosf(dotv / denom));
-    const bool visible = fabsf(angle) <= P.half_fov;                                          // NaN (0/0) compares false: occluded
-    obs[0] = h[0]; obs[1] = h[1]; obs[2] = h[2]; obs[3] = h[3]; obs[4] = h[4]; obs[5] = h[5];
-    obs[6] = o9; obs[7] = o10; obs[8] = o11;
-    obs[9] = visible ? rx : o9; obs[10] = visible ? ry : o10; obs[11] = visible ? rz : o11;
-    obs[12] = f13; obs[13] = f14; obs[14] = f15; obs[15] = visible ? 1.0f : 0.0f;
+    op[0] = s.qx - s.px; op[1] = s.qy - s.py; op[2] = s.qz - s.pz;
+    game_observe(P.half_fov, s, k, obs);
 }
 
 __global__ __launch_bounds__(LG_DEC_BLOCK) void k_dec_post(lg_dec_game_params P, lg_dec_game_buffers B, int64_t step_arg) {

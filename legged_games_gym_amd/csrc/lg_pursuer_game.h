@@ -10,17 +10,21 @@ int launch_pursuer_post(const lg_game_params &P, const lg_pursuer_params &Q, con
 
 extern "C" {
 
-int lg_pursuer_post(const lg_game_params *P, const lg_pursuer_params *Q, const lg_game_buffers *B, float *predator_command, int64_t common_step_counter,
-                    void *stream) {
-    if (!Q) return fail(-1, "null argument");
-    if (int rc = game_check(P, B)) return rc;
+// the ranges of the scripted rule (Q is not null): game_quotient is exact for 1 <= L <= 2^20
+static int pursuer_check(const lg_pursuer_params *Q) {
     if (Q->max_episode_length < 1 || Q->max_episode_length > (1 << 20))
         return fail(-2, "lg_pursuer_params: max_episode_length must be in 1 .. 2^20");
     if (!(Q->max_lin_vel >= Q->min_lin_vel)) return fail(-2, "lg_pursuer_params: max_lin_vel must not be below min_lin_vel");
     if (!(Q->gain > 0.0f)) return fail(-2, "lg_pursuer_params: gain must be positive");
-    if (!B->ll_root_states || !B->ll_env_origins || !B->ll_rew_buf || !B->ll_reset_buf || !B->predator_pos || !B->obs || !B->rew || !B->reset_buf ||
-        !B->curr_episode_step || !B->episode_length_buf || !B->episode_sums) return fail(-1, "lg_pursuer_post: a buffer pointer is null");
-    if (common_step_counter < 0 && !B->ll_step_counter) return fail(-9, "common_step_counter = -1 needs the low-level step_counter buffer");
+    return 0;
+}
+
+int lg_pursuer_post(const lg_game_params *P, const lg_pursuer_params *Q, const lg_game_buffers *B, float *predator_command, int64_t common_step_counter,
+                    void *stream) {
+    if (!Q) return fail(-1, "null argument");
+    if (int rc = game_check(P, B)) return rc;
+    if (int rc = pursuer_check(Q)) return rc;
+    if (int rc = game_post_check("lg_pursuer_post", B, false, common_step_counter)) return rc;
     HIP_TRY((hipError_t)lg::launch_pursuer_post(*P, *Q, *B, predator_command, common_step_counter, stream));
     return 0;
 }
