@@ -262,6 +262,7 @@ class PPO:
             std = self.actor_critic.std
             self._d_std = std.grad                      # the loss kernels write d loss / d std here
             self._mlp = None                            # descriptors hold the old .grad addresses
+            self._dp_graphs, self._dp_key = None, None  # ... and so do the captured data-parallel graphs
         return self._gflat
 
     def _allreduce_flat(self, adaptive):
@@ -275,12 +276,23 @@ class PPO:
             self._stats[2:3].copy_(flat[-1:])
 
     def after_optimizer_load(self):
-        """The optimiser's tensors were replaced (checkpoint resume): re-link the device learning rate, drop the captured graph."""
+        """The optimiser's tensors were replaced (checkpoint resume): re-link the device learning rate, drop the captured graphs
+        (the single-process update graph and the data-parallel "pre" / "post" graphs: their Adam launches hold the old state addresses)."""
         if self._graph_ok:
             for g in self.optimizer.param_groups:
                 self._lr.copy_(torch.as_tensor(g["lr"], device=self.device).float().reshape(()))
                 g["lr"] = self._lr
             self._graph, self._updates_done = None, 0
+            self._dp_graphs, self._dp_key = None, None
+
+    def _dp_state_key(self):
+        """Addresses the captured data-parallel graphs bake in besides the storage's: Adam's state tensors and the flat gradient buffer."""
+        ptrs = []
+        for q in self.actor_critic.parameters():
+            stt = self.optimizer.state.get(q) or {}
+            ptrs += [stt[k].data_ptr() if torch.is_tensor(stt.get(k)) else 0 for k in ("exp_avg", "exp_avg_sq", "step")]
+        flat = getattr(self, "_gflat", None)
+        return tuple(ptrs) + (flat.data_ptr() if flat is not None else 0,)
 
     # ------------------------------------------------------------------ captured mini-batch step
     def _flat(self):
@@ -591,7 +603,7 @@ class PPO:
             self._perm_buf = torch.zeros(nmb * mb, dtype=torch.int64, device=self.device)
             self._acc = torch.zeros(2, device=self.device)
             self._dp_graphs = None
-        key = (st.observations.data_ptr(), st.advantages.data_ptr(), st.returns.data_ptr(), mb)
+        key = (st.observations.data_ptr(), st.advantages.data_ptr(), st.returns.data_ptr(), mb) + self._dp_state_key()
         if getattr(self, "_dp_key", None) != key:
             self._dp_key, self._dp_graphs = key, None
         self._acc.zero_()
