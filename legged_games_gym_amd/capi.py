@@ -570,6 +570,48 @@ def outcome_pursuer_post(params: lg_game_params, pursuer: lg_pursuer_params, buf
         raise RuntimeError(f"lg_outcome_pursuer_post failed ({rc}): {lib.lg_last_error().decode()}")
 
 
+# ----------------------------------------------------------------------------- decentralised game's outcome statistics (include/legged_dec_game_outcome.h)
+LG_DEC_OUTCOME_NUM_COUNTS, LG_DEC_OUTCOME_NUM_MEANS = 6, 5
+DEC_OUTCOME_COUNTS = ("episodes", "captured", "timed_out", "fell", "ll_timed_out", "steps")     # the order of accum / totals
+DEC_OUTCOME_MEANS = DEC_OUTCOME_COUNTS[1:]                                                      # the order of means: four rates, mean steps
+
+
+class lg_dec_outcome_buffers(C.Structure):
+    """include/legged_dec_game_outcome.h: lg_dec_outcome_buffers (raw device pointers)."""
+    _fields_ = [("ll_time_out_buf", _PU8), ("accum", C.POINTER(u64)), ("means", _PF), ("totals", C.POINTER(u64))]
+
+
+DEC_OUTCOME_BUFFER_FIELDS = [name for name, _ in lg_dec_outcome_buffers._fields_]
+DEC_OUTCOME_SYMBOLS = ["lg_dec_outcome_post", "lg_dec_outcome_sizeof"]
+
+
+def bind_dec_outcome_prototypes(lib):
+    """Attach argtypes/restype for the entry points of legged_dec_game_outcome.h and check the struct layout."""
+    lib.lg_dec_outcome_post.argtypes = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), C.POINTER(lg_dec_outcome_buffers), i64, C.c_void_p]
+    lib.lg_dec_outcome_post.restype = C.c_int
+    lib.lg_dec_outcome_sizeof.argtypes, lib.lg_dec_outcome_sizeof.restype = [C.c_int], C.c_int
+    if lib.lg_dec_outcome_sizeof(0) != C.sizeof(lg_dec_outcome_buffers):
+        raise RuntimeError(f"struct layout mismatch for lg_dec_outcome_buffers: C {lib.lg_dec_outcome_sizeof(0)} vs ctypes {C.sizeof(lg_dec_outcome_buffers)}")
+    return lib
+
+
+def dec_outcome_buffers(pointers: Dict[str, int]) -> lg_dec_outcome_buffers:
+    """``lg_dec_outcome_buffers`` from a name -> device address table (missing names stay null)."""
+    b = lg_dec_outcome_buffers()
+    types = dict(lg_dec_outcome_buffers._fields_)
+    for name in DEC_OUTCOME_BUFFER_FIELDS:
+        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
+    return b
+
+
+def dec_outcome_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, outcome: lg_dec_outcome_buffers, common_step_counter: int, stream: int = 0):
+    """``lg_dec_outcome_post``: ``lg_dec_game_post`` that also counts why the done envs' episodes ended."""
+    lib = load_library()
+    rc = lib.lg_dec_outcome_post(C.byref(params), C.byref(buffers), C.byref(outcome), int(common_step_counter), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_outcome_post failed ({rc}): {lib.lg_last_error().decode()}")
+
+
 def load_library():
     """Load the HIP extension or fail loudly -- never a CPU substitute."""
     global _lib
@@ -580,7 +622,7 @@ def load_library():
         raise RuntimeError(
             f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_")))))
+    _lib = bind_dec_outcome_prototypes(bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_"))))))
     if _lib.lg_abi_version() != LG_ABI_VERSION:
         raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
     return _lib

@@ -18,14 +18,20 @@ int lg_dec_game_pre(const lg_dec_game_params *P, const lg_dec_game_buffers *B, v
     return 0;
 }
 
-int lg_dec_game_post(const lg_dec_game_params *P, const lg_dec_game_buffers *B, int64_t common_step_counter, void *stream) {
-    if (int rc = dec_game_check(P, B)) return rc;
+// what lg_dec_game_post and lg_dec_outcome_post (lg_dec_game_outcome_entry.h) require of their buffers, after dec_game_check
+static int dec_game_post_check(const char *who, const lg_dec_game_params *P, const lg_dec_game_buffers *B, int64_t common_step_counter) {
     if (!B->command_pred || !B->ll_root_states || !B->ll_dof_state || !B->ll_env_origins || !B->ll_rew_buf || !B->ll_reset_buf || !B->predator_pos ||
         !B->obs_prey || !B->obs_pred || !B->rew_prey || !B->rew_pred || !B->reset_buf || !B->time_out_buf || !B->curr_episode_step ||
         !B->episode_length_buf || !B->episode_sums || !B->episode_means || !B->extras_accum || !B->extras_ticket)
-        return fail(-1, "lg_dec_game_post: a buffer pointer is null");
+        return fail(-1, "%s: a buffer pointer is null", who);
     if (!(P->max_episode_length_s > 0.0f)) return fail(-2, "lg_dec_game_params: max_episode_length_s must be positive");
     if (common_step_counter < 0 && !B->ll_step_counter) return fail(-9, "common_step_counter = -1 needs the low-level step_counter buffer");
+    return 0;
+}
+
+int lg_dec_game_post(const lg_dec_game_params *P, const lg_dec_game_buffers *B, int64_t common_step_counter, void *stream) {
+    if (int rc = dec_game_check(P, B)) return rc;
+    if (int rc = dec_game_post_check("lg_dec_game_post", P, B, common_step_counter)) return rc;
     HIP_TRY((hipError_t)lg::launch_dec_post(*P, *B, common_step_counter, stream));
     return 0;
 }

@@ -1,0 +1,25 @@
+// lg_dec_game_outcome_entry.h -- C entry points of the decentralised game's outcome statistics (include/legged_dec_game_outcome.h).  Host
+// code only: the kernel lives in lg_dec_game_outcome.hip behind launch_dec_outcome.  Included from lg_kernels.hip after lg_dec_game.h
+// (dec_game_check, dec_game_post_check).
+#pragma once
+#include "../../include/legged_dec_game_outcome.h"
+
+namespace lg {
+int launch_dec_outcome(const lg_dec_game_params &P, const lg_dec_game_buffers &B, const lg_dec_outcome_buffers &O, int64_t step,
+                       void *stream);      // lg_dec_game_outcome.hip; returns the hipError_t of the launch
+}
+
+extern "C" {
+
+int lg_dec_outcome_post(const lg_dec_game_params *P, const lg_dec_game_buffers *B, const lg_dec_outcome_buffers *O, int64_t common_step_counter, void *stream) {
+    if (!O) return fail(-1, "lg_dec_outcome_post: lg_dec_outcome_buffers is null");
+    if (int rc = dec_game_check(P, B)) return rc;
+    if (!O->ll_time_out_buf || !O->accum || !O->means || !O->totals) return fail(-1, "lg_dec_outcome_post: a pointer of lg_dec_outcome_buffers is null");
+    if (int rc = dec_game_post_check("lg_dec_outcome_post", P, B, common_step_counter)) return rc;
+    HIP_TRY((hipError_t)lg::launch_dec_outcome(*P, *B, *O, common_step_counter, stream));
+    return 0;
+}
+
+int lg_dec_outcome_sizeof(int which) { return which == 0 ? (int)sizeof(lg_dec_outcome_buffers) : -1; }
+
+}  // extern "C"

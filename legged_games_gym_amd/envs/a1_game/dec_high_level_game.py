@@ -14,6 +14,12 @@ positions, four visibility flags) to its command ``(lin_vel_x, lin_vel_y, ang_ve
 
     lg_dec_game_act (three actors + the clips)  ->  lg_step  ->  lg_dec_game_post
 
+Outcome statistics (off by default; ``env.outcome_stats = True`` on the config object or ``enable_outcome_stats()``): the last launch of
+every step path becomes ``lg_dec_outcome_post`` (include/legged_dec_game_outcome.h), which writes what ``lg_dec_game_post`` writes, bit for
+bit, and also counts inside the launch why the done envs' episodes ended.  ``extras["episode"]`` then additionally holds five device scalars
+``outcome_*`` -- the shares of captures, game time-outs, falls and low-level time-outs among the done envs and their mean episode length --
+and ``outcome_totals()`` the running integer sums.  A step is still three launches and a rollout still one graph replay.
+
 ``agent_view(agent, opponent)`` gives one agent's single-agent surface (what ``rl.OnPolicyRunner`` drives) with the other agent acting
 inside every step.  Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G10 onward)."""
 import numpy as np
@@ -57,6 +63,9 @@ class DecHighLevelGame(GameBase):
         self._init_buffers()
         self._prepare_reward_functions()
         self._pack()
+        self._outcome = None
+        if getattr(cfg.env, "outcome_stats", False):           # no field of the registered config classes: they stay value for value the reference's
+            self.enable_outcome_stats()
         self.init_done = True
 
     # ------------------------------------------------------------------ hot path
@@ -86,8 +95,49 @@ class DecHighLevelGame(GameBase):
         capi.dec_game_pre(self._P, B, stream)
         actions = self.ll_policy(ll.obs_buf)
         ll.step(actions)
-        capi.dec_game_post(self._P, B, ll.common_step_counter, stream)
+        self._post(B, ll.common_step_counter, stream)
         return self._step_result()
+
+    def _post(self, B, common_step_counter, stream):
+        """The last launch of every step path: ``lg_dec_game_post``, or ``lg_dec_outcome_post`` with the outcome statistics on."""
+        if self._outcome is None:
+            capi.dec_game_post(self._P, B, common_step_counter, stream)
+        else:
+            capi.dec_outcome_post(self._P, B, self._outcome, common_step_counter, stream)
+
+    # ------------------------------------------------------------------ outcome statistics
+    def enable_outcome_stats(self, on=True):
+        """Switch the outcome statistics on or off.  On: ``_post`` issues ``lg_dec_outcome_post`` on every step path and ``extras["episode"]``
+        additionally holds 0-dim views ``outcome_captured``, ``outcome_timed_out``, ``outcome_fell``, ``outcome_ll_timed_out`` (shares of the
+        done envs of the last step in which an env was done; an env may raise several) and ``outcome_steps`` (their mean episode length in
+        high-level steps).  Off: the launches and the extras of the plain task.  The totals are kept across a switch;
+        ``reset_outcome_totals()`` zeroes them.  A graph captured before the switch keeps the launch it was captured with."""
+        for key in [k for k in self.extras["episode"] if k.startswith("outcome_")]:
+            del self.extras["episode"][key]
+        if not on:
+            self._outcome = None
+            return
+        if getattr(self, "_outcome_accum", None) is None:
+            dev = self.device
+            self._outcome_accum = torch.zeros(capi.LG_DEC_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
+            self._outcome_means = torch.zeros(capi.LG_DEC_OUTCOME_NUM_MEANS, device=dev, dtype=torch.float)
+            self._outcome_totals = torch.zeros(capi.LG_DEC_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
+        self._outcome = capi.dec_outcome_buffers({"ll_time_out_buf": self.ll_env._sim.buf["time_out_buf"].data_ptr(), "accum": self._outcome_accum.data_ptr(),
+                                                  "means": self._outcome_means.data_ptr(), "totals": self._outcome_totals.data_ptr()})
+        self.extras["episode"].update({f"outcome_{name}": self._outcome_means[i] for i, name in enumerate(capi.DEC_OUTCOME_MEANS)})
+
+    def outcome_totals(self):
+        """Running sums since construction or the last ``reset_outcome_totals()``, as Python ints after ONE synchronising copy:
+        ``episodes, captured, timed_out, fell, ll_timed_out, steps``."""
+        if getattr(self, "_outcome_totals", None) is None:
+            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
+        return dict(zip(capi.DEC_OUTCOME_COUNTS, (int(v) for v in self._outcome_totals.cpu().tolist())))
+
+    def reset_outcome_totals(self):
+        """Zero the running sums (stream-ordered: no synchronisation)."""
+        if getattr(self, "_outcome_totals", None) is None:
+            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
+        self._outcome_totals.zero_()
 
     def _step_result(self):
         return (self.obs_buf_pred, self.obs_buf_prey, self.privileged_obs_buf_pred, self.privileged_obs_buf_prey, self.rew_buf_pred, self.rew_buf_prey,
@@ -101,7 +151,7 @@ class DecHighLevelGame(GameBase):
         capi.dec_game_pre(self._P, B, stream)
         actions = self.ll_policy(ll.obs_buf)
         ll._sim.step(actions, -1)
-        capi.dec_game_post(self._P, B, -1, stream)
+        self._post(B, -1, stream)
 
     def make_graphed_step(self, policy_pred, policy_prey, warmup=3, steps_per_replay=1):
         """Capture ``step(policy_pred(obs_buf_pred), policy_prey(obs_buf_prey))`` into one HIP graph and return a zero-argument callable that
@@ -196,23 +246,25 @@ class DecHighLevelGame(GameBase):
             self._unflip_observations()
             raise
         ll.step(ll_actions)
-        capi.dec_game_post(self._P, B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
+        self._post(B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
         return pred, prey, self._step_result()
 
-    def make_graphed_policy_step(self, fused_pred, fused_prey, warmup=3, steps_per_replay=1):
+    def make_graphed_policy_step(self, fused_pred, fused_prey, warmup=3, steps_per_replay=1, deterministic_pred=False, deterministic_prey=False):
         """``make_graphed_step`` with both actors on the device: the graph is ``lg_dec_game_act`` -> ``lg_step`` -> ``lg_dec_game_post`` per
         step, the observations stay in one buffer per agent.  Both ``FusedActor`` s must draw their noise stream from the low-level sim's
         device step counter (``FusedActor(..., step_counter=env.ll_env._sim.buf["step_counter"])``).  Returns a zero-argument callable that
-        replays the graph; the actors' ``output_buffers(num_envs)`` then hold the commands and the means of the last step."""
+        replays the graph; the actors' ``output_buffers(num_envs)`` then hold the commands and the means of the last step.
+        ``deterministic_pred`` / ``deterministic_prey``: that agent's command is its clipped mean (evaluation)."""
         sim = self.ll_env._sim
         for fused in (fused_pred, fused_prey):
             if fused.step_counter is None or fused.step_counter.data_ptr() != sim.buf["step_counter"].data_ptr():
                 raise ValueError("make_graphed_policy_step needs FusedActors on the low-level sim's device step counter")
 
         def device_step():
-            _, _, ll_actions, B = self._act(fused_pred, fused_prey, self.obs_buf_pred, self.obs_buf_prey, self.obs_buf_pred, self.obs_buf_prey, False, False)
+            _, _, ll_actions, B = self._act(fused_pred, fused_prey, self.obs_buf_pred, self.obs_buf_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
+                                            deterministic_prey)
             sim.step(ll_actions, -1)
-            capi.dec_game_post(self._P, B, -1, torch.cuda.current_stream(self.device).cuda_stream)
+            self._post(B, -1, torch.cuda.current_stream(self.device).cuda_stream)
         self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)
         return replay
 

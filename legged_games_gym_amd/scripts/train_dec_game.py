@@ -4,7 +4,8 @@
 Predator and prey are trained in alternating evolutions (``rl.DecGamePolicyRunner``): ``--max_evolutions`` evolutions of
 ``--max_iterations`` PPO iterations each (defaults: the registered train cfg's ``runner.max_evolutions`` / ``runner.max_iterations``).
 ``--device_rollout`` trains on the device path: both agents' actors on the matrix cores, three launches per step, every rollout one graph
-replay (off by default: the generic VecEnv loop).  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
+replay (off by default: the generic VecEnv loop).  ``--outcome_stats`` (either path) logs who wins: the shares of captures, game time-outs,
+falls and low-level time-outs among the finished episodes and their mean length, as ``Episode/outcome_*`` of both agents' tables.  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
 from legged_games_gym_amd.envs import a1_game
 from legged_games_gym_amd.utils import get_args
@@ -19,6 +20,8 @@ def train(args):
     a1_game.register_dec()
     if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
         task_registry.get_cfgs(args.task)[1].runner.device_rollout = True
+    if args.outcome_stats:                   # read with getattr() by the env: no field of the registered config classes
+        task_registry.get_cfgs(args.task)[0].env.outcome_stats = True
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     runner, train_cfg = task_registry.make_dec_alg_runner(env=env, name=args.task, args=args)
     runner.learn(max_num_evolutions=train_cfg.runner.max_evolutions, num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)

@@ -170,7 +170,7 @@ def get_args(argv=None):
                    help="high_level_game: train on the device rollout (runner key of the same name: MFMA high-level actor, three launches per step, one graph "
                         "replay per rollout); an actor shape the kernels refuse falls back to the generic loop with a message")
     p.add_argument("--outcome_stats", action="store_true", default=False,
-                   help="high_level_game / scripted_predator_game: count inside the post-step launch why episodes end (captured, left the arena, fell, "
+                   help="the game tasks (dec_high_level_game: scripts/train_dec_game.py): count inside the post-step launch why episodes end (captured, left the arena, fell, "
                         "survived) and log the rates as Episode/outcome_*; the scripts set env.outcome_stats on the registration they use")
     p.add_argument("--max_evolutions", type=int, help="dec_high_level_game: how often predator and prey alternate (scripts/train_dec_game.py)")
     # flags gymutil.parse_arguments contributes

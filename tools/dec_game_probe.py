@@ -7,11 +7,20 @@ alternating pairs (``--replays`` replays per timing, HIP events around them), th
 minimum and maximum time per actor stage are reported per env count.  Actors are seeded random-init networks of the task's shapes
 (3-512-256-128-2, 16-512-256-128-4, 235-512-256-128-12): the time does not depend on the weights.
 
-    python tools/dec_game_probe.py [--envs 2000 4096] [--out profiles/dec_game_act.json]"""
+    python tools/dec_game_probe.py [--envs 2000 4096] [--out profiles/dec_game_act.json]
+
+``--outcome`` builds two ``DecHighLevelGame`` envs per size in one process, the outcome statistics off and on, and times their graphed
+three-launch policy step (lg_dec_game_act, k_step, then k_dec_post against k_dec_outcome), alternating repeats; median and min .. max per
+variant and of the difference on - off repeat by repeat -> profiles/dec_outcome_step.json.  The low-level policy is a seeded random-init
+checkpoint written to a temporary directory: the kernels' cost does not depend on the weights.
+
+    python tools/dec_game_probe.py --outcome [--envs 2000 4096] [--step-replays 2000] [--repeats 5]"""
 import argparse
 import json
 import os
+import statistics
 import sys
+import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
 sys.path.insert(0, REPO)
@@ -96,6 +105,89 @@ def measure(n, graph_steps, replays, pairs, discard):
     return {k: {"median_us": sorted(v)[len(v) // 2], "min_us": min(v), "max_us": max(v), "repeats_us": v} for k, v in times.items()}
 
 
+def make_env(n, mesh, tmp):
+    from legged_games_gym_amd.envs import task_registry
+    from legged_games_gym_amd.envs.a1_game import DecHighLevelGame, DecHighLevelGameCfg as Cfg
+    from legged_games_gym_amd.utils import get_args, set_seed
+    from legged_games_gym_amd.utils.helpers import class_to_dict, parse_sim_params
+    a1_cfg, a1_train = task_registry.get_cfgs("a1")
+    torch.manual_seed(0)
+    ac = ActorCritic(a1_cfg.env.num_observations, a1_cfg.env.num_observations, a1_cfg.env.num_actions, **class_to_dict(a1_train.policy))
+    ckpt = os.path.join(tmp, "model_0.pt")
+    torch.save({"model_state_dict": ac.state_dict(), "optimizer_state_dict": {}, "iter": 0, "infos": None}, ckpt)
+    cfg = Cfg()
+    cfg.env.num_envs, cfg.env.ll_policy_path, cfg.terrain.mesh_type, cfg.seed = n, ckpt, mesh, 1
+    args = get_args(["--headless", "--sim_device", DEV, "--rl_device", DEV])
+    set_seed(1)
+    env = DecHighLevelGame(cfg, parse_sim_params(args, {"sim": class_to_dict(cfg.sim)}), args.physics_engine, DEV, True)
+    env.reset()
+    return env
+
+
+def timed(fn, count):
+    """Mean microseconds per call of ``fn`` over ``count`` calls, device events around the whole window."""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(count):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return 1000.0 * a.elapsed_time(b) / count
+
+
+def spread(xs):
+    return {"median_us": statistics.median(xs), "min_us": min(xs), "max_us": max(xs), "repeats_us": xs}
+
+
+def outcome_main(args):
+    """The graphed three-launch policy step with the outcome statistics off (k_dec_post, the kernel of the plain task) and on
+    (k_dec_outcome): same process, same sizes, alternating repeats; the difference on - off repeat by repeat."""
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.step_replays, "repeats": args.repeats,
+              "unit": "us per graphed three-launch policy step", "envs": {}}
+    names = ("dec_high_level_game", "dec_high_level_game_outcome")
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            envs, steps = [], []
+            for on in (False, True):
+                env = make_env(n, args.mesh, tmp)
+                if on:
+                    env.enable_outcome_stats()           # before the capture: the graph keeps the launch the switch selected
+                ctr = env.ll_env._sim.buf["step_counter"]
+                torch.manual_seed(1)
+                fused = [FusedActor(ActorCritic(no, no, na, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV), DEV, seed=seed, step_counter=ctr)
+                         for no, na, seed in ((3, 2, 1 + 7919 + 104729), (16, 4, 1 + 7919))]
+                envs.append(env)
+                steps.append(env.make_graphed_policy_step(*fused))
+                assert env.last_act_rc == 0
+            for fn in steps:
+                timed(fn, args.step_replays // 4)                # warm both graphs before the first timed window
+            t = [[], []]
+            for _ in range(args.repeats):
+                for i, fn in enumerate(steps):
+                    t[i].append(timed(fn, args.step_replays))
+            row = {f"{name}_policy_step": spread(x) for name, x in zip(names, t)}
+            row["outcome_minus_plain"] = spread([y - x for x, y in zip(t[0], t[1])])
+            for env in envs:
+                assert torch.isfinite(env.obs_buf_prey).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            totals = envs[1].outcome_totals()
+            assert totals["episodes"] > 0 and not any(k.startswith("outcome_") for k in envs[0].extras["episode"])
+            row["dec_high_level_game_outcome_totals"] = totals
+            result["envs"][str(n)] = row
+            print(f"{n} envs, graphed three-launch policy step: " + "; ".join(
+                f"{name} {statistics.median(x):.1f} us ({min(x):.1f} .. {max(x):.1f})" for name, x in zip(names, t)), flush=True)
+            d = row["outcome_minus_plain"]
+            print(f"  statistics on - off {d['median_us']:+.2f} us ({d['min_us']:+.2f} .. {d['max_us']:+.2f})", flush=True)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_outcome_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
+DEFAULT_OUT = os.path.join(REPO, "profiles", "dec_game_act.json")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--envs", type=int, nargs="+", default=[2000, 4096])
@@ -103,8 +195,14 @@ def main():
     ap.add_argument("--replays", type=int, default=2)
     ap.add_argument("--pairs", type=int, default=10)
     ap.add_argument("--discard", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "dec_game_act.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--outcome", action="store_true", help="time the graphed policy step with the outcome statistics off and on; writes profiles/dec_outcome_step.json")
+    ap.add_argument("--step-replays", type=int, default=2000, help="--outcome: replays of the captured step per timed window")
+    ap.add_argument("--repeats", type=int, default=5, help="--outcome: timed windows per variant, alternating")
+    ap.add_argument("--mesh", default="plane", help="--outcome: terrain of the low-level env (the registered task: plane)")
     args = ap.parse_args()
+    if args.outcome:
+        return outcome_main(args)
     out = {"device": torch.cuda.get_device_name(0), "graph_steps": args.graph_steps, "replays": args.replays, "pairs": args.pairs, "discarded_pairs": args.discard,
            "unit": "us per actor stage of one step", "role_order": "low-level, prey, predator (the other orders are not timed)",
            "envs": {str(n): measure(n, args.graph_steps, args.replays, args.pairs, args.discard) for n in args.envs}}
