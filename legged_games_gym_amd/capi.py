@@ -612,6 +612,76 @@ def dec_outcome_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, o
         raise RuntimeError(f"lg_dec_outcome_post failed ({rc}): {lib.lg_last_error().decode()}")
 
 
+# ----------------------------------------------------------------------------- decentralised game's opponent pool (include/legged_dec_game_pool.h)
+LG_DEC_POOL_MAX, LG_DEC_POOL_BLOCK_ENVS = 16, 32
+DEC_POOL_ROLES = {"prey": 1, "pred": 2}
+
+
+class lg_dec_pool_info(C.Structure):
+    """include/legged_dec_game_pool.h: lg_dec_pool_info (what ``lg_dec_pool_query`` reports)."""
+    _fields_ = [("count", i32), ("role", i32), ("device", i32), ("_pad", i32), ("table", C.c_void_p)]
+
+
+DEC_POOL_SYMBOLS = ["lg_dec_pool_create", "lg_dec_pool_destroy", "lg_dec_pool_query", "lg_dec_pool_act", "lg_dec_pool_sizeof"]
+
+
+def bind_dec_pool_prototypes(lib):
+    """Attach argtypes/restype for the entry points of legged_dec_game_pool.h and check the struct layout."""
+    vp = C.c_void_p
+    lib.lg_dec_pool_create.argtypes, lib.lg_dec_pool_create.restype = [C.POINTER(vp), i32, i32, i32, C.POINTER(vp)], C.c_int
+    lib.lg_dec_pool_destroy.argtypes, lib.lg_dec_pool_destroy.restype = [vp], C.c_int
+    lib.lg_dec_pool_query.argtypes, lib.lg_dec_pool_query.restype = [vp, C.POINTER(lg_dec_pool_info)], C.c_int
+    lib.lg_dec_pool_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), vp, vp, vp, vp, vp, vp, u64, u64, i64, vp,
+                                    i32, i32, C.POINTER(lg_dec_act_outputs), C.POINTER(lg_dec_act_outputs), vp]
+    lib.lg_dec_pool_act.restype = C.c_int
+    lib.lg_dec_pool_sizeof.argtypes, lib.lg_dec_pool_sizeof.restype = [C.c_int], C.c_int
+    if lib.lg_dec_pool_sizeof(0) != C.sizeof(lg_dec_pool_info):
+        raise RuntimeError(f"struct layout mismatch for lg_dec_pool_info: C {lib.lg_dec_pool_sizeof(0)} vs ctypes {C.sizeof(lg_dec_pool_info)}")
+    return lib
+
+
+def dec_pool_create(member_handles, role: str, device: int = 0) -> C.c_void_p:
+    """``lg_dec_pool_create`` over ``lg_policy`` handles (``FusedActor.handle``); ``role`` is "prey" or "pred".  The handles must outlive the
+    pool and must not be re-created (``FusedActor.sync`` does; ``sync_device`` repacks in place, which the pool follows)."""
+    lib = load_library()
+    handles = (C.c_void_p * len(member_handles))(*[h.value if isinstance(h, C.c_void_p) else h for h in member_handles])
+    out = C.c_void_p()
+    rc = lib.lg_dec_pool_create(handles, len(member_handles), DEC_POOL_ROLES[role], int(device), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_pool_create failed ({rc}): {lib.lg_last_error().decode()}")
+    return out
+
+
+def dec_pool_destroy(pool):
+    if pool:
+        load_library().lg_dec_pool_destroy(pool)
+
+
+def dec_pool_query(pool) -> lg_dec_pool_info:
+    lib, info = load_library(), lg_dec_pool_info()
+    rc = lib.lg_dec_pool_query(pool, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_pool_query failed ({rc}): {lib.lg_last_error().decode()}")
+    return info
+
+
+def dec_pool_act(pred_policy, prey_policy, ll_policy, pool_pred, block_slot_pred: Optional[int], pool_prey, block_slot_prey: Optional[int],
+                 params: lg_dec_game_params, buffers: lg_dec_game_buffers, pred_obs: int, prey_obs: int, ll_obs: int, ll_actions: int, mean_pred: int,
+                 mean_prey: int, seed_pred: int, seed_prey: int, step: int, step_counter: Optional[int], deterministic_pred: bool, deterministic_prey: bool,
+                 out_pred: Optional[lg_dec_act_outputs] = None, out_prey: Optional[lg_dec_act_outputs] = None, stream: int = 0) -> int:
+    """``lg_dec_pool_act``: ``lg_dec_game_act`` with the weights of a pooled role chosen per 32-env block.  ``pool_*``: a pool handle or None,
+    ``block_slot_*``: the device address of its int32 slot table.  Returns 0, or -4 when there is no shared kernel for the wide precision /
+    the shapes (the caller then issues ``lg_policy_act`` per member + ``lg_dec_game_pre``); raises on any other error."""
+    lib = load_library()
+    rc = lib.lg_dec_pool_act(pred_policy, prey_policy, ll_policy, pool_pred, block_slot_pred, pool_prey, block_slot_prey, C.byref(params), C.byref(buffers),
+                             pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey, int(seed_pred), int(seed_prey), int(step), step_counter,
+                             int(bool(deterministic_pred)), int(bool(deterministic_prey)), C.byref(out_pred) if out_pred is not None else None,
+                             C.byref(out_prey) if out_prey is not None else None, stream)
+    if rc not in (0, -4):
+        raise RuntimeError(f"lg_dec_pool_act failed ({rc}): {lib.lg_last_error().decode()}")
+    return rc
+
+
 def load_library():
     """Load the HIP extension or fail loudly -- never a CPU substitute."""
     global _lib
@@ -622,7 +692,7 @@ def load_library():
         raise RuntimeError(
             f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_dec_outcome_prototypes(bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_"))))))
+    _lib = bind_dec_pool_prototypes(bind_dec_outcome_prototypes(bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_")))))))
     if _lib.lg_abi_version() != LG_ABI_VERSION:
         raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
     return _lib

@@ -20,6 +20,9 @@ bit, and also counts inside the launch why the done envs' episodes ended.  ``ext
 ``outcome_*`` -- the shares of captures, game time-outs, falls and low-level time-outs among the done envs and their mean episode length --
 and ``outcome_totals()`` the running integer sums.  A step is still three launches and a rollout still one graph replay.
 
+``step_policy`` / ``make_graphed_policy_step`` take an ``rl.OpponentPool`` in place of either ``FusedActor``: the actor launch is then
+``lg_dec_pool_act`` (include/legged_dec_game_pool.h), the same launch with that role's weights chosen per 32-env block from the pool.
+
 ``agent_view(agent, opponent)`` gives one agent's single-agent surface (what ``rl.OnPolicyRunner`` drives) with the other agent acting
 inside every step.  Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G10 onward)."""
 import numpy as np
@@ -166,8 +169,14 @@ class DecHighLevelGame(GameBase):
         the prey's observations copied to ``obs_prey_out`` (where ``lg_dec_game_post`` then shifts the history in place) -- one launch.
         Separate launches when the actor triple or the wide precision has no shared kernel (rc -4).  ``out_*``: dicts of optional float32
         outputs ``sample`` / ``sigma`` / ``log_prob`` / ``obs_copy`` (the rollout storage's copy of the observations read).
+        ``fused_pred`` / ``fused_prey`` may each be an ``rl.OpponentPool`` instead of a ``FusedActor``: the launch is then ``lg_dec_pool_act``
+        (include/legged_dec_game_pool.h), which takes that role's weights, biases and std per 32-env block from the pool member its slot table
+        names; the pool's ``live`` actor supplies seed, step source and output buffers.  Its rc -4 path is one ``lg_policy_act`` on all envs
+        per member in use, rows selected by block.
         Returns ``(command_pred, mean_pred), (command_prey, mean_prey), ll_actions, buffers``."""
         ll, n = self.ll_env, self.num_envs
+        pool_pred, pool_prey = (f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey))
+        fused_pred, fused_prey = _live(fused_pred), _live(fused_prey)
         for name, t, width in (("predator", obs_pred_in, self.num_obs_pred), ("prey", obs_prey_in, self.num_obs_prey)):
             if t.shape != (n, width) or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError(f"{name} observations must be a contiguous float32 [{n},{width}] tensor")
@@ -201,10 +210,17 @@ class DecHighLevelGame(GameBase):
             raise ValueError("the two FusedActors must count their noise steps alike (both on the low-level sim's device step counter, or both on the host)")
         if fused_pred.seed == fused_prey.seed:
             raise ValueError("the two FusedActors need different seeds: they draw their noise under the same purposes")
-        rc = capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, obs_pred_in.data_ptr(), obs_prey_in.data_ptr(),
-                               ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed,
-                               step_y, ctr_y, deterministic_pred, deterministic_prey, outputs(out_pred, None),
-                               outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
+        if pool_pred is None and pool_prey is None:
+            rc = capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, obs_pred_in.data_ptr(), obs_prey_in.data_ptr(),
+                                   ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed,
+                                   step_y, ctr_y, deterministic_pred, deterministic_prey, outputs(out_pred, None),
+                                   outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
+        else:
+            pool_args = [a for pool in (pool_pred, pool_prey) for a in ((pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None))]
+            rc = capi.dec_pool_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *pool_args, self._P, B, obs_pred_in.data_ptr(),
+                                   obs_prey_in.data_ptr(), ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(),
+                                   fused_pred.seed, fused_prey.seed, step_y, ctr_y, deterministic_pred, deterministic_prey, outputs(out_pred, None),
+                                   outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
         self.last_act_rc = rc                                  # 0: the shared launch ran; -4: the separate launches below
         if rc == 0:
             fused_pred.next_step(); fused_prey.next_step()     # the launch used this step of both noise streams
@@ -212,12 +228,17 @@ class DecHighLevelGame(GameBase):
                 obs_prey_out.copy_(obs_prey_in)
             return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
         # rc -4, nothing was launched: lg_policy_act x 3 + lg_dec_game_pre (decided per call: lg_mlp_wide_set_precision may change between calls)
-        for fused, obs_in, det, out in ((fused_pred, obs_pred_in, deterministic_pred, out_pred), (fused_prey, obs_prey_in, deterministic_prey, out_prey)):
-            command, mean = fused.act_with_mean(obs_in, det)
+        for fused, pool, obs_in, det, out in ((fused_pred, pool_pred, obs_pred_in, deterministic_pred, out_pred),
+                                              (fused_prey, pool_prey, obs_prey_in, deterministic_prey, out_prey)):
+            if pool is None:
+                command, mean = fused.act_with_mean(obs_in, det)
+            else:
+                command, mean, std = pool.act_separate(obs_in, det)          # per member in use, rows by block; std [n, actions] of the rows' members
             if out.get("sample") is not None:
                 out["sample"].view(n, -1).copy_(command)
             if out.get("sigma") is not None or out.get("log_prob") is not None:
-                std = fused.ac.std.detach()
+                if pool is None:
+                    std = fused.ac.std.detach()
                 if out.get("sigma") is not None:
                     out["sigma"].view(n, -1).copy_(std.expand(n, -1))
                 if out.get("log_prob") is not None:
@@ -256,7 +277,7 @@ class DecHighLevelGame(GameBase):
         replays the graph; the actors' ``output_buffers(num_envs)`` then hold the commands and the means of the last step.
         ``deterministic_pred`` / ``deterministic_prey``: that agent's command is its clipped mean (evaluation)."""
         sim = self.ll_env._sim
-        for fused in (fused_pred, fused_prey):
+        for fused in (_live(fused_pred), _live(fused_prey)):
             if fused.step_counter is None or fused.step_counter.data_ptr() != sim.buf["step_counter"].data_ptr():
                 raise ValueError("make_graphed_policy_step needs FusedActors on the low-level sim's device step counter")
 
@@ -318,8 +339,8 @@ class DecHighLevelGame(GameBase):
         return self.privileged_obs_buf_prey
 
     def agent_view(self, agent, opponent):
-        """The single-agent surface of ``agent`` ("pred" or "prey") with ``opponent`` -- a ``FusedActor`` (device path) or a torch policy
-        ``obs -> sampled actions`` (generic path) -- acting for the other agent inside every step."""
+        """The single-agent surface of ``agent`` ("pred" or "prey") with ``opponent`` -- a ``FusedActor`` or an ``rl.OpponentPool`` (device path)
+        or a torch policy ``obs -> sampled actions`` (generic path) -- acting for the other agent inside every step."""
         return AgentView(self, agent, opponent)
 
     # ------------------------------------------------------------------ set-up
@@ -439,6 +460,11 @@ class DecHighLevelGame(GameBase):
                                           obs_pred=obs_pred.data_ptr(), obs_prey=obs_prey.data_ptr()))
 
 
+def _live(fused):
+    """The ``FusedActor`` that supplies seed, step source and output buffers: ``fused`` itself, or the live member of an ``rl.OpponentPool``."""
+    return fused.live if getattr(fused, "is_opponent_pool", False) else fused
+
+
 class AgentView:
     """One agent of a ``DecHighLevelGame`` as a single-agent env: the surface ``rl.OnPolicyRunner`` drives for ``high_level_game``
     (``step`` on the generic path, ``step_policy`` on the device path).  The opponent produces the other agent's command inside every step
@@ -528,7 +554,7 @@ class AgentView:
         return self._result(self.env.step(other, actions))
 
     def step_policy(self, fused, deterministic=False, sample=None, sigma=None, log_prob=None, obs_copy=None):
-        """Device path: ``opponent`` is a ``FusedActor``.  Returns ``(command, mean), (obs, None, rew, dones, extras)`` of this agent, the
+        """Device path: ``opponent`` is a ``FusedActor`` or an ``rl.OpponentPool`` (a mixture of opponents by 32-env block).  Returns ``(command, mean), (obs, None, rew, dones, extras)`` of this agent, the
         contract of ``HighLevelGame.step_policy``."""
         mine = {k: v for k, v in (("sample", sample), ("sigma", sigma), ("log_prob", log_prob), ("obs_copy", obs_copy)) if v is not None}
         if self.agent == "pred":

@@ -14,6 +14,7 @@ from .actor_critic import ActorCritic
 from .ppo import PPO, RolloutStorage
 from .runner import OnPolicyRunner
 from .dec_runner import DecGamePolicyRunner
+from .opponent_pool import OpponentPool, assign_blocks
 
 
 
@@ -23,4 +24,4 @@ def FusedActor(*args, **kwargs):
     return _F(*args, **kwargs)
 
 
-__all__ = ["ActorCritic", "PPO", "RolloutStorage", "OnPolicyRunner", "DecGamePolicyRunner", "FusedActor"]
+__all__ = ["ActorCritic", "PPO", "RolloutStorage", "OnPolicyRunner", "DecGamePolicyRunner", "FusedActor", "OpponentPool", "assign_blocks"]

@@ -7,7 +7,16 @@ storage -- the learner kernels and the device rollout come with them.  Evolution
 odd (the argument order of the reference's ``step``) for ``num_learning_iterations`` PPO iterations; the other agent acts with its current
 policy, sampling, and is not updated.  The combined ``model_<it>.pt`` and ``progress.csv`` follow the training agent's runner (``runner.save_interval``,
 every logged iteration).  ``OnPolicyRunner.learn`` captures its rollout graph when it is called, i.e. at the start of every
-evolution, so a graph never outlives an update of the opponent it replays; the opponent's ``FusedActor`` is repacked in place besides."""
+evolution, so a graph never outlives an update of the opponent it replays; the opponent's ``FusedActor`` is repacked in place besides.
+
+Opponent pool (runner keys ``opponent_pool_size``, default 0 = off, and ``opponent_latest_share``, default 0.5; read with ``.get()``, no
+fields of the config classes; device path only).  Alternating best responses can go round in circles, so the opponent of the learning agent
+may be a mixture: every agent X has an ``OpponentPool`` around its ``FusedActor``, and the OTHER agent's view plays against it -- the live X
+in the share ``opponent_latest_share`` of the 32-env blocks, up to ``opponent_pool_size`` frozen earlier versions of X in the rest.  At the
+START of an evolution that trains X, X's current weights are pushed into X's pool, so the pool holds strictly earlier versions than its
+live member; the pool the training view plays against is then re-assigned (which block meets which member) with a generator seeded from
+``(seed, evolution)`` before ``runner.learn`` captures its graph.  The opponent samples, pooled or not, and the outcome statistics stay
+pooled over all opponents."""
 import os
 import re
 
@@ -36,6 +45,25 @@ class DecGamePolicyRunner:
                 self.runners[a]._fused, self.runners[a]._game_rollout = None, False
                 self.views[a].opponent = self._sampling_policy(other)
         self.device_path = device_path
+        self.pool_size = int(self.cfg.get("opponent_pool_size", 0) or 0)
+        self.latest_share = float(self.cfg.get("opponent_latest_share", 0.5))
+        self.seed = int(train_cfg.get("seed", 1) or 0)
+        self.pools = {}
+        if self.pool_size > 0:
+            if not device_path:
+                raise ValueError("opponent_pool_size > 0 needs device_rollout (runner key / --device_rollout): the pool is one actor launch with the weights "
+                                 "chosen per 32-env block, which only the device path has")
+            from .opponent_pool import OpponentPool
+            from .actor_critic import ActorCritic
+            for a in AGENTS:
+                view, policy_cfg = self.views[a], self.runners[a].policy_cfg
+
+                def make_actor_critic(view=view, policy_cfg=policy_cfg):      # the private module of one snapshot member: the shapes of the agent's own
+                    return ActorCritic(view.num_obs, view.num_obs, view.num_actions, **policy_cfg).to(device)
+                self.pools[a] = OpponentPool(fused[a], make_actor_critic, self.pool_size, a, seed=self.seed, latest_share=self.latest_share,
+                                             num_envs=env.num_envs)
+            for a in AGENTS:                              # a view's opponent: the pool of the OTHER agent's versions
+                self.views[a].opponent = self.pools["prey" if a == "pred" else "pred"]
         self.current_evolution = 0
         if log_dir is not None:
             for a in AGENTS:
@@ -83,6 +111,10 @@ class DecGamePolicyRunner:
         for e in range(self.current_evolution, self.current_evolution + max_num_evolutions):
             agent = self.agent_of(e)
             runner = self.runners[agent]
+            if self.pools:
+                other = "prey" if agent == "pred" else "pred"
+                self.pools[agent].push(runner.alg.actor_critic.state_dict())      # at the START: the pool holds strictly earlier versions than its live member
+                self.pools[other].assign(torch.Generator().manual_seed((self.seed * 1000003 + e) & 0x7FFFFFFFFFFFFFFF))      # before learn captures its graph
             runner.learn(num_learning_iterations=num_learning_iterations, init_at_random_ep_len=False)
             if runner._fused is not None:
                 runner._fused.sync_device()                # the other view's opponent: this agent's new weights, repacked in place
@@ -111,8 +143,10 @@ class DecGamePolicyRunner:
         iters = iters or {}
         os.makedirs(os.path.dirname(path), exist_ok=True)
         halves = {a: self._half(a, iters.get(a)) for a in AGENTS}
-        torch.save({"pred": halves["pred"], "prey": halves["prey"], "evolution": self.current_evolution,
-                    "iter": halves["pred"]["iter"] + halves["prey"]["iter"]}, path)
+        d = {"pred": halves["pred"], "prey": halves["prey"], "evolution": self.current_evolution, "iter": halves["pred"]["iter"] + halves["prey"]["iter"]}
+        if self.pools:                                     # the snapshots, so that a resumed run meets the same mixture
+            d["pool"] = {a: self.pools[a].state() for a in AGENTS}
+        torch.save(d, path)
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device, weights_only=True)
@@ -127,6 +161,9 @@ class DecGamePolicyRunner:
                 r._fused.sync_device()
             r.current_learning_iteration = half["iter"]
         self.current_evolution = d["evolution"]
+        if self.pools and "pool" in d:                     # checkpoints without it load as before: the pools start empty
+            for a in AGENTS:
+                self.pools[a].load_state(d["pool"][a])
         return None
 
     def get_inference_policy(self, agent, device=None):

@@ -50,6 +50,7 @@ class FusedActor:
         rc = self.lib.lg_policy_create(dims, wp, bp, std.ctypes.data_as(PF), self.device.index or 0, C.byref(self.handle))
         if rc != 0:
             raise RuntimeError(f"lg_policy_create failed ({rc}): {self.lib.lg_last_error().decode()}")
+        self.creations = getattr(self, "creations", 0) + 1      # how often the handle was (re-)created: what holds its device addresses (rl.OpponentPool) compares it
         self.num_actions = lin[3].out_features
 
     def sync_device(self):

@@ -1,0 +1,165 @@
+"""``OpponentPool``: the opponent of a learning agent of ``dec_high_level_game`` as a mixture -- the live opponent in part of the envs, frozen
+earlier versions of it in the rest -- in ONE actor launch (``lg_dec_pool_act``, include/legged_dec_game_pool.h).
+
+A role's workgroup of the shared actor launch serves 32 envs, so the unit of the mixture is the 32-env block: a device table names, for every
+block, the pool member whose weights, biases and std the block's workgroup streams.  Member 0 is the live opponent's ``FusedActor`` (its
+weights keep following ``sync_device()``); members 1 .. ``capacity`` are ``FusedActor`` s over private ``ActorCritic`` copies, created once, so
+the C-side table of operand addresses never changes: ``push`` loads a snapshot into the next ring slot IN PLACE, and ``assign`` rewrites the
+slot table IN PLACE -- both are visible underneath a captured graph at its next replay.
+
+``DecHighLevelGame.step_policy`` / ``make_graphed_policy_step`` and ``AgentView.step_policy`` accept a pool wherever they accept a
+``FusedActor`` opponent; the pool's ``live`` actor supplies the noise seed, the step source and the output buffers."""
+import torch
+
+from .. import capi
+
+BLOCK = capi.LG_DEC_POOL_BLOCK_ENVS
+
+
+def assign_blocks(num_blocks, filled, latest_share, generator):
+    """The slot of every 32-env block, an int32 CPU tensor ``[num_blocks]`` with values in ``0 .. filled``: 0 is the live member, ``s >= 1``
+    snapshot ``s``.  ``latest_share == 0`` gives no live block, otherwise ``max(1, round(latest_share * num_blocks))`` blocks are live; which
+    ones is a permutation drawn from ``generator``, and the remaining blocks are dealt round-robin over the ``filled`` snapshots in the
+    permuted order, so the snapshots' counts differ by at most one.  With ``filled == 0`` every block is live.  By block and at random, not by
+    env range: terrain types are contiguous in env index, and a contiguous split would confound opponent with terrain."""
+    if num_blocks < 1 or filled < 0 or not 0.0 <= latest_share <= 1.0:
+        raise ValueError(f"assign_blocks: num_blocks >= 1, filled >= 0 and 0 <= latest_share <= 1, got {(num_blocks, filled, latest_share)}")
+    slots = torch.zeros(num_blocks, dtype=torch.int32)
+    if filled == 0:
+        return slots
+    perm = torch.randperm(num_blocks, generator=generator)
+    live = 0 if latest_share == 0 else min(num_blocks, max(1, round(latest_share * num_blocks)))
+    rest = perm[live:]
+    slots[rest] = 1 + (torch.arange(len(rest), dtype=torch.int32) % filled)
+    return slots
+
+
+class OpponentPool:
+    is_opponent_pool = True
+
+    def __init__(self, live, make_actor_critic, capacity, role, seed=0, latest_share=0.5, num_envs=None):
+        """``live``: the opponent's current ``FusedActor``.  ``make_actor_critic``: zero-argument factory of an ``ActorCritic`` of the live one's
+        shape on its device (one private copy per snapshot member).  ``role``: "prey" or "pred", the role the pool's members play.  ``seed``
+        seeds ``assign()`` when it is called without a generator.  ``num_envs`` sizes the slot table (otherwise the first use does)."""
+        if role not in capi.DEC_POOL_ROLES:
+            raise ValueError(f"role must be one of {tuple(capi.DEC_POOL_ROLES)}, got {role!r}")
+        if not 1 <= int(capacity) <= capi.LG_DEC_POOL_MAX - 1:
+            raise ValueError(f"capacity must be 1 .. {capi.LG_DEC_POOL_MAX - 1} (LG_DEC_POOL_MAX - 1: member 0 is the live actor), got {capacity}")
+        from .fused_actor import FusedActor
+        self._pool = None
+        self.live, self.role, self.capacity, self.seed, self.latest_share = live, role, int(capacity), int(seed), float(latest_share)
+        self.device = live.device
+        self.members = [live]
+        for _ in range(self.capacity):
+            ac = make_actor_critic()
+            ac.load_state_dict(live.ac.state_dict())              # never assigned before its first push; a stale table still meets a sane actor
+            self.members.append(FusedActor(ac, self.device, seed=live.seed, step_counter=live.step_counter))
+        self.filled, self._next = 0, 0                           # snapshots written; ring position of the next push (member 1 + _next)
+        self._creations = [m.creations for m in self.members]
+        self._pool = capi.dec_pool_create([m.handle.value for m in self.members], role, self.device.index or 0)
+        self._slots = self._slots_host = self._scratch = None
+        self._assignments = 0
+        if num_envs is not None:
+            self.slot_table(num_envs)
+
+    # ------------------------------------------------------------------ what the env reads
+    @property
+    def handle(self):
+        """The ``lg_dec_pool`` handle.  Its table holds the members' operand addresses as they were at construction: a member whose
+        ``lg_policy`` was re-created (``FusedActor.sync()``; ``sync_device()`` repacks in place) would leave it dangling."""
+        if [m.creations for m in self.members] != self._creations:       # (not the handles' values: a re-created handle may get the old address)
+            raise RuntimeError("a member's lg_policy handle was re-created (FusedActor.sync()); a pool's members are updated with sync_device() only")
+        return self._pool
+
+    def slot_table(self, num_envs):
+        """The device int32 table ``[ceil(num_envs / 32)]`` the launch reads (all live until ``assign`` / ``set_slots``)."""
+        blocks = (int(num_envs) + BLOCK - 1) // BLOCK
+        if self._slots is None:
+            self._slots = torch.zeros(blocks, dtype=torch.int32, device=self.device)
+            self._slots_host = torch.zeros(blocks, dtype=torch.int32)
+        elif self._slots.shape[0] != blocks:
+            raise ValueError(f"the pool's slot table serves {self._slots.shape[0]} blocks, not the {blocks} of {num_envs} envs")
+        return self._slots
+
+    def set_slots(self, slots):
+        """Rewrite the slot table in place (same address: a captured graph reads the new table at its next replay)."""
+        slots = torch.as_tensor(slots, dtype=torch.int32).cpu().contiguous()
+        if self._slots is None:
+            self._slots = torch.zeros(len(slots), dtype=torch.int32, device=self.device)
+        if slots.shape != self._slots.shape:
+            raise ValueError(f"the pool's slot table has {self._slots.shape[0]} blocks, got {tuple(slots.shape)}")
+        self._slots_host = slots.clone()
+        self._slots.copy_(slots)
+
+    def assign(self, generator=None):
+        """Draw a new assignment of blocks to members (``assign_blocks``) and write it to the device table.  Returns the CPU table."""
+        if self._slots is None:
+            raise RuntimeError("the slot table has no size yet: construct the pool with num_envs or call slot_table(num_envs) first")
+        if generator is None:
+            generator = torch.Generator().manual_seed(self.seed + self._assignments)
+        self._assignments += 1
+        slots = assign_blocks(self._slots.shape[0], self.filled, self.latest_share, generator)
+        self.set_slots(slots)
+        return slots
+
+    # ------------------------------------------------------------------ snapshots
+    def push(self, state_dict):
+        """Load ``state_dict`` (of the live actor's ``ActorCritic``) into the next ring slot, the oldest snapshot overwritten, and repack that
+        member on the device -- in place, so it is visible underneath a captured graph.  Returns the member's index."""
+        index = 1 + self._next
+        member = self.members[index]
+        member.ac.load_state_dict(state_dict)
+        member.sync_device()
+        self._next = (self._next + 1) % self.capacity
+        self.filled = min(self.filled + 1, self.capacity)
+        return index
+
+    def state(self):
+        """For checkpoints: the snapshots' state dicts (clones), ``filled`` and the ring position."""
+        return {"filled": self.filled, "next": self._next,
+                "snapshots": [{k: v.detach().clone() for k, v in m.ac.state_dict().items()} for m in self.members[1:]]}
+
+    def load_state(self, d):
+        snapshots = d["snapshots"]
+        if len(snapshots) != self.capacity:
+            raise ValueError(f"the checkpoint's pool has {len(snapshots)} snapshot members, this pool {self.capacity}")
+        for member, sd in zip(self.members[1:], snapshots):
+            member.ac.load_state_dict(sd)
+            member.sync_device()
+        self.filled, self._next = int(d["filled"]), int(d["next"])
+
+    # ------------------------------------------------------------------ separate launches (no shared kernel: wide precision 0)
+    def act_separate(self, obs, deterministic):
+        """What the pooled launch computes for this role without it: for every member in use one ``lg_policy_act`` on ALL envs with the live
+        actor's seed and this step, rows selected by the block mask.  Returns ``(sample, mean, std)``: the first two in the live actor's
+        output buffers, ``std`` [n, actions] the rows' members' std.  Counts one step of the live actor's noise stream."""
+        live, n = self.live, obs.shape[0]
+        lib = live.lib
+        actions, mean = live.output_buffers(n)
+        if self._scratch is None or self._scratch[0].shape != actions.shape:
+            self._scratch = (torch.empty_like(actions), torch.empty_like(mean))
+        a, mu = self._scratch
+        self.slot_table(n)
+        host = self._slots_host.clamp(0, self.capacity)                     # the kernel's clamp to [0, count)
+        env_slot = self._slots.clamp(0, self.capacity).long().repeat_interleave(BLOCK)[:n].unsqueeze(1)
+        step, ctr = live.next_step()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        std = torch.empty_like(actions)
+        for k, s in enumerate(sorted(set(host.tolist()))):
+            member = self.members[s]
+            rc = lib.lg_policy_act(member.handle, obs.data_ptr(), a.data_ptr(), mu.data_ptr(), n, live.seed, step, ctr, int(bool(deterministic)), stream)
+            if rc != 0:
+                raise RuntimeError(f"lg_policy_act failed ({rc}): {lib.lg_last_error().decode()}")
+            rows = env_slot == s
+            member_std = member.ac.std.detach().expand(n, -1)
+            if k == 0:
+                actions.copy_(a); mean.copy_(mu); std.copy_(member_std)
+            else:
+                actions.copy_(torch.where(rows, a, actions)); mean.copy_(torch.where(rows, mu, mean)); std.copy_(torch.where(rows, member_std, std))
+        return actions, mean, std
+
+    def __del__(self):
+        try:
+            capi.dec_pool_destroy(self._pool)
+        except Exception:
+            pass

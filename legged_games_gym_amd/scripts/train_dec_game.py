@@ -5,7 +5,10 @@ Predator and prey are trained in alternating evolutions (``rl.DecGamePolicyRunne
 ``--max_iterations`` PPO iterations each (defaults: the registered train cfg's ``runner.max_evolutions`` / ``runner.max_iterations``).
 ``--device_rollout`` trains on the device path: both agents' actors on the matrix cores, three launches per step, every rollout one graph
 replay (off by default: the generic VecEnv loop).  ``--outcome_stats`` (either path) logs who wins: the shares of captures, game time-outs,
-falls and low-level time-outs among the finished episodes and their mean length, as ``Episode/outcome_*`` of both agents' tables.  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
+falls and low-level time-outs among the finished episodes and their mean length, as ``Episode/outcome_*`` of both agents' tables.
+``--opponent_pool K [--opponent_latest_share F]`` (device path only) lets the opponent of the learning agent be a mixture: the live opponent
+in the share F (default 0.5) of the 32-env blocks, up to K frozen earlier versions of it in the rest (``rl.OpponentPool``, DESIGN.md G19);
+the checkpoints then carry the pools.  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
 from legged_games_gym_amd.envs import a1_game
 from legged_games_gym_amd.utils import get_args
@@ -20,6 +23,9 @@ def train(args):
     a1_game.register_dec()
     if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
         task_registry.get_cfgs(args.task)[1].runner.device_rollout = True
+    if args.opponent_pool:                   # runner keys, read with .get() as well
+        runner_cfg = task_registry.get_cfgs(args.task)[1].runner
+        runner_cfg.opponent_pool_size, runner_cfg.opponent_latest_share = args.opponent_pool, args.opponent_latest_share
     if args.outcome_stats:                   # read with getattr() by the env: no field of the registered config classes
         task_registry.get_cfgs(args.task)[0].env.outcome_stats = True
     env, env_cfg = task_registry.make_env(name=args.task, args=args)

@@ -173,6 +173,11 @@ def get_args(argv=None):
                    help="the game tasks (dec_high_level_game: scripts/train_dec_game.py): count inside the post-step launch why episodes end (captured, left the arena, fell, "
                         "survived) and log the rates as Episode/outcome_*; the scripts set env.outcome_stats on the registration they use")
     p.add_argument("--max_evolutions", type=int, help="dec_high_level_game: how often predator and prey alternate (scripts/train_dec_game.py)")
+    p.add_argument("--opponent_pool", type=int, default=0,
+                   help="dec_high_level_game with --device_rollout: train each agent against a pool of this many frozen earlier versions of its opponent "
+                        "besides the live one (runner key opponent_pool_size; 0 = off, at most 15)")
+    p.add_argument("--opponent_latest_share", type=float, default=0.5,
+                   help="with --opponent_pool: the share of the 32-env blocks that meet the live opponent (runner key opponent_latest_share)")
     # flags gymutil.parse_arguments contributes
     p.add_argument("--sim_device", type=str, default="cuda:0")
     p.add_argument("--pipeline", type=str, default="gpu")

@@ -14,7 +14,14 @@ three-launch policy step (lg_dec_game_act, k_step, then k_dec_post against k_dec
 variant and of the difference on - off repeat by repeat -> profiles/dec_outcome_step.json.  The low-level policy is a seeded random-init
 checkpoint written to a temporary directory: the kernels' cost does not depend on the weights.
 
-    python tools/dec_game_probe.py --outcome [--envs 2000 4096] [--step-replays 2000] [--repeats 5]"""
+    python tools/dec_game_probe.py --outcome [--envs 2000 4096] [--step-replays 2000] [--repeats 5]
+
+``--pool`` times the actor stage with an opponent pool on the prey role (``lg_dec_pool_act``, include/legged_dec_game_pool.h) against the
+plain ``lg_dec_game_act``, the way the default mode times its two variants: graphs of ``--graph-steps`` stages, replayed in alternating
+rounds in one process.  Variants: the plain launch, and the pooled launch with 1, 4 and 8 members (``--members``), the 32-env blocks dealt
+round-robin over the members, so that M weight sets are in flight at once -> profiles/dec_pool_act.json.
+
+    python tools/dec_game_probe.py --pool [--envs 2000 4096] [--members 1 4 8]"""
 import argparse
 import json
 import os
@@ -103,6 +110,88 @@ def measure(n, graph_steps, replays, pairs, discard):
             if pair >= discard:
                 times[name].append(a.elapsed_time(b) * 1000.0 / (replays * graph_steps))
     return {k: {"median_us": sorted(v)[len(v) // 2], "min_us": min(v), "max_us": max(v), "repeats_us": v} for k, v in times.items()}
+
+
+def alternate(graphs, replays, graph_steps, pairs, discard):
+    """Replay the graphs in alternating rounds; microseconds per captured stage, the first ``discard`` rounds dropped."""
+    times = {k: [] for k in graphs}
+    for pair in range(pairs + discard):
+        for name, g in graphs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(replays):
+                g.replay()
+            b.record()
+            torch.cuda.synchronize()
+            if pair >= discard:
+                times[name].append(a.elapsed_time(b) * 1000.0 / (replays * graph_steps))
+    return {k: {"median_us": sorted(v)[len(v) // 2], "min_us": min(v), "max_us": max(v), "repeats_us": v} for k, v in times.items()}
+
+
+def measure_pool(n, members, graph_steps, replays, pairs, discard):
+    """The plain launch and the pooled launch with M members on the prey role, M in ``members``: blocks round-robin over the members."""
+    pred, ll = actor(3, 2, 5), actor(235, 12, 4)
+    preys = [actor(16, 4, 100 + k) for k in range(max(members))]
+    z = lambda *s: torch.zeros(*s, device=DEV)
+    prey_obs, pred_obs, ll_obs = torch.randn(n, 16, device=DEV), torch.randn(n, 3, device=DEV), torch.randn(n, 235, device=DEV)
+    cy, cp, llc, act, my, mp = z(n, 4), z(n, 2), z(n, 4), z(n, 12), z(n, 4), z(n, 2)
+    P = params(n)
+    B = capi.dec_game_buffers({"command_prey": cy.data_ptr(), "command_pred": cp.data_ptr(), "ll_commands": llc.data_ptr()})
+    counter = torch.zeros(1, dtype=torch.int64, device=DEV)
+    seed_prey, seed_pred = 1 + 7919, 1 + 7919 + 104729
+    blocks = (n + capi.LG_DEC_POOL_BLOCK_ENVS - 1) // capi.LG_DEC_POOL_BLOCK_ENVS
+    pools = {m: (capi.dec_pool_create([a.handle for a in preys[:m]], "prey"), (torch.arange(blocks) % m).int().to(DEV)) for m in members}
+
+    def plain():
+        st = torch.cuda.current_stream().cuda_stream
+        if capi.dec_game_act(pred.handle, preys[0].handle, ll.handle, P, B, pred_obs.data_ptr(), prey_obs.data_ptr(), ll_obs.data_ptr(), act.data_ptr(),
+                             mp.data_ptr(), my.data_ptr(), seed_pred, seed_prey, -1, counter.data_ptr(), False, False, None, None, st) != 0:
+            raise RuntimeError("lg_dec_game_act refused the actor triple (rc -4)")
+
+    def pooled(m):
+        pool, slots = pools[m]
+
+        def launch():
+            st = torch.cuda.current_stream().cuda_stream
+            if capi.dec_pool_act(pred.handle, None, ll.handle, None, None, pool, slots.data_ptr(), P, B, pred_obs.data_ptr(), prey_obs.data_ptr(),
+                                 ll_obs.data_ptr(), act.data_ptr(), mp.data_ptr(), my.data_ptr(), seed_pred, seed_prey, -1, counter.data_ptr(), False, False,
+                                 None, None, st) != 0:
+                raise RuntimeError("lg_dec_pool_act refused the launch (rc -4)")
+        return launch
+
+    graphs = {}
+    for name, fn in [("lg_dec_game_act", plain)] + [(f"lg_dec_pool_act_{m}_members", pooled(m)) for m in members]:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(5):
+                fn()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(graph_steps):
+                fn()
+        graphs[name] = g
+    result = alternate(graphs, replays, graph_steps, pairs, discard)
+    torch.cuda.synchronize()
+    assert torch.isfinite(cy).all() and torch.isfinite(cp).all() and torch.isfinite(act).all()
+    del graphs
+    for pool, _ in pools.values():
+        capi.dec_pool_destroy(pool)
+    return result
+
+
+def pool_main(args):
+    out = {"device": torch.cuda.get_device_name(0), "graph_steps": args.graph_steps, "replays": args.replays, "pairs": args.pairs, "discarded_pairs": args.discard,
+           "unit": "us per actor stage of one step", "pooled_role": "prey", "assignment": "block b -> member b % M",
+           "envs": {str(n): measure_pool(n, args.members, args.graph_steps, args.replays, args.pairs, args.discard) for n in args.envs}}
+    path = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_pool_act.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as fh:
+        json.dump(out, fh, indent=1)
+    for n, r in out["envs"].items():
+        print(f"{n} envs: " + "; ".join(f"{k} {v['median_us']:.1f} us ({v['min_us']:.1f} .. {v['max_us']:.1f})" for k, v in r.items()), flush=True)
+    print("wrote", path)
 
 
 def make_env(n, mesh, tmp):
@@ -200,9 +289,13 @@ def main():
     ap.add_argument("--step-replays", type=int, default=2000, help="--outcome: replays of the captured step per timed window")
     ap.add_argument("--repeats", type=int, default=5, help="--outcome: timed windows per variant, alternating")
     ap.add_argument("--mesh", default="plane", help="--outcome: terrain of the low-level env (the registered task: plane)")
+    ap.add_argument("--pool", action="store_true", help="time lg_dec_pool_act with --members members on the prey role against lg_dec_game_act; writes profiles/dec_pool_act.json")
+    ap.add_argument("--members", type=int, nargs="+", default=[1, 4, 8], help="--pool: pool sizes to time")
     args = ap.parse_args()
     if args.outcome:
         return outcome_main(args)
+    if args.pool:
+        return pool_main(args)
     out = {"device": torch.cuda.get_device_name(0), "graph_steps": args.graph_steps, "replays": args.replays, "pairs": args.pairs, "discarded_pairs": args.discard,
            "unit": "us per actor stage of one step", "role_order": "low-level, prey, predator (the other orders are not timed)",
            "envs": {str(n): measure(n, args.graph_steps, args.replays, args.pairs, args.discard) for n in args.envs}}
