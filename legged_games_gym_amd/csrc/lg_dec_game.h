@@ -36,6 +36,27 @@ int lg_dec_game_post(const lg_dec_game_params *P, const lg_dec_game_buffers *B, 
     return 0;
 }
 
+// The arguments of k_dec_act, which k_pool_act takes too (lg_dec_game_pool_entry.h); the callers have checked the handles and the buffers.
+// A null outputs struct asks for none of the optional outputs.
+static void fill_dec_act_args(lg::DecActArgs &g, const lg_policy *pred, const lg_policy *prey, const lg_policy *ll, const lg_dec_game_params *P,
+                              const lg_dec_game_buffers *B, const float *pred_obs, const float *prey_obs, const float *ll_obs, float *ll_actions,
+                              float *mean_pred, float *mean_prey, uint64_t seed_pred, uint64_t seed_prey, int64_t step, const int64_t *step_counter,
+                              int32_t deterministic_pred, int32_t deterministic_prey, const lg_dec_act_outputs *out_pred, const lg_dec_act_outputs *out_prey) {
+    const lg_dec_act_outputs none = {nullptr, nullptr, nullptr, nullptr};
+    const lg_dec_act_outputs &op = out_pred ? *out_pred : none, &oy = out_prey ? *out_prey : none;
+    fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed_prey, step, step_counter, 1);
+    fill_policy_args(prey, g.prey.base, prey_obs, oy.sample, mean_prey, P->num_envs, seed_prey, step, step_counter, deterministic_prey);
+    fill_policy_args(pred, g.pred.base, pred_obs, op.sample, mean_pred, P->num_envs, seed_pred, step, step_counter, deterministic_pred);
+    fill_wide_operands(ll, g.ll.wb, g.ll.bb);
+    fill_wide_operands(prey, g.prey.wb, g.prey.bb);
+    fill_wide_operands(pred, g.pred.wb, g.pred.bb);
+    g.P = *P;
+    g.a_prey = {B->command_prey, oy.sigma, oy.log_prob, oy.obs_copy};
+    g.a_pred = {B->command_pred, op.sigma, op.log_prob, op.obs_copy};
+    g.ll_commands = B->ll_commands;
+    g.blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;
+}
+
 int lg_dec_game_act(lg_policy *pred, lg_policy *prey, lg_policy *ll, const lg_dec_game_params *P, const lg_dec_game_buffers *B, const float *pred_obs,
                     const float *prey_obs, const float *ll_obs, float *ll_actions, float *mean_pred, float *mean_prey, uint64_t seed_pred, uint64_t seed_prey,
                     int64_t step, const int64_t *step_counter, int32_t deterministic_pred, int32_t deterministic_prey, const lg_dec_act_outputs *out_pred,
@@ -49,22 +70,9 @@ int lg_dec_game_act(lg_policy *pred, lg_policy *prey, lg_policy *ll, const lg_de
     if (g_wide_precision != 1 || !prey_ok || !pred_ok || !ll_ok)
         return fail(-4, "the shared actor launch is compiled for the 3-512-256-128-2 / 16-512-256-128-4 / 235-512-256-128 triple at wide precision 1; use lg_policy_act x 3 + lg_dec_game_pre");
     if (seed_pred == seed_prey) return fail(-2, "lg_dec_game_act: seed_pred and seed_prey must differ (the sampled roles share their noise purposes)");
-    const lg_dec_act_outputs none = {nullptr, nullptr, nullptr, nullptr};
-    const lg_dec_act_outputs &op = out_pred ? *out_pred : none, &oy = out_prey ? *out_prey : none;
     lg::DecActArgs g;
-    fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed_prey, step, step_counter, 1);
-    fill_policy_args(prey, g.prey.base, prey_obs, oy.sample, mean_prey, P->num_envs, seed_prey, step, step_counter, deterministic_prey);
-    fill_policy_args(pred, g.pred.base, pred_obs, op.sample, mean_pred, P->num_envs, seed_pred, step, step_counter, deterministic_pred);
-    for (int i = 0; i < 4; i++) {
-        g.ll.wb[i] = reinterpret_cast<const lg::bf16x8g *>(ll->d_wb[i]); g.ll.bb[i] = ll->d_bb[i];
-        g.prey.wb[i] = reinterpret_cast<const lg::bf16x8g *>(prey->d_wb[i]); g.prey.bb[i] = prey->d_bb[i];
-        g.pred.wb[i] = reinterpret_cast<const lg::bf16x8g *>(pred->d_wb[i]); g.pred.bb[i] = pred->d_bb[i];
-    }
-    g.P = *P;
-    g.a_prey = {B->command_prey, oy.sigma, oy.log_prob, oy.obs_copy};
-    g.a_pred = {B->command_pred, op.sigma, op.log_prob, op.obs_copy};
-    g.ll_commands = B->ll_commands;
-    g.blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;
+    fill_dec_act_args(g, pred, prey, ll, P, B, pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey, seed_pred, seed_prey, step, step_counter,
+                      deterministic_pred, deterministic_prey, out_pred, out_prey);
     HIP_TRY((hipError_t)lg::launch_dec_act(g, stream));
     return 0;
 }

@@ -14,7 +14,7 @@
 #include "lg_policy.h"
 #include "lg_dec_game_post.h"  // dec_post_env<OUTCOME>: one env of the post stage (shared with lg_dec_game_outcome.hip)
 #include "lg_dec_game_common.h"
-#include "lg_dec_game_act.h"   // dec_actor_role<K0S, ROLE>: one role of the shared actor launch (shared with lg_pool_act.hip)
+#include "lg_dec_game_act.h"   // dec_actor_role<ROLE>: one role of the shared actor launch (shared with lg_pool_act.hip)
 
 namespace lg {
 
@@ -102,9 +102,9 @@ int launch_policy_act_wide_one_tile(const PolicyWideArgs &W, void *stream) {
 __global__ void __launch_bounds__(64 * LG_PW_WAVES) k_dec_act(const DecActArgs G) {
     __shared__ bf16x8g xa[16][2][64], xb[32][2][64];               // as k_policy_act_wide: obs / x2 in xa, x1 / x3 in xb (96 KB), the same for all roles
     const int role = (int)blockIdx.x / G.blocks, blk = (int)blockIdx.x - role * G.blocks;      // every role has `blocks` workgroups, the low-level role the first
-    if (role == 0) dec_actor_role<15, 0>(G.ll, G, blk, xa, xb);
-    else if (role == 1) dec_actor_role<1, 1>(G.prey, G, blk, xa, xb);
-    else dec_actor_role<1, 2>(G.pred, G, blk, xa, xb);
+    if (role == 0) dec_actor_role<0>(G.ll, G, blk, xa, xb);
+    else if (role == 1) dec_actor_role<1>(G.prey, G, blk, xa, xb);
+    else dec_actor_role<2>(G.pred, G, blk, xa, xb);
 }
 
 int launch_dec_act(const DecActArgs &G, void *stream) {

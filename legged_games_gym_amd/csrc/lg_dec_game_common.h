@@ -19,8 +19,9 @@ int launch_policy_act_wide_one_tile(const PolicyWideArgs &W, void *stream);
 // As k_prey_act (lg_game_common.h): the low-level policy reads the observation the previous low-level step left, and the two agents read
 // their own observation buffers, so nothing in one actor depends on another inside a step.  Workgroups are split by role: the low-level
 // role (235 inputs, deterministic) on the first `blocks` workgroups, then the prey role (16 inputs, sampled), then the predator role
-// (3 inputs, sampled).  A role is the body of k_policy_act_wide with the role-local workgroup index and its own seed: every MFMA sees the
-// operands of the stand-alone launch in the same order.  Each sampled role's wave-0 epilogue does its agent's half of k_dec_pre in registers.
+// (3 inputs, sampled).  A role is a call of wide_actor_body (lg_policy.h), as k_policy_act_wide is, with the role-local workgroup index and
+// its own seed: every MFMA sees the operands of the stand-alone launch in the same order.  Each sampled role's wave-0 epilogue does its
+// agent's half of k_dec_pre in registers.
 struct DecActAgent {
     float *command;                        // [N, actions] clipped (/ wrapped) command: what k_dec_pre leaves in the caller's tensor
     float *sigma, *log_prob, *obs_copy;    // optional: [N, actions] broadcast std, [N] log N(sample; mean, std) summed over the actions, [N, obs] the observations read

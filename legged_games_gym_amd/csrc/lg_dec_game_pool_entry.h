@@ -1,6 +1,6 @@
 // lg_dec_game_pool_entry.h -- C entry points of the decentralised game's opponent pool (include/legged_dec_game_pool.h).  Host code only:
 // the kernel lives in lg_pool_act.hip behind launch_pool_act (lg_pool_act.h).  Included from lg_kernels.hip after lg_dec_game.h
-// (dec_game_check) and the fused-actor host code (lg_policy, fill_policy_args, g_wide_precision).
+// (dec_game_check, fill_dec_act_args) and the fused-actor host code (lg_policy, fill_wide_operands, g_wide_precision).
 #pragma once
 #include "lg_pool_act.h"
 
@@ -29,7 +29,7 @@ int lg_dec_pool_create(lg_policy *const *members, int32_t count, int32_t role, i
     lg::DecPoolEntry rows[LG_DEC_POOL_MAX];
     for (int i = 0; i < LG_DEC_POOL_MAX; i++) {
         const lg_policy *p = members[i < count ? i : 0];
-        for (int l = 0; l < 4; l++) { rows[i].wb[l] = reinterpret_cast<const lg::bf16x8g *>(p->d_wb[l]); rows[i].bb[l] = p->d_bb[l]; }
+        fill_wide_operands(p, rows[i].wb, rows[i].bb);
         rows[i].std = p->d_std;
     }
     HIP_TRY(hipSetDevice(device));
@@ -74,23 +74,9 @@ int lg_dec_pool_act(lg_policy *pred, lg_policy *prey, lg_policy *ll, const lg_de
     const bool ll_ok = ll->wide && ll->tiles[0] == 15;
     if (g_wide_precision != 1 || !prey_ok || !pred_ok || !ll_ok)
         return fail(-4, "the pooled actor launch is compiled for the 3-512-256-128-2 / 16-512-256-128-4 / 235-512-256-128 triple at wide precision 1; use lg_policy_act per member + lg_dec_game_pre");
-    const lg_dec_act_outputs none = {nullptr, nullptr, nullptr, nullptr};
-    const lg_dec_act_outputs &op = out_pred ? *out_pred : none, &oy = out_prey ? *out_prey : none;
     lg::PoolActArgs a;
-    lg::DecActArgs &g = a.act;
-    fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed_prey, step, step_counter, 1);
-    fill_policy_args(py, g.prey.base, prey_obs, oy.sample, mean_prey, P->num_envs, seed_prey, step, step_counter, deterministic_prey);
-    fill_policy_args(pd, g.pred.base, pred_obs, op.sample, mean_pred, P->num_envs, seed_pred, step, step_counter, deterministic_pred);
-    for (int i = 0; i < 4; i++) {
-        g.ll.wb[i] = reinterpret_cast<const lg::bf16x8g *>(ll->d_wb[i]); g.ll.bb[i] = ll->d_bb[i];
-        g.prey.wb[i] = reinterpret_cast<const lg::bf16x8g *>(py->d_wb[i]); g.prey.bb[i] = py->d_bb[i];
-        g.pred.wb[i] = reinterpret_cast<const lg::bf16x8g *>(pd->d_wb[i]); g.pred.bb[i] = pd->d_bb[i];
-    }
-    g.P = *P;
-    g.a_prey = {B->command_prey, oy.sigma, oy.log_prob, oy.obs_copy};
-    g.a_pred = {B->command_pred, op.sigma, op.log_prob, op.obs_copy};
-    g.ll_commands = B->ll_commands;
-    g.blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;
+    fill_dec_act_args(a.act, pd, py, ll, P, B, pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey, seed_pred, seed_prey, step, step_counter,
+                      deterministic_pred, deterministic_prey, out_pred, out_prey);
     a.prey = {pool_prey ? pool_prey->d_table : nullptr, pool_prey ? block_slot_prey : nullptr, pool_prey ? pool_prey->count : 0, 0};
     a.pred = {pool_pred ? pool_pred->d_table : nullptr, pool_pred ? block_slot_pred : nullptr, pool_pred ? pool_pred->count : 0, 0};
     HIP_TRY((hipError_t)lg::launch_pool_act(a, stream));

@@ -94,10 +94,8 @@ int lg_game_act(lg_policy *hl, lg_policy *ll, const lg_game_params *P, const lg_
     lg::PreyActArgs g;
     fill_policy_args(hl, g.hl.base, hl_obs, sample, mean, P->num_envs, seed, step, step_counter, deterministic);
     fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed, step, step_counter, 1);
-    for (int i = 0; i < 4; i++) {
-        g.hl.wb[i] = reinterpret_cast<const lg::bf16x8g *>(hl->d_wb[i]); g.hl.bb[i] = hl->d_bb[i];
-        g.ll.wb[i] = reinterpret_cast<const lg::bf16x8g *>(ll->d_wb[i]); g.ll.bb[i] = ll->d_bb[i];
-    }
+    fill_wide_operands(hl, g.hl.wb, g.hl.bb);
+    fill_wide_operands(ll, g.ll.wb, g.ll.bb);
     g.P = *P; g.command = B->command; g.ll_commands = B->ll_commands;
     g.sigma = sigma; g.log_prob = log_prob; g.obs_copy = obs_copy;
     const int blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;

@@ -1,4 +1,5 @@
 // lg_game_act.h -- k_prey_act: both actors of a high-level game step and the command clip in one launch (include/legged_game.h: lg_game_act).
+// Each role is a call of wide_actor_body (lg_policy.h); what is here is the role split and the high-level role's wave-0 epilogue.
 // Included by lg_game_act.hip only, after lg_policy.h (see lg_game_common.h for the design and lg_game.h for why it is a unit of its own).
 #pragma once
 #include "lg_game_common.h"
@@ -46,109 +47,23 @@ LG_DEV void prey_command_epilogue(const PreyActArgs &G, int env, int h, bool liv
     }
 }
 
-template <int K0S, bool HL>
-LG_DEV void prey_actor_role(const PolicyWideArgs &W, const PreyActArgs &G, const int blk, bf16x8g (*xa)[2][64], bf16x8g (*xb)[2][64]) {
-    const PolicyArgs &A = W.base;
-    constexpr int NW = LG_PW_WAVES, H1T = 16, H2T = 8, H3T = 4;
-    constexpr int T1 = H1T / NW, T2 = H2T / NW, T3 = 1;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5;
-    const int wv = (wave + blk) % NW;
-    const int r0 = (blk * 5) % K0S, r1 = (blk * 5) % (2 * H1T), r2 = (blk * 5) % (2 * H2T);
-    const bool on2 = wv * T2 < H2T, on3 = wv * T3 < H3T;
-    const int64_t step = A.step >= 0 ? A.step : (A.step_counter ? A.step_counter[0] + 1 : 0);
-    int env = blk * LG_PW_ENVS + (lane & 31);
-    const bool live = env < A.num_envs;
-    if (!live) env = A.num_envs - 1;
-    const float *o = A.obs + (size_t)env * A.num_obs;
-    WideStream<K0S, T1> s1;
-    s1.prime(W.wb[0], wv * T1, r0, lane);
-    for (int s = wave; s < K0S; s += NW) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) { const int k = 16 * s + 8 * h + i; v[i] = k < A.num_obs ? o[k] : 0.0f; }
-        if (HL && G.obs_copy && live) {                            // the rollout storage's / the other ping-pong buffer's copy of what was read
-#pragma unroll
-            for (int i = 0; i < 8; i++) { const int k = 16 * s + 8 * h + i; if (k < A.num_obs) G.obs_copy[(size_t)env * A.num_obs + k] = v[i]; }
-        }
-        bf16x8g hi, lo;
-        split8(v, hi, lo);
-        xa[s][0][lane] = hi; xa[s][1][lane] = lo;
-    }
-    float ns[2][4], by[2][4];                                      // std * eps (0 when deterministic), output bias: the noise block of k_policy_act_wide
-    if (wave == 0) {
-#pragma unroll
-        for (int ii = 0; ii < 2; ii++) {
-            const int g = 2 * ii + h;
-#pragma unroll
-            for (int r = 0; r < 4; r++) { ns[ii][r] = 0.0f; by[ii][r] = 0.0f; }
-            if (4 * g >= A.num_actions) continue;
-            float u[4];
-            rand4(A.seed ^ 0x9E3779B97F4A7C15ull, env, step, 100 + g, 0, u);
-            const float rad0 = sqrtf(-2.0f * __logf(fmaxf(u[0], 1e-12f))), rad1 = sqrtf(-2.0f * __logf(fmaxf(u[2], 1e-12f)));
-            float s0, c0, sn1, c1;
-            __sincosf(6.2831853f * u[1], &s0, &c0);
-            __sincosf(6.2831853f * u[3], &sn1, &c1);
-            const float eps[4] = {rad0 * c0, rad0 * s0, rad1 * c1, rad1 * sn1};
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int a = 4 * g + r;
-                if (a < A.num_actions) { by[ii][r] = W.bb[3][a]; ns[ii][r] = A.deterministic ? 0.0f : A.std[a] * eps[r]; }
-            }
-        }
-    }
-    __syncthreads();
-    f32x16p a1[T1];
-    s1.run(W.wb[0], xa, wv * T1, r0, lane, a1);
-    WideStream<2 * H1T, T2> s2;
-    if (on2) s2.prime(W.wb[1], wv * T2, r1, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    wide_epilogue<T1>(a1, W.bb[0], xb, wv * T1, lane);
-    __syncthreads();
-    f32x16p a2[T2];
-    WideStream<2 * H2T, T3> s3;
-    if (on2) s2.run(W.wb[1], xb, wv * T2, r1, lane, a2);
-    if (on3) s3.prime(W.wb[2], wv * T3, r2, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    if (on2) wide_epilogue<T2>(a2, W.bb[1], xa, wv * T2, lane);
-    __syncthreads();
-    f32x16p a3[T3];
-    WideStream<2 * H3T, 1> s4;
-    if (on3) s3.run(W.wb[2], xa, wv * T3, r2, lane, a3);
-    if (wave == 0) s4.prime(W.wb[3], 0, 0, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    if (on3) wide_epilogue<T3>(a3, W.bb[2], xb, wv * T3, lane);
-    __syncthreads();
-    if (wave != 0) return;
-    f32x16p y[1];
-    s4.run(W.wb[3], xb, 0, 0, lane, y);
-    if constexpr (HL) {                                            // six actions: lane (env, h) holds actions 4h .. 4h + 3 in registers 0..3
+// wave 0's tail of the high-level role: six actions, lane (env, h) holds actions 4h .. 4h + 3 in registers 0..3
+struct PreyCommandEpilogue {
+    const PreyActArgs &G;
+    LG_DEV void operator()(const PolicyArgs &, int env, int h, bool live, const f32x16p &y, const float (&by)[2][4], const float (&ns)[2][4]) const {
         float m[4], v[4];
 #pragma unroll
-        for (int r = 0; r < 4; r++) { m[r] = y[0][r] + by[0][r]; v[r] = m[r] + ns[0][r]; }
+        for (int r = 0; r < 4; r++) { m[r] = y[r] + by[0][r]; v[r] = m[r] + ns[0][r]; }
         prey_command_epilogue(G, env, h, live, m, v);
-    } else {
-#pragma unroll
-        for (int ii = 0; ii < 2; ii++) {
-            const int g = 2 * ii + h;
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int a = 4 * g + r;
-                if (a < A.num_actions && live) {
-                    const float mm = y[0][4 * ii + r] + by[ii][r];
-                    if (A.mean) A.mean[(size_t)env * A.num_actions + a] = mm;
-                    A.actions[(size_t)env * A.num_actions + a] = mm + ns[ii][r];
-                }
-            }
-        }
     }
-}
+};
 
 __global__ void __launch_bounds__(64 * LG_PW_WAVES) k_prey_act(const PreyActArgs G) {
     __shared__ bf16x8g xa[16][2][64], xb[32][2][64];               // as k_policy_act_wide: obs / x2 in xa, x1 / x3 in xb (96 KB), the same for both roles
     const bool first = (int)blockIdx.x < G.ll_blocks;              // both roles have ll_blocks workgroups, the low-level role the first
     const int blk = first ? (int)blockIdx.x : (int)blockIdx.x - G.ll_blocks;
-    if (first) prey_actor_role<15, false>(G.ll, G, blk, xa, xb);
-    else prey_actor_role<2, true>(G.hl, G, blk, xa, xb);
+    if (first) wide_actor_body<15, 16, 8, 4>(G.ll, blk, xa, xb, WideNoTap{}, WideActStores{});
+    else wide_actor_body<2, 16, 8, 4>(G.hl, blk, xa, xb, WideObsCopy{G.obs_copy}, PreyCommandEpilogue{G});
 }
 
 int launch_prey_act(const PreyActArgs &G, int blocks, void *stream) {

@@ -26,9 +26,10 @@ LG_DEV float game_wrap_to_pi(float a) {                                         
 // At 2000 envs each fills 63 workgroups of a 256-CU chip: the two run side by side, workgroups split by role -- the low-level role
 // (235 inputs: the longer weight stream) on the first `ll_blocks` workgroups, the high-level role (19 inputs, ~0.6 x the weights) behind it.
 // The other order was timed and is no different (DESIGN.md section 5 has the figures).
-// A role is the body of k_policy_act_wide (lg_policy.h) with the role-local workgroup index in place of blockIdx.x (env base, wave share
-// wv, k-step rotations r0..r2) and the same rand4 keying: every MFMA sees the operands of the stand-alone launch in the same order, the
-// results are bit-identical (the roles are compiled with the default contraction, as lg_policy.h is: lg_game_act.h).
+// A role is a call of wide_actor_body (lg_policy.h), the function k_policy_act_wide itself calls, with the role-local workgroup index where
+// the stand-alone kernel passes blockIdx.x (env base, wave share wv, k-step rotations r0..r2) and the same rand4 keying: every MFMA sees the
+// operands of the stand-alone launch in the same order, the results are bit-identical (the roles are compiled with the default
+// contraction, as lg_policy.h is: lg_game_act.h).
 struct PreyActArgs {
     PolicyWideArgs hl, ll;                 // high-level: sampled, hl.base.actions = unclipped sample or null; low-level: deterministic
     lg_game_params P;

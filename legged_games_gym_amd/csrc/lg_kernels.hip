@@ -2993,6 +2993,11 @@ static void fill_policy_args(const lg_policy *p, PolicyArgs &a, const float *obs
     for (int i = 0; i < 4; i++) { a.w[i] = p->d_w[i]; a.b[i] = p->d_b[i]; }
 }
 
+// the split-bf16 operand stream of a wide handle: the wb / bb of a PolicyWideArgs or of a pool's table row
+static void fill_wide_operands(const lg_policy *p, const lg::bf16x8g *(&wb)[4], const float *(&bb)[4]) {
+    for (int i = 0; i < 4; i++) { wb[i] = reinterpret_cast<const lg::bf16x8g *>(p->d_wb[i]); bb[i] = p->d_bb[i]; }
+}
+
 int lg_policy_act(lg_policy *p, const float *obs, float *actions, float *mean, int32_t num_envs, uint64_t seed, int64_t step,
                   const int64_t *step_counter, int32_t deterministic, void *stream) {
     if (!p || !obs || !actions) return fail(-1, "null argument");
@@ -3004,7 +3009,7 @@ int lg_policy_act(lg_policy *p, const float *obs, float *actions, float *mean, i
     const int t0 = p->tiles[0], t1 = p->tiles[1], t2 = p->tiles[2], t3 = p->tiles[3];
     if (p->wide && g_wide_precision == 1 && (t0 == 15 || t0 == 11 || t0 == 2 || t0 == 1)) {          // 32 envs per workgroup on the bf16 matrix cores
         lg::PolicyWideArgs w; w.base = a;
-        for (int i = 0; i < 4; i++) { w.wb[i] = reinterpret_cast<const lg::bf16x8g *>(p->d_wb[i]); w.bb[i] = p->d_bb[i]; }
+        fill_wide_operands(p, w.wb, w.bb);
         if (t0 == 1) { HIP_TRY((hipError_t)lg::launch_policy_act_wide_one_tile(w, st)); return 0; }   // dec game: 16 / 3-512-256-128 (1..16 inputs), lg_dec_game.hip
         dim3 gw((num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS), bw(64 * LG_PW_WAVES);
         if (t0 == 15) hipLaunchKernelGGL((lg::k_policy_act_wide<15, 16, 8, 4>), gw, bw, 0, st, w);     // rough: 235-512-256-128

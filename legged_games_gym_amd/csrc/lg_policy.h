@@ -279,23 +279,60 @@ __device__ unsigned long long g_chain_prof[2048 * 16];
 #else
 #define CHAIN_STAMP(i) do { } while (0)
 #endif
+// What differs between the kernels built from wide_actor_body: the tap sees the eight observation values of a k-step before they are split,
+// the epilogue is wave 0's tail on the last layer's accumulators.
+//   tap(A, env, s, h, live, v)               v[i] = observation 16s + 8h + i of `env` (0 past num_obs)
+//   epilogue(A, env, h, live, y, by, ns)     lane (env, h), register 4ii + r of y: action 8ii + 4h + r before its bias by[ii][r]; ns = std * eps
+struct WideNoTap {
+    LG_DEV void operator()(const PolicyArgs &, int, int, int, bool, const float (&)[8]) const {}
+};
+struct WideObsCopy {                                               // the rollout storage's / the other ping-pong buffer's copy of what was read
+    float *dst;                                                    // [N, num_obs], or null: nothing is written
+    LG_DEV void operator()(const PolicyArgs &A, int env, int s, int h, bool live, const float (&v)[8]) const {
+        if (dst && live) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) { const int k = 16 * s + 8 * h + i; if (k < A.num_obs) dst[(size_t)env * A.num_obs + k] = v[i]; }
+        }
+    }
+};
+struct WideActStores {                                             // the stores of lg_policy_act: mean (optional) and mean + noise
+    LG_DEV void operator()(const PolicyArgs &A, int env, int h, bool live, const f32x16p &y, const float (&by)[2][4], const float (&ns)[2][4]) const {
+#pragma unroll
+        for (int ii = 0; ii < 2; ii++) {
+            const int g = 2 * ii + h;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int a = 4 * g + r;
+                if (a < A.num_actions && live) {
+                    const float m = y[4 * ii + r] + by[ii][r];
+                    if (A.mean) A.mean[(size_t)env * A.num_actions + a] = m;
+                    A.actions[(size_t)env * A.num_actions + a] = m + ns[ii][r];
+                }
+            }
+        }
+    }
+};
+
+// The wide actor for the 32 envs of workgroup `blk`: the ONE copy of the chain.  k_policy_act_wide calls it with blockIdx.x, the shared
+// actor launches of the game tasks (k_prey_act, k_dec_act, k_pool_act) with the role-local workgroup index, so a role sees every operand
+// of the stand-alone launch in the same order.  `blk` sets the env base, the wave share wv and the k-step rotations r0..r2; its type is
+// deduced (unsigned from blockIdx.x, int from a role split) because fixing it moves hipcc's register allocation of one caller or another.
+// Must be called by all LG_PW_WAVES waves of the workgroup (contains barriers); xa holds max(K0S, 2 H2T) k-steps, xb 2 max(H1T, H3T).
 // K0S = ceil(num_obs / 16) k-steps of layer 0; H1T/H2T/H3T = hidden widths / 32.  Every wave's weight stream runs ahead of the
 // layer barriers: the ring of layer l+1 is primed before layer l's epilogue, so no layer starts with an empty pipeline.
-template <int K0S, int H1T, int H2T, int H3T>
-__global__ void __launch_bounds__(64 * LG_PW_WAVES) k_policy_act_wide(const PolicyWideArgs W) {
+template <int K0S, int H1T, int H2T, int H3T, class Idx, class Tap, class Epilogue>
+LG_DEV void wide_actor_body(const PolicyWideArgs &W, const Idx blk, bf16x8g (*xa)[2][64], bf16x8g (*xb)[2][64], const Tap &tap, const Epilogue &epilogue) {
     const PolicyArgs &A = W.base;
     constexpr int NW = LG_PW_WAVES;
     static_assert(H1T % NW == 0 && (H2T % NW == 0 || H2T <= NW) && H3T <= NW, "tiles per wave");
     constexpr int T1 = H1T / NW, T2 = H2T >= NW ? H2T / NW : 1, T3 = 1;
-    constexpr int KA = K0S > 2 * H2T ? K0S : 2 * H2T, KB = H1T > H3T ? 2 * H1T : 2 * H3T;
-    __shared__ bf16x8g xa[KA][2][64], xb[KB][2][64];               // ping-pong activations: obs / x2 in xa, x1 / x3 in xb (96 KB)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5;
-    const int wv = (wave + blockIdx.x) % NW;                       // which share of the output tiles this wave takes (rotates over workgroups)
-    const int r0 = (blockIdx.x * 5) % K0S, r1 = (blockIdx.x * 5) % (2 * H1T), r2 = (blockIdx.x * 5) % (2 * H2T);
+    const int wv = (wave + blk) % NW;                              // which share of the output tiles this wave takes (rotates over workgroups)
+    const int r0 = (blk * 5) % K0S, r1 = (blk * 5) % (2 * H1T), r2 = (blk * 5) % (2 * H2T);
     const bool on2 = wv * T2 < H2T, on3 = wv * T3 < H3T;
     CHAIN_STAMP(0);
     const int64_t step = A.step >= 0 ? A.step : (A.step_counter ? A.step_counter[0] + 1 : 0);
-    int env = blockIdx.x * LG_PW_ENVS + (lane & 31);
+    int env = blk * LG_PW_ENVS + (lane & 31);
     const bool live = env < A.num_envs;
     if (!live) env = A.num_envs - 1;
     const float *o = A.obs + (size_t)env * A.num_obs;
@@ -305,6 +342,7 @@ __global__ void __launch_bounds__(64 * LG_PW_WAVES) k_policy_act_wide(const Poli
         float v[8];                                                // the ring, as the learner's chain does, changes nothing here: measured)
 #pragma unroll
         for (int i = 0; i < 8; i++) { const int k = 16 * s + 8 * h + i; v[i] = k < A.num_obs ? o[k] : 0.0f; }
+        tap(A, env, s, h, live, v);
         bf16x8g hi, lo;
         split8(v, hi, lo);
         xa[s][0][lane] = hi; xa[s][1][lane] = lo;
@@ -368,20 +406,15 @@ __global__ void __launch_bounds__(64 * LG_PW_WAVES) k_policy_act_wide(const Poli
     f32x16p y[1];
     s4.run(W.wb[3], xb, 0, 0, lane, y);
     CHAIN_STAMP(8);
-#pragma unroll
-    for (int ii = 0; ii < 2; ii++) {
-        const int g = 2 * ii + h;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int a = 4 * g + r;
-            if (a < A.num_actions && live) {
-                const float m = y[0][4 * ii + r] + by[ii][r];
-                if (A.mean) A.mean[(size_t)env * A.num_actions + a] = m;
-                A.actions[(size_t)env * A.num_actions + a] = m + ns[ii][r];
-            }
-        }
-    }
+    epilogue(A, env, h, live, y[0], by, ns);
     CHAIN_STAMP(9);
+}
+
+template <int K0S, int H1T, int H2T, int H3T>
+__global__ void __launch_bounds__(64 * LG_PW_WAVES) k_policy_act_wide(const PolicyWideArgs W) {
+    constexpr int KA = K0S > 2 * H2T ? K0S : 2 * H2T, KB = H1T > H3T ? 2 * H1T : 2 * H3T;
+    __shared__ bf16x8g xa[KA][2][64], xb[KB][2][64];               // ping-pong activations: obs / x2 in xa, x1 / x3 in xb (96 KB)
+    wide_actor_body<K0S, H1T, H2T, H3T>(W, blockIdx.x, xa, xb, WideNoTap{}, WideActStores{});
 }
 
 // ------------------------------------------------------------------ the same chain as the LEARNER's forward pass

@@ -2,8 +2,9 @@
 // weights of a sampled role chosen per 32-env block from a pool of actors.  A translation unit of its own, reached through launch_pool_act
 // (lg_pool_act.h), so that the code hipcc generates for the kernels of lg_dec_game.hip and lg_kernels.hip does not depend on it.
 //
-// The roles are dec_actor_role (lg_dec_game_act.h), the body of k_dec_act: a block computes, bit for bit, what k_dec_act computes for it
-// when launched with the block's member as the role's handle.  Only the addresses of the weight, bias and std operands differ.
+// The roles are dec_actor_role (lg_dec_game_act.h), the calls of wide_actor_body that k_dec_act makes: a block computes, bit for bit, what
+// k_dec_act computes for it when launched with the block's member as the role's handle.  Only the addresses of the weight, bias and std
+// operands differ.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -37,9 +38,9 @@ __global__ void __launch_bounds__(64 * LG_PW_WAVES) k_pool_act(const PoolActArgs
     __shared__ bf16x8g xa[16][2][64], xb[32][2][64];               // as k_dec_act (96 KB), the same for all roles
     const DecActArgs &D = G.act;
     const int role = (int)blockIdx.x / D.blocks, blk = (int)blockIdx.x - role * D.blocks;      // every role has `blocks` workgroups, the low-level role the first
-    if (role == 0) dec_actor_role<15, 0>(D.ll, D, blk, xa, xb);
-    else if (role == 1) dec_actor_role<1, 1>(pool_role_args(D.prey, G.prey, blk), D, blk, xa, xb);
-    else dec_actor_role<1, 2>(pool_role_args(D.pred, G.pred, blk), D, blk, xa, xb);
+    if (role == 0) dec_actor_role<0>(D.ll, D, blk, xa, xb);
+    else if (role == 1) dec_actor_role<1>(pool_role_args(D.prey, G.prey, blk), D, blk, xa, xb);
+    else dec_actor_role<2>(pool_role_args(D.pred, G.pred, blk), D, blk, xa, xb);
 }
 
 int launch_pool_act(const PoolActArgs &G, void *stream) {
