@@ -682,6 +682,50 @@ def dec_pool_act(pred_policy, prey_policy, ll_policy, pool_pred, block_slot_pred
     return rc
 
 
+# ----------------------------------------------------------------------------- outcome statistics per pool member (include/legged_dec_game_member_outcome.h)
+LG_DEC_MEMBER_OUTCOME_ROWS = LG_DEC_POOL_MAX
+
+
+class lg_dec_member_outcome_buffers(C.Structure):
+    """include/legged_dec_game_member_outcome.h: lg_dec_member_outcome_buffers (raw device pointers and the pool's member count)."""
+    _fields_ = [("block_slot", C.POINTER(i32)), ("member_accum", C.POINTER(u64)), ("member_totals", C.POINTER(u64)), ("count", i32), ("_pad", i32)]
+
+
+DEC_MEMBER_OUTCOME_BUFFER_FIELDS = ["block_slot", "member_accum", "member_totals"]       # the pointers
+DEC_MEMBER_OUTCOME_SYMBOLS = ["lg_dec_member_outcome_post", "lg_dec_member_outcome_sizeof"]
+
+
+def bind_dec_member_outcome_prototypes(lib):
+    """Attach argtypes/restype for the entry points of legged_dec_game_member_outcome.h and check the struct layout."""
+    lib.lg_dec_member_outcome_post.argtypes = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), C.POINTER(lg_dec_outcome_buffers),
+                                               C.POINTER(lg_dec_member_outcome_buffers), i64, C.c_void_p]
+    lib.lg_dec_member_outcome_post.restype = C.c_int
+    lib.lg_dec_member_outcome_sizeof.argtypes, lib.lg_dec_member_outcome_sizeof.restype = [C.c_int], C.c_int
+    if lib.lg_dec_member_outcome_sizeof(0) != C.sizeof(lg_dec_member_outcome_buffers):
+        raise RuntimeError(f"struct layout mismatch for lg_dec_member_outcome_buffers: C {lib.lg_dec_member_outcome_sizeof(0)} vs ctypes "
+                           f"{C.sizeof(lg_dec_member_outcome_buffers)}")
+    return lib
+
+
+def dec_member_outcome_buffers(pointers: Dict[str, int], count: int) -> lg_dec_member_outcome_buffers:
+    """``lg_dec_member_outcome_buffers`` from a name -> device address table (missing names stay null) and the pool's member count."""
+    b = lg_dec_member_outcome_buffers()
+    types = dict(lg_dec_member_outcome_buffers._fields_)
+    for name in DEC_MEMBER_OUTCOME_BUFFER_FIELDS:
+        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
+    b.count = int(count)
+    return b
+
+
+def dec_member_outcome_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, outcome: lg_dec_outcome_buffers, members: lg_dec_member_outcome_buffers,
+                            common_step_counter: int, stream: int = 0):
+    """``lg_dec_member_outcome_post``: ``lg_dec_outcome_post`` that also keeps the six counts per opponent-pool member."""
+    lib = load_library()
+    rc = lib.lg_dec_member_outcome_post(C.byref(params), C.byref(buffers), C.byref(outcome), C.byref(members), int(common_step_counter), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_member_outcome_post failed ({rc}): {lib.lg_last_error().decode()}")
+
+
 def load_library():
     """Load the HIP extension or fail loudly -- never a CPU substitute."""
     global _lib
@@ -692,7 +736,7 @@ def load_library():
         raise RuntimeError(
             f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_dec_pool_prototypes(bind_dec_outcome_prototypes(bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_")))))))
+    _lib = bind_dec_member_outcome_prototypes(bind_dec_pool_prototypes(bind_dec_outcome_prototypes(bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_"))))))))
     if _lib.lg_abi_version() != LG_ABI_VERSION:
         raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
     return _lib

@@ -3510,3 +3510,4 @@ int lg_compute_observations_only(lg_sim *s, int64_t common_step_counter, void *s
 #include "lg_game_outcome_entry.h"  // outcome statistics: entry points of include/legged_game_outcome.h (kernels: lg_game_outcome.hip)
 #include "lg_dec_game_outcome_entry.h"  // decentralised game's outcome statistics: include/legged_dec_game_outcome.h (kernel: lg_dec_game_outcome.hip)
 #include "lg_dec_game_pool_entry.h"  // decentralised game's opponent pool: include/legged_dec_game_pool.h (kernel: lg_pool_act.hip)
+#include "lg_member_outcome_entry.h"  // outcome statistics per pool member: include/legged_dec_game_member_outcome.h (kernel: lg_member_outcome.hip)

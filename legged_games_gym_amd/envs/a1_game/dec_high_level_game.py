@@ -23,6 +23,10 @@ and ``outcome_totals()`` the running integer sums.  A step is still three launch
 ``step_policy`` / ``make_graphed_policy_step`` take an ``rl.OpponentPool`` in place of either ``FusedActor``: the actor launch is then
 ``lg_dec_pool_act`` (include/legged_dec_game_pool.h), the same launch with that role's weights chosen per 32-env block from the pool.
 
+Outcomes per pool member (off by default; ``enable_member_outcomes(pool)``, needs the outcome statistics): the last launch becomes
+``lg_dec_member_outcome_post`` (include/legged_dec_game_member_outcome.h), ``lg_dec_outcome_post`` that also keeps the six counts per member
+of that pool, read back with ``pool.member_totals_host()``.  Everything else comes out bit-identical.
+
 ``agent_view(agent, opponent)`` gives one agent's single-agent surface (what ``rl.OnPolicyRunner`` drives) with the other agent acting
 inside every step.  Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G10 onward)."""
 import numpy as np
@@ -67,6 +71,7 @@ class DecHighLevelGame(GameBase):
         self._prepare_reward_functions()
         self._pack()
         self._outcome = None
+        self._member_pool = self._member_outcome = None
         if getattr(cfg.env, "outcome_stats", False):           # no field of the registered config classes: they stay value for value the reference's
             self.enable_outcome_stats()
         self.init_done = True
@@ -102,11 +107,14 @@ class DecHighLevelGame(GameBase):
         return self._step_result()
 
     def _post(self, B, common_step_counter, stream):
-        """The last launch of every step path: ``lg_dec_game_post``, or ``lg_dec_outcome_post`` with the outcome statistics on."""
+        """The last launch of every step path: ``lg_dec_game_post``, or ``lg_dec_outcome_post`` with the outcome statistics on, or
+        ``lg_dec_member_outcome_post`` with them on and a pool bound (``enable_member_outcomes``)."""
         if self._outcome is None:
             capi.dec_game_post(self._P, B, common_step_counter, stream)
-        else:
+        elif self._member_outcome is None:
             capi.dec_outcome_post(self._P, B, self._outcome, common_step_counter, stream)
+        else:
+            capi.dec_member_outcome_post(self._P, B, self._outcome, self._member_outcome, common_step_counter, stream)
 
     # ------------------------------------------------------------------ outcome statistics
     def enable_outcome_stats(self, on=True):
@@ -128,6 +136,21 @@ class DecHighLevelGame(GameBase):
         self._outcome = capi.dec_outcome_buffers({"ll_time_out_buf": self.ll_env._sim.buf["time_out_buf"].data_ptr(), "accum": self._outcome_accum.data_ptr(),
                                                   "means": self._outcome_means.data_ptr(), "totals": self._outcome_totals.data_ptr()})
         self.extras["episode"].update({f"outcome_{name}": self._outcome_means[i] for i, name in enumerate(capi.DEC_OUTCOME_MEANS)})
+
+    def enable_member_outcomes(self, pool):
+        """Keep the outcome counts per member of ``pool`` (an ``rl.OpponentPool``) as well, or stop doing so (``None``).  With a pool bound and
+        the outcome statistics on, ``_post`` issues ``lg_dec_member_outcome_post`` on every step path, given the pool's slot table, ``count = 1 +
+        capacity`` and the pool's count buffers: an episode is counted for the member its 32-env block has in the step in which it ends
+        (DESIGN.md section 8, G20).  Everything ``lg_dec_outcome_post`` writes is unchanged; read the counts with
+        ``pool.member_totals_host()``.  A graph captured earlier keeps the launch it was captured with."""
+        if pool is None:
+            self._member_pool = self._member_outcome = None
+            return
+        if self._outcome is None:
+            raise RuntimeError("outcomes per pool member need the outcome statistics: call enable_outcome_stats() (or set env.outcome_stats = True) first")
+        self._member_pool = pool                                   # keeps the buffers alive
+        self._member_outcome = capi.dec_member_outcome_buffers({"block_slot": pool.slot_table(self.num_envs).data_ptr(), "member_accum": pool.member_accum.data_ptr(),
+                                                                "member_totals": pool.member_totals.data_ptr()}, 1 + pool.capacity)
 
     def outcome_totals(self):
         """Running sums since construction or the last ``reset_outcome_totals()``, as Python ints after ONE synchronising copy:

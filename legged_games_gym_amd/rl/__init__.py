@@ -14,7 +14,7 @@ from .actor_critic import ActorCritic
 from .ppo import PPO, RolloutStorage
 from .runner import OnPolicyRunner
 from .dec_runner import DecGamePolicyRunner
-from .opponent_pool import OpponentPool, assign_blocks
+from .opponent_pool import OpponentPool, apportion, assign_blocks, assign_blocks_weighted, learner_win_rate, pfsp_weights
 
 
 
@@ -24,4 +24,5 @@ def FusedActor(*args, **kwargs):
     return _F(*args, **kwargs)
 
 
-__all__ = ["ActorCritic", "PPO", "RolloutStorage", "OnPolicyRunner", "DecGamePolicyRunner", "FusedActor", "OpponentPool", "assign_blocks"]
+__all__ = ["ActorCritic", "PPO", "RolloutStorage", "OnPolicyRunner", "DecGamePolicyRunner", "FusedActor", "OpponentPool", "assign_blocks", "assign_blocks_weighted",
+           "apportion", "learner_win_rate", "pfsp_weights"]

@@ -16,7 +16,15 @@ in the share ``opponent_latest_share`` of the 32-env blocks, up to ``opponent_po
 START of an evolution that trains X, X's current weights are pushed into X's pool, so the pool holds strictly earlier versions than its
 live member; the pool the training view plays against is then re-assigned (which block meets which member) with a generator seeded from
 ``(seed, evolution)`` before ``runner.learn`` captures its graph.  The opponent samples, pooled or not, and the outcome statistics stay
-pooled over all opponents."""
+pooled over all opponents unless they are on together with a pool:
+
+Outcomes per pool member and prioritised opponents.  With a pool and the outcome statistics on
+(``env.outcome_stats`` / ``--outcome_stats``), the pool the training view plays against is bound with ``env.enable_member_outcomes`` before
+``runner.learn`` captures its graph, so the post launch also counts the outcomes per member, and after every evolution
+``<log_dir>/opponents.csv`` gets one row per member of that pool: its blocks, the six counts OF THIS EVOLUTION and the learner's win rate.
+Runner key ``opponent_priority`` (a float power, default 0 = off; read with ``.get()``; ``--opponent_priority``): above 0 the non-live blocks
+are dealt in proportion to ``pfsp_weights`` of the pool's running counts -- a past opponent the learner loses to gets more envs -- instead of
+round-robin; it needs ``opponent_pool_size > 0`` and the outcome statistics.  With priority 0 the calls to ``assign`` are unchanged."""
 import os
 import re
 
@@ -25,11 +33,27 @@ import torch
 from .runner import OnPolicyRunner
 
 AGENTS = ("pred", "prey")
+OPPONENT_COLUMNS = ("evolution", "agent", "member", "pushed_at", "blocks", "episodes", "captured", "timed_out", "fell", "ll_timed_out", "steps", "learner_win_rate")
+
+
+def opponent_priority_of(runner_cfg, env):
+    """The runner key ``opponent_priority`` (0 when absent), refused where it cannot work: it weights the pool's members by the outcome counts
+    per member, so it needs the pool and the outcome statistics."""
+    priority = float(runner_cfg.get("opponent_priority", 0) or 0)
+    if priority < 0:
+        raise ValueError(f"opponent_priority must be >= 0, got {priority}")
+    if priority > 0 and int(runner_cfg.get("opponent_pool_size", 0) or 0) <= 0:
+        raise ValueError("opponent_priority > 0 needs an opponent pool: set the runner key opponent_pool_size > 0 (--opponent_pool K)")
+    if priority > 0 and getattr(env, "_outcome", None) is None:
+        raise ValueError("opponent_priority > 0 needs the outcome statistics: set env.outcome_stats = True (--outcome_stats); the weights come from "
+                         "the outcome counts per pool member")
+    return priority
 
 
 class DecGamePolicyRunner:
     def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
         self.env, self.cfg, self.device, self.log_dir = env, train_cfg["runner"], device, log_dir
+        self.priority = opponent_priority_of(self.cfg, env)       # before anything is built
         self.views = {a: env.agent_view(a, None) for a in AGENTS}
         self.runners = {}
         for a in AGENTS:
@@ -111,16 +135,56 @@ class DecGamePolicyRunner:
         for e in range(self.current_evolution, self.current_evolution + max_num_evolutions):
             agent = self.agent_of(e)
             runner = self.runners[agent]
+            counted = None
             if self.pools:
                 other = "prey" if agent == "pred" else "pred"
-                self.pools[agent].push(runner.alg.actor_critic.state_dict())      # at the START: the pool holds strictly earlier versions than its live member
-                self.pools[other].assign(torch.Generator().manual_seed((self.seed * 1000003 + e) & 0x7FFFFFFFFFFFFFFF))      # before learn captures its graph
+                self.pools[agent].push(runner.alg.actor_critic.state_dict(), pushed_at=e)      # at the START: the pool holds strictly earlier versions than its live member
+                generator = torch.Generator().manual_seed((self.seed * 1000003 + e) & 0x7FFFFFFFFFFFFFFF)
+                if self.priority > 0:
+                    self.pools[other].assign(generator, self.opponent_weights(agent))
+                else:
+                    self.pools[other].assign(generator)    # before learn captures its graph
+                if getattr(self.env, "_outcome", None) is not None:
+                    self.env.enable_member_outcomes(self.pools[other])             # before learn captures its graph, too
+                    counted = (self.pools[other], self.pools[other].member_totals_host())
             runner.learn(num_learning_iterations=num_learning_iterations, init_at_random_ep_len=False)
             if runner._fused is not None:
                 runner._fused.sync_device()                # the other view's opponent: this agent's new weights, repacked in place
+            if counted is not None and self.log_dir is not None:
+                self._log_opponents(e, agent, *counted)
             self.current_evolution = e + 1
             if self.log_dir is not None:
                 self.save(os.path.join(self.log_dir, f"model_{self.current_learning_iteration}.pt"))
+
+    def opponent_weights(self, agent):
+        """``pfsp_weights`` of the snapshots 1 .. ``filled`` of the pool that ``agent`` plays against, from that pool's running counts (one
+        synchronising copy): ``agent`` 's wins and episodes against every snapshot, to the power ``opponent_priority``."""
+        from .opponent_pool import pfsp_weights
+        pool = self.pools["prey" if agent == "pred" else "pred"]
+        rows = pool.member_totals_host()[1:]
+        episodes = [r["episodes"] for r in rows]
+        wins = [r["captured"] if agent == "pred" else r["episodes"] - r["captured"] for r in rows]
+        return pfsp_weights(wins, episodes, self.priority)
+
+    def _log_opponents(self, evolution, agent, pool, before):
+        """``<log_dir>/opponents.csv``: one row per member 0 .. ``filled`` of the pool ``agent`` has just played against -- the evolution that
+        pushed it (empty for the live member 0), its 32-env blocks, the six outcome counts of THIS evolution (the running counts now less
+        ``before``) and ``agent`` 's win rate in them (empty without an episode)."""
+        from .. import capi
+        from .opponent_pool import learner_win_rate
+        os.makedirs(self.log_dir, exist_ok=True)
+        path = os.path.join(self.log_dir, "opponents.csv")
+        new = not os.path.isfile(path)
+        blocks = torch.bincount(pool._slots_host.clamp(0, pool.capacity).long(), minlength=pool.filled + 1).tolist()
+        with open(path, "a") as fh:
+            if new:
+                fh.write(",".join(OPPONENT_COLUMNS) + "\n")
+            for m, (now, then) in enumerate(zip(pool.member_totals_host(), before)):
+                row = {k: now[k] - then[k] for k in capi.DEC_OUTCOME_COUNTS}
+                pushed = "" if m == 0 or pool.pushed_at[m - 1] is None else pool.pushed_at[m - 1]
+                rate = learner_win_rate(row, agent)
+                fh.write(",".join(str(v) for v in (evolution, agent, m, pushed, blocks[m], *(row[k] for k in capi.DEC_OUTCOME_COUNTS),
+                                                   "" if rate != rate else repr(rate))) + "\n")
 
     def _log_row(self, iteration, agent, agent_iteration):
         """``<log_dir>/progress.csv``: one row per iteration with an ``agent`` column (the per-agent runners write the full scalar tables under

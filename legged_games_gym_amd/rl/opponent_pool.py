@@ -8,7 +8,13 @@ the C-side table of operand addresses never changes: ``push`` loads a snapshot i
 slot table IN PLACE -- both are visible underneath a captured graph at its next replay.
 
 ``DecHighLevelGame.step_policy`` / ``make_graphed_policy_step`` and ``AgentView.step_policy`` accept a pool wherever they accept a
-``FusedActor`` opponent; the pool's ``live`` actor supplies the noise seed, the step source and the output buffers."""
+``FusedActor`` opponent; the pool's ``live`` actor supplies the noise seed, the step source and the output buffers.
+
+Outcomes per member (include/legged_dec_game_member_outcome.h): the pool owns the device counts ``member_totals``
+``[16, 6]`` that ``lg_dec_member_outcome_post`` keeps once ``DecHighLevelGame.enable_member_outcomes(pool)`` has bound the pool.  They feed the
+prioritised deal: ``learner_win_rate`` -> ``pfsp_weights`` -> ``apportion`` -> ``assign_blocks_weighted`` (``assign(weights=...)``)."""
+from fractions import Fraction
+
 import torch
 
 from .. import capi
@@ -34,6 +40,76 @@ def assign_blocks(num_blocks, filled, latest_share, generator):
     return slots
 
 
+def learner_win_rate(totals_row, learner):
+    """The share of the episodes of ``totals_row`` (a dict with ``episodes`` and ``captured``) that the ``learner`` ("pred" or "prey") won:
+    ``captured / episodes`` for the predator, ``1 - captured / episodes`` for the prey.  The flags of an episode's end are not exclusive, so
+    "not captured" is the prey's win here, whatever else ended the episode.  NaN without an episode."""
+    if learner not in ("pred", "prey"):
+        raise ValueError(f"learner must be 'pred' or 'prey', got {learner!r}")
+    episodes, captured = int(totals_row["episodes"]), int(totals_row["captured"])
+    if episodes == 0:
+        return float("nan")
+    rate = captured / episodes
+    return rate if learner == "pred" else 1.0 - rate
+
+
+def pfsp_weights(wins, episodes, power):
+    """Prioritised fictitious self-play: the weight of a past opponent is ``(1 - (wins + 1) / (episodes + 2)) ** power``, ``wins`` the learner's
+    wins in ``episodes`` episodes against it.  The Laplace term gives a member that has not been met a win rate of 0.5; ``power = 0`` gives
+    all ones (the uniform deal).  Returns a list of floats."""
+    if len(wins) != len(episodes):
+        raise ValueError("pfsp_weights: wins and episodes must have one entry per member")
+    if power < 0:
+        raise ValueError(f"pfsp_weights: power must be >= 0, got {power}")
+    out = []
+    for w, n in zip(wins, episodes):
+        if not 0 <= w <= n:
+            raise ValueError(f"pfsp_weights: 0 <= wins <= episodes, got {(w, n)}")
+        out.append(1.0 if power == 0 else (1.0 - (w + 1.0) / (n + 2.0)) ** float(power))
+    return out
+
+
+def apportion(weights, total):
+    """Integer shares of ``total`` in proportion to ``weights`` by the largest-remainder method: the floors of the quotas, then one more to
+    the largest remainders, ties going to the lower index.  When ``total >= len(weights)`` every member first gets 1 share and the rest is
+    apportioned, so a member with a small weight keeps being measured.  All-zero weights count as equal.  Deterministic."""
+    k, total = len(weights), int(total)
+    if total < 0 or any(not w >= 0 for w in weights):
+        raise ValueError(f"apportion: total >= 0 and weights >= 0, got {(list(weights), total)}")
+    if k == 0:
+        return []
+    weights = [Fraction(float(w)) for w in weights]              # exact: the floors and the order of the remainders do not depend on rounding
+    if sum(weights) <= 0:
+        weights = [Fraction(1)] * k
+    base = 1 if total >= k else 0
+    rest, scale = total - base * k, sum(weights)
+    quotas = [rest * w / scale for w in weights]
+    shares = [q.numerator // q.denominator for q in quotas]
+    order = sorted(range(k), key=lambda i: (-(quotas[i] - shares[i]), i))
+    for i in order[:rest - sum(shares)]:
+        shares[i] += 1
+    return [base + s for s in shares]
+
+
+def assign_blocks_weighted(num_blocks, filled, latest_share, weights, generator):
+    """``assign_blocks`` with the non-live blocks dealt in proportion to ``weights`` (one per snapshot 1 .. ``filled``): the live blocks are
+    drawn exactly as there, and the rest of the permuted order is cut into runs of the lengths ``apportion(weights, rest)``, snapshot 1
+    first.  With equal weights the snapshots' counts are those of ``assign_blocks``."""
+    if num_blocks < 1 or filled < 0 or not 0.0 <= latest_share <= 1.0:
+        raise ValueError(f"assign_blocks_weighted: num_blocks >= 1, filled >= 0 and 0 <= latest_share <= 1, got {(num_blocks, filled, latest_share)}")
+    if len(weights) != filled:
+        raise ValueError(f"assign_blocks_weighted: one weight per filled snapshot ({filled}), got {len(weights)}")
+    slots = torch.zeros(num_blocks, dtype=torch.int32)
+    if filled == 0:
+        return slots
+    perm = torch.randperm(num_blocks, generator=generator)
+    live = 0 if latest_share == 0 else min(num_blocks, max(1, round(latest_share * num_blocks)))
+    rest = perm[live:]
+    shares = apportion(weights, len(rest))
+    slots[rest] = torch.repeat_interleave(1 + torch.arange(filled, dtype=torch.int32), torch.tensor(shares, dtype=torch.long))
+    return slots
+
+
 class OpponentPool:
     is_opponent_pool = True
 
@@ -55,6 +131,10 @@ class OpponentPool:
             ac.load_state_dict(live.ac.state_dict())              # never assigned before its first push; a stale table still meets a sane actor
             self.members.append(FusedActor(ac, self.device, seed=live.seed, step_counter=live.step_counter))
         self.filled, self._next = 0, 0                           # snapshots written; ring position of the next push (member 1 + _next)
+        self.pushed_at = [None] * self.capacity                  # per snapshot member 1 .. capacity: the evolution that pushed it (None: not told)
+        # the six outcome counts per member (lg_dec_member_outcome_post): rows = members, never re-allocated (a captured graph holds the addresses)
+        self.member_accum = torch.zeros(capi.LG_DEC_MEMBER_OUTCOME_ROWS, capi.LG_DEC_OUTCOME_NUM_COUNTS, dtype=torch.int64, device=self.device)
+        self.member_totals = torch.zeros_like(self.member_accum)
         self._creations = [m.creations for m in self.members]
         self._pool = capi.dec_pool_create([m.handle.value for m in self.members], role, self.device.index or 0)
         self._slots = self._slots_host = self._scratch = None
@@ -91,33 +171,57 @@ class OpponentPool:
         self._slots_host = slots.clone()
         self._slots.copy_(slots)
 
-    def assign(self, generator=None):
-        """Draw a new assignment of blocks to members (``assign_blocks``) and write it to the device table.  Returns the CPU table."""
+    def assign(self, generator=None, weights=None):
+        """Draw a new assignment of blocks to members and write it to the device table: ``assign_blocks``, or with ``weights`` (one per filled
+        snapshot) ``assign_blocks_weighted``.  Returns the CPU table."""
         if self._slots is None:
             raise RuntimeError("the slot table has no size yet: construct the pool with num_envs or call slot_table(num_envs) first")
         if generator is None:
             generator = torch.Generator().manual_seed(self.seed + self._assignments)
         self._assignments += 1
-        slots = assign_blocks(self._slots.shape[0], self.filled, self.latest_share, generator)
+        if weights is None:
+            slots = assign_blocks(self._slots.shape[0], self.filled, self.latest_share, generator)
+        else:
+            slots = assign_blocks_weighted(self._slots.shape[0], self.filled, self.latest_share, list(weights), generator)
         self.set_slots(slots)
         return slots
 
     # ------------------------------------------------------------------ snapshots
-    def push(self, state_dict):
+    def push(self, state_dict, pushed_at=None):
         """Load ``state_dict`` (of the live actor's ``ActorCritic``) into the next ring slot, the oldest snapshot overwritten, and repack that
-        member on the device -- in place, so it is visible underneath a captured graph.  Returns the member's index."""
+        member on the device -- in place, so it is visible underneath a captured graph.  ``pushed_at``: the evolution that pushes (recorded
+        per snapshot).  The outcome counts of the overwritten row and of row 0 are zeroed, in place and stream-ordered: the live member is
+        about to be trained, so both rows stand for new opponents.  Returns the member's index."""
         index = 1 + self._next
         member = self.members[index]
         member.ac.load_state_dict(state_dict)
         member.sync_device()
+        self.pushed_at[index - 1] = None if pushed_at is None else int(pushed_at)
+        self.reset_member_totals(rows=(0, index))
         self._next = (self._next + 1) % self.capacity
         self.filled = min(self.filled + 1, self.capacity)
         return index
 
+    # ------------------------------------------------------------------ outcomes per member
+    def member_totals_host(self):
+        """The running counts of members 0 .. ``filled`` as a list of dicts (``capi.DEC_OUTCOME_COUNTS`` -> int), after ONE synchronising copy."""
+        rows = self.member_totals[:self.filled + 1].cpu().tolist()
+        return [dict(zip(capi.DEC_OUTCOME_COUNTS, (int(v) for v in row))) for row in rows]
+
+    def reset_member_totals(self, rows=None):
+        """Zero the running counts of ``rows`` (all when None): in place and stream-ordered, no synchronisation."""
+        if rows is None:
+            self.member_totals.zero_()
+        else:
+            for r in rows:
+                self.member_totals[int(r)].zero_()
+
     def state(self):
-        """For checkpoints: the snapshots' state dicts (clones), ``filled`` and the ring position."""
+        """For checkpoints: the snapshots' state dicts (clones), ``filled``, the ring position, the evolution that pushed each snapshot (-1: not
+        told) and the outcome counts per member."""
         return {"filled": self.filled, "next": self._next,
-                "snapshots": [{k: v.detach().clone() for k, v in m.ac.state_dict().items()} for m in self.members[1:]]}
+                "snapshots": [{k: v.detach().clone() for k, v in m.ac.state_dict().items()} for m in self.members[1:]],
+                "pushed_at": [-1 if p is None else int(p) for p in self.pushed_at], "member_totals": self.member_totals.detach().cpu().clone()}
 
     def load_state(self, d):
         snapshots = d["snapshots"]
@@ -127,6 +231,10 @@ class OpponentPool:
             member.ac.load_state_dict(sd)
             member.sync_device()
         self.filled, self._next = int(d["filled"]), int(d["next"])
+        if "pushed_at" in d:                                      # checkpoints without these keys load as before
+            self.pushed_at = [None if int(p) < 0 else int(p) for p in d["pushed_at"]]
+        if "member_totals" in d:
+            self.member_totals.copy_(torch.as_tensor(d["member_totals"], dtype=torch.int64))
 
     # ------------------------------------------------------------------ separate launches (no shared kernel: wide precision 0)
     def act_separate(self, obs, deterministic):

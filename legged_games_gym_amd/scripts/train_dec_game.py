@@ -8,7 +8,9 @@ replay (off by default: the generic VecEnv loop).  ``--outcome_stats`` (either p
 falls and low-level time-outs among the finished episodes and their mean length, as ``Episode/outcome_*`` of both agents' tables.
 ``--opponent_pool K [--opponent_latest_share F]`` (device path only) lets the opponent of the learning agent be a mixture: the live opponent
 in the share F (default 0.5) of the 32-env blocks, up to K frozen earlier versions of it in the rest (``rl.OpponentPool``, DESIGN.md G19);
-the checkpoints then carry the pools.  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
+the checkpoints then carry the pools.  With ``--outcome_stats`` as well, the outcomes are also counted per pool member and logged to
+``opponents.csv``, and ``--opponent_priority P`` (P > 0) deals the non-live blocks by prioritised fictitious self-play: a past opponent the
+learner loses to gets more envs.  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
 from legged_games_gym_amd.envs import a1_game
 from legged_games_gym_amd.utils import get_args
@@ -26,6 +28,8 @@ def train(args):
     if args.opponent_pool:                   # runner keys, read with .get() as well
         runner_cfg = task_registry.get_cfgs(args.task)[1].runner
         runner_cfg.opponent_pool_size, runner_cfg.opponent_latest_share = args.opponent_pool, args.opponent_latest_share
+    if args.opponent_priority:               # a runner key as well; the runner refuses it without the pool or the outcome statistics
+        task_registry.get_cfgs(args.task)[1].runner.opponent_priority = args.opponent_priority
     if args.outcome_stats:                   # read with getattr() by the env: no field of the registered config classes
         task_registry.get_cfgs(args.task)[0].env.outcome_stats = True
     env, env_cfg = task_registry.make_env(name=args.task, args=args)

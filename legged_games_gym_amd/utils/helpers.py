@@ -178,6 +178,9 @@ def get_args(argv=None):
                         "besides the live one (runner key opponent_pool_size; 0 = off, at most 15)")
     p.add_argument("--opponent_latest_share", type=float, default=0.5,
                    help="with --opponent_pool: the share of the 32-env blocks that meet the live opponent (runner key opponent_latest_share)")
+    p.add_argument("--opponent_priority", type=float, default=0.0,
+                   help="with --opponent_pool and --outcome_stats: deal the non-live blocks in proportion to (1 - learner's win rate against the member) ** P "
+                        "instead of round-robin (runner key opponent_priority; 0 = off)")
     # flags gymutil.parse_arguments contributes
     p.add_argument("--sim_device", type=str, default="cuda:0")
     p.add_argument("--pipeline", type=str, default="gpu")

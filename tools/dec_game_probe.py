@@ -21,7 +21,15 @@ plain ``lg_dec_game_act``, the way the default mode times its two variants: grap
 rounds in one process.  Variants: the plain launch, and the pooled launch with 1, 4 and 8 members (``--members``), the 32-env blocks dealt
 round-robin over the members, so that M weight sets are in flight at once -> profiles/dec_pool_act.json.
 
-    python tools/dec_game_probe.py --pool [--envs 2000 4096] [--members 1 4 8]"""
+    python tools/dec_game_probe.py --pool [--envs 2000 4096] [--members 1 4 8]
+
+``--member-outcome`` times the graphed three-launch policy step with an opponent pool of 4 members on the prey role and the outcome
+statistics on, its last launch ``lg_dec_outcome_post`` (k_dec_outcome) against ``lg_dec_member_outcome_post`` (k_member_outcome, include/
+legged_dec_game_member_outcome.h: the counts kept per pool member as well), by the method of ``--outcome``: both variants in one process,
+alternating repeats, HIP events, median and min .. max per variant and of the difference repeat by repeat ->
+profiles/dec_member_outcome_step.json.
+
+    python tools/dec_game_probe.py --member-outcome [--envs 2000 4096] [--step-replays 2000] [--repeats 5]"""
 import argparse
 import json
 import os
@@ -274,6 +282,60 @@ def outcome_main(args):
     print("wrote", out)
 
 
+def member_outcome_main(args):
+    """The graphed three-launch policy step against a 4-member prey pool with the outcome statistics on, the last launch k_dec_outcome (pooled
+    counts) against k_member_outcome (the counts per pool member as well): same process, same sizes, alternating repeats; the difference
+    member - pooled repeat by repeat."""
+    from legged_games_gym_amd.rl import OpponentPool
+    members = 4
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.step_replays, "repeats": args.repeats, "pool_role": "prey",
+              "pool_members": members, "unit": "us per graphed three-launch policy step", "envs": {}}
+    names = ("lg_dec_outcome_post", "lg_dec_member_outcome_post")
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            envs, steps, pools = [], [], []
+            for per_member in (False, True):
+                env = make_env(n, args.mesh, tmp)
+                env.enable_outcome_stats()
+                ctr = env.ll_env._sim.buf["step_counter"]
+                torch.manual_seed(1)
+                pred, prey = [FusedActor(ActorCritic(no, no, na, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV), DEV, seed=seed, step_counter=ctr)
+                              for no, na, seed in ((3, 2, 1 + 7919 + 104729), (16, 4, 1 + 7919))]
+                pool = OpponentPool(prey, lambda: ActorCritic(16, 16, 4, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV), members - 1, "prey", seed=1, num_envs=n)
+                for k in range(members - 1):
+                    torch.manual_seed(10 + k)
+                    pool.push(ActorCritic(16, 16, 4, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV).state_dict(), pushed_at=k)
+                pool.set_slots(torch.arange(pool.slot_table(n).shape[0]) % members)          # the blocks dealt round-robin: all four members in flight
+                if per_member:
+                    env.enable_member_outcomes(pool)     # before the capture: the graph keeps the launch the switch selected
+                envs.append(env); pools.append(pool)
+                steps.append(env.make_graphed_policy_step(pred, pool))
+                assert env.last_act_rc == 0
+            for fn in steps:
+                timed(fn, args.step_replays // 4)                # warm both graphs before the first timed window
+            t = [[], []]
+            for _ in range(args.repeats):
+                for i, fn in enumerate(steps):
+                    t[i].append(timed(fn, args.step_replays))
+            row = {f"{name}_policy_step": spread(x) for name, x in zip(names, t)}
+            row["member_minus_pooled"] = spread([y - x for x, y in zip(t[0], t[1])])
+            for env in envs:
+                assert torch.isfinite(env.obs_buf_prey).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            totals, rows = envs[1].outcome_totals(), pools[1].member_totals_host()
+            assert totals["episodes"] > 0 and {k: sum(r[k] for r in rows) for k in totals} == totals and not pools[0].member_totals.any()
+            row["outcome_totals"], row["member_totals"] = totals, rows
+            result["envs"][str(n)] = row
+            print(f"{n} envs, graphed three-launch policy step, last launch: " + "; ".join(
+                f"{name} {statistics.median(x):.1f} us ({min(x):.1f} .. {max(x):.1f})" for name, x in zip(names, t)), flush=True)
+            d = row["member_minus_pooled"]
+            print(f"  per member - pooled {d['median_us']:+.2f} us ({d['min_us']:+.2f} .. {d['max_us']:+.2f})", flush=True)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_member_outcome_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 DEFAULT_OUT = os.path.join(REPO, "profiles", "dec_game_act.json")
 
 
@@ -291,9 +353,13 @@ def main():
     ap.add_argument("--mesh", default="plane", help="--outcome: terrain of the low-level env (the registered task: plane)")
     ap.add_argument("--pool", action="store_true", help="time lg_dec_pool_act with --members members on the prey role against lg_dec_game_act; writes profiles/dec_pool_act.json")
     ap.add_argument("--members", type=int, nargs="+", default=[1, 4, 8], help="--pool: pool sizes to time")
+    ap.add_argument("--member-outcome", action="store_true", help="time the graphed policy step against a 4-member prey pool with lg_dec_outcome_post and with "
+                    "lg_dec_member_outcome_post as the last launch; writes profiles/dec_member_outcome_step.json")
     args = ap.parse_args()
     if args.outcome:
         return outcome_main(args)
+    if args.member_outcome:
+        return member_outcome_main(args)
     if args.pool:
         return pool_main(args)
     out = {"device": torch.cuda.get_device_name(0), "graph_steps": args.graph_steps, "replays": args.replays, "pairs": args.pairs, "discarded_pairs": args.discard,
