@@ -13,6 +13,7 @@
 #include "lg_device.h"
 #include "lg_policy.h"
 #include "lg_dec_game_post.h"  // dec_post_env<OUTCOME>: one env of the post stage (shared with lg_dec_game_outcome.hip)
+#include "lg_outcome_reduce.h" // the reductions, the ticket and the publication behind it (shared with every outcome kernel)
 #include "lg_dec_game_common.h"
 #include "lg_dec_game_act.h"   // dec_actor_role<ROLE>: one role of the shared actor launch (shared with lg_pool_act.hip)
 
@@ -38,52 +39,31 @@ __global__ __launch_bounds__(LG_DEC_BLOCK) void k_dec_pre(lg_dec_game_params P, 
 
 __global__ __launch_bounds__(LG_DEC_BLOCK) void k_dec_post(lg_dec_game_params P, lg_dec_game_buffers B, int64_t step_arg) {
 #pragma clang fp contract(off)
-    __shared__ float s_part[LG_DEC_BLOCK / 64][4];
+    __shared__ float s_part[LG_DEC_WAVES][4];
     const int e = blockIdx.x * LG_DEC_BLOCK + threadIdx.x;
     float red[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (e < P.num_envs) dec_post_env<false>(P, B, nullptr, e, step_arg >= 0 ? step_arg : B.ll_step_counter[0], red, nullptr);
     // extras["episode"] (:298-305): count and episode sums of this workgroup's done envs -> one atomic per value -> the workgroup with the
-    // last ticket publishes the means and leaves accumulator and ticket zeroed for the next launch
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) red[i] += __shfl_xor(red[i], o);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) s_part[threadIdx.x >> 6][i] = red[i];
-    }
+    // last ticket publishes the means and leaves accumulator and ticket zeroed for the next launch (lg_outcome_reduce.h)
+    wave_sum4(red);
+    store_wave_partials(s_part, red);
     __syncthreads();
     if (threadIdx.x != 0) return;
     float tot[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { tot[i] = s_part[0][i]; for (int w = 1; w < LG_DEC_BLOCK / 64; w++) tot[i] += s_part[w][i]; }
-    if (tot[0] > 0.0f) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) atomicAdd(B.extras_accum + i, tot[i]);
-    }
-    __threadfence();                                               // this workgroup's atomics are performed before its ticket is seen
-    const unsigned int ticket = atomicAdd(B.extras_ticket, 1u);
-    if (ticket != gridDim.x - 1) return;
-    __threadfence();                                               // agent-scope acquire
-    // the accumulators were updated with device-scope atomics by other workgroups: read them past the L1
-    const float cnt = __hip_atomic_load(B.extras_accum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int i = 0; i < LG_DEC_NUM_SUMS; i++) {
-        const float v = __hip_atomic_load(B.extras_accum + 1 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cnt > 0.0f) B.episode_means[i] = v / cnt / P.max_episode_length_s;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; i++) __hip_atomic_store(B.extras_accum + i, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(B.extras_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    sum_wave_partials(s_part, tot);
+    if (tot[0] > 0.0f) add_episode_sums(B.extras_accum, tot);
+    if (!draw_last_ticket(B.extras_ticket)) return;
+    publish_episode_means<true>(B.extras_accum, B.episode_means, P.max_episode_length_s);
+    reset_ticket(B.extras_ticket);
 }
 
 int launch_dec_pre(const lg_dec_game_params &P, const lg_dec_game_buffers &B, void *stream) {
-    hipLaunchKernelGGL(k_dec_pre, dim3((P.num_envs + LG_DEC_BLOCK - 1) / LG_DEC_BLOCK), dim3(LG_DEC_BLOCK), 0, (hipStream_t)stream, P, B);
+    hipLaunchKernelGGL(k_dec_pre, dec_grid(P), dim3(LG_DEC_BLOCK), 0, (hipStream_t)stream, P, B);
     return (int)hipGetLastError();
 }
 
 int launch_dec_post(const lg_dec_game_params &P, const lg_dec_game_buffers &B, int64_t step, void *stream) {
-    hipLaunchKernelGGL(k_dec_post, dim3((P.num_envs + LG_DEC_BLOCK - 1) / LG_DEC_BLOCK), dim3(LG_DEC_BLOCK), 0, (hipStream_t)stream, P, B, step);
+    hipLaunchKernelGGL(k_dec_post, dec_grid(P), dim3(LG_DEC_BLOCK), 0, (hipStream_t)stream, P, B, step);
     return (int)hipGetLastError();
 }
 

@@ -9,6 +9,8 @@ namespace lg {
 
 enum { RNG_GAME_DOF = 18 };      // Philox purpose of the joint reset; root and predator: RNG_GAME_ROOT / RNG_GAME_PREDATOR (lg_game_post.h)
 #define LG_DEC_BLOCK 256
+#define LG_DEC_WAVES (LG_DEC_BLOCK / 64)
+inline dim3 dec_grid(const lg_dec_game_params &P) { return dim3((P.num_envs + LG_DEC_BLOCK - 1) / LG_DEC_BLOCK); }      // one thread per env
 
 // One env of post_physics_step (:236-258).  red = (1, evasion sum, pursuit sum, termination sum) of a done env as the sums stood before
 // zeroing (:301-305), untouched otherwise.

@@ -1,6 +1,6 @@
 // lg_member_outcome_entry.h -- C entry points of the decentralised game's outcome statistics per pool member
 // (include/legged_dec_game_member_outcome.h).  Host code only: the kernel lives in lg_member_outcome.hip behind launch_member_outcome.
-// Included from lg_kernels.hip after lg_dec_game.h (dec_game_check, dec_game_post_check).
+// Included from lg_kernels.hip after lg_dec_game.h (dec_game_check, dec_game_post_check) and lg_dec_game_outcome_entry.h (dec_outcome_check).
 #pragma once
 #include "../../include/legged_dec_game_member_outcome.h"
 
@@ -16,7 +16,7 @@ int lg_dec_member_outcome_post(const lg_dec_game_params *P, const lg_dec_game_bu
     if (!O) return fail(-1, "lg_dec_member_outcome_post: lg_dec_outcome_buffers is null");
     if (!M) return fail(-1, "lg_dec_member_outcome_post: lg_dec_member_outcome_buffers is null");
     if (int rc = dec_game_check(P, B)) return rc;
-    if (!O->ll_time_out_buf || !O->accum || !O->means || !O->totals) return fail(-1, "lg_dec_member_outcome_post: a pointer of lg_dec_outcome_buffers is null");
+    if (int rc = dec_outcome_check("lg_dec_member_outcome_post", O)) return rc;
     if (!M->block_slot || !M->member_accum || !M->member_totals) return fail(-1, "lg_dec_member_outcome_post: a pointer of lg_dec_member_outcome_buffers is null");
     if (M->count < 1 || M->count > LG_DEC_MEMBER_OUTCOME_ROWS) return fail(-2, "lg_dec_member_outcome_post: count must be 1 .. LG_DEC_MEMBER_OUTCOME_ROWS");
     if (int rc = dec_game_post_check("lg_dec_member_outcome_post", P, B, common_step_counter)) return rc;
