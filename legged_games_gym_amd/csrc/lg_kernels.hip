@@ -280,7 +280,8 @@ LG_DEV void contact_assemble(const Contact &c, const lg_params &P, float kn, AI 
         pA.v = pA.v - f;
     }
 }
-LG_DEV void contact_evaluate(Contact &c, const lg_params &P, float kn, float mu, S6 acc) {
+// more: another pass follows (wave-uniform) -- only that pass reads the corrector's results
+LG_DEV void contact_evaluate(Contact &c, const lg_params &P, float kn, float mu, S6 acc, bool more = true) {
     if (c.on) {
         V3 v1 = c.vc + (acc.v + cross(acc.w, c.r)) * P.sim_dt;
         float vn = dot(c.n, v1);
@@ -289,6 +290,7 @@ LG_DEV void contact_evaluate(Contact &c, const lg_params &P, float kn, float mu,
         if (fn <= 0.0f) { c.on = false; c.f = v3(0, 0, 0); }
         else {
             c.f = c.n * fn - vt * c.bt + c.fs;                                               // force this pass applied
+            if (!more) return;
             // corrector for the next pass: beyond the cone -> slide with mu f_n against the predicted slip direction;
             // inside it -> re-aim the secant at the predicted end-of-step slip speed (sticking points keep the stick impedance)
             float vtm = sqrtf(dot(vt, vt)), cone = mu * fn;
@@ -585,7 +587,9 @@ struct NoWait { LG_DEV void operator()() const {} };
 // OFFLOAD: the limb bodies' (I0, p0) are computed by the helper waves meanwhile and read from `bt` after `torques_ready`.
 // SC: self-collision (needs `sc`); `last`: the exported net contact forces (Frep / Fbase after this call) include the
 // self-collision forces -- the policy step's last sub-step, or the sub-step entry point.
-template <class T, bool HF, class Ready = NoWait, bool OFFLOAD = false, bool SC = false>
+// LAST_LEAN: the last articulated-body pass skips what only a next pass would read -- the friction corrector of
+// contact_evaluate and the speed-limit detection.
+template <class T, bool HF, class Ready = NoWait, bool OFFLOAD = false, bool SC = false, bool LAST_LEAN = false>
 LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float (&root)[13], float (&q)[T::L], float (&qd)[T::L],
                             const float (&tau)[T::L], float base_mass, float mu,
                             float (&Frep)[T::NREP][3], float (&Fbase)[3], Ready torques_ready = Ready(),
@@ -721,6 +725,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
     for (int j = 0; j < L; j++) vl[j] = 0.0f;
 #pragma unroll 1
     for (int pass = 0; pass < LG_PASSES; pass++) {
+        const bool more = !LAST_LEAN || pass < LG_PASSES - 1;       // wave-uniform: a scalar branch on the loop counter
         AI Ia; S6 pa;
         if constexpr (SC) if (pass == LG_PASSES - 1) {     // self-collision records enter the final pass
             const int ln = threadIdx.x % LG_BLOCK;
@@ -801,7 +806,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
         bool ok = solve6(IAb, rhs, a0);
         if (!ok) { a0[0] = a0[1] = a0[2] = a0[3] = a0[4] = a0[5] = 0.0f; }
         acc0.w = v3(a0[0], a0[1], a0[2]); acc0.v = v3(a0[3], a0[4], a0[5]);
-        contact_evaluate(cb, P, kn, mu, acc0);
+        contact_evaluate(cb, P, kn, mu, acc0, more);
         LG_PROF(PF_BASE);
         S6 a = acc0;
 #pragma unroll
@@ -813,12 +818,12 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
             a.w = ap.w + ax[j] * qdd;
             a.v = ap.v;
             uu[j] = qdd;
-            {
+            if (more) {
                 float lim = tab[j * LG_JS + J_VLIM], qn = qd[j] + dt * qdd;
                 if (lim > 0.0f && vl[j] == 0.0f && fabsf(qn) > lim) vl[j] = qn > 0.0f ? 1.0f : -1.0f;
             }
 #pragma unroll
-            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) contact_evaluate(cl[i], P, kn, mu, a);
+            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) contact_evaluate(cl[i], P, kn, mu, a, more);
         }
         LG_PROF(PF_OUTWARD);
     }
@@ -1691,8 +1696,10 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
                     for (int j = 0; j < L; j++) tau[j] = lds_tau[j][lane];
                 }
             };
-            physics_substep<T, HF, decltype(join), OFF, SC>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, join, sh.bt, sh.fk, &sh.fk_ready, sub0 + it + 1,
-                                                            sc_store.get(), it == P.decimation - 1, SC && NW == LG_STEP_WAVES);
+            // lean last pass: on for the four-wave quadruped kernels on the plane (measured there: DESIGN.md section 10)
+            constexpr bool LEAN = NW == LG_STEP_WAVES && L <= 3 && !HF;
+            physics_substep<T, HF, decltype(join), OFF, SC, LEAN>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, join, sh.bt, sh.fk, &sh.fk_ready, sub0 + it + 1,
+                                                                  sc_store.get(), it == P.decimation - 1, SC && NW == LG_STEP_WAVES);
         } else {
             physics_substep<T, HF, NoWait, false, SC>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, NoWait(), nullptr, nullptr, nullptr, 0,
                                                       sc_store.get(), it == P.decimation - 1);

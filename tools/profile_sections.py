@@ -20,7 +20,7 @@ if LIGHT:
     LIB = os.path.join(CSRC, "liblegged_hip_prof_light.so")
 if sys.argv[1:2] == ["build"]:
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value", "-fno-slp-vectorize",
-           "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-DLG_PROFILE"] + (["-DLG_PROFILE_LIGHT"] if LIGHT else []) + ["-o", LIB, os.path.join(CSRC, "lg_kernels.hip"), os.path.join(CSRC, "lg_game_act.hip")]
+           "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-mllvm", "-amdgpu-mfma-vgpr-form", "-mllvm", "-amdgpu-spill-vgpr-to-agpr=0", "-DLG_PROFILE"] + (["-DLG_PROFILE_LIGHT"] if LIGHT else []) + ["-o", LIB] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))       # every HIP source: the library must load whole
     print(" ".join(cmd)); subprocess.run(cmd, check=True); sys.exit(0)
 
 os.environ["LG_HIP_LIB"] = LIB
