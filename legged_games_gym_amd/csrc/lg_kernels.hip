@@ -84,6 +84,40 @@ struct RollArgs {
     int     *cursor;           // ... and the device-held step the next one resumes at (written by roll_finish)
 };
 
+// Rollout kernel: what the rigid-body wave reads behind the physics of a step, as host-filled blocks of the kernarg image in the order of
+// use.  A step fetches each block with one to three wide scalar loads (karg_request / karg_take) in front of the barrier ahead of its first
+// use -- read field by field through the kernel arguments, every value came as its own scalar load with its own wait in front of the
+// instruction using it, a scalar-cache round trip each on a wave that has nothing else to issue.  Dwords and pointers only, a multiple
+// of 8 dwords each; filled at every launch from the current lg_params / lg_buffers (fill_post_args).
+struct PostHead {              // commands, push, termination: from the last sub-step to the reward terms
+    int32_t  resample_interval, heading_command, push_interval, max_episode_length;
+    float    max_push_vel; uint32_t termination_mask, penalised_mask, _pad0;
+    int64_t *episode_length_buf; float *commands, *contact_forces; uint32_t _pad[2];
+};
+struct PostRew {               // reward terms, their scales, the reset block's inputs
+    float    dt_policy, soft_dof_vel_limit, soft_torque_limit, max_contact_force, base_height_target, tracking_sigma;
+    int32_t  only_positive_rewards; uint32_t slot_mask /* bit t: reward_slot[t] >= 0 */; int32_t num_height_points, terrain_curriculum;
+    float   *last_actions, *feet_air_time; uint8_t *last_contacts;
+    float    reward_scale[LG_NUM_REWARD_TERMS];
+    float   *env_origins; uint32_t _pad[2];
+};
+struct PostObs {               // observations of the step
+    float    obs_scale_lin_vel, obs_scale_ang_vel, obs_scale_dof_pos, obs_scale_dof_vel;
+    float    noise_lin_vel, noise_ang_vel, noise_gravity, noise_dof_pos, noise_dof_vel, clip_observations;
+    int32_t  add_noise, num_obs, num_envs; uint32_t _pad;
+    float   *roll_obs;         // RollArgs::obs
+};
+struct PostStore {             // state write-back per (env, limb) lane ...
+    float   *dof_state, *actions, *torques, *last_actions, *last_dof_vel, *feet_air_time; uint8_t *last_contacts; float *root_states;
+};
+struct PostStoreEnv {          // ... and per env, with the step's row of the rollout storage (requested while the lanes' stores are formed)
+    float   *last_root_vel, *commands, *base_lin_vel, *base_ang_vel, *projected_gravity, *rew_buf; uint8_t *reset_buf, *time_out_buf;
+    int64_t *episode_length_buf; float *roll_rew; uint8_t *roll_done, *roll_time_outs;
+};
+struct PostArgs { PostHead head; PostRew rew; PostObs obs; PostStore store; PostStoreEnv store_env; };
+static_assert(sizeof(PostHead) == 64 && sizeof(PostRew) == 160 && sizeof(PostObs) == 64 && sizeof(PostStore) == 64 && sizeof(PostStoreEnv) == 96, "blocks of whole 8-dword groups, no padding");
+static_assert(LG_NUM_REWARD_TERMS <= 32, "PostRew::slot_mask");
+
 struct KArgs {                 // passed by value: lives in the kernarg segment -> scalar loads
     lg_params  P;
     lg_buffers B;
@@ -107,7 +141,49 @@ struct KArgs {                 // passed by value: lives in the kernarg segment 
     int   spin_limit;             // bound of the LDS hand-over polls (s_sleep rounds); lg_debug_handover() shrinks it
     int   debug_skip;             // test hook: 1 = the rigid-body wave withholds the frame hand-over flag, 2 = the helpers withhold the self-collision flags
     RollArgs roll;                // k_step<..., ROLL> only
+    PostArgs post;                // k_step<..., ROLL> only (behind everything else: only the hidden arguments' offsets move in the other kernels)
 };
+
+// The kernel arguments as one policy step of the rollout kernel sees them (see one_step in k_step): the kernarg segment itself, through a
+// pointer the optimiser cannot follow across the step loop's back edge.  Every other kernel reads its by-value argument.
+template <bool ROLL> LG_DEV const KArgs &step_args(const KArgs &A) {
+    if constexpr (ROLL) {
+        typedef __attribute__((address_space(4))) const KArgs *KernArgs;
+        KernArgs p = (KernArgs)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(p));
+        return *(const KArgs *)p;
+    } else return A;
+}
+
+// One block of the kernarg image (reached through step_args) in scalar registers: karg_request issues s_load_dwordx16 / x8 for the whole
+// block, karg_take waits for them -- once, all of it -- and hands the block over as a value.  The empty asm between the two keeps the
+// optimiser from taking the wide loads apart into one load per field at its point of use.
+typedef uint32_t lg_u32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t lg_u32x8 __attribute__((ext_vector_type(8)));
+template <class S> struct KargFetch {
+    static_assert(sizeof(S) % 32 == 0 && sizeof(S) <= 192, "blocks are fetched 16 and 8 dwords at a time");
+    static constexpr int N16 = sizeof(S) / 64, N8 = sizeof(S) % 64 / 32;
+    lg_u32x16 a[N16 ? N16 : 1];
+    lg_u32x8  b;
+};
+template <class S> LG_DEV KargFetch<S> karg_request(const S &src) {
+    typedef lg_u32x16 __attribute__((aligned(4))) w16;
+    typedef lg_u32x8 __attribute__((aligned(4))) w8;
+    typedef __attribute__((address_space(4))) const char *kptr;
+    const kptr p = (kptr)reinterpret_cast<const char *>(&src);
+    KargFetch<S> f;
+#pragma unroll
+    for (int i = 0; i < KargFetch<S>::N16; i++) f.a[i] = *(__attribute__((address_space(4))) const w16 *)(p + 64 * i);
+    if constexpr (KargFetch<S>::N8 != 0) f.b = *(__attribute__((address_space(4))) const w8 *)(p + 64 * KargFetch<S>::N16);
+    return f;
+}
+template <class S> LG_DEV S karg_take(KargFetch<S> &f) {
+    S out;
+#pragma unroll
+    for (int i = 0; i < KargFetch<S>::N16; i++) { asm volatile("" : "+s"(f.a[i])); __builtin_memcpy(reinterpret_cast<char *>(&out) + 64 * i, &f.a[i], 64); }
+    if constexpr (KargFetch<S>::N8 != 0) { asm volatile("" : "+s"(f.b)); __builtin_memcpy(reinterpret_cast<char *>(&out) + 64 * KargFetch<S>::N16, &f.b, 32); }
+    return out;
+}
 
 // commands.curriculum: the lin_vel_x range every command draw reads (device buffer), or null = the by-value P.cmd_lin_vel_x
 LG_DEV const double *cmd_x_range(const KArgs &A) { return A.P.cmd_curriculum ? A.B.cmd_range : nullptr; }
@@ -589,7 +665,7 @@ struct NoWait { LG_DEV void operator()() const {} };
 // self-collision forces -- the policy step's last sub-step, or the sub-step entry point.
 // LAST_LEAN: the last articulated-body pass skips what only a next pass would read -- the friction corrector of
 // contact_evaluate and the speed-limit detection.
-template <class T, bool HF, class Ready = NoWait, bool OFFLOAD = false, bool SC = false, bool LAST_LEAN = false>
+template <class T, bool HF, class Ready = NoWait, bool OFFLOAD = false, bool SC = false, bool LAST_LEAN = false, bool ROLL = false>
 LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float (&root)[13], float (&q)[T::L], float (&qd)[T::L],
                             const float (&tau)[T::L], float base_mass, float mu,
                             float (&Frep)[T::NREP][3], float (&Fbase)[3], Ready torques_ready = Ready(),
@@ -599,6 +675,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
     constexpr int K = T::K, L = T::L, NPT = T::NPT;
     const lg_params &P = A.P;
     const float dt = P.sim_dt;
+    const int spin_limit_early = ROLL ? A.spin_limit : 0;          // rollout kernel: read here, no scalar load between the torque hand-over and the end of the passes
     const V3 grav = v3(P.gravity[0], P.gravity[1], P.gravity[2]);
     const float kn = P.contact_stiffness * dt + P.contact_damping;
 
@@ -732,7 +809,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
             if (sc_on_helpers) {                           // detection ran on the helper waves during the first pass
                 volatile int4 *rdy = reinterpret_cast<volatile int4 *>(sc->ready);       // one read covers the three helpers' flags
                 bool arrived = false;
-                for (int spin = 0; spin < A.spin_limit; spin++) {                          // bounded, like the fk hand-over
+                for (int spin = 0; spin < (ROLL ? spin_limit_early : A.spin_limit); spin++) {   // bounded, like the fk hand-over
                     const int r1 = rdy->y, r2 = rdy->z, r3 = rdy->w;
                     if (min(r1, min(r2, r3)) >= substep_no) { arrived = true; break; }
                     __builtin_amdgcn_s_sleep(1);
@@ -1110,20 +1187,22 @@ LG_DEV void reset_values(const KArgs &A, const float *tab, int e, int k, int64_t
 
 // ------------------------------------------------------------------ observations (legged_robot.py:212-230, :100-101)
 // lane k owns slots k*L..k*L+L-1 of each of the four 12-wide groups [base|dof_pos|dof_vel|actions]
-template <class T>
+template <class T, bool UB = false /* the step's uniforms come from a fetched PostObs block (rollout kernel), not from A.P */>
 LG_DEV void write_observations(const KArgs &A, int e, int k, bool live, int64_t step, const float *root, const float (&q)[T::L],
                                const float (&qd)[T::L], const float (&act)[T::L], const float *tab, V3 blv, V3 bav, V3 pg,
                                const float (&cmd)[4], bool heights_from_buffer /* k_obs: also the height block, from measured_heights */,
                                const ResetRand<T> *rr = nullptr, int lane = 0, float *obs_out = nullptr /* instead of B.obs_buf (rollout storage) */,
-                               float *lds_row = nullptr /* rollout kernel: LDS copy of this env's row, the next step's actor input */) {
+                               float *lds_row = nullptr /* rollout kernel: LDS copy of this env's row, the next step's actor input */,
+                               const PostObs *ub = nullptr) {
     constexpr int K = T::K, L = T::L;
     const lg_params &P = A.P;
-    float head[12] = {blv.x * P.obs_scale_lin_vel, blv.y * P.obs_scale_lin_vel, blv.z * P.obs_scale_lin_vel,
-                      bav.x * P.obs_scale_ang_vel, bav.y * P.obs_scale_ang_vel, bav.z * P.obs_scale_ang_vel,
+#define LG_OBS_U(f) (UB ? ub->f : P.f)
+    float head[12] = {blv.x * LG_OBS_U(obs_scale_lin_vel), blv.y * LG_OBS_U(obs_scale_lin_vel), blv.z * LG_OBS_U(obs_scale_lin_vel),
+                      bav.x * LG_OBS_U(obs_scale_ang_vel), bav.y * LG_OBS_U(obs_scale_ang_vel), bav.z * LG_OBS_U(obs_scale_ang_vel),
                       pg.x, pg.y, pg.z,
-                      cmd[0] * P.obs_scale_lin_vel, cmd[1] * P.obs_scale_lin_vel, cmd[2] * P.obs_scale_ang_vel};
-    float hnz[12] = {P.noise_lin_vel, P.noise_lin_vel, P.noise_lin_vel, P.noise_ang_vel, P.noise_ang_vel, P.noise_ang_vel,
-                     P.noise_gravity, P.noise_gravity, P.noise_gravity, 0.0f, 0.0f, 0.0f};
+                      cmd[0] * LG_OBS_U(obs_scale_lin_vel), cmd[1] * LG_OBS_U(obs_scale_lin_vel), cmd[2] * LG_OBS_U(obs_scale_ang_vel)};
+    float hnz[12] = {LG_OBS_U(noise_lin_vel), LG_OBS_U(noise_lin_vel), LG_OBS_U(noise_lin_vel), LG_OBS_U(noise_ang_vel), LG_OBS_U(noise_ang_vel), LG_OBS_U(noise_ang_vel),
+                     LG_OBS_U(noise_gravity), LG_OBS_U(noise_gravity), LG_OBS_U(noise_gravity), 0.0f, 0.0f, 0.0f};
     float val[4][L], nz[4][L];
 #pragma unroll
     for (int j = 0; j < L; j++) {
@@ -1131,15 +1210,15 @@ LG_DEV void write_observations(const KArgs &A, int e, int k, bool live, int64_t 
 #pragma unroll
         for (int kk = 1; kk < K; kk++) { hv = (k == kk) ? head[kk * L + j] : hv; hn = (k == kk) ? hnz[kk * L + j] : hn; }
         val[0][j] = hv; nz[0][j] = hn;
-        val[1][j] = (q[j] - tab[j * LG_JS + J_Q0]) * P.obs_scale_dof_pos; nz[1][j] = P.noise_dof_pos;
-        val[2][j] = qd[j] * P.obs_scale_dof_vel; nz[2][j] = P.noise_dof_vel;
+        val[1][j] = (q[j] - tab[j * LG_JS + J_Q0]) * LG_OBS_U(obs_scale_dof_pos); nz[1][j] = LG_OBS_U(noise_dof_pos);
+        val[2][j] = qd[j] * LG_OBS_U(obs_scale_dof_vel); nz[2][j] = LG_OBS_U(noise_dof_vel);
         val[3][j] = act[j]; nz[3][j] = 0.0f;
     }
-    float *obs = (obs_out ? obs_out : A.B.obs_buf) + (size_t)e * P.num_obs;
+    float *obs = (UB ? obs_out : (obs_out ? obs_out : A.B.obs_buf)) + (size_t)e * LG_OBS_U(num_obs);
 #pragma unroll
     for (int g = 0; g < 4; g++) {
         float u[4], u2[4];
-        const bool noisy = P.add_noise && g < 3;                   // the action group's noise scale is 0 (:230): no draw, same value
+        const bool noisy = LG_OBS_U(add_noise) && g < 3;                   // the action group's noise scale is 0 (:230): no draw, same value
         if (noisy) {
             if (rr) { rr->get(ResetRand<T>::NOISE + g * ResetRand<T>::NZB, lane, u); if (L > 4) rr->get(ResetRand<T>::NOISE + g * ResetRand<T>::NZB + 1, lane, u2); }
             else {
@@ -1154,11 +1233,12 @@ LG_DEV void write_observations(const KArgs &A, int e, int k, bool live, int64_t 
                 float uj = (j < 4) ? u[j & 3] : u2[j & 3];
                 o += (2.0f * uj - 1.0f) * nz[g][j];
             }
-            o = fminf(fmaxf(o, -P.clip_observations), P.clip_observations);
+            o = fminf(fmaxf(o, -LG_OBS_U(clip_observations)), LG_OBS_U(clip_observations));
             if (live) obs[g * 12 + k * L + j] = o;
             if (lds_row) lds_row[g * 12 + k * L + j] = o;
         }
     }
+#undef LG_OBS_U
     if (P.measure_heights && heights_from_buffer) {
         const float *mh = A.B.measured_heights + (size_t)e * P.num_height_points;
         const int nchunk = (P.num_height_points + 3) >> 2;
@@ -1543,7 +1623,8 @@ template <class T> struct SelfStore<true, T> { SelfLds<T> lds; LG_DEV SelfLds<T>
 
 // SC: self-collision between the robot's own links (asset.self_collisions = 0; compiled for the quadruped layouts)
 template <class T, bool NET, bool HF, bool POL = false, int NW = LG_STEP_WAVES, bool SC = false, bool ROLL = false>
-__global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
+__global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A_launch) {
+    const KArgs &A = A_launch;
     static_assert(!NET || (NW == LG_STEP_WAVES && 1 + T::L == NW), "one actuator wave per joint of the limb");
     static_assert(!ROLL || (POL && !HF), "the multi-step rollout kernel is the fused-actor kernel on the plane");
     static_assert(!POL || (NET && NW == LG_POLICY_WAVES && T::K * T::L <= 16), "fused policy needs the four-wave actuator-net kernel");
@@ -1608,6 +1689,15 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     // acquire; all of an env's data stays inside its workgroup), per-step outputs go to the [t] slice of the rollout storage.
     const int e_wg = e, k_wg = k;
     auto one_step = [&](const int rt) {
+    // ROLL: the same for the UNIFORM side.  Loop-invariant code motion lifted every kernel argument a step reads (some 60 buffer pointers,
+    // the reward / observation / noise scales, 20 Philox round keys per draw site) above the step loop, 104 scalar registers could not hold
+    // them, and each use inside the loop came back as a v_readlane from a VGPR lane (542 spilled scalars, 2882 reloads in the kernel text).
+    // A step reads its arguments through a kernel-argument pointer that is re-derived and laundered here: nothing read through it can be
+    // hoisted, and the reads stay scalar loads from the kernarg segment (no copy of KArgs, no device buffer that outlives the launch).
+    const KArgs &A = step_args<ROLL>(A_launch);
+    const lg_params &P = A.P;
+    const lg_buffers &B = A.B;
+    const int N = P.num_envs;
     // ROLL: the loop must not become one giant live range -- without this, loop-invariant code motion hoists the limb-table reads, the
     // per-env constants and the actuator weights of EVERY section above the loop and spills ~260 registers per lane.  Laundering the
     // lane's (env, limb) indices through an empty asm makes every address of the step depend on a per-iteration value.
@@ -1624,7 +1714,7 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     const int64_t step = step0 + rt;
     const int sub0 = ROLL ? rt * P.decimation : 0;
     float *const roll_accum = ROLL ? A.roll.extras + (size_t)rt * (LG_NUM_REWARD_TERMS + 2) : nullptr;
-    float *const roll_obs_out = ROLL ? A.roll.obs + (size_t)(rt + 1) * N * P.num_obs : nullptr;
+    float *const roll_obs_out = nullptr;                        // (ROLL: formed behind P3 from the fetched PostObs block)
 
     if (POL) {
         if (ROLL) {
@@ -1698,7 +1788,7 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
             };
             // lean last pass: on for the four-wave quadruped kernels on the plane (measured there: DESIGN.md section 10)
             constexpr bool LEAN = NW == LG_STEP_WAVES && L <= 3 && !HF;
-            physics_substep<T, HF, decltype(join), OFF, SC, LEAN>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, join, sh.bt, sh.fk, &sh.fk_ready, sub0 + it + 1,
+            physics_substep<T, HF, decltype(join), OFF, SC, LEAN, ROLL>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, join, sh.bt, sh.fk, &sh.fk_ready, sub0 + it + 1,
                                                                   sc_store.get(), it == P.decimation - 1, SC && NW == LG_STEP_WAVES);
         } else {
             physics_substep<T, HF, NoWait, false, SC>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, NoWait(), nullptr, nullptr, nullptr, 0,
@@ -1711,13 +1801,19 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
         asm volatile("" : "+v"(e));
         d0 = e * ND + k * L;
     }
-    int64_t ep_len = B.episode_length_buf[e] + 1;                                   // :114
+    // ROLL: the uniforms of this stretch come in blocks (PostArgs): `U_(block value, argument)` is the argument itself in every other kernel
+#define U_(blk, arg) (ROLL ? (blk) : (arg))
+    // (and lg_rollout_policy runs without height measurements: their code is not compiled into this wave's post-physics stretch)
+    PostHead ph; PostRew pr; PostObs po; PostStore ps; PostStoreEnv pe;
+    KargFetch<PostRew> pr_f; KargFetch<PostObs> po_f; KargFetch<PostStore> ps_f; KargFetch<PostStoreEnv> pe_f;
+    if constexpr (ROLL) { KargFetch<PostHead> ph_f = karg_request(A.post.head); ph = karg_take(ph_f); }
+    int64_t ep_len = U_(ph.episode_length_buf, B.episode_length_buf)[e] + 1;                                   // :114
     V3 blv = quat_rotate_inverse(root + 3, v3(root[7], root[8], root[9]));          // :118-121
     V3 bav = quat_rotate_inverse(root + 3, v3(root[10], root[11], root[12]));
     V3 pg = quat_rotate_inverse(root + 3, v3(0, 0, -1));
     float cmd[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) cmd[i] = B.commands[(size_t)e * 4 + i];
+    for (int i = 0; i < 4; i++) cmd[i] = U_(ph.commands, B.commands)[(size_t)e * 4 + i];
     // Height-field builds of the short chains: everything else the reward / reset block reads from memory is requested here, in front of the
     // two barriers of the height crew, not at its point of use behind them (a barrier is a fence: the compiler cannot lift a load over it,
     // and each was a bare L2 round trip): 66.0 -> 65.3 us on the same box.  Cassie's kernels have no register to hold them that long
@@ -1737,37 +1833,39 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     sh.pose[lane][0] = root[0]; sh.pose[lane][1] = root[1]; sh.pose[lane][2] = root[2]; sh.pose[lane][3] = root[5]; sh.pose[lane][4] = root[6];
     __syncthreads();                                               // P1 (also publishes the helpers' uniforms)
     // _post_physics_step_callback :329-345
-    if (ep_len % P.resample_interval == 0) {
+    if (ep_len % U_(ph.resample_interval, P.resample_interval) == 0) {
         if (NW > 1) { float u[4]; reset_rand.get(ResetRand<T>::CMD_STEP, lane, u); resample_commands_u(P, s_xr, u, cmd); }
         else resample_commands(P, s_xr, e, step, RNG_CMD_STEP, cmd);
     }
-    if (P.heading_command) {
+    if (U_(ph.heading_command, P.heading_command)) {
         V3 fwd = quat_apply(root + 3, v3(1, 0, 0));
         float heading = atan2f(fwd.y, fwd.x);
         cmd[2] = fminf(fmaxf(0.5f * wrap_to_pi(cmd[3] - heading), -1.0f), 1.0f);
     }
     HeightCrew<T, NW> hc;
     float hsum = 0.0f;
-    if (P.measure_heights) hsum = hc.template sample<HF>(A, e, k, live, root[0], root[1], root[2], root[5], root[6]);
+    if (U_(0, P.measure_heights)) hsum = hc.template sample<HF>(A, e, k, live, root[0], root[1], root[2], root[5], root[6]);
     sh.hsum[0][lane] = hsum;
+    if constexpr (ROLL) pr_f = karg_request(A.post.rew);          // arrives under the barrier
     __syncthreads();                                               // P2
+    if constexpr (ROLL) pr = karg_take(pr_f);
     if (NW == 4) hsum = (sh.hsum[0][lane] + sh.hsum[1][lane]) + (sh.hsum[2][lane] + sh.hsum[3][lane]);
     else if (NW == 2) hsum = sh.hsum[0][lane] + sh.hsum[1][lane];
-    if (P.push_interval > 0 && step % P.push_interval == 0) {                     // _push_robots :438-444
+    if (U_(ph.push_interval, P.push_interval) > 0 && step % U_(ph.push_interval, P.push_interval) == 0) {                     // _push_robots :438-444
         float u[4];
         if (NW > 1) reset_rand.get(ResetRand<T>::PUSH, lane, u);
         else rand4(P.seed, e, step, RNG_PUSH, 0, u);
-        root[7] = urange(-P.max_push_vel, P.max_push_vel, u[0]);
-        root[8] = urange(-P.max_push_vel, P.max_push_vel, u[1]);
+        root[7] = urange(-U_(ph.max_push_vel, P.max_push_vel), U_(ph.max_push_vel, P.max_push_vel), u[0]);
+        root[8] = urange(-U_(ph.max_push_vel, P.max_push_vel), U_(ph.max_push_vel, P.max_push_vel), u[1]);
     }
 
     // contact_forces (net contact force tensor, last sub-step) -- also the inputs of termination / rewards
     const int rep0 = 1 + k * NREP;
     if (live) {
-        float *cf = B.contact_forces + ((size_t)e * (1 + K * NREP) + rep0) * 3;
+        float *cf = U_(ph.contact_forces, B.contact_forces) + ((size_t)e * (1 + K * NREP) + rep0) * 3;
 #pragma unroll
         for (int r = 0; r < NREP; r++) { cf[3 * r] = Frep[r][0]; cf[3 * r + 1] = Frep[r][1]; cf[3 * r + 2] = Frep[r][2]; }
-        if (k == 0) { float *c0 = B.contact_forces + (size_t)e * (1 + K * NREP) * 3; c0[0] = Fbase[0]; c0[1] = Fbase[1]; c0[2] = Fbase[2]; }
+        if (k == 0) { float *c0 = U_(ph.contact_forces, B.contact_forces) + (size_t)e * (1 + K * NREP) * 3; c0[0] = Fbase[0]; c0[1] = Fbase[1]; c0[2] = Fbase[2]; }
     }
     LG_PROF(PF_POST_HEIGHTS);
     // check_termination :139-145
@@ -1776,15 +1874,15 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
 #pragma unroll
     for (int r = 0; r < NREP; r++) {
         float n = sqrtf(Frep[r][0] * Frep[r][0] + Frep[r][1] * Frep[r][1] + Frep[r][2] * Frep[r][2]);
-        if ((A.termination_mask >> (rep0 + r)) & 1u) term_local |= (n > 1.0f);
-        if ((A.penalised_mask >> (rep0 + r)) & 1u) coll_local += (n > 0.1f) ? 1.0f : 0.0f;
+        if ((U_(ph.termination_mask, A.termination_mask) >> (rep0 + r)) & 1u) term_local |= (n > 1.0f);
+        if ((U_(ph.penalised_mask, A.penalised_mask) >> (rep0 + r)) & 1u) coll_local += (n > 0.1f) ? 1.0f : 0.0f;
     }
     float nbase = sqrtf(Fbase[0] * Fbase[0] + Fbase[1] * Fbase[1] + Fbase[2] * Fbase[2]);
     int contact_term = group_or<K>(term_local);
-    if (A.termination_mask & 1u) contact_term |= (nbase > 1.0f);
+    if (U_(ph.termination_mask, A.termination_mask) & 1u) contact_term |= (nbase > 1.0f);
     float coll = group_sum<K>(coll_local);
-    if (A.penalised_mask & 1u) coll += (nbase > 0.1f) ? 1.0f : 0.0f;
-    const bool time_out = ep_len > P.max_episode_length;
+    if (U_(ph.penalised_mask, A.penalised_mask) & 1u) coll += (nbase > 0.1f) ? 1.0f : 0.0f;
+    const bool time_out = ep_len > U_(ph.max_episode_length, P.max_episode_length);
     int bad = 0;                                    // safety net: a non-finite state ends the episode
 #pragma unroll
     for (int i = 0; i < 13; i++) bad |= !isfinite(root[i]);
@@ -1796,18 +1894,18 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     // compute_reward :193-210 ; terms :872-969, cassie.py:43-46
     if (!EARLY_POST) {
 #pragma unroll
-        for (int j = 0; j < L; j++) { last_act[j] = B.last_actions[d0 + j]; if (L > 3) last_qd[j] = B.last_dof_vel[d0 + j]; }
+        for (int j = 0; j < L; j++) { last_act[j] = U_(pr.last_actions, B.last_actions)[d0 + j]; if (L > 3) last_qd[j] = B.last_dof_vel[d0 + j]; }
     }
     float s_ar = 0, s_acc = 0, s_lim = 0, s_dv = 0, s_dvl = 0, s_tl = 0, s_tq = 0, s_ss = 0;
 #pragma unroll
     for (int j = 0; j < L; j++) {
         const float *tj = tab + j * LG_JS;
         float da = last_act[j] - act[j]; s_ar += da * da;
-        float dd = (last_qd[j] - qd[j]) / P.dt_policy; s_acc += dd * dd;
+        float dd = (last_qd[j] - qd[j]) / U_(pr.dt_policy, P.dt_policy); s_acc += dd * dd;
         float ol = -fminf(q[j] - tj[J_SLO], 0.0f); ol += fmaxf(q[j] - tj[J_SHI], 0.0f); s_lim += ol;
         s_dv += qd[j] * qd[j];
-        s_dvl += fminf(fmaxf(fabsf(qd[j]) - tj[J_DVL] * P.soft_dof_vel_limit, 0.0f), 1.0f);
-        s_tl += fmaxf(fabsf(tau[j]) - tj[J_TLIM] * P.soft_torque_limit, 0.0f);
+        s_dvl += fminf(fmaxf(fabsf(qd[j]) - tj[J_DVL] * U_(pr.soft_dof_vel_limit, P.soft_dof_vel_limit), 0.0f), 1.0f);
+        s_tl += fmaxf(fabsf(tau[j]) - tj[J_TLIM] * U_(pr.soft_torque_limit, P.soft_torque_limit), 0.0f);
         s_tq += tau[j] * tau[j];
         s_ss += fabsf(q[j] - tj[J_Q0]);
     }
@@ -1816,25 +1914,25 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     const float *ff = Frep[T::FOOT_REP];
     const float cmd_xy = sqrtf(cmd[0] * cmd[0] + cmd[1] * cmd[1]);
     float fnorm = sqrtf(ff[0] * ff[0] + ff[1] * ff[1] + ff[2] * ff[2]);
-    float fcf = group_sum<K>(fmaxf(fnorm - P.max_contact_force, 0.0f));
+    float fcf = group_sum<K>(fmaxf(fnorm - U_(pr.max_contact_force, P.max_contact_force), 0.0f));
     int stumble = group_or<K>(sqrtf(ff[0] * ff[0] + ff[1] * ff[1]) > 5.0f * fabsf(ff[2]) ? 1 : 0);
     float nfly = group_sum<K>(ff[2] > 0.1f ? 1.0f : 0.0f);
     float air = 0.0f;
-    if (!EARLY_POST) { fat = B.feet_air_time[(size_t)e * K + k]; lc = B.last_contacts[(size_t)e * K + k]; }
-    if (P.reward_scale[LG_REW_FEET_AIR_TIME] != 0.0f) {
+    if (!EARLY_POST) { fat = U_(pr.feet_air_time, B.feet_air_time)[(size_t)e * K + k]; lc = U_(pr.last_contacts, B.last_contacts)[(size_t)e * K + k]; }
+    if (U_(pr.reward_scale[LG_REW_FEET_AIR_TIME], P.reward_scale[LG_REW_FEET_AIR_TIME]) != 0.0f) {
         bool contact = ff[2] > 1.0f, filt = contact || lc;
         lc = (uint8_t)contact;
         bool first = (fat > 0.0f) && filt;
-        fat += P.dt_policy;
+        fat += U_(pr.dt_policy, P.dt_policy);
         air = (fat - 0.5f) * (first ? 1.0f : 0.0f);
         fat *= filt ? 0.0f : 1.0f;
         air = group_sum<K>(air) * ((cmd_xy > 0.1f) ? 1.0f : 0.0f);
     }
-    const float base_h = P.measure_heights ? group_sum<K>(hsum) / (float)P.num_height_points : root[2];
+    const float base_h = U_(0, P.measure_heights) ? group_sum<K>(hsum) / (float)U_(pr.num_height_points, P.num_height_points) : root[2];
     float term[LG_NUM_REWARD_TERMS];
     term[LG_REW_ACTION_RATE] = s_ar;
     term[LG_REW_ANG_VEL_XY] = bav.x * bav.x + bav.y * bav.y;
-    term[LG_REW_BASE_HEIGHT] = (base_h - P.base_height_target) * (base_h - P.base_height_target);
+    term[LG_REW_BASE_HEIGHT] = (base_h - U_(pr.base_height_target, P.base_height_target)) * (base_h - U_(pr.base_height_target, P.base_height_target));
     term[LG_REW_COLLISION] = coll;
     term[LG_REW_DOF_ACC] = s_acc;
     term[LG_REW_DOF_POS_LIMITS] = s_lim;
@@ -1852,25 +1950,25 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     term[LG_REW_TORQUES] = s_tq;
     {
         float ex = cmd[0] - blv.x, ey = cmd[1] - blv.y, ew = cmd[2] - bav.z;
-        term[LG_REW_TRACKING_LIN_VEL] = __expf(-(ex * ex + ey * ey) / P.tracking_sigma);
-        term[LG_REW_TRACKING_ANG_VEL] = __expf(-(ew * ew) / P.tracking_sigma);
+        term[LG_REW_TRACKING_LIN_VEL] = __expf(-(ex * ex + ey * ey) / U_(pr.tracking_sigma, P.tracking_sigma));
+        term[LG_REW_TRACKING_ANG_VEL] = __expf(-(ew * ew) / U_(pr.tracking_sigma, P.tracking_sigma));
     }
     LG_PROF(PF_POST_TERMS);
     float rew = 0.0f;
     const bool writer = live && k == 0;
     float r_t[LG_NUM_REWARD_TERMS];                     // scaled terms; exactly 0 for disabled ones (x + 0 == x: the sum order is the oracle's)
 #pragma unroll
-    for (int t = 0; t < LG_NUM_REWARD_TERMS; t++) r_t[t] = (P.reward_slot[t] >= 0) ? term[t] * P.reward_scale[t] : 0.0f;
+    for (int t = 0; t < LG_NUM_REWARD_TERMS; t++) r_t[t] = U_((pr.slot_mask >> t) & 1u, P.reward_slot[t] >= 0) ? term[t] * U_(pr.reward_scale[t], P.reward_scale[t]) : 0.0f;
 #pragma unroll
     for (int t = 0; t < LG_NUM_REWARD_TERMS; t++) if (t != LG_REW_TERMINATION) rew += r_t[t];
-    if (P.only_positive_rewards) rew = fmaxf(rew, 0.0f);
+    if (U_(pr.only_positive_rewards, P.only_positive_rewards)) rew = fmaxf(rew, 0.0f);
     rew += r_t[LG_REW_TERMINATION];                     // added after the clip (:208-210)
 #pragma unroll
     for (int t = 0; t < LG_NUM_REWARD_TERMS; t++) sh.r_t[t][lane] = r_t[t];       // episode sums: helper wave, after P3
 
     LG_PROF(PF_POST_REWARD);
     // reset_idx for terminated envs (predicated epilogue) :128-129, anymal.py:56-60
-    if (!EARLY_POST) { origin[0] = B.env_origins[(size_t)e * 3]; origin[1] = B.env_origins[(size_t)e * 3 + 1]; origin[2] = B.env_origins[(size_t)e * 3 + 2]; }
+    if (!EARLY_POST) { const float *eo = U_(pr.env_origins, B.env_origins); origin[0] = eo[(size_t)e * 3]; origin[1] = eo[(size_t)e * 3 + 1]; origin[2] = eo[(size_t)e * 3 + 2]; }
     if (reset) {
         int level = 0; bool level_changed = false;
         reset_values<T>(A, tab, e, k, step, root, q, qd, cmd, origin, level, level_changed, s_xr, NW > 1 ? &reset_rand : nullptr, lane);
@@ -1882,8 +1980,10 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     }
 
     sh.rst[lane] = reset ? 1 : 0; sh.root_z[lane] = root[2];
-    if (NW > 1 && P.terrain_curriculum) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // terrain_levels stores precede the ticket (helper wave 1, after P3)
+    if (NW > 1 && U_(pr.terrain_curriculum, P.terrain_curriculum)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // terrain_levels stores precede the ticket (helper wave 1, after P3)
+    if constexpr (ROLL) { po_f = karg_request(A.post.obs); ps_f = karg_request(A.post.store); }
     __syncthreads();                                               // P3: helpers write the height observations / actuator state
+    if constexpr (ROLL) { po = karg_take(po_f); ps = karg_take(ps_f); }
     if (NW == 1) { EpisodeSums es; const bool keep = live && k == 0; if (keep) es.load(A, e); es.template update<K>(A, e, lane, sh, keep, accum_slot(A, step)); }   // no helper wave: keep the sums here
 
     LG_PROF(PF_POST_RESET);
@@ -1891,8 +1991,10 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
     { int nr = 0; for (int i = 0; i < LG_BLOCK; i += K) nr += sh.rst[i]; LG_PROF_NOTE(18, (unsigned long long)nr); }
 #endif
     // compute_observations :130 (stale base-frame quantities for reset envs, as in the reference)
-    write_observations<T>(A, e, k, live, step, root, q, qd, act, tab, blv, bav, pg, cmd, false, NW > 1 ? &reset_rand : nullptr, lane, roll_obs_out, ROLL ? lds_obs[lane / K] : nullptr);
-    if (P.measure_heights) {
+    if constexpr (ROLL) write_observations<T, true>(A, e, k, live, step, root, q, qd, act, tab, blv, bav, pg, cmd, false, &reset_rand, lane,
+                                                    po.roll_obs + (size_t)(rt + 1) * po.num_envs * po.num_obs, lds_obs[lane / K], &po);
+    else write_observations<T>(A, e, k, live, step, root, q, qd, act, tab, blv, bav, pg, cmd, false, NW > 1 ? &reset_rand : nullptr, lane, roll_obs_out, ROLL ? lds_obs[lane / K] : nullptr);
+    if (U_(0, P.measure_heights)) {
         if (NW > 1) {
             float un[HeightCrew<T, NW>::NCH][4];
 #pragma unroll
@@ -1903,38 +2005,42 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
 
     LG_PROF(PF_POST_OBS);
     // ---- write persistent state back (written once per env-step)
+    if constexpr (ROLL) pe_f = karg_request(A.post.store_env);
     if (live) {
 #pragma unroll
         for (int j = 0; j < L; j++) {
-            reinterpret_cast<float2 *>(B.dof_state)[d0 + j] = make_float2(q[j], qd[j]);
-            B.actions[d0 + j] = act[j];
-            B.torques[d0 + j] = tau[j];
-            B.last_actions[d0 + j] = act[j];                      // :132 (after the reset zeroing, as in the reference)
-            B.last_dof_vel[d0 + j] = qd[j];                       // :133
+            reinterpret_cast<float2 *>(U_(ps.dof_state, B.dof_state))[d0 + j] = make_float2(q[j], qd[j]);
+            U_(ps.actions, B.actions)[d0 + j] = act[j];
+            U_(ps.torques, B.torques)[d0 + j] = tau[j];
+            U_(ps.last_actions, B.last_actions)[d0 + j] = act[j];                      // :132 (after the reset zeroing, as in the reference)
+            U_(ps.last_dof_vel, B.last_dof_vel)[d0 + j] = qd[j];                       // :133
         }
-        B.feet_air_time[(size_t)e * K + k] = fat;
-        B.last_contacts[(size_t)e * K + k] = lc;
+        U_(ps.feet_air_time, B.feet_air_time)[(size_t)e * K + k] = fat;
+        U_(ps.last_contacts, B.last_contacts)[(size_t)e * K + k] = lc;
+        if constexpr (ROLL) pe = karg_take(pe_f);                  // (every wave has a live lane)
         if (k == 0) {
 #pragma unroll
-            for (int i = 0; i < 13; i++) B.root_states[(size_t)e * 13 + i] = root[i];
+            for (int i = 0; i < 13; i++) U_(ps.root_states, B.root_states)[(size_t)e * 13 + i] = root[i];
 #pragma unroll
-            for (int i = 0; i < 6; i++) B.last_root_vel[(size_t)e * 6 + i] = root[7 + i];     // :134
+            for (int i = 0; i < 6; i++) U_(pe.last_root_vel, B.last_root_vel)[(size_t)e * 6 + i] = root[7 + i];     // :134
 #pragma unroll
-            for (int i = 0; i < 4; i++) B.commands[(size_t)e * 4 + i] = cmd[i];
-            B.base_lin_vel[(size_t)e * 3] = blv.x; B.base_lin_vel[(size_t)e * 3 + 1] = blv.y; B.base_lin_vel[(size_t)e * 3 + 2] = blv.z;
-            B.base_ang_vel[(size_t)e * 3] = bav.x; B.base_ang_vel[(size_t)e * 3 + 1] = bav.y; B.base_ang_vel[(size_t)e * 3 + 2] = bav.z;
-            B.projected_gravity[(size_t)e * 3] = pg.x; B.projected_gravity[(size_t)e * 3 + 1] = pg.y; B.projected_gravity[(size_t)e * 3 + 2] = pg.z;
-            B.rew_buf[e] = rew;
-            B.reset_buf[e] = (uint8_t)reset;
-            B.time_out_buf[e] = (uint8_t)time_out;
-            B.episode_length_buf[e] = ep_len;
-            if (ROLL) {
-                A.roll.rew[(size_t)rt * N + e] = rew;
-                A.roll.done[(size_t)rt * N + e] = (uint8_t)reset;
-                A.roll.time_outs[(size_t)rt * N + e] = (uint8_t)time_out;
+            for (int i = 0; i < 4; i++) U_(pe.commands, B.commands)[(size_t)e * 4 + i] = cmd[i];
+            float *const o_blv = U_(pe.base_lin_vel, B.base_lin_vel), *const o_bav = U_(pe.base_ang_vel, B.base_ang_vel), *const o_pg = U_(pe.projected_gravity, B.projected_gravity);
+            o_blv[(size_t)e * 3] = blv.x; o_blv[(size_t)e * 3 + 1] = blv.y; o_blv[(size_t)e * 3 + 2] = blv.z;
+            o_bav[(size_t)e * 3] = bav.x; o_bav[(size_t)e * 3 + 1] = bav.y; o_bav[(size_t)e * 3 + 2] = bav.z;
+            o_pg[(size_t)e * 3] = pg.x; o_pg[(size_t)e * 3 + 1] = pg.y; o_pg[(size_t)e * 3 + 2] = pg.z;
+            U_(pe.rew_buf, B.rew_buf)[e] = rew;
+            U_(pe.reset_buf, B.reset_buf)[e] = (uint8_t)reset;
+            U_(pe.time_out_buf, B.time_out_buf)[e] = (uint8_t)time_out;
+            U_(pe.episode_length_buf, B.episode_length_buf)[e] = ep_len;
+            if constexpr (ROLL) {
+                pe.roll_rew[(size_t)rt * po.num_envs + e] = rew;
+                pe.roll_done[(size_t)rt * po.num_envs + e] = (uint8_t)reset;
+                pe.roll_time_outs[(size_t)rt * po.num_envs + e] = (uint8_t)time_out;
             }
         }
     }
+#undef U_
     // ---- the workgroup that finishes last turns the accumulated sums into extras["episode"] (was a second launch).
     // Its inputs are device-scope atomics (performed at the memory side: no cache write-back / invalidate is needed, and an
     // agent-scope release fence per workgroup measured +6 us); the ticket is taken after this wave's own memory operations
@@ -1960,6 +2066,10 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A) {
 #endif
         }
         // the segment's finisher: the workgroup that takes the last ticket (behind its waves' drained memory operations)
+        // (its arguments through a pointer of its own: read through A_launch they are loaded at kernel entry and held, spilled, across the loop)
+        const KArgs &A = step_args<ROLL>(A_launch);
+        const lg_params &P = A.P;
+        const int N = P.num_envs;
         const int roll_end = s_roll[1];
         const bool tick = P.cmd_curriculum && (step0 + roll_end - 1) % P.max_episode_length == 0;   // the slice ends in a curriculum tick
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2420,6 +2530,36 @@ static void fill_args(const lg_sim *s, KArgs &a, int64_t step) {
     a.accum_alt = s->d_accum_alt; a.defer = s->defer; a.flush_parts = 0;
     a.status = s->h_status; a.spin_limit = s->spin_limit; a.debug_skip = s->debug_skip;
     memset(&a.roll, 0, sizeof a.roll);
+}
+// lg_rollout_policy: the blocks the rollout kernel's rigid-body wave fetches behind the physics of each step (PostArgs), from the
+// parameters and bindings in force at THIS launch (a.P, a.B, a.roll as filled above).
+static void fill_post_args(KArgs &a) {
+    const lg_params &P = a.P; const lg_buffers &B = a.B;
+    memset(&a.post, 0, sizeof a.post);
+    PostHead &h = a.post.head;
+    h.resample_interval = P.resample_interval; h.heading_command = P.heading_command; h.push_interval = P.push_interval;
+    h.max_episode_length = P.max_episode_length; h.max_push_vel = P.max_push_vel; h.termination_mask = a.termination_mask;
+    h.penalised_mask = a.penalised_mask;
+    h.episode_length_buf = B.episode_length_buf; h.commands = B.commands; h.contact_forces = B.contact_forces;
+    PostRew &r = a.post.rew;
+    r.dt_policy = P.dt_policy; r.soft_dof_vel_limit = P.soft_dof_vel_limit; r.soft_torque_limit = P.soft_torque_limit;
+    r.max_contact_force = P.max_contact_force; r.base_height_target = P.base_height_target; r.tracking_sigma = P.tracking_sigma;
+    r.only_positive_rewards = P.only_positive_rewards; r.num_height_points = P.num_height_points; r.terrain_curriculum = P.terrain_curriculum;
+    for (int t = 0; t < LG_NUM_REWARD_TERMS; t++) { r.reward_scale[t] = P.reward_scale[t]; if (P.reward_slot[t] >= 0) r.slot_mask |= 1u << t; }
+    r.last_actions = B.last_actions; r.feet_air_time = B.feet_air_time; r.last_contacts = B.last_contacts; r.env_origins = B.env_origins;
+    PostObs &o = a.post.obs;
+    o.obs_scale_lin_vel = P.obs_scale_lin_vel; o.obs_scale_ang_vel = P.obs_scale_ang_vel; o.obs_scale_dof_pos = P.obs_scale_dof_pos;
+    o.obs_scale_dof_vel = P.obs_scale_dof_vel; o.noise_lin_vel = P.noise_lin_vel; o.noise_ang_vel = P.noise_ang_vel; o.noise_gravity = P.noise_gravity;
+    o.noise_dof_pos = P.noise_dof_pos; o.noise_dof_vel = P.noise_dof_vel; o.clip_observations = P.clip_observations;
+    o.add_noise = P.add_noise; o.num_obs = P.num_obs; o.num_envs = P.num_envs; o.roll_obs = a.roll.obs;
+    PostStore &w = a.post.store;
+    w.dof_state = B.dof_state; w.actions = B.actions; w.torques = B.torques; w.last_actions = B.last_actions; w.last_dof_vel = B.last_dof_vel;
+    w.feet_air_time = B.feet_air_time; w.last_contacts = B.last_contacts; w.root_states = B.root_states;
+    PostStoreEnv &v = a.post.store_env;
+    v.last_root_vel = B.last_root_vel;
+    v.commands = B.commands; v.base_lin_vel = B.base_lin_vel; v.base_ang_vel = B.base_ang_vel; v.projected_gravity = B.projected_gravity;
+    v.rew_buf = B.rew_buf; v.reset_buf = B.reset_buf; v.time_out_buf = B.time_out_buf; v.episode_length_buf = B.episode_length_buf;
+    v.roll_rew = a.roll.rew; v.roll_done = a.roll.done; v.roll_time_outs = a.roll.time_outs;
 }
 // Entry check of every call on a handle: a status bit set by an earlier launch is an error from now on (sticky).
 static int status_error(const lg_sim *s) {
@@ -3383,6 +3523,7 @@ int lg_rollout_policy(lg_sim *s, lg_policy *p, const lg_rollout_buffers *r, uint
     a.roll.done = r->dones; a.roll.time_outs = r->time_outs; a.roll.extras = s->d_roll_extras;
     a.roll.obs0 = r->obs0;
     a.roll.cursor = reinterpret_cast<int *>(s->d_roll_extras + LG_MAX_ROLL_STEPS * stride);
+    fill_post_args(a);
     // commands.curriculum: the workgroups never meet between steps, so no launch may run past a curriculum tick -- a FIXED number of
     // launches of the same kernel (a captured graph holds them all), each resuming where the previous one stopped; left-over ones exit at once
     const int launches = s->P.cmd_curriculum ? 1 + (r->steps + s->P.max_episode_length - 1) / s->P.max_episode_length : 1;
