@@ -1,7 +1,7 @@
 // lg_dec_game.hip -- the kernels of the decentralised predator-prey game (include/legged_dec_game.h): k_dec_pre / k_dec_post, and the
 // lg_policy_act instantiations for actors with one input tile (the 16-input prey actor, the 3-input predator actor).  A translation unit of
 // its own, reached through the launchers of lg_dec_game_common.h, so that the code hipcc generates for the kernels of lg_kernels.hip does
-// not depend on it (see lg_game.h).  The C entry points are in lg_dec_game.h (lg_kernels.hip).
+// not depend on it (see lg_game.h).  The C entry points are in lg_dec_game.h (lg_game_entry.hip).
 //
 // Floating point: contraction is OFF in k_dec_pre / k_dec_post, every expression rounds once per operation in the order written, so the
 // results are bit-comparable with the NumPy float32 restatement (tests/dec_game_twin.py) except behind sqrtf / acosf (1 ulp on this build)
@@ -9,7 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define LG_POLICY_BLOCKS_ONLY      // lg_policy.h without its two non-template pack kernels (they belong to lg_kernels.hip)
+#define LG_POLICY_BLOCKS_ONLY      // lg_policy.h without its two non-template pack kernels (they belong to lg_learner.hip)
 #include "lg_device.h"
 #include "lg_policy.h"
 #include "lg_dec_game_post.h"  // dec_post_env<OUTCOME>: one env of the post stage (shared with lg_dec_game_outcome.hip)
@@ -67,7 +67,7 @@ int launch_dec_post(const lg_dec_game_params &P, const lg_dec_game_buffers &B, i
     return (int)hipGetLastError();
 }
 
-// the actor kernels are compiled with the default contraction, as in lg_kernels.hip: the pragmas above are function-local
+// the actor kernels are compiled with the default contraction, as in lg_learner.hip: the pragmas above are function-local
 int launch_policy_act_one_tile(const PolicyArgs &A, void *stream) {
     hipLaunchKernelGGL((k_policy_act<1, 32, 16, 8>), dim3((A.num_envs + 15) / 16), dim3(64 * LG_POLICY_WAVES), 0, (hipStream_t)stream, A);
     return (int)hipGetLastError();

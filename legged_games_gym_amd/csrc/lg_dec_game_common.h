@@ -1,6 +1,6 @@
-// lg_dec_game_common.h -- what lg_kernels.hip (the C entry points of include/legged_dec_game.h in lg_dec_game.h, the lg_policy_act dispatch) and
-// lg_dec_game.hip (the kernels) share: the launchers.  Needs lg_policy.h.  The kernels are a translation unit of their own for the reason
-// lg_game_act.hip is one: a kernel built from the wide actor blocks inside lg_kernels.hip moves hipcc's register allocation of the
+// lg_dec_game_common.h -- what lg_game_entry.hip (the C entry points of include/legged_dec_game.h in lg_dec_game.h), lg_learner.hip (the
+// lg_policy_act dispatch) and lg_dec_game.hip (the kernels) share: the launchers.  Needs lg_policy.h.  The kernels are a translation unit of their own for the reason
+// lg_game_act.hip is one: a kernel built from the wide actor blocks next to the lg_policy_act dispatch moves hipcc's register allocation of the
 // k_policy_act_wide instantiations there (lg_game.h).
 #pragma once
 #include "../../include/legged_dec_game.h"

@@ -1,7 +1,7 @@
 // lg_dec_game_outcome.hip -- the post stage of the decentralised predator-prey game with outcome statistics
 // (include/legged_dec_game_outcome.h): k_dec_outcome, reached through launch_dec_outcome.  A translation unit of its own, as every game
 // kernel outside lg_game.h is, so that the code hipcc generates for the kernels of lg_kernels.hip and lg_dec_game.hip does not depend on
-// it (see lg_game.h).  The C entry point is in lg_dec_game_outcome_entry.h (lg_kernels.hip).
+// it (see lg_game.h).  The C entry point is in lg_dec_game_outcome_entry.h (lg_game_entry.hip).
 //
 // The per-env body is dec_post_env<true> (lg_dec_game_post.h), the one k_dec_post runs with OUTCOME = false, so everything that kernel
 // writes per env comes out bit-identical.  The addition: where k_dec_post folds the causes of an episode's end into `done`, this kernel

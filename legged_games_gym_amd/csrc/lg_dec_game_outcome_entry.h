@@ -1,7 +1,8 @@
 // lg_dec_game_outcome_entry.h -- C entry points of the decentralised game's outcome statistics (include/legged_dec_game_outcome.h).  Host
-// code only: the kernel lives in lg_dec_game_outcome.hip behind launch_dec_outcome.  Included from lg_kernels.hip after lg_dec_game.h
-// (dec_game_check, dec_game_post_check).
+// code only: the kernel lives in lg_dec_game_outcome.hip behind launch_dec_outcome.  An entry header of lg_game_entry.hip; includes what it
+// uses.
 #pragma once
+#include "lg_dec_game.h"            // fail / HIP_TRY (lg_host.h), dec_game_check, dec_game_post_check
 #include "../../include/legged_dec_game_outcome.h"
 
 namespace lg {
@@ -12,12 +13,12 @@ int launch_dec_outcome(const lg_dec_game_params &P, const lg_dec_game_buffers &B
 extern "C" {
 
 static int dec_outcome_check(const char *who, const lg_dec_outcome_buffers *O) {      // also lg_member_outcome_entry.h
-    if (!O->ll_time_out_buf || !O->accum || !O->means || !O->totals) return fail(-1, "%s: a pointer of lg_dec_outcome_buffers is null", who);
+    if (!O->ll_time_out_buf || !O->accum || !O->means || !O->totals) return lg::fail(-1, "%s: a pointer of lg_dec_outcome_buffers is null", who);
     return 0;
 }
 
 int lg_dec_outcome_post(const lg_dec_game_params *P, const lg_dec_game_buffers *B, const lg_dec_outcome_buffers *O, int64_t common_step_counter, void *stream) {
-    if (!O) return fail(-1, "lg_dec_outcome_post: lg_dec_outcome_buffers is null");
+    if (!O) return lg::fail(-1, "lg_dec_outcome_post: lg_dec_outcome_buffers is null");
     if (int rc = dec_game_check(P, B)) return rc;
     if (int rc = dec_outcome_check("lg_dec_outcome_post", O)) return rc;
     if (int rc = dec_game_post_check("lg_dec_outcome_post", P, B, common_step_counter)) return rc;

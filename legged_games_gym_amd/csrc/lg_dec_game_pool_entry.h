@@ -1,7 +1,9 @@
 // lg_dec_game_pool_entry.h -- C entry points of the decentralised game's opponent pool (include/legged_dec_game_pool.h).  Host code only:
-// the kernel lives in lg_pool_act.hip behind launch_pool_act (lg_pool_act.h).  Included from lg_kernels.hip after lg_dec_game.h
-// (dec_game_check, fill_dec_act_args) and the fused-actor host code (lg_policy, fill_wide_operands, g_wide_precision).
+// the kernel lives in lg_pool_act.hip behind launch_pool_act (lg_pool_act.h).  An entry header of lg_game_entry.hip; includes what it
+// uses.
 #pragma once
+#include <new>
+#include "lg_dec_game.h"            // fail / HIP_TRY, lg_policy, fill_wide_operands, wide_precision (lg_host.h); dec_game_check, fill_dec_act_args
 #include "lg_pool_act.h"
 
 struct lg_dec_pool {
@@ -18,42 +20,42 @@ static bool dec_pool_shape_ok(const lg_policy *p, int role) {
 extern "C" {
 
 int lg_dec_pool_create(lg_policy *const *members, int32_t count, int32_t role, int32_t device, lg_dec_pool **out) {
-    if (!members || !out) return fail(-1, "null argument");
-    if (count < 1 || count > LG_DEC_POOL_MAX) return fail(-2, "lg_dec_pool_create: count must be 1 .. LG_DEC_POOL_MAX (16)");
-    if (role != 1 && role != 2) return fail(-2, "lg_dec_pool_create: role must be 1 (prey) or 2 (predator)");
+    if (!members || !out) return lg::fail(-1, "null argument");
+    if (count < 1 || count > LG_DEC_POOL_MAX) return lg::fail(-2, "lg_dec_pool_create: count must be 1 .. LG_DEC_POOL_MAX (16)");
+    if (role != 1 && role != 2) return lg::fail(-2, "lg_dec_pool_create: role must be 1 (prey) or 2 (predator)");
     for (int i = 0; i < count; i++) {
-        if (!members[i]) return fail(-1, "lg_dec_pool_create: a member is null");
-        if (!dec_pool_shape_ok(members[i], role)) return fail(-4, "lg_dec_pool_create: a member is not a %s actor", role == 1 ? "16-512-256-128-4 prey" : "3-512-256-128-2 predator");
-        if (members[i]->device != device) return fail(-2, "lg_dec_pool_create: a member lives on another device");
+        if (!members[i]) return lg::fail(-1, "lg_dec_pool_create: a member is null");
+        if (!dec_pool_shape_ok(members[i], role)) return lg::fail(-4, "lg_dec_pool_create: a member is not a %s actor", role == 1 ? "16-512-256-128-4 prey" : "3-512-256-128-2 predator");
+        if (members[i]->device != device) return lg::fail(-2, "lg_dec_pool_create: a member lives on another device");
     }
     lg::DecPoolEntry rows[LG_DEC_POOL_MAX];
     for (int i = 0; i < LG_DEC_POOL_MAX; i++) {
         const lg_policy *p = members[i < count ? i : 0];
-        fill_wide_operands(p, rows[i].wb, rows[i].bb);
+        lg::fill_wide_operands(p, rows[i].wb, rows[i].bb);
         rows[i].std = p->d_std;
     }
     HIP_TRY(hipSetDevice(device));
     lg_dec_pool *pool = new (std::nothrow) lg_dec_pool();
-    if (!pool) return fail(-5, "out of host memory");
+    if (!pool) return lg::fail(-5, "out of host memory");
     pool->d_table = nullptr; pool->first = members[0]; pool->count = count; pool->role = role; pool->device = device;
     if (hipMalloc(&pool->d_table, sizeof rows) != hipSuccess || hipMemcpy(pool->d_table, rows, sizeof rows, hipMemcpyHostToDevice) != hipSuccess) {
         if (pool->d_table) (void)hipFree(pool->d_table);
         delete pool;
-        return fail(-10, "lg_dec_pool_create: the device table could not be allocated or copied");
+        return lg::fail(-10, "lg_dec_pool_create: the device table could not be allocated or copied");
     }
     *out = pool;
     return 0;
 }
 
 int lg_dec_pool_destroy(lg_dec_pool *pool) {
-    if (!pool) return fail(-1, "null argument");
+    if (!pool) return lg::fail(-1, "null argument");
     if (pool->d_table) (void)hipFree(pool->d_table);
     delete pool;
     return 0;
 }
 
 int lg_dec_pool_query(const lg_dec_pool *pool, lg_dec_pool_info *info) {
-    if (!pool || !info) return fail(-1, "null argument");
+    if (!pool || !info) return lg::fail(-1, "null argument");
     info->count = pool->count; info->role = pool->role; info->device = pool->device; info->_pad = 0; info->table = pool->d_table;
     return 0;
 }
@@ -64,16 +66,16 @@ int lg_dec_pool_act(lg_policy *pred, lg_policy *prey, lg_policy *ll, const lg_de
                     const int64_t *step_counter, int32_t deterministic_pred, int32_t deterministic_prey, const lg_dec_act_outputs *out_pred,
                     const lg_dec_act_outputs *out_prey, void *stream) {
     if (int rc = dec_game_check(P, B)) return rc;
-    if ((!pred && !pool_pred) || (!prey && !pool_prey) || !ll || !pred_obs || !prey_obs || !ll_obs || !ll_actions || !mean_pred || !mean_prey) return fail(-1, "null argument");
-    if ((pool_pred && !block_slot_pred) || (pool_prey && !block_slot_prey)) return fail(-1, "lg_dec_pool_act: a pool needs its block_slot table");
-    if (!B->command_prey || !B->command_pred || !B->ll_commands) return fail(-1, "lg_dec_pool_act needs command_prey, command_pred and ll_commands");
-    if (seed_pred == seed_prey) return fail(-2, "lg_dec_pool_act: seed_pred and seed_prey must differ (the sampled roles share their noise purposes)");
+    if ((!pred && !pool_pred) || (!prey && !pool_prey) || !ll || !pred_obs || !prey_obs || !ll_obs || !ll_actions || !mean_pred || !mean_prey) return lg::fail(-1, "null argument");
+    if ((pool_pred && !block_slot_pred) || (pool_prey && !block_slot_prey)) return lg::fail(-1, "lg_dec_pool_act: a pool needs its block_slot table");
+    if (!B->command_prey || !B->command_pred || !B->ll_commands) return lg::fail(-1, "lg_dec_pool_act needs command_prey, command_pred and ll_commands");
+    if (seed_pred == seed_prey) return lg::fail(-2, "lg_dec_pool_act: seed_pred and seed_prey must differ (the sampled roles share their noise purposes)");
     const lg_policy *py = pool_prey ? pool_prey->first : prey, *pd = pool_pred ? pool_pred->first : pred;
     const bool prey_ok = pool_prey ? pool_prey->role == 1 : dec_pool_shape_ok(prey, 1);
     const bool pred_ok = pool_pred ? pool_pred->role == 2 : dec_pool_shape_ok(pred, 2);
     const bool ll_ok = ll->wide && ll->tiles[0] == 15;
-    if (g_wide_precision != 1 || !prey_ok || !pred_ok || !ll_ok)
-        return fail(-4, "the pooled actor launch is compiled for the 3-512-256-128-2 / 16-512-256-128-4 / 235-512-256-128 triple at wide precision 1; use lg_policy_act per member + lg_dec_game_pre");
+    if (lg::wide_precision() != 1 || !prey_ok || !pred_ok || !ll_ok)
+        return lg::fail(-4, "the pooled actor launch is compiled for the 3-512-256-128-2 / 16-512-256-128-4 / 235-512-256-128 triple at wide precision 1; use lg_policy_act per member + lg_dec_game_pre");
     lg::PoolActArgs a;
     fill_dec_act_args(a.act, pd, py, ll, P, B, pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey, seed_pred, seed_prey, step, step_counter,
                       deterministic_pred, deterministic_prey, out_pred, out_prey);

@@ -7,11 +7,13 @@
 // Floating point: contraction is OFF in this header, every expression rounds once per operation in the order written.  The results are then
 // bit-comparable with a NumPy float32 restatement (tests/game_twin.py) except behind sqrtf / acosf, which are 1-ulp on this build.
 //
-// Included from lg_kernels.hip after its error helpers (fail / HIP_TRY).  The shared actor kernel behind lg_game_act, k_prey_act, lives in
-// lg_game_act.h and is compiled in a translation unit of its own (lg_game_act.hip): inside lg_kernels.hip its presence alone changes hipcc's
-// register allocation of the existing k_policy_act_wide instantiations (211 / 214 -> 216 / 212 VGPRs).  What both units share -- the
+// The first of the entry headers of lg_game_entry.hip; includes what it uses (lg_host.h: fail / HIP_TRY, lg_policy and its fill helpers).  The
+// shared actor kernel behind lg_game_act, k_prey_act, lives in lg_game_act.h and is compiled in a translation unit of its own
+// (lg_game_act.hip): in one unit with the k_policy_act_wide instantiations of lg_policy_act (lg_learner.hip) its presence alone changes
+// hipcc's register allocation of those (211 / 214 -> 216 / 212 VGPRs).  What both units share -- the
 // clip / wrap helpers, the kernel's argument struct, its launcher -- is in lg_game_common.h.
 #pragma once
+#include "lg_host.h"
 #include "lg_game_common.h"
 #include "lg_game_post.h"      // game_post_env: the body of k_game_post, shared with the other post kernels
 
@@ -49,8 +51,8 @@ __global__ __launch_bounds__(LG_GAME_BLOCK) void k_game_post(lg_game_params P, l
 extern "C" {
 
 static int game_check(const lg_game_params *P, const lg_game_buffers *B) {
-    if (!P || !B) return fail(-1, "null argument");
-    if (P->num_envs < 1 || P->decimation < 0) return fail(-2, "lg_game_params: num_envs must be >= 1 and decimation >= 0");
+    if (!P || !B) return lg::fail(-1, "null argument");
+    if (P->num_envs < 1 || P->decimation < 0) return lg::fail(-2, "lg_game_params: num_envs must be >= 1 and decimation >= 0");
     return 0;
 }
 
@@ -59,14 +61,14 @@ static int game_check(const lg_game_params *P, const lg_game_buffers *B) {
 static int game_post_check(const char *who, const lg_game_buffers *B, bool need_command, int64_t common_step_counter) {
     if ((need_command && !B->command) || !B->ll_root_states || !B->ll_env_origins || !B->ll_rew_buf || !B->ll_reset_buf || !B->predator_pos || !B->obs ||
         !B->rew || !B->reset_buf || !B->curr_episode_step || !B->episode_length_buf || !B->episode_sums)
-        return fail(-1, "%s: a buffer pointer is null", who);
-    if (common_step_counter < 0 && !B->ll_step_counter) return fail(-9, "common_step_counter = -1 needs the low-level step_counter buffer");
+        return lg::fail(-1, "%s: a buffer pointer is null", who);
+    if (common_step_counter < 0 && !B->ll_step_counter) return lg::fail(-9, "common_step_counter = -1 needs the low-level step_counter buffer");
     return 0;
 }
 
 int lg_game_pre(const lg_game_params *P, const lg_game_buffers *B, void *stream) {
     if (int rc = game_check(P, B)) return rc;
-    if (!B->command || !B->ll_commands) return fail(-1, "lg_game_pre needs command and ll_commands");
+    if (!B->command || !B->ll_commands) return lg::fail(-1, "lg_game_pre needs command and ll_commands");
     hipLaunchKernelGGL(lg::k_game_pre, dim3((P->num_envs + LG_GAME_BLOCK - 1) / LG_GAME_BLOCK), dim3(LG_GAME_BLOCK), 0, (hipStream_t)stream, *P, *B);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -85,17 +87,17 @@ int lg_game_act(lg_policy *hl, lg_policy *ll, const lg_game_params *P, const lg_
                 float *ll_actions, float *mean, uint64_t seed, int64_t step, const int64_t *step_counter, int32_t deterministic,
                 float *sample, float *sigma, float *log_prob, float *obs_copy, void *stream) {
     if (int rc = game_check(P, B)) return rc;
-    if (!hl || !ll || !hl_obs || !ll_obs || !ll_actions || !mean) return fail(-1, "null argument");
-    if (!B->command || !B->ll_commands) return fail(-1, "lg_game_act needs command and ll_commands");
+    if (!hl || !ll || !hl_obs || !ll_obs || !ll_actions || !mean) return lg::fail(-1, "null argument");
+    if (!B->command || !B->ll_commands) return lg::fail(-1, "lg_game_act needs command and ll_commands");
     const bool hl_ok = hl->wide && hl->dims[0] == LG_GAME_NUM_OBS && hl->dims[4] == LG_GAME_NUM_ACTIONS;
     const bool ll_ok = ll->wide && ll->tiles[0] == 15;
-    if (g_wide_precision != 1 || !hl_ok || !ll_ok)
-        return fail(-4, "the shared actor launch is compiled for the 19-512-256-128-6 / 235-512-256-128 pair at wide precision 1; use lg_policy_act x 2 + lg_game_pre");
+    if (lg::wide_precision() != 1 || !hl_ok || !ll_ok)
+        return lg::fail(-4, "the shared actor launch is compiled for the 19-512-256-128-6 / 235-512-256-128 pair at wide precision 1; use lg_policy_act x 2 + lg_game_pre");
     lg::PreyActArgs g;
-    fill_policy_args(hl, g.hl.base, hl_obs, sample, mean, P->num_envs, seed, step, step_counter, deterministic);
-    fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed, step, step_counter, 1);
-    fill_wide_operands(hl, g.hl.wb, g.hl.bb);
-    fill_wide_operands(ll, g.ll.wb, g.ll.bb);
+    lg::fill_policy_args(hl, g.hl.base, hl_obs, sample, mean, P->num_envs, seed, step, step_counter, deterministic);
+    lg::fill_policy_args(ll, g.ll.base, ll_obs, ll_actions, nullptr, P->num_envs, seed, step, step_counter, 1);
+    lg::fill_wide_operands(hl, g.hl.wb, g.hl.bb);
+    lg::fill_wide_operands(ll, g.ll.wb, g.ll.bb);
     g.P = *P; g.command = B->command; g.ll_commands = B->ll_commands;
     g.sigma = sigma; g.log_prob = log_prob; g.obs_copy = obs_copy;
     const int blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;

@@ -1,4 +1,4 @@
-// lg_game_common.h -- what lg_game.h (k_game_pre / k_game_post and the C entry points, in lg_kernels.hip) and lg_game_act.h (k_prey_act, in
+// lg_game_common.h -- what lg_game.h (k_game_pre / k_game_post and the C entry points, in lg_game_entry.hip) and lg_game_act.h (k_prey_act, in
 // lg_game_act.hip) share: the clip / wrap helpers, the argument struct of k_prey_act and its launcher.  Needs lg_policy.h.
 // The helpers switch floating-point contraction off inside their bodies; this header sets no file-wide pragma.
 #pragma once

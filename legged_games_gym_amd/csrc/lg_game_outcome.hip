@@ -1,7 +1,7 @@
 // lg_game_outcome.hip -- the post stage of the predator-prey game with outcome statistics (include/legged_game_outcome.h): the two
 // instantiations of k_outcome_post (lg_game_outcome.h), reached through launch_outcome_post.  A translation unit of its own, as every game
 // kernel outside lg_game.h is, so that the code hipcc generates for the kernels of lg_kernels.hip does not depend on it (see lg_game.h).
-// The C entry points are in lg_game_outcome_entry.h (lg_kernels.hip).
+// The C entry points are in lg_game_outcome_entry.h (lg_game_entry.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

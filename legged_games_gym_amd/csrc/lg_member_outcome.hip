@@ -1,7 +1,7 @@
 // lg_member_outcome.hip -- the post stage of the decentralised predator-prey game with the outcome statistics kept per opponent-pool member
 // (include/legged_dec_game_member_outcome.h): k_member_outcome, reached through launch_member_outcome.  A translation unit of its own, as
 // every game kernel outside lg_game.h is, so that the code hipcc generates for the other kernels does not depend on it (see lg_game.h).
-// The C entry point is in lg_member_outcome_entry.h (lg_kernels.hip).
+// The C entry point is in lg_member_outcome_entry.h (lg_game_entry.hip).
 //
 // The per-env body is dec_post_env<true> (lg_dec_game_post.h) and the pooled reductions are those of k_dec_outcome (lg_dec_game_outcome.hip),
 // the same functions (lg_outcome_reduce.h), so everything that kernel writes comes out bit-identical.  The addition: a pool block is 32 envs and a wave 64, so

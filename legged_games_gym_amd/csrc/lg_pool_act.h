@@ -1,4 +1,4 @@
-// lg_pool_act.h -- what lg_kernels.hip (the C entry points of include/legged_dec_game_pool.h, in lg_dec_game_pool_entry.h) and lg_pool_act.hip
+// lg_pool_act.h -- what lg_game_entry.hip (the C entry points of include/legged_dec_game_pool.h, in lg_dec_game_pool_entry.h) and lg_pool_act.hip
 // (k_pool_act) share: one row of a pool's device table, the kernel's argument struct and its launcher.  Needs lg_policy.h and
 // lg_dec_game_common.h.  The kernel is a translation unit of its own for the reason lg_dec_game.hip is one (lg_dec_game_common.h).
 #pragma once

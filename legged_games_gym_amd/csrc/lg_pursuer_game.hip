@@ -1,7 +1,7 @@
 // lg_pursuer_game.hip -- k_pursuer_post: the post stage of the predator-prey game with the reference's scripted pursuer
 // (include/legged_pursuer_game.h; reference high_level_game.py:265-324 with `command=None`).  A translation unit of its own, reached through
 // launch_pursuer_post, so that the code hipcc generates for the kernels of lg_kernels.hip does not depend on it (see lg_game.h).  The C
-// entry points are in lg_pursuer_game.h (lg_kernels.hip).
+// entry points are in lg_pursuer_game.h (lg_game_entry.hip).
 //
 // The body is game_post_env<true, false> (lg_game_post.h), shared with the other post kernels: k_game_post with the predator's velocity
 // computed by the scripted rule in place of the two loads from `command`.  Floating point: contraction is OFF there, so the results are
