@@ -293,6 +293,33 @@ def test_shared_actor_launch_is_bit_identical_to_the_separate_launches(n, headin
     assert torch.equal(cy, det_y) and torch.equal(llc, det_y) and torch.equal(cp, keep[1])
 
 
+def test_shared_actor_launch_matches_float64_forwards():
+    """k_dec_act against references computed outside any kernel, at the smallest size with a second workgroup per role (n = 33): both
+    agents' means and the deterministic low-level actions are float64 forwards (``actor_forward64`` from the modules' arrays) of the three
+    actors, within 1e-4 of the output scale, the bar of the split-bf16 actors above."""
+    from legged_games_gym_amd import capi
+    from tests.recurrent_ref import actor_forward64, actor_params64
+    assert capi.load_library().lg_mlp_wide_set_precision(1) == 1
+    n = 33
+    (prey_ac, pred_ac, ll_ac), (prey, pred, ll) = three_actors()
+    gen = torch.Generator().manual_seed(133)
+    prey_obs, pred_obs = (torch.randn(n, 16, generator=gen) * 3.0).to(DEV), (torch.randn(n, 3, generator=gen) * 3.0).to(DEV)
+    ll_obs = (torch.randn(n, 235, generator=gen) * 1.5).to(DEV)
+    f = lambda *s: torch.full(s, float("nan"), device=DEV)
+    cy, cp, llc, act, my, mp = f(n, 4), f(n, 2), f(n, 4), f(n + 5, 12), f(n + 5, 4), f(n + 5, 2)
+    B = capi.dec_game_buffers({"command_prey": cy.data_ptr(), "command_pred": cp.data_ptr(), "ll_commands": llc.data_ptr()})
+    assert capi.dec_game_act(pred.handle, prey.handle, ll.handle, pack_params(dt.params(num_envs=n)), B, pred_obs.data_ptr(), prey_obs.data_ptr(),
+                             ll_obs.data_ptr(), act.data_ptr(), mp.data_ptr(), my.data_ptr(), 12161 + 104729, 12161, 110, None, False, False, None, None,
+                             torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(act[n:]).all()) and bool(torch.isnan(my[n:]).all()) and bool(torch.isnan(mp[n:]).all())
+    for name, got, ac, obs in (("prey mean", my[:n], prey_ac, prey_obs), ("predator mean", mp[:n], pred_ac, pred_obs), ("low-level actions", act[:n], ll_ac, ll_obs)):
+        want = actor_forward64(*actor_params64(ac.actor), obs.cpu().double().numpy())
+        err, scale = float(np.abs(got.cpu().double().numpy() - want).max()), max(1.0, float(np.abs(want).max()))
+        print(f"[observed] k_dec_act n {n} {name}: err {err:.3e}, scale {scale:.3f}")
+        assert err < 1e-4 * scale, (name, err, scale)
+
+
 def test_shared_actor_launch_refuses_precision_0_other_shapes_and_equal_seeds():
     from legged_games_gym_amd import capi
     from legged_games_gym_amd.rl import ActorCritic, FusedActor

@@ -4,6 +4,7 @@ separate launches at wide precision 0; a captured graph follows ``push`` and ``a
 checkpoints."""
 import os
 
+import numpy as np
 import pytest
 import torch
 
@@ -156,6 +157,27 @@ def test_pooled_launch_is_bit_identical_per_block_to_the_plain_launch_with_the_b
                           torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         assert torch.equal(got["prey"]["command"], det["prey"]) and torch.equal(got["pred"]["command"], det["pred"]) and torch.equal(got["prey"]["ll_commands"], scratch)
+
+
+def test_pooled_launch_matches_float64_forwards_of_each_blocks_member(actors):
+    """k_pool_act against references computed outside any kernel, at the smallest size with a second block (n = 33, block 0 -> member 1,
+    block 1 -> member 2 for the prey; 2 and 0 for the predator): each row's mean is the float64 forward (``actor_forward64`` from the
+    modules' arrays) of its block's member, the low-level actions that of the low-level actor, within 1e-4 of the output scale, the bar
+    of the split-bf16 actors (tests/test_gpu_dec_game.py)."""
+    from tests.recurrent_ref import actor_forward64, actor_params64
+    n = 33
+    L = Launch(actors, n, False)
+    slots = {"prey": torch.tensor([1, 2], dtype=torch.int32), "pred": torch.tensor([2, 0], dtype=torch.int32)}
+    got = L.pooled(slots["pred"].to(DEV), slots["prey"].to(DEV))
+    checks = [("low-level actions", got["ll_actions"], actor_forward64(*actor_params64(actors["ll"].ac.actor), L.ll_obs.cpu().double().numpy()))]
+    for who, obs in (("prey", L.prey_obs), ("pred", L.pred_obs)):
+        per_member = [actor_forward64(*actor_params64(m.ac.actor), obs.cpu().double().numpy()) for m in actors[who]]
+        rows = slots[who].long().repeat_interleave(32)[:n].numpy()
+        checks.append((f"{who} mean", got[who]["mean"], np.stack(per_member)[rows, np.arange(n)]))
+    for name, have, want in checks:
+        err, scale = float(np.abs(have.cpu().double().numpy() - want).max()), max(1.0, float(np.abs(want).max()))
+        print(f"[observed] k_pool_act n {n} {name}: err {err:.3e}, scale {scale:.3f}")
+        assert err < 1e-4 * scale, (name, err, scale)
 
 
 def test_pool_creation_checks_every_members_shape_and_the_launch_the_pools_role(actors):

@@ -155,6 +155,35 @@ def test_shared_actor_launch_is_bit_identical_to_the_separate_launches(n, headin
     assert torch.equal(command2, det) and torch.equal(mean2, mean)
 
 
+def test_shared_actor_launch_matches_float64_forwards():
+    """k_prey_act against references computed outside any kernel, at the smallest size with a second workgroup per role (n = 33): the
+    high-level means and the deterministic low-level actions are float64 forwards (``actor_forward64`` from the modules' arrays) of the two
+    actors, within 1e-4 of the output scale, the bar of the split-bf16 actors (tests/test_gpu_env_surface.py)."""
+    from legged_games_gym_amd import capi
+    from legged_games_gym_amd.rl import ActorCritic, FusedActor
+    from tests.recurrent_ref import actor_forward64, actor_params64
+    assert capi.load_library().lg_mlp_wide_set_precision(1) == 1
+    n = 33
+    hl_ac = high_level_actor(seed=3, std=STD, bias=BIAS)
+    torch.manual_seed(4)
+    ll_ac = ActorCritic(235, 235, 12, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV)
+    hl, ll = FusedActor(hl_ac, DEV, seed=11), FusedActor(ll_ac, DEV, seed=1)
+    gen = torch.Generator().manual_seed(133)
+    hl_obs, ll_obs = (torch.randn(n, 19, generator=gen) * 3.0).to(DEV), (torch.randn(n, 235, generator=gen) * 1.5).to(DEV)
+    f = lambda *s: torch.full(s, float("nan"), device=DEV)
+    command, llc, act, mean = f(n, 6), f(n, 4), f(n + 5, 12), f(n + 5, 6)
+    B = capi.game_buffers({"command": command.data_ptr(), "ll_commands": llc.data_ptr()})
+    assert capi.game_act(hl.handle, ll.handle, pack_params(tw.params(num_envs=n)), B, hl_obs.data_ptr(), ll_obs.data_ptr(), act.data_ptr(), mean.data_ptr(),
+                         4242, 110, None, False, stream=torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(act[n:]).all()) and bool(torch.isnan(mean[n:]).all())
+    for name, got, ac, obs in (("high-level mean", mean[:n], hl_ac, hl_obs), ("low-level actions", act[:n], ll_ac, ll_obs)):
+        want = actor_forward64(*actor_params64(ac.actor), obs.cpu().double().numpy())
+        err, scale = float(np.abs(got.cpu().double().numpy() - want).max()), max(1.0, float(np.abs(want).max()))
+        print(f"[observed] k_prey_act n {n} {name}: err {err:.3e}, scale {scale:.3f}")
+        assert err < 1e-4 * scale, (name, err, scale)
+
+
 def test_shared_actor_launch_refuses_precision_0_and_other_shapes():
     from legged_games_gym_amd import capi
     from legged_games_gym_amd.rl import ActorCritic, FusedActor

@@ -1,13 +1,14 @@
 """The LSTM cell of the recurrent policy on the GPU (``lg_lstm_step``, include/legged_recurrent.h) against the float64 restatement of
-``tests/recurrent_ref.py``, the ``RecurrentFusedActor`` against the torch module, and the runner's device rollout against batch-mode
-evaluation of what it stored.  Inputs uniform in [-3, 3] and torch's default initialisation: the float32 ``nn.LSTM`` itself stays
+``tests/recurrent_ref.py`` (also with saturated gates and with NaN / Inf in the stale state of reset rows), the ``RecurrentFusedActor``
+against the torch module (the default policy of ``anymal_c_rough`` against a float64 copy), and the runner's device rollout against
+batch-mode evaluation of what it stored.  Inputs uniform in [-3, 3] and torch's default initialisation: the float32 ``nn.LSTM`` itself stays
 within 7.5e-7 of float64 there, so 2e-5 (the bar of ``tests/test_gpu_rl.py``) leaves room for the 1-ulp ``v_rcp`` / ``v_exp``."""
 import numpy as np
 import pytest
 import torch
 import torch.nn as nn
 
-from tests.recurrent_ref import lstm_params64, lstm_step64
+from tests.recurrent_ref import lstm_params64, lstm_step64, saturating_bias
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -39,9 +40,11 @@ def _stream():
     return torch.cuda.current_stream(torch.device(DEV)).cuda_stream
 
 
-@pytest.mark.parametrize("I,H,N", [(19, 32, 1), (3, 32, 33), (48, 64, 37), (235, 256, 64), (256, 256, 96)])
+@pytest.mark.parametrize("I,H,N", [(19, 32, 1), (3, 32, 33), (48, 64, 37), (235, 256, 64), (256, 256, 96),
+                                   (1, 32, 32), (17, 160, 65), (40, 224, 33), (30, 128, 64)])
 def test_one_step_matches_float64(I, H, N):
-    """Both roles in one launch (the critic with another num_in), each role alone, and reset null / zero / set / mixed."""
+    """Both roles in one launch (the critic with another num_in), each role alone, and reset null / zero / set / mixed.  The last four
+    shapes: one input; 5, 7 and 4 waves; N a multiple of 32; k-step counts with remainder 1 (17 and 89 k-steps) and 3 (79, 83)."""
     DeviceLstm, lstm_step, lib = _cells()
     Ic = I + 7 if I + 7 <= 256 else I - 7
     rnn_a, rnn_c = _rnn(I, H, 1), _rnn(Ic, H, 2)
@@ -221,6 +224,84 @@ def test_load_device_equals_create():
     assert np.abs(outs[0][0].cpu().double().numpy() - lstm_step64(lstm_params64(rnn), x.cpu().numpy(), h.cpu().numpy(), c.cpu().numpy())[0]).max() < TOL
 
 
+# ---------------------------------------------------------------------------------------------------------------- edges of the cell
+def test_saturated_gates_stay_finite_and_exact():
+    """Pre-activations of 30, 100 and 1e4 of either sign in every gate (``saturating_bias``): the 1-ulp ``v_exp_f32`` overflows to inf or
+    underflows to 0 there, and sigma / tanh must come out as exactly 0 / 1 / -1, never NaN.  24 steps from a zero state, eager.  c grows to
+    about 15 in the units whose forget gate is pinned open, so the bar is TOL of the output scale, separately for h and c."""
+    I, H, N, T = 19, 64, 37, 24
+    DeviceLstm, lstm_step, lib = _cells()
+    rnn = _rnn(I, H, 6)
+    with torch.no_grad():
+        rnn.bias_ih_l0.add_(torch.from_numpy(saturating_bias(H)).float().to(DEV))
+    cell = DeviceLstm(rnn, DEV)
+    gen = torch.Generator().manual_seed(13)
+    xs = _uniform(gen, T, N, I)
+    p = lstm_params64(rnn)
+    st = [(torch.zeros(N, H, device=DEV), torch.zeros(N, H, device=DEV)) for _ in range(2)]
+    h, c = np.zeros((N, H)), np.zeros((N, H))
+    err_h = err_c = scale_h = scale_c = 0.0
+    for t in range(T):
+        lstm_step(lib, cell, None, xs[t], None, None, st[t & 1], st[1 - (t & 1)], None, None, N, _stream())
+        torch.cuda.synchronize()
+        got_h, got_c = st[1 - (t & 1)]
+        h, c = lstm_step64(p, xs[t].cpu().numpy(), h, c)
+        assert bool(torch.isfinite(got_h).all()) and bool(torch.isfinite(got_c).all()), t
+        assert bool((got_h[:, 4::8] == 0.0).all()), t            # output gate at -1e4: sigma is exactly 0
+        assert bool((got_c[:, 2::8] == 1.0).all()), t            # i at +1e4, f at -1e4 and g at +30 (tanh of 14.6 or more is 1.0f): c = 0 c + 1 * 1
+        err_h, err_c = max(err_h, np.abs(got_h.cpu().double().numpy() - h).max()), max(err_c, np.abs(got_c.cpu().double().numpy() - c).max())
+        scale_h, scale_c = max(scale_h, np.abs(h).max()), max(scale_c, np.abs(c).max())
+    print(f"[observed] saturated gates: h err {err_h:.3e} (max |h| {scale_h:.3f}), c err {err_c:.3e} (max |c| {scale_c:.3f})")
+    assert scale_c > 10.0                                        # the pinned-open forget gates did accumulate
+    assert err_h < TOL * max(1.0, scale_h) and err_c < TOL * max(1.0, scale_c), (err_h, err_c)
+
+
+@pytest.mark.parametrize("roles", ["both", "critic"])
+def test_a_reset_row_ignores_its_stale_state(roles):
+    """A row whose reset flag is set (any non-zero byte: 1, 2, 255) starts from zeros by SELECTION: NaN and Inf in its ``h_in`` / ``c_in``
+    must not reach any output (0 * NaN is NaN: a multiply-by-mask would leak), nor NaN rows behind row N of ``x``, ``h_in``, ``c_in``.  The
+    outputs are finite and bit-equal to the run with zeros in those places."""
+    DeviceLstm, lstm_step, lib = _cells()
+    I, Ic, H, N, extra = 19, 26, 64, 37, 5
+    rnn_a, rnn_c = _rnn(I, H, 1), _rnn(Ic, H, 2)
+    la, lc = (DeviceLstm(rnn_a, DEV) if roles == "both" else None), DeviceLstm(rnn_c, DEV)
+    gen = torch.Generator().manual_seed(21)
+    rows = torch.arange(N)
+    flagged = rows % 3 == 0
+    flags = torch.where(flagged, torch.tensor([1, 2, 255], dtype=torch.uint8)[(rows // 3) % 3], torch.zeros((), dtype=torch.uint8)).to(DEV)
+    assert set(flags[flagged.to(DEV)].tolist()) == {1, 2, 255} and int(flags[~flagged.to(DEV)].max()) == 0
+
+    def padded(width, poison, scale=1.0):
+        """[N, width] uniform values as a view of a buffer whose rows behind N are NaN; ``poison``: NaN (and an Inf of either sign) in the
+        reset rows.  Returns that view and one with zeros in the reset rows."""
+        full = torch.full((N + extra, width), float("nan"))
+        full[:N] = (torch.rand(N, width, generator=gen) * 2.0 - 1.0) * scale
+        clean = full.clone()
+        clean[:N][flagged] = 0.0
+        if poison:
+            full[:N][flagged] = float("nan")
+            full[3, 1], full[6, width - 1] = float("inf"), float("-inf")
+        return full.to(DEV)[:N], clean.to(DEV)[:N]
+
+    xa, xc = padded(I, False, 3.0)[0], padded(Ic, False, 3.0)[0]
+    states = [padded(H, True) for _ in range(4)]                 # h_a, c_a, h_c, c_c: (poisoned, zeros in the same places)
+    results = []
+    for k in (0, 1):
+        ha, ca, hc, cc = (s[k] for s in states)
+        full, outs = zip(*[_padded(N, H) for _ in range(4)])
+        lstm_step(lib, la, lc, xa, xc, flags, (ha, ca), (outs[0], outs[1]), (hc, cc), (outs[2], outs[3]), N, _stream())
+        torch.cuda.synchronize()
+        for f in full:
+            assert torch.isnan(f[N:]).all()
+        results.append([o.clone() for o in (outs if roles == "both" else outs[2:])])
+    for got, want in zip(*results):
+        assert bool(torch.isfinite(got).all()) and torch.equal(got, want)
+    live = (~flagged).to(DEV)
+    assert not torch.equal(results[0][-1][live], torch.zeros_like(results[0][-1][live]))
+    want_c = lstm_step64(lstm_params64(rnn_c), xc.cpu().numpy(), states[2][1].cpu().numpy(), states[3][1].cpu().numpy(), flagged.numpy())
+    assert np.abs(results[0][-2].cpu().double().numpy() - want_c[0]).max() < TOL and np.abs(results[0][-1].cpu().double().numpy() - want_c[1]).max() < TOL
+
+
 # ---------------------------------------------------------------------------------------------------------------- RecurrentFusedActor
 def _recurrent_policy(H=64, seed=7):
     from legged_games_gym_amd.rl import ActorCriticRecurrent
@@ -288,6 +369,46 @@ def test_recurrent_fused_actor_follows_the_module_and_draws_the_fused_actors_noi
         peek = rfa.peek_critic(obs[1]).clone()
         assert all(torch.equal(a, b) for a, b in zip(before, rfa.state_c[rfa._flip]))
         assert float((peek - ac.memory_c(obs[1]).squeeze(0)).abs().max()) < TOL
+
+
+def test_default_policy_of_the_rough_task_through_the_wrapper():
+    """``ActorCriticRecurrent``'s defaults on ``anymal_c_rough``: 235 observations, 256 units per memory, the 256-512-256-128-12 actor
+    (dynamic LDS above 64 KB).  Four steps with dones (one env done twice in a row) against a float64 CPU copy of the module stepped with
+    ``Memory.reset`` semantics: the means and the critic memory's output, TOL of the output scale."""
+    import copy
+    from legged_games_gym_amd.rl import ActorCriticRecurrent
+    from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor
+    N, T = 33, 4
+    torch.manual_seed(8)
+    ac = ActorCriticRecurrent(235, 235, 12, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128], rnn_hidden_size=256).to(DEV)
+    assert ac.memory_a.rnn.hidden_size == 256 and ac.actor[0].in_features == 256
+    ac64 = copy.deepcopy(ac).double().cpu()
+    rfa = RecurrentFusedActor(ac, DEV, seed=5)
+    gen = torch.Generator().manual_seed(10)
+    obs = _uniform(gen, T, N, 235)
+    dones = torch.rand(T, N, generator=gen) < 0.25
+    dones[:, 32] = torch.tensor([False, True, True, False])      # the single row of the second workgroup: done twice in a row
+    dones[0, 0] = True
+    with torch.no_grad():
+        for t in range(T):
+            reset = dones[t - 1].to(DEV) if t else None
+            _, mean, h_c = rfa.act_with_mean(obs[t], obs[t], reset)
+            torch.cuda.synchronize()
+            o64 = obs[t].cpu().double()
+            want_mean = ac64.act_inference(o64).numpy()
+            want_hc = ac64.memory_c(o64).squeeze(0).numpy()
+            ac64.reset(dones[t])
+            e_m, e_h = np.abs(mean.cpu().double().numpy() - want_mean).max(), np.abs(h_c.cpu().double().numpy() - want_hc).max()
+            s_m, s_h = max(1.0, np.abs(want_mean).max()), max(1.0, np.abs(want_hc).max())
+            print(f"[observed] rough default policy step {t}: mean err {e_m:.3e} (scale {s_m:.3f}), critic memory err {e_h:.3e} (scale {s_h:.3f})")
+            assert e_m < TOL * s_m and e_h < TOL * s_h, (t, e_m, e_h)
+        before = [x.clone() for pair in (rfa.state_a[rfa._flip], rfa.state_c[rfa._flip]) for x in pair]
+        peek = rfa.peek_critic(obs[0], dones[T - 1].to(DEV)).clone()
+        torch.cuda.synchronize()
+        after = [x for pair in (rfa.state_a[rfa._flip], rfa.state_c[rfa._flip]) for x in pair]
+        assert all(torch.equal(a, b) for a, b in zip(before, after))
+        want_peek = ac64.memory_c(obs[0].cpu().double()).squeeze(0).numpy()      # (ac64 was reset with dones[T - 1] above)
+        assert np.abs(peek.cpu().double().numpy() - want_peek).max() < TOL * max(1.0, np.abs(want_peek).max())
 
 
 # ---------------------------------------------------------------------------------------------------------------- runner

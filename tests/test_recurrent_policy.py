@@ -9,7 +9,8 @@ import torch
 
 from legged_games_gym_amd.rl import PPO, ActorCriticRecurrent, OnPolicyRunner
 from legged_games_gym_amd.rl.actor_critic import split_and_pad_trajectories, unpad_trajectories
-from tests.recurrent_ref import lstm_params64, lstm_step64
+from tests import recurrent_ref
+from tests.recurrent_ref import actor_forward64, actor_params64, lstm_params64, lstm_step64, saturating_bias
 
 KEYS = (["std"] + [f"{net}.{i}.{w}" for net in ("actor", "critic") for i in (0, 2, 4, 6) for w in ("weight", "bias")]
         + [f"memory_{m}.rnn.{w}" for m in ("a", "c") for w in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")])
@@ -96,6 +97,93 @@ def test_rollout_mode_matches_float64_restatement():
     (h_a, c_a), (h_c, c_c) = ac.get_hidden_states()
     keep = (~dones[T - 1]).double().numpy()[:, None]
     assert np.abs(h_a[0].double().numpy() - ha * keep).max() < 1e-5 and np.abs(c_c[0].double().numpy() - cc * keep).max() < 1e-5
+
+
+def _lstm_case(saturate, I=19, H=64, N=5, T=6):
+    """A default-initialised ``nn.LSTM`` (optionally with the saturating biases), ``x`` uniform in [-3, 3] and reset flags on some rows."""
+    torch.manual_seed(4)
+    rnn = torch.nn.LSTM(I, H)
+    if saturate:
+        with torch.no_grad():
+            rnn.bias_ih_l0.add_(torch.from_numpy(saturating_bias(H)).float())
+    gen = torch.Generator().manual_seed(11)
+    xs = torch.rand(T, N, I, generator=gen) * 6.0 - 3.0
+    resets = torch.rand(T, N, generator=gen) < 0.2
+    return rnn, xs, resets
+
+
+def test_overflow_free_sigmoid_leaves_the_lstm_reference_where_it_was(monkeypatch):
+    """``_sigmoid`` through tanh against the textbook 1 / (1 + exp(-v)) it replaced, on the inputs of the GPU tests (default weights, ``x``
+    in [-3, 3], 24 steps from a zero state with resets): no result of ``lstm_step64`` moves by more than 1e-15.  At |v| = 1e4 the new form
+    is exactly 0 / 1 and raises no warning."""
+    rnn, xs, resets = _lstm_case(False, T=24)
+    p = lstm_params64(rnn)
+
+    def run():
+        h = c = np.zeros((xs.shape[1], 64))
+        out = []
+        for t in range(xs.shape[0]):
+            h, c = lstm_step64(p, xs[t].numpy(), h, c, resets[t].numpy())
+            out += [h, c]
+        return np.stack(out)
+
+    new = run()
+    monkeypatch.setattr(recurrent_ref, "_sigmoid", lambda v: 1.0 / (1.0 + np.exp(-v)))
+    old = run()
+    moved = float(np.abs(new - old).max())
+    print(f"lstm_step64, tanh-form against exp-form sigmoid over 24 steps: max move {moved:.3e}")
+    assert moved <= 1e-15 and float(np.abs(old).max()) > 0.5
+    monkeypatch.undo()
+    with np.errstate(all="raise"):
+        s = recurrent_ref._sigmoid(np.array([-1e4, -800.0, 0.0, 800.0, 1e4]))
+    assert s.tolist() == [0.0, 0.0, 0.5, 1.0, 1.0]
+
+
+@pytest.mark.parametrize("saturate", [False, True], ids=["default", "saturated"])
+def test_lstm_reference_agrees_with_a_float64_nn_lstm(saturate):
+    """``lstm_step64`` against a ``.double()`` copy of ``nn.LSTM`` stepped with ``Memory.reset`` semantics (a reset row starts from zeros),
+    to 1e-12; with the saturating biases (pre-activations up to 1e4) nothing overflows and every value stays finite."""
+    import copy
+    rnn, xs, resets = _lstm_case(saturate)
+    rnn64, p = copy.deepcopy(rnn).double(), lstm_params64(rnn)
+    N, H = xs.shape[1], 64
+    h = c = np.zeros((N, H))
+    th, tc = torch.zeros(1, N, H, dtype=torch.float64), torch.zeros(1, N, H, dtype=torch.float64)
+    worst = 0.0
+    with torch.no_grad(), np.errstate(over="raise", invalid="raise"):
+        for t in range(xs.shape[0]):
+            h, c = lstm_step64(p, xs[t].numpy(), h, c, resets[t].numpy())
+            keep = (~resets[t]).double().view(1, N, 1)
+            _, (th, tc) = rnn64(xs[t].double().unsqueeze(0), (th * keep, tc * keep))
+            worst = max(worst, float(np.abs(h - th[0].numpy()).max()), float(np.abs(c - tc[0].numpy()).max()))
+    print(f"lstm_step64 against nn.LSTM.double(), saturate {saturate}: max diff {worst:.3e}, max |c| {float(np.abs(c).max()):.2f}")
+    assert np.isfinite(h).all() and np.isfinite(c).all() and worst < 1e-12
+    if saturate:
+        assert (h[:, 4::8] == 0.0).all() and np.abs(c[:, 2::8] - 1.0).max() < 1e-11      # o at -1e4; i at +1e4, f at -1e4, g at +30
+
+
+def test_actor_reference_agrees_with_a_float64_sequential():
+    """``actor_forward64`` from explicit arrays against a ``.double()`` copy of the actor ``nn.Sequential`` to 1e-12, with biases in [-1, 1],
+    at default weights and at weights x 3 (both ELU branches taken in every layer)."""
+    import copy
+    torch.manual_seed(2)
+    ac = ActorCriticRecurrent(7, 7, 5, actor_hidden_dims=[32, 64, 32], critic_hidden_dims=[16, 16, 16], rnn_hidden_size=32)
+    gen = torch.Generator().manual_seed(3)
+    h = torch.rand(9, 32, generator=gen) * 2.0 - 1.0
+    for gain in (1.0, 3.0):
+        with torch.no_grad():
+            for m in ac.actor:
+                if isinstance(m, torch.nn.Linear):
+                    m.weight.mul_(gain)
+                    m.bias.copy_(torch.rand(m.bias.shape, generator=gen) * 2.0 - 1.0)
+            want = copy.deepcopy(ac.actor).double()(h.double()).numpy()
+        w, b = actor_params64(ac.actor)
+        assert [x.shape for x in w] == [(32, 32), (64, 32), (32, 64), (5, 32)]
+        got = actor_forward64(w, b, h.numpy())
+        print(f"actor_forward64 against Sequential.double(), gain {gain}: max diff {float(np.abs(got - want).max()):.3e}, scale {float(np.abs(want).max()):.2f}")
+        assert got.shape == (9, 5) and np.abs(got - want).max() < 1e-12
+        pre = h.double().numpy() @ w[0].T + b[0]
+        assert (pre < -0.5).any() and (pre > 0.5).any()
 
 
 def _mlp64(seq, x):
