@@ -131,6 +131,8 @@ class RolloutStorage:
         adv = 0
         for step in reversed(range(self.num_transitions_per_env)):
             nxt = last_values if step == self.num_transitions_per_env - 1 else self.values[step + 1]
+            # (tests/test_ppo_tail_ref.py drives this scan on double tensors and stands in for `dones`: it answers `[step].float()` only --
+            # read the flags another way and that test fails with an AttributeError until its stand-in follows)
             not_done = 1.0 - self.dones[step].float()
             delta = self.rewards[step] + not_done * gamma * nxt - self.values[step]
             adv = delta + not_done * gamma * lam * adv

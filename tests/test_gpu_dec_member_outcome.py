@@ -403,3 +403,17 @@ def test_runner_deals_by_priority_from_the_logged_counts(tmp_path, monkeypatch, 
         episodes.append(sum(int(r["episodes"]) for r in mine))
         wins.append(sum(int(r["captured"]) for r in mine))
     assert runner.opponent_weights("pred") == pfsp_weights(wins, episodes, 1.0) and episodes[0] > 0 and episodes[1] == 0
+
+
+@pytest.mark.parametrize("n", [33, 300])
+def test_member_kernel_matches_the_twin_directly(n):
+    """k_member_outcome against the NumPy twin itself, not through k_dec_outcome: one launch under the cycling slot table at 33 envs (a wave
+    that holds two members) and at 300 (a second workgroup with a ragged last block), every per-env array, the episode sums and the episode
+    means under the comparison tests/test_gpu_dec_game.py holds lg_dec_game_post to."""
+    from tests.dec_game_fixtures import check_call
+    c = mf.case(n)
+    name, table, count = next(t for t in mf.slot_tables(n) if t[0] == "cycle")
+    L = MemberLauncher(c["s"], [call_of(c)], table, count)
+    L.launch(0, counter_on_device=bool(n % 2))
+    check_call(c["p"], c["s"], L.outputs(), c["info"], c["want"], extra_ulp=2)
+    assert c["want"]["reset_buf"].any() and not c["want"]["reset_buf"].all()

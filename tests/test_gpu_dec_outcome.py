@@ -471,3 +471,17 @@ def test_crossplay_swaps_weights_under_one_graph_and_restores_the_start_exactly(
     t = again["totals"]
     assert t[2][2] == t[0][0] == t[0][2] == t[2][0] == both["totals"][0][0]
     assert t[0][1] == t[2][1] == both["totals"][0][1] and t[1][0] == t[1][2] == both["totals"][1][0] and t[1][1] == both["totals"][1][1]
+
+
+@pytest.mark.parametrize("termination", of.TERMINATIONS)
+def test_outcome_kernel_matches_the_twin_directly(termination):
+    """k_dec_outcome against the NumPy twin itself, not through k_dec_post: one launch at 257 envs (two workgroups, the second nearly empty),
+    every per-env array, the episode sums and the episode means under the comparison tests/test_gpu_dec_game.py holds lg_dec_game_post to."""
+    from tests.dec_game_fixtures import check_call
+    c = of.case(257, termination)
+    s = c["s"]
+    call = dict(p=c["p"], step=c["step"], command_pred=s["command_pred"], ll_rew=s["ll_rew"], ll_reset=s["ll_reset"], ll_time_out=c["ll_time_out"])
+    L = Launcher(s, [call])
+    L.launch(0, counter_on_device=True)
+    check_call(c["p"], s, L.outputs(), c["info"], c["want"], extra_ulp=2)
+    assert c["want"]["reset_buf"].any() and not c["want"]["reset_buf"].all()

@@ -343,3 +343,24 @@ def test_play_game_reports_the_totals_of_its_rollout(tmp_path, monkeypatch, scri
         assert (got is None and math.isnan(v)) or got == v
     text = capsys.readouterr().out
     assert "not counted" in text and "captured" in text and "survived" in text
+
+
+@pytest.mark.parametrize("scripted", [False, True])
+@pytest.mark.parametrize("radius", of.RADII)
+def test_outcome_kernels_match_the_twin_directly(radius, scripted):
+    """Both builds of k_outcome_post against the NumPy twin itself, not through the plain kernels: one launch at 257 envs (two workgroups,
+    the second nearly empty), every per-env array under the comparison tests/test_gpu_game.py and tests/test_gpu_pursuer_game.py hold
+    lg_game_post / lg_pursuer_post to, and the pursuer's velocity bit for bit."""
+    from tests.game_fixtures import check_call
+    c = of.case(257, radius)
+    s = c["s"] if scripted else c["s_plain"]
+    want, info = (c["want"], c["info"]) if scripted else tw.post(c["p"], s, step=c["step"])
+    tw.assert_margins(c["p"], info)
+    call = dict(p=c["p"], q=c["q"], step=c["step"], command=s["command"], ll_rew=s["ll_rew"], ll_reset=s["ll_reset"], ll_time_out=c["ll_time_out"])
+    L = Launcher(s, [call], scripted)
+    L.launch(0, counter_on_device=True)
+    got = L.outputs()
+    check_call(c["p"], s, got, info, want, extra_ulp=2)
+    if scripted:
+        np.testing.assert_array_equal(got["predator_command"].view(np.uint32), info["predator_command"].view(np.uint32))
+    assert want["reset_buf"].any() and not want["reset_buf"].all()

@@ -68,10 +68,23 @@ def test_reset_is_bit_exact(task):
     # subset reset leaves the others untouched
     before = get(d, "dof_state").copy()
     ids = np.array([1, 5, 64, 129], dtype=np.int32)
+    # actuator-net tasks (k_reset<AnymalTraits, true>): the LSTM state of the reset envs is zeroed (anymal.py:56-60), both layers, nothing else
+    net = task in ("anymal_c_flat", "anymal_b")
+    assert net == ("sea_hidden_state" in o.buf and o.buf["sea_hidden_state"] is not None)
+    sea = {}
+    if net:
+        rng = np.random.default_rng(12)
+        for k in ("sea_hidden_state", "sea_cell_state"):
+            sea[k] = rng.uniform(0.5, 1.5, o.buf[k].shape).astype(np.float32) * rng.choice([-1.0, 1.0], o.buf[k].shape).astype(np.float32)
+            put(o, d, k, sea[k])
     o.reset_idx(ids, 7); d.reset_idx(torch.from_numpy(ids), 7)
     after = get(d, "dof_state").reshape(N, 12, 2)
     keep = np.setdiff1d(np.arange(N), ids)
     assert np.array_equal(after[keep], before.reshape(N, 12, 2)[keep]) and maxdiff(o, d, "dof_state") == 0.0
+    for k, loaded in sea.items():
+        got = get(d, k).reshape(2, N, 12, 8)
+        assert np.array_equal(got, o.buf[k].reshape(2, N, 12, 8)), k
+        assert (got[:, ids] == 0.0).all() and np.array_equal(got[:, keep], loaded.reshape(2, N, 12, 8)[:, keep]), k
 
 
 @pytest.mark.parametrize("task", ["anymal_c_flat", "cassie", "anymal_c_rough", "a1", "anymal_b"])
@@ -544,3 +557,28 @@ def test_reset_idx_matches_reference_fixture(task, golden_dir):
     cfg, names, w, d = _device_for_full_fixture(g, task)
     d.reset_idx(torch.from_numpy(g["env_ids"].astype(np.int32)), int(g["step"]))
     check_reset_idx_outputs(lambda k: get(d, k), g, names)
+
+
+@pytest.mark.parametrize("task", ["anymal_c_flat", "anymal_c_rough", "cassie"])
+def test_observations_only_parity(task):
+    """lg_compute_observations_only (k_obs: the quadruped and the biped build) against the oracle's compute_observations_only on one seeded
+    state -- base-frame velocities and projected gravity are inputs here, not recomputed -- at an env count that leaves the last workgroup
+    ragged, for two step counters (the noise is keyed by the counter).  Tolerance: that of obs_buf in test_post_physics_block_parity."""
+    N = 130
+    cfg, robot, p, names, o, d = pair(task, N)
+    put(o, d, "env_origins", grid_origins(N))
+    for k, v in synth_state(robot, p, N, seed=17).items():
+        put(o, d, k, v.numpy())
+    rng = np.random.default_rng(4)
+    for k in ("base_lin_vel", "base_ang_vel", "projected_gravity"):
+        put(o, d, k, rng.normal(0.0, 1.0, o.buf[k].shape))
+    seen = []
+    for counter in (3, 4):
+        put(o, d, "obs_buf", np.full(o.buf["obs_buf"].shape, 7.0))          # every element is rewritten
+        o.compute_observations_only(counter); d.compute_observations_only(counter)
+        assert maxdiff(o, d, "obs_buf") <= 3e-6, (counter, maxdiff(o, d, "obs_buf"))
+        seen.append(get(d, "obs_buf").copy())
+        assert np.isfinite(seen[-1]).all() and not (seen[-1] == 7.0).any()
+    if cfg.noise.add_noise:                       # another counter, other noise
+        assert not np.array_equal(seen[0], seen[1])
+    assert np.abs(seen[0]).max() > 0.5

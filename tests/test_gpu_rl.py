@@ -188,6 +188,7 @@ def test_adam_kernel_matches_torch_adam_with_clipping(wide):
             assert float((a - b).detach().abs().max()) < 2e-6, it
         for a, b in zip(nets[0].parameters(), nets[1].parameters()):
             assert float((opts[0].state[a]["exp_avg_sq"] - opts[1].state[b]["exp_avg_sq"]).abs().max()) < 1e-6
+            assert float((opts[0].state[a]["exp_avg"] - opts[1].state[b]["exp_avg"]).abs().max()) < 1e-6
             assert float(opts[0].state[a]["step"]) == float(opts[1].state[b]["step"])
 
 
