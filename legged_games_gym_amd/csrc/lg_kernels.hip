@@ -333,8 +333,40 @@ template <bool HF> LG_DEV void hf_contact(const KArgs &A, const HfFetch &f, floa
 // ------------------------------------------------------------------ one 5 ms rigid-body step for (env, limb)
 struct Contact { V3 r, n, vc, f, fs; float depth, bt, vtn; bool on; };   // fs: constant sliding force of the corrector pass
 
+// Plane builds (HF = false): the ground normal is e_z, and the three contact functions are written with it taken out -- a product with
+// the literal 0 of n is an instruction the compiler may not drop (no fast-math), and the general text spends two thirds of
+// contact_assemble on them.  What is left is formed in the general text's order and with ITS roundings as hipcc contracts it for
+// n = (0, 0, 1): the dropped terms are exact zeros, so a plane build computes what it computed before up to the sign of a zero
+// (non-finite states, which the env reset discards, aside).  prod_rn / sub_rn keep a product that the general text rounds before
+// its sum, or a difference of two rounded values, out of an FMA; where the general text does contract, the FMA is written out.
+LG_DEV float prod_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+LG_DEV float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+// K depth - kn v_n.  K depth does not change over the passes and is shared by assemble and evaluate: hipcc forms it once, rounded,
+// in front of the pass loop and contracts the OTHER product into the difference
+LG_DEV float plane_normal_force(const lg_params &P, float kn, float depth, float vz) {
+    return __builtin_fmaf(-kn, vz, prod_rn(P.contact_stiffness, depth));
+}
+LG_DEV V3 plane_force(const Contact &c, V3 v, float fn) {              // n fn - vt bt + fs: fs.z and vt.z are zeros
+    return v3(sub_rn(c.fs.x, prod_rn(v.x, c.bt)), sub_rn(c.fs.y, prod_rn(v.y, c.bt)), fn);
+}
+LG_DEV float plane_slip_speed(V3 v) { return sqrtf(__builtin_fmaf(v.x, v.x, prod_rn(v.y, v.y))); }
+
 // fprev = previous sub-step's net contact force on the point's report body (seeds the friction secant)
+template <bool HF>
 LG_DEV void contact_setup(Contact &c, const lg_params &P, float mu, V3 r, V3 n, float depth, V3 vc, V3 fprev) {
+    if constexpr (!HF) {                                  // c.n is never read in a plane build
+        c.r = r; c.depth = depth; c.vc = vc; c.on = depth > -P.contact_margin; c.f = v3(0, 0, 0); c.fs = v3(0, 0, 0);
+        c.vtn = plane_slip_speed(vc);
+        float fn_est = fmaxf(fprev.z, 0.0f);
+        c.bt = fminf(P.friction_damping, mu * fn_est / fmaxf(c.vtn, P.stick_velocity));
+        return;
+    }
     c.r = r; c.n = n; c.depth = depth; c.vc = vc; c.on = depth > -P.contact_margin; c.f = v3(0, 0, 0); c.fs = v3(0, 0, 0);
     float vn0 = dot(n, vc);
     V3 vt0 = vc - n * vn0;
@@ -342,7 +374,32 @@ LG_DEV void contact_setup(Contact &c, const lg_params &P, float mu, V3 r, V3 n, 
     float fn_est = fmaxf(dot(n, fprev), 0.0f);
     c.bt = fminf(P.friction_damping, mu * fn_est / fmaxf(c.vtn, P.stick_velocity));
 }
+template <bool HF>
 LG_DEV void contact_assemble(const Contact &c, const lg_params &P, float kn, AI &IA, S6 &pA) {
+    if constexpr (!HF) {
+        if (c.on) {
+            const float dt = P.sim_dt;
+            const V3 f = plane_force(c, c.vc, plane_normal_force(P, kn, c.depth, c.vc.z));
+            ai_add_point(IA, dt * c.bt, c.r);
+            // rank-1 term k g g^T with g = (r x e_z, e_z) = (r.y, -r.x, 0, 0, 0, 1): six entries instead of 21
+            const float kk = kn - c.bt, k = prod_rn(dt, kk), kx = prod_rn(k, c.r.x), ky = prod_rn(k, c.r.y);
+            IA.A[0] = __builtin_fmaf(ky, c.r.y, IA.A[0]); IA.A[1] = __builtin_fmaf(-c.r.x, ky, IA.A[1]); IA.A[3] = __builtin_fmaf(kx, c.r.x, IA.A[3]);
+            IA.H[2] = __builtin_fmaf(c.r.y, k, IA.H[2]); IA.H[5] = __builtin_fmaf(-c.r.x, k, IA.H[5]);
+            IA.M[5] = __builtin_fmaf(dt, kk, IA.M[5]);
+            // r x f as cross() contracts it with a per-pass f.  Written out: f.z does not change over the passes here, and with cross()
+            // its products would be formed in front of the pass loop, rounded, which turns the contraction of the first row around
+            const V3 rxf = v3(__builtin_fmaf(c.r.y, f.z, -prod_rn(c.r.z, f.y)), __builtin_fmaf(c.r.z, f.x, -prod_rn(c.r.x, f.z)),
+                              __builtin_fmaf(c.r.x, f.y, -prod_rn(c.r.y, f.x)));
+            pA.w = pA.w - rxf;
+            pA.v = pA.v - f;
+            // The six entries a plane contact leaves alone (the general text adds an exact zero to them here) would now be the same
+            // in every pass for the last body of the chain, whose IA is I0 plus its contacts, and hipcc would form the products of the
+            // H diagonal with the joint axis (U = IA S) once in front of the pass loop, rounded, where it contracts them inside the loop
+            // today (1 - 2 ulp in the joint accelerations).  The empty asm emits nothing; it only keeps those products where they were.
+            asm volatile("" : "+v"(IA.H[0]), "+v"(IA.H[4]), "+v"(IA.H[8]), "+v"(IA.M[1]), "+v"(IA.M[2]), "+v"(IA.M[4]));
+        }
+        return;
+    }
     if (c.on) {
         const float dt = P.sim_dt;
         float vn = dot(c.n, c.vc);
@@ -355,7 +412,23 @@ LG_DEV void contact_assemble(const Contact &c, const lg_params &P, float kn, AI 
     }
 }
 // more: another pass follows (wave-uniform) -- only that pass reads the corrector's results
+template <bool HF>
 LG_DEV void contact_evaluate(Contact &c, const lg_params &P, float kn, float mu, S6 acc, bool more = true) {
+    if constexpr (!HF) {
+        if (c.on) {
+            V3 v1 = c.vc + (acc.v + cross(acc.w, c.r)) * P.sim_dt;
+            float fn = plane_normal_force(P, kn, c.depth, v1.z);
+            if (fn <= 0.0f) { c.on = false; c.f = v3(0, 0, 0); }
+            else {
+                c.f = plane_force(c, v1, fn);
+                if (!more) return;
+                float vtm = plane_slip_speed(v1), cone = mu * fn;           // the corrector, as below with vt = (v1.x, v1.y, 0)
+                if (c.bt * vtm > cone) { const float s = -cone / vtm; c.fs = v3(v1.x * s, v1.y * s, 0.0f); c.bt = 0.0f; }
+                else if (c.bt > 0.0f) c.bt = fminf(P.friction_damping, cone / fmaxf(vtm, P.stick_velocity));
+            }
+        }
+        return;
+    }
     if (c.on) {
         V3 v1 = c.vc + (acc.v + cross(acc.w, c.r)) * P.sim_dt;
         float vn = dot(c.n, v1);
@@ -766,12 +839,12 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
     {   // the samples have had the whole kinematics pass to arrive
         float dep; V3 n;
         hf_contact<HF>(A, fb, root[2] + cb.r.z, cb.depth, dep, n);
-        contact_setup(cb, P, mu, cb.r, n, dep, cb.vc, v3(Fbase[0], Fbase[1], Fbase[2]));
+        contact_setup<HF>(cb, P, mu, cb.r, n, dep, cb.vc, v3(Fbase[0], Fbase[1], Fbase[2]));
         cb.on = cb.on && (lane_k < A.base.num_pts);
 #pragma unroll
         for (int i = 0; i < NPT; i++) {
             hf_contact<HF>(A, fl[i], cl[i].vtn, cl[i].depth, dep, n);
-            contact_setup(cl[i], P, mu, cl[i].r, n, dep, cl[i].vc,
+            contact_setup<HF>(cl[i], P, mu, cl[i].r, n, dep, cl[i].vc,
                           v3(Frep[T::pt_rep(i)][0], Frep[T::pt_rep(i)][1], Frep[T::pt_rep(i)][2]));
         }
     }
@@ -827,7 +900,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
             const float *tj = tab + j * LG_JS;
             AI IA = I0[j]; S6 pA = p0[j];
 #pragma unroll
-            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) { LG_PROF_COUNT(0, cl[i].on); contact_assemble(cl[i], P, kn, IA, pA); }
+            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) { LG_PROF_COUNT(0, cl[i].on); contact_assemble<HF>(cl[i], P, kn, IA, pA); }
             if (j < L - 1) { ai_add(IA, Ia); pA = pA + pa; }
             U[j] = ai_mul_w(IA, ax[j]);
             float damp = tj[J_DAMP];
@@ -860,7 +933,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
         LG_PROF(PF_INWARD);
         LG_PROF_COUNT(1, cb.on);
         LG_PROF_COUNT(2, any_self);
-        contact_assemble(cb, P, kn, Ia, pa);      // this lane's base point (about the base origin, like Ia after the shift)
+        contact_assemble<HF>(cb, P, kn, Ia, pa);      // this lane's base point (about the base origin, like Ia after the shift)
         if (SC && any_self) {                     // (final pass only) reactions of this limb's base contacts: force -n f0 on the base, implicit in the base's motion
             const int ln = threadIdx.x % LG_BLOCK;
 #pragma unroll
@@ -881,7 +954,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
         bool ok = solve6(IAb, rhs, a0);
         if (!ok) { a0[0] = a0[1] = a0[2] = a0[3] = a0[4] = a0[5] = 0.0f; }
         acc0.w = v3(a0[0], a0[1], a0[2]); acc0.v = v3(a0[3], a0[4], a0[5]);
-        contact_evaluate(cb, P, kn, mu, acc0, more);
+        contact_evaluate<HF>(cb, P, kn, mu, acc0, more);
         LG_PROF(PF_BASE);
         S6 a = acc0;
 #pragma unroll
@@ -898,7 +971,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
                 if (lim > 0.0f && vl[j] == 0.0f && fabsf(qn) > lim) vl[j] = qn > 0.0f ? 1.0f : -1.0f;
             }
 #pragma unroll
-            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) contact_evaluate(cl[i], P, kn, mu, a, more);
+            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) contact_evaluate<HF>(cl[i], P, kn, mu, a, more);
         }
         LG_PROF(PF_OUTWARD);
     }
