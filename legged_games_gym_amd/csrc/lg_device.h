@@ -63,6 +63,19 @@ LG_DEV void ai_add_point(AI &I, float m, V3 c) {
     I.H[1] -= m * c.z; I.H[2] += m * c.y; I.H[3] += m * c.z; I.H[5] -= m * c.x; I.H[6] -= m * c.y; I.H[7] += m * c.x;
     I.M[0] += m; I.M[3] += m; I.M[5] += m;
 }
+// Rigid inertia about the body's reference point, the ten numbers it has: A (xx,xy,xz,yy,yz,zz), h = m c (H = [h]x) and m (M = m 1).
+// What the passes hold per body across a sub-step, and what the helper waves hand over; ri_expand() writes the 21 entries out where
+// a pass starts from them (the eleven zeros, copies and negations cost no register there: literals and source modifiers).  The sums
+// that follow keep their general text (ai_add, ai_mul_w): assigning the child's entry where it meets a literal zero instead of adding
+// it changes how hipcc contracts the neighbouring sums of ai_shift / ai_add_rank1 (ulp-level differences in every kernel).
+struct RI { float A[6]; V3 h; float m; };
+LG_DEV void ri_expand(AI &I, const RI &r) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) I.A[i] = r.A[i];
+    I.H[0] = 0.0f; I.H[1] = -r.h.z; I.H[2] = r.h.y; I.H[3] = r.h.z; I.H[4] = 0.0f; I.H[5] = -r.h.x; I.H[6] = -r.h.y; I.H[7] = r.h.x; I.H[8] = 0.0f;
+    I.M[0] = r.m; I.M[1] = 0.0f; I.M[2] = 0.0f; I.M[3] = r.m; I.M[4] = 0.0f; I.M[5] = r.m;
+}
+LG_DEV void ri_expand(AI &I, const AI &r) { I = r; }          // height-field builds hold the 21 entries (lg_kernels.hip: RigidOf)
 LG_DEV void ai_add_rank1(AI &I, float k, V3 gw, V3 gv) {
     float w[3] = {gw.x, gw.y, gw.z}, v[3] = {gv.x, gv.y, gv.z};
     int t = 0;

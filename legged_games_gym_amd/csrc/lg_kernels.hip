@@ -392,10 +392,11 @@ LG_DEV void contact_assemble(const Contact &c, const lg_params &P, float kn, AI 
                               __builtin_fmaf(c.r.x, f.y, -prod_rn(c.r.y, f.x)));
             pA.w = pA.w - rxf;
             pA.v = pA.v - f;
-            // The six entries a plane contact leaves alone (the general text adds an exact zero to them here) would now be the same
-            // in every pass for the last body of the chain, whose IA is I0 plus its contacts, and hipcc would form the products of the
-            // H diagonal with the joint axis (U = IA S) once in front of the pass loop, rounded, where it contracts them inside the loop
-            // today (1 - 2 ulp in the joint accelerations).  The empty asm emits nothing; it only keeps those products where they were.
+            // The six entries a plane contact leaves alone (the general text adds an exact zero to them here; literal zeros of ri_expand()
+            // for the last body of the chain) would be the same in every pass for that body, whose IA is its rigid inertia plus its
+            // contacts, and hipcc would form the products of the H diagonal with the joint axis (U = IA S) once in front of the pass loop,
+            // rounded, where it contracts them inside the loop today (1 - 2 ulp in the joint accelerations).  The empty asm emits nothing
+            // but the moves that put the zeros into registers; it keeps those products where they were.
             asm volatile("" : "+v"(IA.H[0]), "+v"(IA.H[4]), "+v"(IA.H[8]), "+v"(IA.M[1]), "+v"(IA.M[2]), "+v"(IA.M[4]));
         }
         return;
@@ -461,6 +462,35 @@ LG_DEV V3 clamp_norm(V3 a, float lim) {           // asset.max_linear/angular_ve
 }
 
 // rigid-body inertia about the body's own reference point and bias force (gyroscopic - gravity), world axes
+// The inertia leaves in its compact form (RI): the A block as ai_add_point() forms it, h = m c rounded once (what 0 +- m c.k gave
+// when H started from zero), and m.
+LG_DEV void body_terms(V3 grav, float m, V3 com_l, const float *Il, const M3 &R, V3 w, V3 v, RI &I0, S6 &p0) {
+    V3 c = mul(R, com_l);
+    M3 Ilf; Ilf.m[0] = Il[0]; Ilf.m[1] = Il[1]; Ilf.m[2] = Il[2]; Ilf.m[3] = Il[1]; Ilf.m[4] = Il[3]; Ilf.m[5] = Il[4];
+    Ilf.m[6] = Il[2]; Ilf.m[7] = Il[4]; Ilf.m[8] = Il[5];
+    M3 Rt;
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j2 = 0; j2 < 3; j2++) Rt.m[3 * i + j2] = R.m[3 * j2 + i];
+    M3 Ic = mul(mul(R, Ilf), Rt);
+    I0.A[0] = Ic.m[0]; I0.A[1] = Ic.m[1]; I0.A[2] = Ic.m[2]; I0.A[3] = Ic.m[4]; I0.A[4] = Ic.m[5]; I0.A[5] = Ic.m[8];
+    {
+        float cc = dot(c, c);
+        I0.A[0] += m * (cc - c.x * c.x); I0.A[1] -= m * c.x * c.y; I0.A[2] -= m * c.x * c.z;
+        I0.A[3] += m * (cc - c.y * c.y); I0.A[4] -= m * c.y * c.z; I0.A[5] += m * (cc - c.z * c.z);
+    }
+    I0.h = v3(prod_rn(m, c.x), prod_rn(m, c.y), prod_rn(m, c.z));
+    I0.m = m;
+    V3 l = (v + cross(w, c)) * m;
+    V3 n = mul(Ic, w) + cross(c, l);
+    V3 fg = grav * m;
+    p0.w = (cross(w, n) + cross(v, l)) - cross(c, fg);
+    p0.v = cross(w, l) - fg;
+}
+// the same with all 21 entries (height-field builds): the general text, H and M started from zero
+// (a copy, not a shared front end: with the common text moved into one template the height-field kernels' instruction text and
+// their results change, like everything that touches how hipcc contracts these sums -- DESIGN.md section 5)
 LG_DEV void body_terms(V3 grav, float m, V3 com_l, const float *Il, const M3 &R, V3 w, V3 v, AI &I0, S6 &p0) {
     V3 c = mul(R, com_l);
     M3 Ilf; Ilf.m[0] = Il[0]; Ilf.m[1] = Il[1]; Ilf.m[2] = Il[2]; Ilf.m[3] = Il[1]; Ilf.m[4] = Il[3]; Ilf.m[5] = Il[4];
@@ -507,9 +537,17 @@ LG_DEV FkOut fk_joint(const float *tj, const M3 &Rpar, V3 wpar, V3 vpar, float q
     o.v = vpar + cross(wpar, o.db);
     return o;
 }
-// LDS hand-over of the limb bodies' (I0, p0) when the helper waves compute them (k_step, quadruped kernels): 28 floats per
-// (joint, lane) as 7 float4.
-#define LG_BT_QUADS 7
+// What a build holds per body across the passes and hands over: plane builds the compact rigid inertia, height-field builds all 21
+// entries -- their sums are not bit-identical from the compact record, so they keep the form they had.
+template <bool HF> struct RigidOf { typedef RI type; };
+template <> struct RigidOf<true> { typedef AI type; };
+// LDS hand-over of the limb bodies' (I0, p0) when the helper waves compute them (k_step, quadruped kernels): the ten numbers of the
+// rigid inertia and the six of the bias force, 16 floats per (joint, lane) as 4 float4; 21 + 6 floats as 7 float4 in height-field builds.
+template <bool HF> struct BtQuads { static constexpr int N = HF ? 7 : 4; };
+LG_DEV void bt_store(float4 (*dst)[LG_BLOCK], int lane, const RI &I, const S6 &p) {
+    dst[0][lane] = make_float4(I.A[0], I.A[1], I.A[2], I.A[3]); dst[1][lane] = make_float4(I.A[4], I.A[5], I.h.x, I.h.y);
+    dst[2][lane] = make_float4(I.h.z, I.m, p.w.x, p.w.y); dst[3][lane] = make_float4(p.w.z, p.v.x, p.v.y, p.v.z);
+}
 LG_DEV void bt_store(float4 (*dst)[LG_BLOCK], int lane, const AI &I, const S6 &p) {
     dst[0][lane] = make_float4(I.A[0], I.A[1], I.A[2], I.A[3]); dst[1][lane] = make_float4(I.A[4], I.A[5], I.H[0], I.H[1]);
     dst[2][lane] = make_float4(I.H[2], I.H[3], I.H[4], I.H[5]); dst[3][lane] = make_float4(I.H[6], I.H[7], I.H[8], I.M[0]);
@@ -521,6 +559,11 @@ LG_DEV void bt_load(const float4 (*src)[LG_BLOCK], int lane, AI &I, S6 &p) {
     I.A[0] = a.x; I.A[1] = a.y; I.A[2] = a.z; I.A[3] = a.w; I.A[4] = b.x; I.A[5] = b.y; I.H[0] = b.z; I.H[1] = b.w;
     I.H[2] = c.x; I.H[3] = c.y; I.H[4] = c.z; I.H[5] = c.w; I.H[6] = d.x; I.H[7] = d.y; I.H[8] = d.z; I.M[0] = d.w;
     I.M[1] = e.x; I.M[2] = e.y; I.M[3] = e.z; I.M[4] = e.w; I.M[5] = f.x; p.w = v3(f.y, f.z, f.w); p.v = v3(g.x, g.y, g.z);
+}
+LG_DEV void bt_load(const float4 (*src)[LG_BLOCK], int lane, RI &I, S6 &p) {
+    float4 a = src[0][lane], b = src[1][lane], c = src[2][lane], d = src[3][lane];
+    I.A[0] = a.x; I.A[1] = a.y; I.A[2] = a.z; I.A[3] = a.w; I.A[4] = b.x; I.A[5] = b.y; I.h = v3(b.z, b.w, c.x); I.m = c.y;
+    p.w = v3(c.z, c.w, d.x); p.v = v3(d.y, d.z, d.w);
 }
 
 // ------------------------------------------------------------------ self-collision (asset.self_collisions = 0; DESIGN.md "Self-collision")
@@ -692,7 +735,24 @@ LG_DEV void self_detect(const KArgs &A, const float *lds_tab, int ln, int m, Sel
         sc.rec[m][ga][3][ln] = make_float4(best.f0 / (1.0f + kn * dt * (1.0f / mA + 1.0f / best_mB)), (float)best_i, 0.0f, 0.0f);
     }
 }
-// Rigid-body wave, before the final pass: fold the limb side of every record into the carrying body's rigid terms.
+// Rigid-body wave, before the final pass: which records this lane has (bit m * NGRP + g).  Returns (wave-uniform) whether any lane of
+// the wave has one.
+template <class T>
+LG_DEV bool self_mask(int ln, const SelfLds<T> &sc, unsigned &mask) {
+    float coef[T::K][T::NGRP];                                        // all record headers in flight at once (one LDS latency, not K * NGRP)
+    mask = 0;
+#pragma unroll
+    for (int m = 0; m < T::K; m++)
+#pragma unroll
+        for (int g = 0; g < T::NGRP; g++) coef[m][g] = sc.rec[m][g][1][ln].w;
+#pragma unroll
+    for (int m = 0; m < T::K; m++)
+#pragma unroll
+        for (int g = 0; g < T::NGRP; g++) if (coef[m][g] >= 0.0f) mask |= 1u << (m * T::NGRP + g);
+    return __builtin_amdgcn_ballot_w64(mask != 0) != 0;
+}
+// Height-field builds (21-entry form, I0 a general matrix), before the final pass: fold the limb side of every record into the carrying
+// body's rigid terms.  The text these builds had before the compact form, kept whole: their instruction text is unchanged.
 // Returns (wave-uniform) whether any lane of the wave has a record.
 template <class T>
 LG_DEV bool self_apply(int ln, const V3 (&db)[T::L], AI (&I0)[T::L], S6 (&p0)[T::L], const SelfLds<T> &sc) {
@@ -728,6 +788,31 @@ LG_DEV bool self_apply(int ln, const V3 (&db)[T::L], AI (&I0)[T::L], S6 (&p0)[T:
     return true;
 }
 
+// Plane builds (compact form): final pass, body j of the inward loop, between the expansion of its rigid inertia and its ground contacts: fold the limb side of
+// the records that body j carries into (IA, pA), in (partner, group) order.  The rigid inertia kept across the passes stays compact.
+template <class T>
+LG_DEV void self_fold(int j, unsigned mask, int ln, const V3 (&db)[T::L], AI &IA, S6 &pA, const SelfLds<T> &sc) {
+#pragma unroll
+    for (int m = 0; m < T::K; m++) {
+#pragma unroll
+        for (int g = 0; g < T::NGRP; g++) {
+            const int jc = T::pt_joint(T::grp_c0(g));                     // compile time after unrolling
+            if (jc != j) continue;
+            const bool hit = (mask >> (m * T::NGRP + g)) & 1u;
+            if (__builtin_amdgcn_ballot_w64(hit) == 0) continue;
+            if (hit) {
+                const float4 r0 = sc.rec[m][g][0][ln], r1 = sc.rec[m][g][1][ln];
+                V3 rj = db[0];
+#pragma unroll
+                for (int jj = 1; jj <= jc; jj++) rj = rj + db[jj];
+                const V3 n = xyz(r0), r = xyz(r1) - rj, f = n * r0.w;
+                ai_add_rank1(IA, r1.w, cross(r, n), n);
+                pA.w = pA.w - cross(r, f); pA.v = pA.v - f;
+            }
+        }
+    }
+}
+
 // `torques_ready` runs between the kinematics half (needs no torques) and the articulated-body passes: the fused step
 // uses it to join the actuator waves, which compute this sub-step's torques meanwhile (k_step).
 struct NoWait { LG_DEV void operator()() const {} };
@@ -740,7 +825,7 @@ template <class T, bool HF, class Ready = NoWait, bool OFFLOAD = false, bool SC 
 LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float (&root)[13], float (&q)[T::L], float (&qd)[T::L],
                             const float (&tau)[T::L], float base_mass, float mu,
                             float (&Frep)[T::NREP][3], float (&Fbase)[3], Ready torques_ready = Ready(),
-                            const float4 (*bt)[LG_BT_QUADS][LG_BLOCK] = nullptr, float4 (*fkout)[4][LG_BLOCK] = nullptr,
+                            const float4 (*bt)[BtQuads<HF>::N][LG_BLOCK] = nullptr, float4 (*fkout)[4][LG_BLOCK] = nullptr,
                             volatile int *fk_ready = nullptr, int substep_no = 0, SelfLds<T> *sc = nullptr, bool last = true,
                             bool sc_on_helpers = false /* the three helper waves run self_detect (four-wave kernels) */) {
     constexpr int K = T::K, L = T::L, NPT = T::NPT;
@@ -757,7 +842,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
     const V3 w0 = v3(root[10], root[11], root[12]), v0 = v3(root[7], root[8], root[9]);
     V3 db[L], ax[L];
     S6 C[L];
-    AI I0[L], I0b;
+    typename RigidOf<HF>::type I0[L], I0b;     // plane builds: compact across the passes, expanded where a pass starts from them
     S6 p0[L], p0b;
     Contact cb, cl[NPT];
     HfFetch fb, fl[NPT];               // ground samples of all collision points: fetched here, evaluated after the loop
@@ -864,6 +949,8 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
         for (int j = 0; j < L; j++) bt_load(bt[j], threadIdx.x % LG_BLOCK, I0[j], p0[j]);
     }
     bool any_self = false;                                 // wave-uniform
+    const int ln_sc = threadIdx.x % LG_BLOCK;              // the lane's column of the self-collision records
+    unsigned self_hits = 0;                                // plane builds: this lane's self-collision records (self_mask); both stay false / 0 until the final pass
     bool sc_missed = false;                                // the self-collision hand-over poll ran out (sticky device status)
     LG_PROF(PF_TORQUE);
     // ---- articulated-body passes with the contact impedances folded in
@@ -893,12 +980,15 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
                 for (int m = 0; m < K; m++) self_detect<T>(A, tab - lane_k * Tab<T>::STRIDE, ln, m, *sc);
                 __builtin_amdgcn_wave_barrier();
             }
-            any_self = self_apply<T>(ln, db, I0, p0, *sc);
+            if constexpr (HF) any_self = self_apply<T>(ln, db, I0, p0, *sc);
+            else any_self = self_mask<T>(ln, *sc, self_hits);
         }
 #pragma unroll
         for (int j = L - 1; j >= 0; j--) {
             const float *tj = tab + j * LG_JS;
-            AI IA = I0[j]; S6 pA = p0[j];
+            AI IA; S6 pA = p0[j];
+            ri_expand(IA, I0[j]);
+            if (SC && !HF && any_self) self_fold<T>(j, self_hits, ln_sc, db, IA, pA, *sc);     // (final pass only) I0, then self terms, then ground contacts
 #pragma unroll
             for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) { LG_PROF_COUNT(0, cl[i].on); contact_assemble<HF>(cl[i], P, kn, IA, pA); }
             if (j < L - 1) { ai_add(IA, Ia); pA = pA + pa; }
@@ -948,7 +1038,8 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
             }
         }
         group_sum<K>(Ia, pa);                     // (limb0+limb1)+(limb2+limb3) on every lane of the env
-        AI IAb = I0b; S6 pAb = p0b;
+        AI IAb; S6 pAb = p0b;
+        ri_expand(IAb, I0b);
         ai_add(IAb, Ia); pAb = pAb + pa;
         float rhs[6] = {-pAb.w.x, -pAb.w.y, -pAb.w.z, -pAb.v.x, -pAb.v.y, -pAb.v.z}, a0[6];
         bool ok = solve6(IAb, rhs, a0);
@@ -1466,7 +1557,7 @@ LG_DEV void curriculum_apply(const KArgs &A, int t, int nt, int64_t step, float 
 // of every lane (state resident in their registers for the whole step) and compute each sub-step's torques while wave 0
 // does the torque-independent kinematics half.  Hand-over through LDS (lds_x -> lds_tau), two barriers per sub-step.
 // Post-physics, every variant: the helper waves join the height sampling / height observations (HeightCrew), 4 x the lanes.
-template <bool OFF, int L = 3> struct StepSharedT {              // LDS hand-over between the rigid-body wave and the helpers
+template <bool OFF, int L = 3, bool HF = false> struct StepSharedT {              // LDS hand-over between the rigid-body wave and the helpers
     float pose[LG_BLOCK][5];                                     // x, y, z, q.z, q.w of the lane's env after the last sub-step
     float hsum[LG_STEP_WAVES][LG_BLOCK];                         // partial sums of (root z - height) per wave
     float root_z[LG_BLOCK];                                      // root z after the reset decision (observation input, Q7)
@@ -1474,7 +1565,7 @@ template <bool OFF, int L = 3> struct StepSharedT {              // LDS hand-ove
     float r_t[LG_NUM_REWARD_TERMS][LG_BLOCK];                    // this step's scaled reward terms, for the episode-sum bookkeeping
     // body-terms offload (quadruped kernels, 4 waves): sub-step inputs of the lane and the helpers' (I0, p0) per joint
     float4 fk[OFF ? L : 1][4][LG_BLOCK];                         // per joint: world rotation (9), angular (3) and origin (3) velocity of the body
-    float4 bt[OFF ? L : 1][LG_BT_QUADS][LG_BLOCK];
+    float4 bt[OFF ? L : 1][BtQuads<HF>::N][LG_BLOCK];
     int    fk_ready;                                             // = sub-step number once the rigid-body wave has published fk[] (polled by the helpers)
 };
 
@@ -1528,7 +1619,7 @@ template <class T, bool NET, bool HF, int NW, bool SC = false> struct HelperWave
     static constexpr bool OFF = NW >= 2;                         // the helpers also compute (I0, p0) of the limb bodies each sub-step:
                                                                  // wave w takes bodies w-1, w-1 + (NW-1), ...
     static LG_DEV void run(const KArgs &A, int wave, int lane, int e, int k, int d0, bool live, int64_t step, const float *tab,
-                           float2 (*lds_x)[LG_BLOCK], float (*lds_tau)[LG_BLOCK], StepSharedT<OFF, T::L> &sh, SelfLds<T> *sc = nullptr,
+                           float2 (*lds_x)[LG_BLOCK], float (*lds_tau)[LG_BLOCK], StepSharedT<OFF, T::L, HF> &sh, SelfLds<T> *sc = nullptr,
                            const float *lds_tab = nullptr, ResetRand<T> *reset_rand = nullptr, int *s_last = nullptr, float4 (*hnoise)[LG_BLOCK] = nullptr,
                            int sub0 = 0 /* sub-steps before this policy step in the launch (rollout kernel) */, float *roll_accum = nullptr /* rollout kernel: this step's episode accumulators */,
                            bool tick_step = false /* curriculum_tick_step(A, step), decided by the caller (no 64-bit modulo in the rollout kernel's loop) */) {
@@ -1576,7 +1667,7 @@ template <class T, bool NET, bool HF, int NW, bool SC = false> struct HelperWave
                         float Il[6];
 #pragma unroll
                         for (int i = 0; i < 6; i++) Il[i] = tb[J_INERTIA + i];
-                        AI I0; S6 p0;
+                        typename RigidOf<HF>::type I0; S6 p0;
                         body_terms(v3(P.gravity[0], P.gravity[1], P.gravity[2]), tb[J_MASS], v3(tb[J_COM], tb[J_COM + 1], tb[J_COM + 2]), Il, R,
                                    v3(f2.y, f2.z, f2.w), v3(f3.x, f3.y, f3.z), I0, p0);
                         bt_store(sh.bt[b], lane, I0, p0);
@@ -1706,7 +1797,7 @@ __global__ void __launch_bounds__(NW * LG_BLOCK) k_step(const KArgs A_launch) {
     __shared__ float2 lds_x[NET ? L : 1][LG_BLOCK];             // actuator inputs (pos_err, vel) of the sub-step, [joint][lane]
     __shared__ float lds_tau[NET ? L : 1][LG_BLOCK];            // actuator torques of the sub-step
     constexpr bool OFF = NW >= 2;
-    __shared__ StepSharedT<OFF, L> sh;
+    __shared__ StepSharedT<OFF, L, HF> sh;
     __shared__ SelfStore<SC, T> sc_store;
     __shared__ ResetRand<T> reset_rand;                         // NW > 1: the step's state-independent uniforms for every lane, drawn by the helper waves
     __shared__ float4 hnoise[NW > 1 ? HeightCrew<T, NW>::NCH : 1][LG_BLOCK];     // ... and this wave's height-noise blocks
