@@ -818,7 +818,7 @@ LG_DEV void self_fold(int j, unsigned mask, int ln, const V3 (&db)[T::L], AI &IA
 struct NoWait { LG_DEV void operator()() const {} };
 // OFFLOAD: the limb bodies' (I0, p0) are computed by the helper waves meanwhile and read from `bt` after `torques_ready`.
 // SC: self-collision (needs `sc`); `last`: the exported net contact forces (Frep / Fbase after this call) include the
-// self-collision forces -- the policy step's last sub-step, or the sub-step entry point.
+// self-collision forces -- the policy step's last sub-step, or the sub-step entry point called with write_contacts.
 // LAST_LEAN: the last articulated-body pass skips what only a next pass would read -- the friction corrector of
 // contact_evaluate and the speed-limit detection.
 template <class T, bool HF, class Ready = NoWait, bool OFFLOAD = false, bool SC = false, bool LAST_LEAN = false, bool ROLL = false>
@@ -2446,8 +2446,11 @@ __global__ void __launch_bounds__(LG_BLOCK) k_physics(const KArgs A, const float
         const float *c0 = B.contact_forces + (size_t)e * (1 + K * NREP) * 3;
         Fbase[0] = c0[0]; Fbase[1] = c0[1]; Fbase[2] = c0[2];
     }
-    write_contacts = 1;           // the net contact forces also seed the next sub-step's friction estimate
-    physics_substep<T, HF, NoWait, false, SC>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, NoWait(), nullptr, nullptr, nullptr, 0, sc_store.get(), true);
+    // write_contacts: the exported forces include the self-collision forces (as the CPU twin's entry point does), as after a policy step's last
+    // sub-step; the net GROUND contact forces are written either way, they seed the next sub-step's friction estimate
+    const bool with_self = write_contacts != 0;
+    write_contacts = 1;
+    physics_substep<T, HF, NoWait, false, SC>(A, tab, k, root, q, qd, tau, base_mass, mu, Frep, Fbase, NoWait(), nullptr, nullptr, nullptr, 0, sc_store.get(), with_self);
     if (!live) return;
 #pragma unroll
     for (int j = 0; j < L; j++) { B.dof_state[2 * (d0 + j)] = q[j]; B.dof_state[2 * (d0 + j) + 1] = qd[j]; }

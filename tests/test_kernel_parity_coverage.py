@@ -27,10 +27,13 @@ A, C = "AnymalTraits", "CassieTraits"
 PARITY, FULL, SELF = "tests/test_gpu_parity.py", "tests/test_gpu_full_size.py", "tests/test_gpu_self_collision.py"
 ROLL, VARIANTS = "tests/test_gpu_rollout_oracle.py", "tests/test_gpu_step_variants.py"
 A1_VARIANTS = f"{VARIANTS}::test_a1_step_variants_against_the_oracle"       # A1 (PD) x plane / height field x SC x NW 4 / 2 / 1
+HF = "tests/test_gpu_hf_contact.py"                                         # designed slopes, risers and map edges, N = 40 (NW = 4)
+HF_STEP, HF_SUBSTEP = f"{HF}::test_step_against_the_oracle", f"{HF}::test_substep_against_the_oracle"
+HF_PHYSICS = [HF_SUBSTEP, f"{HF}::test_kernel_force_direction", f"{HF}::test_rotation_equivalence_on_the_device"]
 
 COVERAGE = {
     # quadruped, PD control (a1)
-    **{k_step(A, 0, hf, 0, nw, sc): [A1_VARIANTS] for hf in (0, 1) for nw in (1, 2, 4) for sc in (0, 1)},
+    **{k_step(A, 0, hf, 0, nw, sc): [A1_VARIANTS] + ([HF_STEP] if hf and nw == 4 else []) for hf in (0, 1) for nw in (1, 2, 4) for sc in (0, 1)},
     # quadruped, actuator net, plane (anymal_c_flat: self-collision on; anymal_b: off)
     k_step(A, 1, 0, 0, 4, 0): [f"{PARITY}::test_full_step_parity"],
     k_step(A, 1, 0, 0, 4, 1): [f"{PARITY}::test_full_step_parity", f"{PARITY}::test_tiny_and_ragged_env_counts",
@@ -38,20 +41,20 @@ COVERAGE = {
     # ... with the actor fused in (lg_step_policy) and T steps per launch (lg_rollout_policy)
     **{k_step(A, 1, 0, 1, 4, sc, roll): [f"{ROLL}::test_rollout_kernel_against_the_oracle_every_step"] for sc in (0, 1) for roll in (0, 1)},
     # quadruped, actuator net, height field (anymal_c_rough)
-    k_step(A, 1, 1, 0, 4, 0): [f"{FULL}::test_config3_anymal_rough_4096_full_terrain", f"{FULL}::test_trimesh_vertical_faces_parity"],
-    k_step(A, 1, 1, 0, 4, 1): [f"{VARIANTS}::test_anymal_rough_heightfield_with_self_collision"],
+    k_step(A, 1, 1, 0, 4, 0): [f"{FULL}::test_config3_anymal_rough_4096_full_terrain", f"{FULL}::test_trimesh_vertical_faces_parity", HF_STEP],
+    k_step(A, 1, 1, 0, 4, 1): [f"{VARIANTS}::test_anymal_rough_heightfield_with_self_collision", HF_STEP],
     # biped (cassie), PD control
     k_step(C, 0, 0, 0, 4, 0): [f"{PARITY}::test_full_step_parity"],
     k_step(C, 0, 0, 0, 2, 0): [f"{PARITY}::test_step_parity_with_fewer_helper_waves"],
     k_step(C, 0, 0, 0, 1, 0): [f"{PARITY}::test_step_parity_with_fewer_helper_waves"],
-    **{k_step(C, 0, 1, 0, nw, 0): [f"{FULL}::test_cassie_heightfield_step_parity"] for nw in (1, 2, 4)},
+    **{k_step(C, 0, 1, 0, nw, 0): [f"{FULL}::test_cassie_heightfield_step_parity"] + ([HF_STEP] if nw == 4 else []) for nw in (1, 2, 4)},
     # one 5 ms rigid-body sub-step (lg_physics_substep)
     k_physics(A, 0, 0): [f"{PARITY}::test_physics_substep_parity"],
     k_physics(A, 0, 1): [f"{PARITY}::test_physics_substep_parity", f"{SELF}::test_substep_parity_with_crossed_legs"],
-    k_physics(A, 1, 0): [f"{FULL}::test_trimesh_vertical_faces_parity"],
-    k_physics(A, 1, 1): [f"{SELF}::test_substep_parity_with_crossed_legs"],
+    k_physics(A, 1, 0): [f"{FULL}::test_trimesh_vertical_faces_parity"] + HF_PHYSICS,
+    k_physics(A, 1, 1): [f"{SELF}::test_substep_parity_with_crossed_legs", HF_SUBSTEP, f"{HF}::test_rotation_equivalence_on_the_device"],
     k_physics(C, 0, 0): [f"{PARITY}::test_physics_substep_parity"],
-    k_physics(C, 1, 0): [f"{PARITY}::test_physics_substep_parity"],
+    k_physics(C, 1, 0): [f"{PARITY}::test_physics_substep_parity", HF_SUBSTEP, f"{HF}::test_rotation_equivalence_on_the_device"],
 }
 
 

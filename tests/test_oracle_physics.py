@@ -506,6 +506,21 @@ def test_trimesh_riser_is_a_vertical_face_and_heightfield_a_ramp(oracle_lib):
     rf = hf[:, :2]                                                                          # ramp: normal (-2, 0, 1) / sqrt(5)
     ratio = np.abs(rf[..., 0]) / np.abs(rf[..., 2])
     assert (rf[..., 2] > 10.0).all() and (ratio > 1.0).all() and (ratio < 3.0).all()
+    # frictionless variant (friction_coeffs = -ground_friction: mu_bar = 0): the force of the single-sphere foot IS f_n n, so its direction
+    # is the ramp normal (-2, 0, 1) / sqrt(5) within the bound of tests/test_hf_cases.test_oracle_force_direction (4 x the oracle's worst
+    # over all designed fields, 4.4e-6 per component), and the ratio is 2 within 3 sqrt(5) times that (d ratio = sqrt(5) (d n_x + 2 d n_z))
+    from tests.hf_cases import DIRECTION_BOUND
+    terr, cfg, robot, p, names, model, w, x_face = _riser_setup("heightfield")
+    o = OracleSim(p, model, robot, w)
+    o.set_terrain(terr.heightsamples, terr.env_origins)
+    riser_state(o, p, robot, 4, x_face)
+    o.buf["friction_coeffs"][:] = -p.ground_friction
+    o.physics_substep(np.zeros((4, 12), np.float32), True)
+    f = o.buf["contact_forces"][:, [bn.index("LF_FOOT"), bn.index("RF_FOOT")], :].astype(np.float64)
+    assert (f[..., 2] > 10.0).all()
+    unit = f / np.linalg.norm(f, axis=-1, keepdims=True)
+    assert np.abs(unit - np.array([-2.0, 0.0, 1.0]) / np.sqrt(5.0)).max() <= DIRECTION_BOUND["smooth"]
+    assert np.abs(np.abs(f[..., 0]) / f[..., 2] - 2.0).max() <= 3.0 * np.sqrt(5.0) * DIRECTION_BOUND["smooth"]
 
 
 def test_foot_overhanging_a_stair_edge_is_carried_by_the_edge(oracle_lib):
