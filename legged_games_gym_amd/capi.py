@@ -5,6 +5,10 @@ This is the "thin C-ABI" of the north star: Python hands raw device pointers
 the role ``gymapi``/``gymtorch`` play in the reference (call sites
 ``legged_gym/envs/base/legged_robot.py:92-96, 111-112, 410-444, 515-529``).
 
+Every entry point of every public header is one row of ``ABI`` (near the end of this file, after the structs it names);
+``bind_header`` / ``bind_all`` attach the prototypes and check the struct sizes, ``_call`` is the one return-code check and
+``_buffers`` the one cast of a name -> address table into a struct.
+
 There is NO CPU fallback: ``load_library()`` raises if the HIP extension has
 not been built (``python -c "import __graft_entry__ as g; g.build()"``).
 """
@@ -236,84 +240,38 @@ def library_path() -> str:
     return os.environ.get("LG_HIP_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _LIB_NAME)
 
 
-def bind_prototypes(lib, prefix: str):
-    """Attach argtypes/restype for every entry point of legged_hip.h."""
-    vp = C.c_void_p
-    sig = {
-        "create": ([C.POINTER(lg_params), C.POINTER(lg_robot_model), _PF, C.c_int, C.POINTER(vp)], C.c_int),
-        "destroy": ([vp], None),
-        "bind": ([vp, C.POINTER(lg_buffers)], C.c_int),
-        "step": ([vp, vp, i64, vp], C.c_int),
-        "reset_idx": ([vp, vp, i32, i64, vp], C.c_int),
-        "actuator_forward": ([vp, vp, vp, vp, vp, vp, i32, vp], C.c_int),
-        "physics_substep": ([vp, vp, i32, vp], C.c_int),
-        "compute_observations_only": ([vp, i64, vp], C.c_int),
-        "set_params": ([vp, C.POINTER(lg_params)], C.c_int),
-        "set_obs_buffer": ([vp, vp], C.c_int),
-        "last_error": ([], C.c_char_p),
-        "abi_version": ([], C.c_int),
-        "sizeof": ([C.c_int], C.c_int),
-    }
-    if prefix == "lg_":      # the fused actor is a product-only entry point (the oracle side of it is torch fp32)
-        lib.lg_policy_create.argtypes = [C.POINTER(i32), C.POINTER(_PF), C.POINTER(_PF), _PF, C.c_int, C.POINTER(vp)]
-        lib.lg_policy_create.restype = C.c_int
-        lib.lg_policy_destroy.argtypes, lib.lg_policy_destroy.restype = [vp], None
-        lib.lg_policy_act.argtypes = [vp, vp, vp, vp, i32, u64, i64, vp, i32, vp]
-        lib.lg_policy_act.restype = C.c_int
-        lib.lg_policy_load_device.argtypes = [vp, vp, vp, vp, vp]
-        lib.lg_policy_load_device.restype = C.c_int
-        lib.lg_step_policy.argtypes = [vp, vp, vp, vp, vp, u64, i32, i64, vp]
-        lib.lg_step_policy.restype = C.c_int
-        lib.lg_rollout_policy.argtypes = [vp, vp, C.POINTER(lg_rollout_buffers), u64, i32, i64, vp]
-        lib.lg_rollout_policy.restype = C.c_int
-        lib.lg_gae_returns.argtypes = [vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, i32, vp]
-        lib.lg_gae_returns.restype = C.c_int
-        lib.lg_ppo_loss.argtypes = [vp] * 11 + [C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp, i32, i32, vp]
-        lib.lg_ppo_loss.restype = C.c_int
-        lib.lg_mlp_forward.argtypes = [C.POINTER(lg_mlp_net), i32, vp, i32, vp]
-        lib.lg_mlp_forward.restype = C.c_int
-        lib.lg_mlp_workspace_bytes.argtypes = [C.POINTER(lg_mlp_net), i32]
-        lib.lg_mlp_workspace_bytes.restype = C.c_size_t
-        lib.lg_mlp_backward.argtypes = [C.POINTER(lg_mlp_net), i32, vp, i32, vp, C.c_size_t, vp]
-        lib.lg_mlp_backward.restype = C.c_int
-        lib.lg_mlp_wide_workspace_bytes.argtypes = [C.POINTER(lg_mlp_net), i32, i32]
-        lib.lg_mlp_wide_workspace_bytes.restype = C.c_size_t
-        lib.lg_mlp_wide_set_precision.argtypes, lib.lg_mlp_wide_set_precision.restype = [C.c_int], C.c_int
-        lib.lg_mlp_wide_forward.argtypes = [C.POINTER(lg_mlp_net), i32, vp, i32, vp, C.c_size_t, vp]
-        lib.lg_mlp_wide_forward.restype = C.c_int
-        lib.lg_mlp_wide_backward.argtypes = [C.POINTER(lg_mlp_net), i32, vp, i32, vp, C.c_size_t, vp]
-        lib.lg_mlp_wide_backward.restype = C.c_int
-        lib.lg_ppo_minibatch.argtypes = [C.POINTER(lg_mlp_net), vp, i32, C.POINTER(lg_ppo_batch), vp, C.c_size_t, vp]
-        lib.lg_ppo_minibatch.restype = C.c_int
-        lib.lg_adam_step.argtypes = [C.POINTER(lg_adam_tensor), i32, vp, C.c_float, C.c_float, C.c_float, C.c_float, vp, C.c_float, vp, vp]
-        lib.lg_adam_step.restype = C.c_int
-        lib.lg_rollout_finish.argtypes, lib.lg_rollout_finish.restype = [C.POINTER(lg_rollout_post), vp], C.c_int
-        lib.lg_rollout_record.argtypes = [C.POINTER(lg_rollout_step), vp]
-        lib.lg_rollout_record.restype = C.c_int
-        lib.lg_mlp_trace.argtypes, lib.lg_mlp_trace.restype = [vp], None
-        lib.lg_set_deferred_extras.argtypes, lib.lg_set_deferred_extras.restype = [vp, i32], C.c_int
-        lib.lg_extras_flush.argtypes, lib.lg_extras_flush.restype = [vp, i64, vp], C.c_int
-        lib.lg_resample_reset_commands.argtypes, lib.lg_resample_reset_commands.restype = [vp, i64, vp], C.c_int
-        lib.lg_device_status.argtypes, lib.lg_device_status.restype = [vp, i32], C.c_int
-        lib.lg_clear_device_status.argtypes, lib.lg_clear_device_status.restype = [vp], C.c_int
-        lib.lg_debug_handover.argtypes, lib.lg_debug_handover.restype = [vp, i32, i32], C.c_int
-    for name, (args, res) in sig.items():
-        fn = getattr(lib, prefix + name)
-        fn.argtypes, fn.restype = args, res
-    sizeof = getattr(lib, prefix + "sizeof")
-    structs = (lg_params, lg_robot_model, lg_buffers, lg_point) + ((lg_mlp_net, lg_adam_tensor, lg_rollout_step, lg_ppo_batch) if prefix == "lg_" else ())
-    for which, st in enumerate(structs):
-        if sizeof(which) != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {sizeof(which)} vs ctypes {C.sizeof(st)}")
-    return lib
+def load_library():
+    """Load the HIP extension or fail loudly -- never a CPU substitute."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    path = library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _lib = bind_all(C.CDLL(path))
+    if _lib.lg_abi_version() != LG_ABI_VERSION:
+        raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
+    return _lib
 
 
-EXPORTED_SYMBOLS = ["lg_create", "lg_destroy", "lg_bind", "lg_step", "lg_reset_idx", "lg_actuator_forward",
-                    "lg_physics_substep", "lg_compute_observations_only", "lg_set_params", "lg_last_error",
-                    "lg_abi_version", "lg_sizeof", "lg_set_obs_buffer", "lg_policy_create", "lg_policy_destroy", "lg_policy_act",
-                    "lg_step_policy", "lg_gae_returns", "lg_ppo_loss", "lg_policy_load_device", "lg_mlp_forward",
-                    "lg_mlp_workspace_bytes", "lg_mlp_backward", "lg_mlp_wide_workspace_bytes", "lg_mlp_wide_forward", "lg_mlp_wide_backward", "lg_mlp_wide_set_precision", "lg_adam_step", "lg_rollout_record", "lg_mlp_trace", "lg_ppo_minibatch", "lg_set_deferred_extras", "lg_extras_flush",
-                    "lg_device_status", "lg_clear_device_status", "lg_debug_handover", "lg_rollout_policy", "lg_rollout_finish", "lg_resample_reset_commands"]
+def _call(name, *args, ok=(0,)):
+    """Call entry point ``name`` of the library; its return code if that is in ``ok``, otherwise a RuntimeError with ``lg_last_error``."""
+    lib = load_library()
+    rc = getattr(lib, name)(*args)
+    if rc not in ok:
+        raise RuntimeError(f"{name} failed ({rc}): {lib.lg_last_error().decode()}")
+    return rc
+
+
+def _buffers(struct_type, pointers: Dict[str, int], fields=None):
+    """``struct_type`` with its pointer ``fields`` (default: every field) cast from a name -> address table; missing names stay null."""
+    b = struct_type()
+    for name, ctype in struct_type._fields_:
+        if fields is None or name in fields:
+            setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), ctype))
+    return b
 
 
 # ----------------------------------------------------------------------------- game layer (include/legged_game.h)
@@ -343,37 +301,15 @@ class lg_game_buffers(C.Structure):
 
 
 GAME_BUFFER_FIELDS = [name for name, _ in lg_game_buffers._fields_]
-GAME_SYMBOLS = ["lg_game_pre", "lg_game_post", "lg_game_act", "lg_game_sizeof"]
-
-
-def bind_game_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_game.h and check the struct layouts."""
-    vp = C.c_void_p
-    lib.lg_game_pre.argtypes, lib.lg_game_pre.restype = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), vp], C.c_int
-    lib.lg_game_post.argtypes, lib.lg_game_post.restype = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), i64, vp], C.c_int
-    lib.lg_game_act.argtypes = [vp, vp, C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), vp, vp, vp, vp, u64, i64, vp, i32, vp, vp, vp, vp, vp]
-    lib.lg_game_act.restype = C.c_int
-    lib.lg_game_sizeof.argtypes, lib.lg_game_sizeof.restype = [C.c_int], C.c_int
-    for which, st in enumerate((lg_game_params, lg_game_buffers)):
-        if lib.lg_game_sizeof(which) != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {lib.lg_game_sizeof(which)} vs ctypes {C.sizeof(st)}")
-    return lib
 
 
 def game_buffers(pointers: Dict[str, int]) -> lg_game_buffers:
     """``lg_game_buffers`` from a name -> device address table (missing names stay null)."""
-    b = lg_game_buffers()
-    types = dict(lg_game_buffers._fields_)
-    for name in GAME_BUFFER_FIELDS:
-        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
-    return b
+    return _buffers(lg_game_buffers, pointers)
 
 
 def game_pre(params: lg_game_params, buffers: lg_game_buffers, stream: int = 0):
-    lib = load_library()
-    rc = lib.lg_game_pre(C.byref(params), C.byref(buffers), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_game_pre failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_game_pre", C.byref(params), C.byref(buffers), stream)
 
 
 def game_act(hl_policy, ll_policy, params: lg_game_params, buffers: lg_game_buffers, hl_obs: int, ll_obs: int, ll_actions: int, mean: int, seed: int,
@@ -381,19 +317,13 @@ def game_act(hl_policy, ll_policy, params: lg_game_params, buffers: lg_game_buff
              log_prob: Optional[int] = None, obs_copy: Optional[int] = None, stream: int = 0) -> int:
     """``lg_game_act``: both actors of a high-level step and the command clip in one launch.  Returns 0, or -4 when the actor pair /
     wide precision has no shared kernel (the caller then issues ``lg_policy_act`` x 2 + ``lg_game_pre``); raises on any other error."""
-    lib = load_library()
-    rc = lib.lg_game_act(hl_policy, ll_policy, C.byref(params), C.byref(buffers), hl_obs, ll_obs, ll_actions, mean, int(seed), int(step), step_counter,
-                         int(bool(deterministic)), sample, sigma, log_prob, obs_copy, stream)
-    if rc not in (0, -4):
-        raise RuntimeError(f"lg_game_act failed ({rc}): {lib.lg_last_error().decode()}")
-    return rc
+    return _call("lg_game_act", hl_policy, ll_policy, C.byref(params), C.byref(buffers), hl_obs, ll_obs, ll_actions, mean, int(seed), int(step), step_counter,
+                 int(bool(deterministic)), sample, sigma, log_prob, obs_copy, stream, ok=(0, -4))
 
 
 def game_post(params: lg_game_params, buffers: lg_game_buffers, common_step_counter: int, stream: int = 0):
-    lib = load_library()
-    rc = lib.lg_game_post(C.byref(params), C.byref(buffers), int(common_step_counter), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_game_post failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_game_post", C.byref(params), C.byref(buffers), int(common_step_counter), stream)
+
 
 # ----------------------------------------------------------------------------- decentralised game (include/legged_dec_game.h)
 LG_DEC_NUM_OBS_PREY, LG_DEC_NUM_OBS_PRED, LG_DEC_NUM_ACTIONS_PREY, LG_DEC_NUM_ACTIONS_PRED, LG_DEC_NUM_SUMS = 16, 3, 4, 2, 3
@@ -424,7 +354,6 @@ class lg_dec_game_buffers(C.Structure):
 
 
 DEC_GAME_BUFFER_FIELDS = [name for name, _ in lg_dec_game_buffers._fields_]
-DEC_GAME_SYMBOLS = ["lg_dec_game_pre", "lg_dec_game_post", "lg_dec_game_act", "lg_dec_game_sizeof"]
 
 
 class lg_dec_act_outputs(C.Structure):
@@ -432,35 +361,13 @@ class lg_dec_act_outputs(C.Structure):
     _fields_ = [("sample", C.c_void_p), ("sigma", C.c_void_p), ("log_prob", C.c_void_p), ("obs_copy", C.c_void_p)]
 
 
-def bind_dec_game_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_dec_game.h and check the struct layouts."""
-    vp = C.c_void_p
-    lib.lg_dec_game_pre.argtypes, lib.lg_dec_game_pre.restype = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), vp], C.c_int
-    lib.lg_dec_game_post.argtypes, lib.lg_dec_game_post.restype = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), i64, vp], C.c_int
-    lib.lg_dec_game_act.argtypes = [vp, vp, vp, C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), vp, vp, vp, vp, vp, vp, u64, u64, i64, vp, i32, i32,
-                                    C.POINTER(lg_dec_act_outputs), C.POINTER(lg_dec_act_outputs), vp]
-    lib.lg_dec_game_act.restype = C.c_int
-    lib.lg_dec_game_sizeof.argtypes, lib.lg_dec_game_sizeof.restype = [C.c_int], C.c_int
-    for which, st in enumerate((lg_dec_game_params, lg_dec_game_buffers, lg_dec_act_outputs)):
-        if lib.lg_dec_game_sizeof(which) != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {lib.lg_dec_game_sizeof(which)} vs ctypes {C.sizeof(st)}")
-    return lib
-
-
 def dec_game_buffers(pointers: Dict[str, int]) -> lg_dec_game_buffers:
     """``lg_dec_game_buffers`` from a name -> device address table (missing names stay null)."""
-    b = lg_dec_game_buffers()
-    types = dict(lg_dec_game_buffers._fields_)
-    for name in DEC_GAME_BUFFER_FIELDS:
-        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
-    return b
+    return _buffers(lg_dec_game_buffers, pointers)
 
 
 def dec_game_pre(params: lg_dec_game_params, buffers: lg_dec_game_buffers, stream: int = 0):
-    lib = load_library()
-    rc = lib.lg_dec_game_pre(C.byref(params), C.byref(buffers), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_dec_game_pre failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_dec_game_pre", C.byref(params), C.byref(buffers), stream)
 
 
 def dec_game_act(pred_policy, prey_policy, ll_policy, params: lg_dec_game_params, buffers: lg_dec_game_buffers, pred_obs: int, prey_obs: int, ll_obs: int,
@@ -469,20 +376,13 @@ def dec_game_act(pred_policy, prey_policy, ll_policy, params: lg_dec_game_params
                  out_prey: Optional[lg_dec_act_outputs] = None, stream: int = 0) -> int:
     """``lg_dec_game_act``: the three actors of a step and the command clips in one launch.  Returns 0, or -4 when the actor triple / wide
     precision has no shared kernel (the caller then issues ``lg_policy_act`` x 3 + ``lg_dec_game_pre``); raises on any other error."""
-    lib = load_library()
-    rc = lib.lg_dec_game_act(pred_policy, prey_policy, ll_policy, C.byref(params), C.byref(buffers), pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey,
-                             int(seed_pred), int(seed_prey), int(step), step_counter, int(bool(deterministic_pred)), int(bool(deterministic_prey)),
-                             C.byref(out_pred) if out_pred is not None else None, C.byref(out_prey) if out_prey is not None else None, stream)
-    if rc not in (0, -4):
-        raise RuntimeError(f"lg_dec_game_act failed ({rc}): {lib.lg_last_error().decode()}")
-    return rc
+    return _call("lg_dec_game_act", pred_policy, prey_policy, ll_policy, C.byref(params), C.byref(buffers), pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey,
+                 int(seed_pred), int(seed_prey), int(step), step_counter, int(bool(deterministic_pred)), int(bool(deterministic_prey)),
+                 C.byref(out_pred) if out_pred is not None else None, C.byref(out_prey) if out_prey is not None else None, stream, ok=(0, -4))
 
 
 def dec_game_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, common_step_counter: int, stream: int = 0):
-    lib = load_library()
-    rc = lib.lg_dec_game_post(C.byref(params), C.byref(buffers), int(common_step_counter), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_dec_game_post failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_dec_game_post", C.byref(params), C.byref(buffers), int(common_step_counter), stream)
 
 
 # ----------------------------------------------------------------------------- scripted pursuer (include/legged_pursuer_game.h)
@@ -491,27 +391,10 @@ class lg_pursuer_params(C.Structure):
     _fields_ = [("max_lin_vel", f32), ("min_lin_vel", f32), ("gain", f32), ("max_episode_length", i32)]
 
 
-PURSUER_SYMBOLS = ["lg_pursuer_post", "lg_pursuer_sizeof"]
-
-
-def bind_pursuer_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_pursuer_game.h and check the struct layout."""
-    vp = C.c_void_p
-    lib.lg_pursuer_post.argtypes = [C.POINTER(lg_game_params), C.POINTER(lg_pursuer_params), C.POINTER(lg_game_buffers), vp, i64, vp]
-    lib.lg_pursuer_post.restype = C.c_int
-    lib.lg_pursuer_sizeof.argtypes, lib.lg_pursuer_sizeof.restype = [C.c_int], C.c_int
-    if lib.lg_pursuer_sizeof(0) != C.sizeof(lg_pursuer_params):
-        raise RuntimeError(f"struct layout mismatch for lg_pursuer_params: C {lib.lg_pursuer_sizeof(0)} vs ctypes {C.sizeof(lg_pursuer_params)}")
-    return lib
-
-
 def pursuer_post(params: lg_game_params, pursuer: lg_pursuer_params, buffers: lg_game_buffers, predator_command: Optional[int],
                  common_step_counter: int, stream: int = 0):
     """``lg_pursuer_post``: ``lg_game_post`` with the scripted pursuer's velocity, which it writes to ``predator_command`` [N,2] (or None)."""
-    lib = load_library()
-    rc = lib.lg_pursuer_post(C.byref(params), C.byref(pursuer), C.byref(buffers), predator_command, int(common_step_counter), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_pursuer_post failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_pursuer_post", C.byref(params), C.byref(pursuer), C.byref(buffers), predator_command, int(common_step_counter), stream)
 
 
 # ----------------------------------------------------------------------------- game outcome statistics (include/legged_game_outcome.h)
@@ -526,48 +409,23 @@ class lg_outcome_buffers(C.Structure):
 
 
 OUTCOME_BUFFER_FIELDS = [name for name, _ in lg_outcome_buffers._fields_]
-OUTCOME_SYMBOLS = ["lg_outcome_post", "lg_outcome_pursuer_post", "lg_outcome_sizeof"]
-
-
-def bind_outcome_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_game_outcome.h and check the struct layout."""
-    vp = C.c_void_p
-    lib.lg_outcome_post.argtypes = [C.POINTER(lg_game_params), C.POINTER(lg_game_buffers), C.POINTER(lg_outcome_buffers), i64, vp]
-    lib.lg_outcome_post.restype = C.c_int
-    lib.lg_outcome_pursuer_post.argtypes = [C.POINTER(lg_game_params), C.POINTER(lg_pursuer_params), C.POINTER(lg_game_buffers),
-                                            C.POINTER(lg_outcome_buffers), vp, i64, vp]
-    lib.lg_outcome_pursuer_post.restype = C.c_int
-    lib.lg_outcome_sizeof.argtypes, lib.lg_outcome_sizeof.restype = [C.c_int], C.c_int
-    if lib.lg_outcome_sizeof(0) != C.sizeof(lg_outcome_buffers):
-        raise RuntimeError(f"struct layout mismatch for lg_outcome_buffers: C {lib.lg_outcome_sizeof(0)} vs ctypes {C.sizeof(lg_outcome_buffers)}")
-    return lib
 
 
 def outcome_buffers(pointers: Dict[str, int]) -> lg_outcome_buffers:
     """``lg_outcome_buffers`` from a name -> device address table (missing names stay null)."""
-    b = lg_outcome_buffers()
-    types = dict(lg_outcome_buffers._fields_)
-    for name in OUTCOME_BUFFER_FIELDS:
-        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
-    return b
+    return _buffers(lg_outcome_buffers, pointers)
 
 
 def outcome_post(params: lg_game_params, buffers: lg_game_buffers, outcome: lg_outcome_buffers, common_step_counter: int, stream: int = 0):
     """``lg_outcome_post``: ``lg_game_post`` that also counts why the done envs' episodes ended."""
-    lib = load_library()
-    rc = lib.lg_outcome_post(C.byref(params), C.byref(buffers), C.byref(outcome), int(common_step_counter), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_outcome_post failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_outcome_post", C.byref(params), C.byref(buffers), C.byref(outcome), int(common_step_counter), stream)
 
 
 def outcome_pursuer_post(params: lg_game_params, pursuer: lg_pursuer_params, buffers: lg_game_buffers, outcome: lg_outcome_buffers,
                          predator_command: Optional[int], common_step_counter: int, stream: int = 0):
     """``lg_outcome_pursuer_post``: ``lg_pursuer_post`` that also counts why the done envs' episodes ended."""
-    lib = load_library()
-    rc = lib.lg_outcome_pursuer_post(C.byref(params), C.byref(pursuer), C.byref(buffers), C.byref(outcome), predator_command,
-                                     int(common_step_counter), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_outcome_pursuer_post failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_outcome_pursuer_post", C.byref(params), C.byref(pursuer), C.byref(buffers), C.byref(outcome), predator_command,
+          int(common_step_counter), stream)
 
 
 # ----------------------------------------------------------------------------- decentralised game's outcome statistics (include/legged_dec_game_outcome.h)
@@ -582,34 +440,16 @@ class lg_dec_outcome_buffers(C.Structure):
 
 
 DEC_OUTCOME_BUFFER_FIELDS = [name for name, _ in lg_dec_outcome_buffers._fields_]
-DEC_OUTCOME_SYMBOLS = ["lg_dec_outcome_post", "lg_dec_outcome_sizeof"]
-
-
-def bind_dec_outcome_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_dec_game_outcome.h and check the struct layout."""
-    lib.lg_dec_outcome_post.argtypes = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), C.POINTER(lg_dec_outcome_buffers), i64, C.c_void_p]
-    lib.lg_dec_outcome_post.restype = C.c_int
-    lib.lg_dec_outcome_sizeof.argtypes, lib.lg_dec_outcome_sizeof.restype = [C.c_int], C.c_int
-    if lib.lg_dec_outcome_sizeof(0) != C.sizeof(lg_dec_outcome_buffers):
-        raise RuntimeError(f"struct layout mismatch for lg_dec_outcome_buffers: C {lib.lg_dec_outcome_sizeof(0)} vs ctypes {C.sizeof(lg_dec_outcome_buffers)}")
-    return lib
 
 
 def dec_outcome_buffers(pointers: Dict[str, int]) -> lg_dec_outcome_buffers:
     """``lg_dec_outcome_buffers`` from a name -> device address table (missing names stay null)."""
-    b = lg_dec_outcome_buffers()
-    types = dict(lg_dec_outcome_buffers._fields_)
-    for name in DEC_OUTCOME_BUFFER_FIELDS:
-        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
-    return b
+    return _buffers(lg_dec_outcome_buffers, pointers)
 
 
 def dec_outcome_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, outcome: lg_dec_outcome_buffers, common_step_counter: int, stream: int = 0):
     """``lg_dec_outcome_post``: ``lg_dec_game_post`` that also counts why the done envs' episodes ended."""
-    lib = load_library()
-    rc = lib.lg_dec_outcome_post(C.byref(params), C.byref(buffers), C.byref(outcome), int(common_step_counter), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_dec_outcome_post failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_dec_outcome_post", C.byref(params), C.byref(buffers), C.byref(outcome), int(common_step_counter), stream)
 
 
 # ----------------------------------------------------------------------------- decentralised game's opponent pool (include/legged_dec_game_pool.h)
@@ -622,33 +462,12 @@ class lg_dec_pool_info(C.Structure):
     _fields_ = [("count", i32), ("role", i32), ("device", i32), ("_pad", i32), ("table", C.c_void_p)]
 
 
-DEC_POOL_SYMBOLS = ["lg_dec_pool_create", "lg_dec_pool_destroy", "lg_dec_pool_query", "lg_dec_pool_act", "lg_dec_pool_sizeof"]
-
-
-def bind_dec_pool_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_dec_game_pool.h and check the struct layout."""
-    vp = C.c_void_p
-    lib.lg_dec_pool_create.argtypes, lib.lg_dec_pool_create.restype = [C.POINTER(vp), i32, i32, i32, C.POINTER(vp)], C.c_int
-    lib.lg_dec_pool_destroy.argtypes, lib.lg_dec_pool_destroy.restype = [vp], C.c_int
-    lib.lg_dec_pool_query.argtypes, lib.lg_dec_pool_query.restype = [vp, C.POINTER(lg_dec_pool_info)], C.c_int
-    lib.lg_dec_pool_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), vp, vp, vp, vp, vp, vp, u64, u64, i64, vp,
-                                    i32, i32, C.POINTER(lg_dec_act_outputs), C.POINTER(lg_dec_act_outputs), vp]
-    lib.lg_dec_pool_act.restype = C.c_int
-    lib.lg_dec_pool_sizeof.argtypes, lib.lg_dec_pool_sizeof.restype = [C.c_int], C.c_int
-    if lib.lg_dec_pool_sizeof(0) != C.sizeof(lg_dec_pool_info):
-        raise RuntimeError(f"struct layout mismatch for lg_dec_pool_info: C {lib.lg_dec_pool_sizeof(0)} vs ctypes {C.sizeof(lg_dec_pool_info)}")
-    return lib
-
-
 def dec_pool_create(member_handles, role: str, device: int = 0) -> C.c_void_p:
     """``lg_dec_pool_create`` over ``lg_policy`` handles (``FusedActor.handle``); ``role`` is "prey" or "pred".  The handles must outlive the
     pool and must not be re-created (``FusedActor.sync`` does; ``sync_device`` repacks in place, which the pool follows)."""
-    lib = load_library()
     handles = (C.c_void_p * len(member_handles))(*[h.value if isinstance(h, C.c_void_p) else h for h in member_handles])
     out = C.c_void_p()
-    rc = lib.lg_dec_pool_create(handles, len(member_handles), DEC_POOL_ROLES[role], int(device), C.byref(out))
-    if rc != 0:
-        raise RuntimeError(f"lg_dec_pool_create failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_dec_pool_create", handles, len(member_handles), DEC_POOL_ROLES[role], int(device), C.byref(out))
     return out
 
 
@@ -658,10 +477,8 @@ def dec_pool_destroy(pool):
 
 
 def dec_pool_query(pool) -> lg_dec_pool_info:
-    lib, info = load_library(), lg_dec_pool_info()
-    rc = lib.lg_dec_pool_query(pool, C.byref(info))
-    if rc != 0:
-        raise RuntimeError(f"lg_dec_pool_query failed ({rc}): {lib.lg_last_error().decode()}")
+    info = lg_dec_pool_info()
+    _call("lg_dec_pool_query", pool, C.byref(info))
     return info
 
 
@@ -672,14 +489,10 @@ def dec_pool_act(pred_policy, prey_policy, ll_policy, pool_pred, block_slot_pred
     """``lg_dec_pool_act``: ``lg_dec_game_act`` with the weights of a pooled role chosen per 32-env block.  ``pool_*``: a pool handle or None,
     ``block_slot_*``: the device address of its int32 slot table.  Returns 0, or -4 when there is no shared kernel for the wide precision /
     the shapes (the caller then issues ``lg_policy_act`` per member + ``lg_dec_game_pre``); raises on any other error."""
-    lib = load_library()
-    rc = lib.lg_dec_pool_act(pred_policy, prey_policy, ll_policy, pool_pred, block_slot_pred, pool_prey, block_slot_prey, C.byref(params), C.byref(buffers),
-                             pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey, int(seed_pred), int(seed_prey), int(step), step_counter,
-                             int(bool(deterministic_pred)), int(bool(deterministic_prey)), C.byref(out_pred) if out_pred is not None else None,
-                             C.byref(out_prey) if out_prey is not None else None, stream)
-    if rc not in (0, -4):
-        raise RuntimeError(f"lg_dec_pool_act failed ({rc}): {lib.lg_last_error().decode()}")
-    return rc
+    return _call("lg_dec_pool_act", pred_policy, prey_policy, ll_policy, pool_pred, block_slot_pred, pool_prey, block_slot_prey, C.byref(params), C.byref(buffers),
+                 pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey, int(seed_pred), int(seed_prey), int(step), step_counter,
+                 int(bool(deterministic_pred)), int(bool(deterministic_prey)), C.byref(out_pred) if out_pred is not None else None,
+                 C.byref(out_prey) if out_prey is not None else None, stream, ok=(0, -4))
 
 
 # ----------------------------------------------------------------------------- outcome statistics per pool member (include/legged_dec_game_member_outcome.h)
@@ -692,27 +505,11 @@ class lg_dec_member_outcome_buffers(C.Structure):
 
 
 DEC_MEMBER_OUTCOME_BUFFER_FIELDS = ["block_slot", "member_accum", "member_totals"]       # the pointers
-DEC_MEMBER_OUTCOME_SYMBOLS = ["lg_dec_member_outcome_post", "lg_dec_member_outcome_sizeof"]
-
-
-def bind_dec_member_outcome_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_dec_game_member_outcome.h and check the struct layout."""
-    lib.lg_dec_member_outcome_post.argtypes = [C.POINTER(lg_dec_game_params), C.POINTER(lg_dec_game_buffers), C.POINTER(lg_dec_outcome_buffers),
-                                               C.POINTER(lg_dec_member_outcome_buffers), i64, C.c_void_p]
-    lib.lg_dec_member_outcome_post.restype = C.c_int
-    lib.lg_dec_member_outcome_sizeof.argtypes, lib.lg_dec_member_outcome_sizeof.restype = [C.c_int], C.c_int
-    if lib.lg_dec_member_outcome_sizeof(0) != C.sizeof(lg_dec_member_outcome_buffers):
-        raise RuntimeError(f"struct layout mismatch for lg_dec_member_outcome_buffers: C {lib.lg_dec_member_outcome_sizeof(0)} vs ctypes "
-                           f"{C.sizeof(lg_dec_member_outcome_buffers)}")
-    return lib
 
 
 def dec_member_outcome_buffers(pointers: Dict[str, int], count: int) -> lg_dec_member_outcome_buffers:
     """``lg_dec_member_outcome_buffers`` from a name -> device address table (missing names stay null) and the pool's member count."""
-    b = lg_dec_member_outcome_buffers()
-    types = dict(lg_dec_member_outcome_buffers._fields_)
-    for name in DEC_MEMBER_OUTCOME_BUFFER_FIELDS:
-        setattr(b, name, C.cast(C.c_void_p(pointers.get(name, 0) or 0), types[name]))
+    b = _buffers(lg_dec_member_outcome_buffers, pointers, DEC_MEMBER_OUTCOME_BUFFER_FIELDS)
     b.count = int(count)
     return b
 
@@ -720,30 +517,11 @@ def dec_member_outcome_buffers(pointers: Dict[str, int], count: int) -> lg_dec_m
 def dec_member_outcome_post(params: lg_dec_game_params, buffers: lg_dec_game_buffers, outcome: lg_dec_outcome_buffers, members: lg_dec_member_outcome_buffers,
                             common_step_counter: int, stream: int = 0):
     """``lg_dec_member_outcome_post``: ``lg_dec_outcome_post`` that also keeps the six counts per opponent-pool member."""
-    lib = load_library()
-    rc = lib.lg_dec_member_outcome_post(C.byref(params), C.byref(buffers), C.byref(outcome), C.byref(members), int(common_step_counter), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_dec_member_outcome_post failed ({rc}): {lib.lg_last_error().decode()}")
+    _call("lg_dec_member_outcome_post", C.byref(params), C.byref(buffers), C.byref(outcome), C.byref(members), int(common_step_counter), stream)
 
 
 # ---------------------------------------------------------------------------------------------------------------- legged_recurrent.h
-RECURRENT_SYMBOLS = ["lg_lstm_create", "lg_lstm_load_device", "lg_lstm_destroy", "lg_lstm_step",
-                     "lg_lstm_actor_create", "lg_lstm_actor_load_device", "lg_lstm_actor_destroy", "lg_lstm_actor_act"]
 LG_LSTM_MAX_IN, LG_LSTM_MAX_HIDDEN, LG_LSTM_BLOCK_ENVS = 256, 256, 32
-
-
-def bind_recurrent_prototypes(lib):
-    """Attach argtypes/restype for the entry points of legged_recurrent.h (the LSTM cell of a recurrent policy)."""
-    vp = C.c_void_p
-    lib.lg_lstm_create.argtypes, lib.lg_lstm_create.restype = [i32, i32, vp, vp, vp, vp, i32, C.POINTER(vp)], C.c_int
-    lib.lg_lstm_load_device.argtypes, lib.lg_lstm_load_device.restype = [vp, vp, vp, vp, vp, vp], C.c_int
-    lib.lg_lstm_destroy.argtypes, lib.lg_lstm_destroy.restype = [vp], C.c_int
-    lib.lg_lstm_step.argtypes, lib.lg_lstm_step.restype = [vp] * 13 + [i32, vp], C.c_int
-    lib.lg_lstm_actor_create.argtypes, lib.lg_lstm_actor_create.restype = [C.POINTER(i32), i32, C.POINTER(vp)], C.c_int
-    lib.lg_lstm_actor_load_device.argtypes, lib.lg_lstm_actor_load_device.restype = [vp, C.POINTER(vp), C.POINTER(vp), vp, vp], C.c_int
-    lib.lg_lstm_actor_destroy.argtypes, lib.lg_lstm_actor_destroy.restype = [vp], C.c_int
-    lib.lg_lstm_actor_act.argtypes, lib.lg_lstm_actor_act.restype = [vp, vp, vp, vp, i32, u64, i64, vp, i32, vp], C.c_int
-    return lib
 
 
 def lstm_supported(num_in: int, hidden: int) -> bool:
@@ -751,20 +529,134 @@ def lstm_supported(num_in: int, hidden: int) -> bool:
     return 1 <= num_in <= LG_LSTM_MAX_IN and 32 <= hidden <= LG_LSTM_MAX_HIDDEN and hidden % 32 == 0
 
 
-def load_library():
-    """Load the HIP extension or fail loudly -- never a CPU substitute."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_recurrent_prototypes(bind_dec_member_outcome_prototypes(bind_dec_pool_prototypes(bind_dec_outcome_prototypes(bind_outcome_prototypes(bind_pursuer_prototypes(bind_dec_game_prototypes(bind_game_prototypes(bind_prototypes(C.CDLL(path), "lg_")))))))))
-    if _lib.lg_abi_version() != LG_ABI_VERSION:
-        raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
-    return _lib
+# ----------------------------------------------------------------------------- the ABI: every entry point of every header
+_vp, _P, _int = C.c_void_p, C.POINTER, C.c_int
+_SIZEOF = ([_int], _int)
+_DEC_ACT_TAIL = [_P(lg_dec_game_params), _P(lg_dec_game_buffers), _vp, _vp, _vp, _vp, _vp, _vp, u64, u64, i64, _vp, i32, i32,
+                 _P(lg_dec_act_outputs), _P(lg_dec_act_outputs), _vp]
+# header -> ({symbol: (argtypes, restype)} in the header's order, its *_sizeof function or None, the structs that function sizes by index)
+ABI = {
+    "legged_hip.h": ({
+        "lg_create": ([_P(lg_params), _P(lg_robot_model), _PF, _int, _P(_vp)], _int),
+        "lg_destroy": ([_vp], None),
+        "lg_bind": ([_vp, _P(lg_buffers)], _int),
+        "lg_step": ([_vp, _vp, i64, _vp], _int),
+        "lg_set_deferred_extras": ([_vp, i32], _int),
+        "lg_extras_flush": ([_vp, i64, _vp], _int),
+        "lg_reset_idx": ([_vp, _vp, i32, i64, _vp], _int),
+        "lg_actuator_forward": ([_vp, _vp, _vp, _vp, _vp, _vp, i32, _vp], _int),
+        "lg_physics_substep": ([_vp, _vp, i32, _vp], _int),
+        "lg_compute_observations_only": ([_vp, i64, _vp], _int),
+        "lg_resample_reset_commands": ([_vp, i64, _vp], _int),
+        "lg_set_obs_buffer": ([_vp, _vp], _int),
+        "lg_set_params": ([_vp, _P(lg_params)], _int),
+        "lg_policy_create": ([_P(i32), _P(_PF), _P(_PF), _PF, _int, _P(_vp)], _int),
+        "lg_policy_destroy": ([_vp], None),
+        "lg_policy_act": ([_vp, _vp, _vp, _vp, i32, u64, i64, _vp, i32, _vp], _int),
+        "lg_policy_load_device": ([_vp, _vp, _vp, _vp, _vp], _int),
+        "lg_step_policy": ([_vp, _vp, _vp, _vp, _vp, u64, i32, i64, _vp], _int),
+        "lg_rollout_policy": ([_vp, _vp, _P(lg_rollout_buffers), u64, i32, i64, _vp], _int),
+        "lg_gae_returns": ([_vp, _vp, _vp, _vp, C.c_float, C.c_float, _vp, _vp, i32, i32, _vp], _int),
+        "lg_mlp_forward": ([_P(lg_mlp_net), i32, _vp, i32, _vp], _int),
+        "lg_mlp_workspace_bytes": ([_P(lg_mlp_net), i32], C.c_size_t),
+        "lg_mlp_backward": ([_P(lg_mlp_net), i32, _vp, i32, _vp, C.c_size_t, _vp], _int),
+        "lg_mlp_wide_workspace_bytes": ([_P(lg_mlp_net), i32, i32], C.c_size_t),
+        "lg_mlp_wide_set_precision": ([_int], _int),
+        "lg_mlp_wide_forward": ([_P(lg_mlp_net), i32, _vp, i32, _vp, C.c_size_t, _vp], _int),
+        "lg_mlp_wide_backward": ([_P(lg_mlp_net), i32, _vp, i32, _vp, C.c_size_t, _vp], _int),
+        "lg_ppo_minibatch": ([_P(lg_mlp_net), _vp, i32, _P(lg_ppo_batch), _vp, C.c_size_t, _vp], _int),
+        "lg_mlp_trace": ([_vp], None),
+        "lg_rollout_record": ([_P(lg_rollout_step), _vp], _int),
+        "lg_rollout_finish": ([_P(lg_rollout_post), _vp], _int),
+        "lg_adam_step": ([_P(lg_adam_tensor), i32, _vp, C.c_float, C.c_float, C.c_float, C.c_float, _vp, C.c_float, _vp, _vp], _int),
+        "lg_ppo_loss": ([_vp] * 11 + [C.c_float, C.c_float, C.c_float, i32, _vp, _vp, _vp, _vp, i32, i32, _vp], _int),
+        "lg_device_status": ([_vp, i32], _int),
+        "lg_clear_device_status": ([_vp], _int),
+        "lg_debug_handover": ([_vp, i32, i32], _int),
+        "lg_last_error": ([], C.c_char_p),
+        "lg_abi_version": ([], _int),
+        "lg_sizeof": _SIZEOF,
+    }, "lg_sizeof", (lg_params, lg_robot_model, lg_buffers, lg_point, lg_mlp_net, lg_adam_tensor, lg_rollout_step, lg_ppo_batch)),
+    "legged_game.h": ({
+        "lg_game_pre": ([_P(lg_game_params), _P(lg_game_buffers), _vp], _int),
+        "lg_game_post": ([_P(lg_game_params), _P(lg_game_buffers), i64, _vp], _int),
+        "lg_game_act": ([_vp, _vp, _P(lg_game_params), _P(lg_game_buffers), _vp, _vp, _vp, _vp, u64, i64, _vp, i32, _vp, _vp, _vp, _vp, _vp], _int),
+        "lg_game_sizeof": _SIZEOF,
+    }, "lg_game_sizeof", (lg_game_params, lg_game_buffers)),
+    "legged_dec_game.h": ({
+        "lg_dec_game_pre": ([_P(lg_dec_game_params), _P(lg_dec_game_buffers), _vp], _int),
+        "lg_dec_game_post": ([_P(lg_dec_game_params), _P(lg_dec_game_buffers), i64, _vp], _int),
+        "lg_dec_game_act": ([_vp, _vp, _vp] + _DEC_ACT_TAIL, _int),
+        "lg_dec_game_sizeof": _SIZEOF,
+    }, "lg_dec_game_sizeof", (lg_dec_game_params, lg_dec_game_buffers, lg_dec_act_outputs)),
+    "legged_pursuer_game.h": ({
+        "lg_pursuer_post": ([_P(lg_game_params), _P(lg_pursuer_params), _P(lg_game_buffers), _vp, i64, _vp], _int),
+        "lg_pursuer_sizeof": _SIZEOF,
+    }, "lg_pursuer_sizeof", (lg_pursuer_params,)),
+    "legged_game_outcome.h": ({
+        "lg_outcome_post": ([_P(lg_game_params), _P(lg_game_buffers), _P(lg_outcome_buffers), i64, _vp], _int),
+        "lg_outcome_pursuer_post": ([_P(lg_game_params), _P(lg_pursuer_params), _P(lg_game_buffers), _P(lg_outcome_buffers), _vp, i64, _vp], _int),
+        "lg_outcome_sizeof": _SIZEOF,
+    }, "lg_outcome_sizeof", (lg_outcome_buffers,)),
+    "legged_dec_game_outcome.h": ({
+        "lg_dec_outcome_post": ([_P(lg_dec_game_params), _P(lg_dec_game_buffers), _P(lg_dec_outcome_buffers), i64, _vp], _int),
+        "lg_dec_outcome_sizeof": _SIZEOF,
+    }, "lg_dec_outcome_sizeof", (lg_dec_outcome_buffers,)),
+    "legged_dec_game_pool.h": ({
+        "lg_dec_pool_create": ([_P(_vp), i32, i32, i32, _P(_vp)], _int),
+        "lg_dec_pool_destroy": ([_vp], _int),
+        "lg_dec_pool_query": ([_vp, _P(lg_dec_pool_info)], _int),
+        "lg_dec_pool_act": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp] + _DEC_ACT_TAIL, _int),
+        "lg_dec_pool_sizeof": _SIZEOF,
+    }, "lg_dec_pool_sizeof", (lg_dec_pool_info,)),
+    "legged_dec_game_member_outcome.h": ({
+        "lg_dec_member_outcome_post": ([_P(lg_dec_game_params), _P(lg_dec_game_buffers), _P(lg_dec_outcome_buffers), _P(lg_dec_member_outcome_buffers), i64, _vp], _int),
+        "lg_dec_member_outcome_sizeof": _SIZEOF,
+    }, "lg_dec_member_outcome_sizeof", (lg_dec_member_outcome_buffers,)),
+    "legged_recurrent.h": ({
+        "lg_lstm_create": ([i32, i32, _vp, _vp, _vp, _vp, i32, _P(_vp)], _int),
+        "lg_lstm_load_device": ([_vp, _vp, _vp, _vp, _vp, _vp], _int),
+        "lg_lstm_destroy": ([_vp], _int),
+        "lg_lstm_step": ([_vp] * 13 + [i32, _vp], _int),
+        "lg_lstm_actor_create": ([_P(i32), i32, _P(_vp)], _int),
+        "lg_lstm_actor_load_device": ([_vp, _P(_vp), _P(_vp), _vp, _vp], _int),
+        "lg_lstm_actor_destroy": ([_vp], _int),
+        "lg_lstm_actor_act": ([_vp, _vp, _vp, _vp, i32, u64, i64, _vp, i32, _vp], _int),
+    }, None, ()),
+}
+(EXPORTED_SYMBOLS, GAME_SYMBOLS, DEC_GAME_SYMBOLS, PURSUER_SYMBOLS, OUTCOME_SYMBOLS, DEC_OUTCOME_SYMBOLS, DEC_POOL_SYMBOLS, DEC_MEMBER_OUTCOME_SYMBOLS,
+ RECURRENT_SYMBOLS) = (list(functions) for functions, _, _ in ABI.values())
+ALL_SYMBOLS = [symbol for functions, _, _ in ABI.values() for symbol in functions]
+# what the CPU oracle exports of legged_hip.h under its own prefix: the simulator, sized by the first four structs
+ORACLE_SYMBOLS = ("lg_create", "lg_destroy", "lg_bind", "lg_step", "lg_reset_idx", "lg_actuator_forward", "lg_physics_substep",
+                  "lg_compute_observations_only", "lg_set_params", "lg_set_obs_buffer", "lg_last_error", "lg_abi_version", "lg_sizeof")
+
+
+def bind_header(lib, header: str, prefix: str = "lg_"):
+    """Attach argtypes/restype for the entry points of ``header`` and check its struct layouts.  Another ``prefix`` than ``lg_`` is the
+    CPU oracle's build of legged_hip.h."""
+    functions, sizeof, structs = ABI[header]
+    if prefix != "lg_":
+        functions, structs = {symbol: functions[symbol] for symbol in ORACLE_SYMBOLS}, structs[:4]
+    for symbol, (argtypes, restype) in functions.items():
+        fn = getattr(lib, prefix + symbol[3:])
+        fn.argtypes, fn.restype = argtypes, restype
+    for which, st in enumerate(structs):
+        size = getattr(lib, prefix + sizeof[3:])(which)
+        if size != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def bind_prototypes(lib, prefix: str):
+    """``bind_header`` for legged_hip.h, under the name the oracle's loader calls."""
+    return bind_header(lib, "legged_hip.h", prefix)
+
+
+def bind_all(lib):
+    for header in ABI:
+        bind_header(lib, header)
+    return lib
 
 
 class Sim:
@@ -795,9 +687,7 @@ class Sim:
             raise RuntimeError(f"{self.prefix}* call failed ({rc}): {self._fn('last_error')().decode()}")
 
     def bind(self, pointers: Dict[str, int]):
-        for name in BUFFER_FIELDS:
-            ptr = pointers.get(name, 0) or 0
-            setattr(self.buffers, name, C.cast(C.c_void_p(ptr), dict(lg_buffers._fields_)[name]))
+        self.buffers = _buffers(lg_buffers, pointers)
         self._check(self._fn("bind")(self.handle, C.byref(self.buffers)))
 
     def step(self, actions_ptr: int, common_step_counter: int, stream: int = 0):
@@ -810,10 +700,9 @@ class Sim:
 
     def rollout_policy(self, policy_handle, steps: int, obs_ptr: int, actions_ptr: int, mean_ptr, rew_ptr: int, dones_ptr: int, time_outs_ptr: int,
                        seed: int, deterministic: bool, common_step_counter: int, stream: int = 0, obs0_ptr=None):
-        r = lg_rollout_buffers()
+        pointers = {"obs": obs_ptr, "obs0": obs0_ptr, "actions": actions_ptr, "mean": mean_ptr, "rew": rew_ptr, "dones": dones_ptr, "time_outs": time_outs_ptr}
+        r = _buffers(lg_rollout_buffers, pointers, pointers)
         r.steps = int(steps)
-        for name, ptr in (("obs", obs_ptr), ("obs0", obs0_ptr), ("actions", actions_ptr), ("mean", mean_ptr), ("rew", rew_ptr), ("dones", dones_ptr), ("time_outs", time_outs_ptr)):
-            setattr(r, name, C.cast(C.c_void_p(ptr or 0), dict(lg_rollout_buffers._fields_)[name]))
         self._check(self.lib.lg_rollout_policy(self.handle, policy_handle, C.byref(r), int(seed), int(bool(deterministic)), int(common_step_counter), stream))
 
     def set_deferred_extras(self, on: bool):

@@ -29,13 +29,12 @@ of that pool, read back with ``pool.member_totals_host()``.  Everything else com
 
 ``agent_view(agent, opponent)`` gives one agent's single-agent surface (what ``rl.OnPolicyRunner`` drives) with the other agent acting
 inside every step.  Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G10 onward)."""
-import numpy as np
 import torch
 
 from legged_games_gym_amd import LEGGED_GYM_ROOT_DIR, capi
 from legged_games_gym_amd.utils.helpers import class_to_dict
 
-from .game_base import HALF_FOV, LL_REW_WEIGHT, PREDATOR_Z, GameBase
+from .game_base import GameBase
 
 SEED_OFFSET_PREY = 7919                      # noise seeds of the two sampled actors: cfg.seed + these (they share the purposes 100 + g, so they must differ)
 SEED_OFFSET_PRED = 7919 + 104729
@@ -45,6 +44,9 @@ AGENTS = ("pred", "prey")
 
 class DecHighLevelGame(GameBase):
     TASK = "dec_high_level_game"
+    GRAPHED_ACTORS = "FusedActors"
+    OUTCOME_COUNTS, OUTCOME_MEANS, OUTCOME_BUFFERS = capi.DEC_OUTCOME_COUNTS, capi.DEC_OUTCOME_MEANS, staticmethod(capi.dec_outcome_buffers)
+    OUTCOME_TICKET = OUTCOME_ONLY_EPISODE = False     # (the reduction shares the game's extras_ticket; extras["episode"] also holds the reward means)
 
     def __init__(self, cfg, sim_params, physics_engine, sim_device, headless):
         self._init_low_level(cfg, sim_params, physics_engine, sim_device, headless, LEGGED_GYM_ROOT_DIR)
@@ -117,26 +119,6 @@ class DecHighLevelGame(GameBase):
             capi.dec_member_outcome_post(self._P, B, self._outcome, self._member_outcome, common_step_counter, stream)
 
     # ------------------------------------------------------------------ outcome statistics
-    def enable_outcome_stats(self, on=True):
-        """Switch the outcome statistics on or off.  On: ``_post`` issues ``lg_dec_outcome_post`` on every step path and ``extras["episode"]``
-        additionally holds 0-dim views ``outcome_captured``, ``outcome_timed_out``, ``outcome_fell``, ``outcome_ll_timed_out`` (shares of the
-        done envs of the last step in which an env was done; an env may raise several) and ``outcome_steps`` (their mean episode length in
-        high-level steps).  Off: the launches and the extras of the plain task.  The totals are kept across a switch;
-        ``reset_outcome_totals()`` zeroes them.  A graph captured before the switch keeps the launch it was captured with."""
-        for key in [k for k in self.extras["episode"] if k.startswith("outcome_")]:
-            del self.extras["episode"][key]
-        if not on:
-            self._outcome = None
-            return
-        if getattr(self, "_outcome_accum", None) is None:
-            dev = self.device
-            self._outcome_accum = torch.zeros(capi.LG_DEC_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
-            self._outcome_means = torch.zeros(capi.LG_DEC_OUTCOME_NUM_MEANS, device=dev, dtype=torch.float)
-            self._outcome_totals = torch.zeros(capi.LG_DEC_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
-        self._outcome = capi.dec_outcome_buffers({"ll_time_out_buf": self.ll_env._sim.buf["time_out_buf"].data_ptr(), "accum": self._outcome_accum.data_ptr(),
-                                                  "means": self._outcome_means.data_ptr(), "totals": self._outcome_totals.data_ptr()})
-        self.extras["episode"].update({f"outcome_{name}": self._outcome_means[i] for i, name in enumerate(capi.DEC_OUTCOME_MEANS)})
-
     def enable_member_outcomes(self, pool):
         """Keep the outcome counts per member of ``pool`` (an ``rl.OpponentPool``) as well, or stop doing so (``None``).  With a pool bound and
         the outcome statistics on, ``_post`` issues ``lg_dec_member_outcome_post`` on every step path, given the pool's slot table, ``count = 1 +
@@ -151,19 +133,6 @@ class DecHighLevelGame(GameBase):
         self._member_pool = pool                                   # keeps the buffers alive
         self._member_outcome = capi.dec_member_outcome_buffers({"block_slot": pool.slot_table(self.num_envs).data_ptr(), "member_accum": pool.member_accum.data_ptr(),
                                                                 "member_totals": pool.member_totals.data_ptr()}, 1 + pool.capacity)
-
-    def outcome_totals(self):
-        """Running sums since construction or the last ``reset_outcome_totals()``, as Python ints after ONE synchronising copy:
-        ``episodes, captured, timed_out, fell, ll_timed_out, steps``."""
-        if getattr(self, "_outcome_totals", None) is None:
-            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
-        return dict(zip(capi.DEC_OUTCOME_COUNTS, (int(v) for v in self._outcome_totals.cpu().tolist())))
-
-    def reset_outcome_totals(self):
-        """Zero the running sums (stream-ordered: no synchronisation)."""
-        if getattr(self, "_outcome_totals", None) is None:
-            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
-        self._outcome_totals.zero_()
 
     def _step_result(self):
         return (self.obs_buf_pred, self.obs_buf_prey, self.privileged_obs_buf_pred, self.privileged_obs_buf_prey, self.rew_buf_pred, self.rew_buf_prey,
@@ -257,17 +226,7 @@ class DecHighLevelGame(GameBase):
                 command, mean = fused.act_with_mean(obs_in, det)
             else:
                 command, mean, std = pool.act_separate(obs_in, det)          # per member in use, rows by block; std [n, actions] of the rows' members
-            if out.get("sample") is not None:
-                out["sample"].view(n, -1).copy_(command)
-            if out.get("sigma") is not None or out.get("log_prob") is not None:
-                if pool is None:
-                    std = fused.ac.std.detach()
-                if out.get("sigma") is not None:
-                    out["sigma"].view(n, -1).copy_(std.expand(n, -1))
-                if out.get("log_prob") is not None:
-                    out["log_prob"].view(n).copy_(torch.distributions.Normal(mean, std).log_prob(command).sum(-1))
-            if out.get("obs_copy") is not None:
-                out["obs_copy"].view(n, -1).copy_(obs_in)
+            self._fill_optional_outputs(out, n, command, mean, std if pool is not None else fused.ac.std.detach(), obs_in)
         if carry:
             obs_prey_out.copy_(obs_prey_in)
         capi.dec_game_pre(self._P, B, stream)
@@ -301,8 +260,7 @@ class DecHighLevelGame(GameBase):
         ``deterministic_pred`` / ``deterministic_prey``: that agent's command is its clipped mean (evaluation)."""
         sim = self.ll_env._sim
         for fused in (_live(fused_pred), _live(fused_prey)):
-            if fused.step_counter is None or fused.step_counter.data_ptr() != sim.buf["step_counter"].data_ptr():
-                raise ValueError("make_graphed_policy_step needs FusedActors on the low-level sim's device step counter")
+            self._require_device_step_counter(fused)
 
         def device_step():
             _, _, ll_actions, B = self._act(fused_pred, fused_prey, self.obs_buf_pred, self.obs_buf_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
@@ -324,13 +282,7 @@ class DecHighLevelGame(GameBase):
         n = len(ids)
         ll.dof_pos[ids] = ll.default_dof_pos * (0.5 + torch.rand(n, ll.num_dof, device=self.device))     # low_level_game.py:391-392
         ll.dof_vel[ids] = 0.
-        root = ll.base_init_state.repeat(n, 1)
-        root[:, :3] += ll.env_origins[ids]
-        if ll.custom_origins:
-            root[:, :2] += 2.0 * torch.rand(n, 2, device=self.device) - 1.0
-        root[:, 7:13] = torch.rand(n, 6, device=self.device) - 0.5
-        ll.root_states[ids] = root
-        self.predator_pos[ids] = self._place_predator(root[:, :3])
+        self._reset_roots(ids)
         self.obs_buf_prey[ids, 0:12] = self.MAX_REL_POS
         self.obs_buf_prey[ids, 12:16] = 0
         self.obs_buf_pred[ids] = -self.MAX_REL_POS
@@ -424,55 +376,30 @@ class DecHighLevelGame(GameBase):
         """Reference :581-590."""
         self.reward_scales_prey = class_to_dict(self.cfg.rewards_prey.scales)
         self.reward_scales_pred = class_to_dict(self.cfg.rewards_predator.scales)
-        self.command_ranges = class_to_dict(self.cfg.commands.ranges)
-        if self.cfg.terrain.mesh_type not in ["heightfield", "trimesh"]:
-            self.cfg.terrain.curriculum = False
-        self.max_episode_length_s = self.cfg.env.episode_length_s
-        self.max_episode_length = np.ceil(self.max_episode_length_s / self.ll_env.dt)
+        super()._parse_cfg(cfg)
 
     def _pack(self):
         """``lg_dec_game_params`` from the configs and the pointer table of ``lg_dec_game_buffers``."""
         ll, P = self.ll_env, capi.lg_dec_game_params()
-        P.num_envs, P.decimation = self.num_envs, int(ll.cfg.control.decimation)
-        P.heading_command, P.custom_origins = int(bool(self.cfg.commands.heading_command)), int(bool(ll.custom_origins))
+        self._pack_common(P)
         P.only_positive_rewards_prey = int(bool(self.cfg.rewards_prey.only_positive_rewards))
         P.only_positive_rewards_pred = int(bool(self.cfg.rewards_predator.only_positive_rewards))
-        P.max_episode_length = int(self.max_episode_length)
-        seed = getattr(self.cfg, "seed", 1)
-        P.seed = int(seed) if seed is not None and seed >= 0 else 1
-        r = self.command_ranges
-        for name, key in (("cmd_lin_vel_x", "lin_vel_x"), ("cmd_lin_vel_y", "lin_vel_y"), ("predator_lin_vel_x", "predator_lin_vel_x"),
-                          ("predator_lin_vel_y", "predator_lin_vel_y")):
-            capi._fill(getattr(P, name), r[key])
-        P.capture_dist = float(self.capture_dist)
-        P.half_fov, P.max_rel_pos, P.ll_rew_weight = HALF_FOV, self.MAX_REL_POS, LL_REW_WEIGHT
+        P.max_episode_length, P.max_episode_length_s = int(self.max_episode_length), float(self.max_episode_length_s)
         P.scale_evasion_dt = float(self.reward_scales_prey.get("evasion", 0.0))
         P.scale_pursuit_dt = float(self.reward_scales_pred.get("pursuit", 0.0))
         P.scale_termination_prey_dt = float(self.reward_scales_prey.get("termination", 0.0))
-        P.sim_dt, P.predator_z, P.max_episode_length_s = float(ll.cfg.sim.dt), PREDATOR_Z, float(self.max_episode_length_s)
-        capi._fill(P.base_init_state, ll.base_init_state.cpu().numpy())
         capi._fill(P.default_dof_pos, ll.default_dof_pos.cpu().numpy())        # the joint order of the low-level dof_state buffer
         self._P = P
-        b = ll._sim.buf
-        self._pointers = {"ll_root_states": b["root_states"].data_ptr(), "ll_dof_state": b["dof_state"].data_ptr(), "ll_commands": b["commands"].data_ptr(),
-                          "ll_env_origins": b["env_origins"].data_ptr(), "ll_rew_buf": b["rew_buf"].data_ptr(), "ll_reset_buf": b["reset_buf"].data_ptr(),
-                          "ll_step_counter": b["step_counter"].data_ptr(), "predator_pos": self.predator_pos.data_ptr(), "rew_prey": self.rew_buf_prey.data_ptr(),
-                          "rew_pred": self.rew_buf_pred.data_ptr(), "reset_buf": self.reset_buf.data_ptr(), "time_out_buf": self.time_out_buf.data_ptr(),
-                          "curr_episode_step": self.curr_episode_step.data_ptr(), "episode_length_buf": self.episode_length_buf.data_ptr(),
-                          "episode_sums": self._episode_sums.data_ptr(), "episode_means": self._episode_means.data_ptr(),
-                          "extras_accum": self._extras_accum.data_ptr(), "extras_ticket": self._extras_ticket.data_ptr()}
+        self._pointers = dict(self._ll_pointers(), ll_dof_state=ll._sim.buf["dof_state"].data_ptr(), predator_pos=self.predator_pos.data_ptr(),
+                              rew_prey=self.rew_buf_prey.data_ptr(), rew_pred=self.rew_buf_pred.data_ptr(), reset_buf=self.reset_buf.data_ptr(),
+                              time_out_buf=self.time_out_buf.data_ptr(), curr_episode_step=self.curr_episode_step.data_ptr(),
+                              episode_length_buf=self.episode_length_buf.data_ptr(), episode_sums=self._episode_sums.data_ptr(),
+                              episode_means=self._episode_means.data_ptr(), extras_accum=self._extras_accum.data_ptr(),
+                              extras_ticket=self._extras_ticket.data_ptr())
 
     def set_command_ranges(self):
         """Re-pack after ``command_ranges`` / ``capture_dist`` were edited."""
         self._pack()
-
-    def _own(self, command, width, scratch, name):
-        if command.shape != (self.num_envs, width):
-            raise ValueError(f"{name} must be [{self.num_envs},{width}], got {tuple(command.shape)}")
-        if command.dtype != torch.float32 or not command.is_contiguous() or str(command.device) != str(self.device):
-            scratch.copy_(command)
-            command = scratch
-        return command
 
     def _bind(self, command_pred, command_prey, obs_pred, obs_prey):
         """``lg_dec_game_buffers`` for this call: the kernels read and clip the callers' tensors where they are."""

@@ -24,13 +24,12 @@ rates of the step's done envs that were captured / left the arena (prey, predato
 ``outcome_totals()`` the running integer sums.  A step is still three launches and a rollout still one graph replay.
 
 Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G1-G9)."""
-import numpy as np
 import torch
 
 from legged_games_gym_amd import LEGGED_GYM_ROOT_DIR, capi
 from legged_games_gym_amd.utils.helpers import class_to_dict
 
-from .game_base import HALF_FOV, LL_REW_WEIGHT, PREDATOR_Z, GameBase
+from .game_base import GameBase
 
 
 class HighLevelGame(GameBase):
@@ -102,44 +101,6 @@ class HighLevelGame(GameBase):
         else:
             capi.outcome_post(self._P, B, self._outcome, common_step_counter, stream)
 
-    # ------------------------------------------------------------------ outcome statistics
-    def enable_outcome_stats(self, on=True):
-        """Switch the outcome statistics on or off.  On: ``_post`` issues the outcome entry point of the task on every step path and
-        ``extras["episode"]`` holds 0-dim views ``outcome_captured``, ``outcome_prey_out``, ``outcome_predator_out``, ``outcome_fell``,
-        ``outcome_survived`` (shares of the done envs of the last step in which an env was done; an env may raise several) and
-        ``outcome_steps`` (their mean episode length in high-level steps).  Off: the launches of the plain task and ``extras == {}``.
-        The totals are kept across a switch; ``reset_outcome_totals()`` zeroes them.
-
-        A graph captures the launch that the switch selected at capture time: flip the switch BEFORE ``make_graphed_step``,
-        ``make_graphed_policy_step`` or the runner's device rollout capture; a graph captured earlier keeps replaying what it captured."""
-        if not on:
-            self._outcome = None
-            self.extras.pop("episode", None)
-            return
-        if getattr(self, "_outcome_accum", None) is None:
-            dev = self.device
-            self._outcome_accum = torch.zeros(capi.LG_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
-            self._outcome_ticket = torch.zeros(1, device=dev, dtype=torch.int32)
-            self._outcome_means = torch.zeros(capi.LG_OUTCOME_NUM_MEANS, device=dev, dtype=torch.float)
-            self._outcome_totals = torch.zeros(capi.LG_OUTCOME_NUM_COUNTS, device=dev, dtype=torch.int64)
-        self._outcome = capi.outcome_buffers({"ll_time_out_buf": self.ll_env._sim.buf["time_out_buf"].data_ptr(), "accum": self._outcome_accum.data_ptr(),
-                                              "ticket": self._outcome_ticket.data_ptr(), "means": self._outcome_means.data_ptr(),
-                                              "totals": self._outcome_totals.data_ptr()})
-        self.extras["episode"] = {f"outcome_{name}": self._outcome_means[i] for i, name in enumerate(capi.OUTCOME_MEANS)}
-
-    def outcome_totals(self):
-        """Running sums since construction or the last ``reset_outcome_totals()``, as Python ints after ONE synchronising copy:
-        ``episodes, captured, prey_out, predator_out, fell, survived, steps``.  Episodes still running are not in them."""
-        if getattr(self, "_outcome_totals", None) is None:
-            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
-        return dict(zip(capi.OUTCOME_COUNTS, (int(v) for v in self._outcome_totals.cpu().tolist())))
-
-    def reset_outcome_totals(self):
-        """Zero the totals on the current stream (no synchronisation)."""
-        if getattr(self, "_outcome_totals", None) is None:
-            raise RuntimeError("the outcome statistics were never switched on: enable_outcome_stats() or env.outcome_stats = True")
-        self._outcome_totals.zero_()
-
     def _step_result(self):
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
@@ -170,16 +131,8 @@ class HighLevelGame(GameBase):
         # rc -4, nothing was launched: lg_policy_act x 2 + lg_game_pre (decided per call: lg_mlp_wide_set_precision may change between
         # calls), each actor into its own FusedActor's buffers as above
         command, mean = fused_actor.act_with_mean(obs_in, deterministic)
-        if sample is not None:
-            sample.view(n, -1).copy_(command)
-        if sigma is not None or log_prob is not None:
-            std = fused_actor.ac.std.detach()
-            if sigma is not None:
-                sigma.view(n, -1).copy_(std.expand(n, -1))
-            if log_prob is not None:
-                log_prob.view(n).copy_(torch.distributions.Normal(mean, std).log_prob(command).sum(-1))
-        if copy:
-            obs_out.copy_(obs_in)
+        self._fill_optional_outputs({"sample": sample, "sigma": sigma, "log_prob": log_prob, "obs_copy": obs_out if copy else None}, n, command, mean,
+                                    fused_actor.ac.std.detach(), obs_in)
         capi.game_pre(self._P, B, stream)
         ll_actions = self.ll_policy(ll.obs_buf)
         return command, mean, ll_actions, B
@@ -223,10 +176,8 @@ class HighLevelGame(GameBase):
         ``fused_actor`` must draw its noise stream from the low-level sim's device step counter
         (``FusedActor(..., step_counter=env.ll_env._sim.buf["step_counter"])``).  Returns a zero-argument callable that replays the graph;
         ``fused_actor.output_buffers(num_envs)`` then hold the command and the mean of the last step."""
-        ll = self.ll_env
-        sim = ll._sim
-        if fused_actor.step_counter is None or fused_actor.step_counter.data_ptr() != sim.buf["step_counter"].data_ptr():
-            raise ValueError("make_graphed_policy_step needs a FusedActor on the low-level sim's device step counter")
+        sim = self.ll_env._sim
+        self._require_device_step_counter(fused_actor)
 
         def device_step():
             _, _, ll_actions, B = self._act(fused_actor, self.obs_buf, self.obs_buf, deterministic)
@@ -241,16 +192,8 @@ class HighLevelGame(GameBase):
         draws from torch's generator, like the creation-time randomisation of the low-level env."""
         if len(env_ids) == 0:
             return
-        ll = self.ll_env
         ids = torch.as_tensor(env_ids, device=self.device, dtype=torch.long)
-        n = len(ids)
-        root = ll.base_init_state.repeat(n, 1)
-        root[:, :3] += ll.env_origins[ids]
-        if ll.custom_origins:
-            root[:, :2] += 2.0 * torch.rand(n, 2, device=self.device) - 1.0
-        root[:, 7:13] = torch.rand(n, 6, device=self.device) - 0.5
-        ll.root_states[ids] = root
-        self.predator_pos[ids] = self._place_predator(root[:, :3])
+        self._reset_roots(ids)
         self.obs_buf[ids, 0:12] = self.MAX_REL_POS
         self.obs_buf[ids, 12:16] = 0
         self.obs_buf[ids, 16:] = -self.MAX_REL_POS
@@ -301,38 +244,20 @@ class HighLevelGame(GameBase):
     def _parse_cfg(self, cfg):
         """Reference :563-571."""
         self.reward_scales = class_to_dict(self.cfg.rewards.scales)
-        self.command_ranges = class_to_dict(self.cfg.commands.ranges)
-        if self.cfg.terrain.mesh_type not in ["heightfield", "trimesh"]:
-            self.cfg.terrain.curriculum = False
-        self.max_episode_length_s = self.cfg.env.episode_length_s
-        self.max_episode_length = np.ceil(self.max_episode_length_s / self.ll_env.dt)
+        super()._parse_cfg(cfg)
 
     def _pack(self):
         """``lg_game_params`` from the configs and the pointer table of ``lg_game_buffers``."""
-        ll, P = self.ll_env, capi.lg_game_params()
-        P.num_envs, P.decimation = self.num_envs, int(ll.cfg.control.decimation)
-        P.heading_command, P.only_positive_rewards = int(bool(self.cfg.commands.heading_command)), int(bool(self.cfg.rewards.only_positive_rewards))
-        P.custom_origins = int(bool(ll.custom_origins))
-        seed = getattr(self.cfg, "seed", 1)
-        P.seed = int(seed) if seed is not None and seed >= 0 else 1
-        r = self.command_ranges
-        for name, key in (("cmd_lin_vel_x", "lin_vel_x"), ("cmd_lin_vel_y", "lin_vel_y"), ("predator_lin_vel_x", "predator_lin_vel_x"),
-                          ("predator_lin_vel_y", "predator_lin_vel_y")):
-            capi._fill(getattr(P, name), r[key])
-        P.capture_dist = float(self.capture_dist)
+        P = capi.lg_game_params()
+        self._pack_common(P)
+        P.only_positive_rewards = int(bool(self.cfg.rewards.only_positive_rewards))
         P.env_radius = -1.0 if self.cfg.env.env_radius is None else float(self.cfg.env.env_radius)
-        P.half_fov, P.max_rel_pos, P.ll_rew_weight = HALF_FOV, self.MAX_REL_POS, LL_REW_WEIGHT
         P.scale_evasion_dt = float(self.reward_scales.get("evasion", 0.0))
         P.scale_pursuit_dt = float(self.reward_scales.get("pursuit", 0.0))
-        P.sim_dt, P.predator_z = float(ll.cfg.sim.dt), PREDATOR_Z
-        capi._fill(P.base_init_state, ll.base_init_state.cpu().numpy())
         self._P = P
-        b = ll._sim.buf
-        self._pointers = {"ll_root_states": b["root_states"].data_ptr(), "ll_commands": b["commands"].data_ptr(), "ll_env_origins": b["env_origins"].data_ptr(),
-                          "ll_rew_buf": b["rew_buf"].data_ptr(), "ll_reset_buf": b["reset_buf"].data_ptr(), "ll_step_counter": b["step_counter"].data_ptr(),
-                          "predator_pos": self.predator_pos.data_ptr(), "rew": self.rew_buf.data_ptr(), "reset_buf": self.reset_buf.data_ptr(),
-                          "curr_episode_step": self.curr_episode_step.data_ptr(), "episode_length_buf": self.episode_length_buf.data_ptr(),
-                          "episode_sums": self._episode_sums.data_ptr()}
+        self._pointers = dict(self._ll_pointers(), predator_pos=self.predator_pos.data_ptr(), rew=self.rew_buf.data_ptr(), reset_buf=self.reset_buf.data_ptr(),
+                              curr_episode_step=self.curr_episode_step.data_ptr(), episode_length_buf=self.episode_length_buf.data_ptr(),
+                              episode_sums=self._episode_sums.data_ptr())
 
     def set_command_ranges(self):
         """Re-pack after ``command_ranges`` / ``capture_dist`` / ``cfg.env.env_radius`` were edited."""
@@ -340,10 +265,5 @@ class HighLevelGame(GameBase):
 
     def _bind_command(self, command, obs):
         """``lg_game_buffers`` for this call: the kernels read and clip the caller's tensor where it is."""
-        if command.shape != (self.num_envs, self.num_actions):
-            raise ValueError(f"command must be [{self.num_envs},{self.num_actions}], got {tuple(command.shape)}")
-        if command.dtype != torch.float32 or not command.is_contiguous() or str(command.device) != str(self.device):
-            self._command.copy_(command)
-            command = self._command
-        self._keep = command
+        self._keep = command = self._own(command, self.num_actions, self._command, "command")
         return capi.game_buffers(dict(self._pointers, command=command.detach().data_ptr(), obs=obs.data_ptr()))

@@ -18,6 +18,7 @@ Deliberate deviations from reference behaviour are listed in DESIGN.md
 ("Quirks"): ``reset_buf``/``time_out_buf`` are persistent bool tensors (Q1,
 Q4), RNG is counter-based Philox rather than torch's global stream.
 """
+import gc
 import os
 
 import numpy as np
@@ -125,6 +126,10 @@ class LeggedRobot(BaseTask):
 
     def begin_graph_capture(self):
         """Prepare for capturing several step() calls into one HIP graph: the step counter moves to the device."""
+        # Dead reference cycles go NOW: torch.cuda.graph no longer collects before a capture, and a collection that falls inside one runs the
+        # finalizers of whatever the cycles hold -- a Sim's or a FusedActor's hipFree, a CUDAGraph's destruction -- on the capturing thread,
+        # which the runtime does not allow there (the process was seen to abort).  What a captured step itself drops is host-only (ctypes casts).
+        gc.collect()
         self._expose_device_command_range()
         self._sim.buf["step_counter"].fill_(self.common_step_counter)
         self._capturing = True

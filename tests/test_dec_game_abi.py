@@ -48,7 +48,7 @@ def test_library_exports_the_symbols_with_the_ctypes_layouts():
     assert lib.lg_dec_game_sizeof(1) == ctypes.sizeof(capi.lg_dec_game_buffers)
     assert lib.lg_dec_game_sizeof(2) == ctypes.sizeof(capi.lg_dec_act_outputs)
     assert lib.lg_dec_game_sizeof(3) == -1
-    capi.bind_dec_game_prototypes(lib)                                          # raises on a layout mismatch
+    capi.bind_header(lib, "legged_dec_game.h")                                          # raises on a layout mismatch
     assert ctypes.sizeof(capi.lg_dec_game_params) % 8 == 0 and capi.lg_dec_game_params.seed.offset % 8 == 0
     assert capi.lg_dec_game_params.base_init_state.size == 13 * 4 and capi.lg_dec_game_params.default_dof_pos.size == 12 * 4
     decl = re.search(r"\bint\s+lg_dec_game_act\s*\((.*?)\)\s*;", re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "legged_dec_game.h")).read(), flags=re.S),

@@ -56,7 +56,7 @@ def test_library_exports_the_symbols_with_the_ctypes_layout(lib):
     lib.lg_dec_member_outcome_sizeof.argtypes, lib.lg_dec_member_outcome_sizeof.restype = [ctypes.c_int], ctypes.c_int
     assert lib.lg_dec_member_outcome_sizeof(0) == ctypes.sizeof(capi.lg_dec_member_outcome_buffers) == 3 * ctypes.sizeof(ctypes.c_void_p) + 2 * 4
     assert lib.lg_dec_member_outcome_sizeof(1) == -1 and lib.lg_dec_member_outcome_sizeof(-1) == -1
-    capi.bind_dec_member_outcome_prototypes(lib)                                # raises on a layout mismatch
+    capi.bind_header(lib, "legged_dec_game_member_outcome.h")                                # raises on a layout mismatch
     assert [name for name, _ in capi.lg_dec_member_outcome_buffers._fields_] == ["block_slot", "member_accum", "member_totals", "count", "_pad"]
     lib.lg_abi_version.restype = ctypes.c_int
     assert lib.lg_abi_version() == 22
@@ -73,7 +73,7 @@ def _arguments(num_envs=8, count=3):
 
 
 def test_bad_arguments_are_refused_before_any_launch(lib):
-    capi.bind_dec_member_outcome_prototypes(lib)
+    capi.bind_header(lib, "legged_dec_game_member_outcome.h")
     post, r = lib.lg_dec_member_outcome_post, ctypes.byref
     P, B, O, M = _arguments()
     # a null struct; the new one is named

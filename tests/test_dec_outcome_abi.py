@@ -55,7 +55,7 @@ def test_library_exports_the_symbols_with_the_ctypes_layout(lib):
     lib.lg_dec_outcome_sizeof.argtypes, lib.lg_dec_outcome_sizeof.restype = [ctypes.c_int], ctypes.c_int
     assert lib.lg_dec_outcome_sizeof(0) == ctypes.sizeof(capi.lg_dec_outcome_buffers) == 4 * ctypes.sizeof(ctypes.c_void_p)
     assert lib.lg_dec_outcome_sizeof(1) == -1
-    capi.bind_dec_outcome_prototypes(lib)                                       # raises on a layout mismatch
+    capi.bind_header(lib, "legged_dec_game_outcome.h")                                       # raises on a layout mismatch
     assert capi.DEC_OUTCOME_BUFFER_FIELDS == ["ll_time_out_buf", "accum", "means", "totals"]      # no ticket: the launch draws lg_dec_game_buffers.extras_ticket
     lib.lg_abi_version.restype = ctypes.c_int
     assert lib.lg_abi_version() == 22
@@ -71,7 +71,7 @@ def _arguments(num_envs=8):
 
 
 def test_bad_arguments_are_refused_before_any_launch(lib):
-    capi.bind_dec_outcome_prototypes(lib)
+    capi.bind_header(lib, "legged_dec_game_outcome.h")
     r = ctypes.byref
     P, B, O = _arguments()
     # a null struct; the outcome's is named
@@ -97,7 +97,7 @@ def test_bad_arguments_are_refused_before_any_launch(lib):
     Bs = capi.dec_game_buffers({k: (0 if k == "ll_step_counter" else 0x1000) for k in capi.DEC_GAME_BUFFER_FIELDS})
     assert lib.lg_dec_outcome_post(r(P), r(Bs), r(O), -1, None) == -9
     # the plain entry point keeps its codes and its text
-    capi.bind_dec_game_prototypes(lib)
+    capi.bind_header(lib, "legged_dec_game.h")
     assert lib.lg_dec_game_post(r(P), r(Bs), -1, None) == -9
     Bn = capi.dec_game_buffers({k: (0 if k == "obs_pred" else 0x1000) for k in capi.DEC_GAME_BUFFER_FIELDS})
     assert lib.lg_dec_game_post(r(P), r(Bn), 3, None) == -1 and b"lg_dec_game_post: a buffer pointer is null" in lib.lg_last_error()

@@ -57,7 +57,7 @@ def test_library_exports_the_symbols_with_the_ctypes_layout(lib):
     lib.lg_dec_pool_sizeof.argtypes, lib.lg_dec_pool_sizeof.restype = [ctypes.c_int], ctypes.c_int
     assert lib.lg_dec_pool_sizeof(0) == ctypes.sizeof(capi.lg_dec_pool_info) == 4 * 4 + ctypes.sizeof(ctypes.c_void_p)
     assert lib.lg_dec_pool_sizeof(1) == -1 and lib.lg_dec_pool_sizeof(-1) == -1
-    capi.bind_dec_pool_prototypes(lib)                                          # raises on a layout mismatch
+    capi.bind_header(lib, "legged_dec_game_pool.h")                                          # raises on a layout mismatch
     assert len(lib.lg_dec_pool_act.argtypes) == 24                              # the 20 of lg_dec_game_act and two (pool, slot table) pairs
     lib.lg_abi_version.restype = ctypes.c_int
     assert lib.lg_abi_version() == 22
@@ -73,7 +73,7 @@ def _act(lib, pred=0x1000, prey=0x1000, ll=0x1000, pool_pred=None, slot_pred=Non
 
 
 def test_bad_arguments_are_refused_before_any_launch_or_allocation(lib):
-    capi.bind_dec_pool_prototypes(lib)
+    capi.bind_header(lib, "legged_dec_game_pool.h")
     out = ctypes.c_void_p()
     members = (ctypes.c_void_p * 17)(*([0x1000] * 17))                          # never dereferenced: count and role are checked first
     assert lib.lg_dec_pool_create(None, 1, 1, 0, ctypes.byref(out)) == -1

@@ -34,7 +34,7 @@ def test_library_exports_the_game_symbols_with_the_ctypes_layouts():
     assert lib.lg_game_sizeof(0) == ctypes.sizeof(capi.lg_game_params)
     assert lib.lg_game_sizeof(1) == ctypes.sizeof(capi.lg_game_buffers)
     assert lib.lg_game_sizeof(2) == -1
-    capi.bind_game_prototypes(lib)                                              # raises on a layout mismatch
+    capi.bind_header(lib, "legged_game.h")                                              # raises on a layout mismatch
     assert ctypes.sizeof(capi.lg_game_params) % 8 == 0 and capi.lg_game_params.seed.offset % 8 == 0
     assert capi.lg_game_params.base_init_state.size == 13 * 4
 

@@ -25,7 +25,7 @@ def test_header_binding_and_library_export_the_shared_actor_launch():
     if not os.path.isfile(path):
         import __graft_entry__ as entry
         entry.build()
-    lib = capi.bind_game_prototypes(ctypes.CDLL(path))
+    lib = capi.bind_header(ctypes.CDLL(path), "legged_game.h")
     assert hasattr(lib, "lg_game_act") and lib.lg_game_act.restype is ctypes.c_int and len(lib.lg_game_act.argtypes) == 17
     # 17 arguments in the header as well: two handles, params, buffers, 4 required tensors, seed / step / counter / deterministic, 4 optional outputs, stream
     decl = re.search(r"\bint\s+lg_game_act\s*\((.*?)\)\s*;", text, flags=re.S).group(1)

@@ -51,7 +51,7 @@ def test_library_exports_the_outcome_symbols_with_the_ctypes_layout(lib):
     lib.lg_outcome_sizeof.argtypes, lib.lg_outcome_sizeof.restype = [ctypes.c_int], ctypes.c_int
     assert lib.lg_outcome_sizeof(0) == ctypes.sizeof(capi.lg_outcome_buffers) == 5 * ctypes.sizeof(ctypes.c_void_p)
     assert lib.lg_outcome_sizeof(1) == -1
-    capi.bind_outcome_prototypes(lib)                                           # raises on a layout mismatch
+    capi.bind_header(lib, "legged_game_outcome.h")                                           # raises on a layout mismatch
     assert [n for n, _ in capi.lg_outcome_buffers._fields_] == ["ll_time_out_buf", "accum", "ticket", "means", "totals"]
 
 
@@ -67,7 +67,7 @@ def _arguments(num_envs=8):
 
 
 def test_bad_arguments_are_refused_before_any_launch(lib):
-    capi.bind_outcome_prototypes(lib)
+    capi.bind_header(lib, "legged_game_outcome.h")
     r = ctypes.byref
     P, Q, B, O = _arguments()
     # a null struct

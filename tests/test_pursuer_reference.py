@@ -144,7 +144,7 @@ def test_library_exports_the_symbols_with_the_ctypes_layout():
     lib = ctypes.CDLL(path)
     for sym in capi.PURSUER_SYMBOLS:
         assert hasattr(lib, sym), sym
-    capi.bind_pursuer_prototypes(lib)                                                         # raises on a layout mismatch
+    capi.bind_header(lib, "legged_pursuer_game.h")                                                         # raises on a layout mismatch
     assert lib.lg_pursuer_sizeof(0) == ctypes.sizeof(capi.lg_pursuer_params) and lib.lg_pursuer_sizeof(1) == -1
     assert ctypes.sizeof(capi.lg_pursuer_params) % 8 == 0
     assert [n for n, _ in capi.lg_pursuer_params._fields_] == ["max_lin_vel", "min_lin_vel", "gain", "max_episode_length"]

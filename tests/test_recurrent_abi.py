@@ -30,7 +30,7 @@ def lib():
         entry.build()
     lib = ctypes.CDLL(path)
     lib.lg_last_error.restype = ctypes.c_char_p
-    return capi.bind_recurrent_prototypes(lib)
+    return capi.bind_header(lib, "legged_recurrent.h")
 
 
 def test_header_symbol_list_matches_binding_and_is_disjoint_from_the_others():
