@@ -455,6 +455,14 @@ LG_DEV float motor_torque(float tau, float qd, float vlim) {
     float s = (vlim - fabsf(qd)) / (0.1f * vlim);
     return tau * fminf(fmaxf(s, 0.0f), 1.0f);
 }
+// the same value without a branch: where physics_substep takes it once per sub-step, between the torque hand-over barrier and the
+// passes, a branch splits that stretch into basic blocks and hipcc sinks the contact setup from in front of the barrier (computed
+// while the wave waits for the helpers anyway) into the last of them, behind it (+0.8 us per policy step, measured)
+LG_DEV float motor_torque_select(float tau, float qd, float vlim) {
+    const float s = (vlim - fabsf(qd)) / (0.1f * vlim);
+    const float faded = tau * fminf(fmaxf(s, 0.0f), 1.0f);
+    return (vlim <= 0.0f || tau * qd <= 0.0f) ? tau : faded;
+}
 LG_DEV V3 clamp_norm(V3 a, float lim) {           // asset.max_linear/angular_velocity guard; maps inf/NaN to 0
     float n2 = dot(a, a);
     if (!(n2 <= lim * lim)) { float k = (n2 > 0.0f && n2 < INFINITY) ? lim * __builtin_amdgcn_rsqf(n2) : 0.0f; return a * k; }
@@ -829,6 +837,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
                             volatile int *fk_ready = nullptr, int substep_no = 0, SelfLds<T> *sc = nullptr, bool last = true,
                             bool sc_on_helpers = false /* the three helper waves run self_detect (four-wave kernels) */) {
     constexpr int K = T::K, L = T::L, NPT = T::NPT;
+    constexpr bool HELD = !HF && L <= 3;      // plane quadruped builds: the joints' pass constants and pass-invariant terms are taken once per sub-step (below)
     const lg_params &P = A.P;
     const float dt = P.sim_dt;
     const int spin_limit_early = ROLL ? A.spin_limit : 0;          // rollout kernel: read here, no scalar load between the torque hand-over and the end of the passes
@@ -944,7 +953,38 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
     }
     LG_PROF(PF_KINEMATICS);
     torques_ready();
-    if (OFFLOAD) {
+    // HELD: what the passes and the integrator read of the limb table -- damping, armature, speed limit -- as values, requested here with
+    // the body terms (one wait for both) instead of from LDS inside each pass, where a lone wave waits out every round trip; and what the
+    // passes compute from values no pass changes, once: the drive's torque at this speed (mt), and the position-limit spring as a per-lane
+    // flag (lim_lane, bit j), a wave-uniform one (lim_wave: nothing of the block is needed where no lane of the wave is at a limit; one
+    // flag for all joints -- one per joint raised the rollout kernel's spilled scalars 16 -> 23) and its contribution to u (lim_u; the
+    // one to D is added inside the pass, as before).  Each term a pass forms from the held values is written with the contraction the
+    // loaded values got: hipcc rounds a product of loop invariants in front of the loop.  No branch in this stretch: motor_torque_select.
+    float jdamp[L], jarm[L], jvlim[L], mt[L], lim_u[L], lim_kl = 0.0f;
+    unsigned lim_lane = 0, lim_wave = 0;
+    if constexpr (HELD) {
+        float lo[L], hi[L];
+#pragma unroll
+        for (int j = 0; j < L; j++) {
+            const float *tj = tab + j * LG_JS;
+            lo[j] = tj[J_LO]; hi[j] = tj[J_HI]; jvlim[j] = tj[J_VLIM]; jarm[j] = tj[J_ARM]; jdamp[j] = tj[J_DAMP];
+        }
+        if (OFFLOAD) {
+#pragma unroll
+            for (int j = 0; j < L; j++) bt_load(bt[j], threadIdx.x % LG_BLOCK, I0[j], p0[j]);
+        }
+        lim_kl = __builtin_fmaf(dt, P.limit_stiffness, P.limit_damping);
+#pragma unroll
+        for (int j = 0; j < L; j++) {
+            mt[j] = motor_torque_select(tau[j], qd[j], jvlim[j]);
+            const float qp = q[j] + dt * qd[j];
+            const bool blo = qp < lo[j], bhi = qp > hi[j], on = lo[j] <= hi[j] && (blo || bhi);
+            const float viol = q[j] - (blo ? lo[j] : hi[j]);
+            lim_u[j] = __builtin_fmaf(viol, -P.limit_stiffness, -prod_rn(qd[j], lim_kl));     // read only where the flag is set; no branch here either
+            lim_lane |= on ? 1u << j : 0u;
+        }
+        lim_wave = __builtin_amdgcn_ballot_w64(lim_lane != 0) != 0;
+    } else if (OFFLOAD) {
 #pragma unroll
         for (int j = 0; j < L; j++) bt_load(bt[j], threadIdx.x % LG_BLOCK, I0[j], p0[j]);
     }
@@ -993,9 +1033,30 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
             for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) { LG_PROF_COUNT(0, cl[i].on); contact_assemble<HF>(cl[i], P, kn, IA, pA); }
             if (j < L - 1) { ai_add(IA, Ia); pA = pA + pa; }
             U[j] = ai_mul_w(IA, ax[j]);
+            float D, u;
+            if constexpr (HELD) {
+                D = __builtin_fmaf(dt, jdamp[j], dot(ax[j], U[j].w) + jarm[j]);
+                u = __builtin_fmaf(-qd[j], jdamp[j], mt[j] - dot(ax[j], pA.w));
+                LG_PROF_COUNT(3, (lim_lane >> j) & 1u);
+                LG_PROF_COUNT(4, vl[j] != 0.0f);
+                if (lim_wave) {       // wave-uniform: no lane of a robot without position limits enters
+                    if (lim_lane & (1u << j)) {
+                        // the rollout kernel read the spring's constants inside the pass and contracted dt kl into the sum; in every
+                        // other kernel they are arguments by value, and hipcc had rounded the product in front of the loop
+                        if constexpr (ROLL) D = __builtin_fmaf(dt, lim_kl, D);
+                        else D = D + prod_rn(dt, lim_kl);
+                        u = u + lim_u[j];
+                    }
+                }
+                if (vl[j] != 0.0f) {  // implicit damper towards +-v_lim (100x the joint's articulated inertia), reaction on the parent
+                    float Bv = 100.0f * D / dt;
+                    u = __builtin_fmaf(-__builtin_fmaf(-vl[j], jvlim[j], qd[j]), Bv, u);
+                    D = __builtin_fmaf(dt, Bv, D);
+                }
+            } else {
             float damp = tj[J_DAMP];
-            float D = dot(ax[j], U[j].w) + tj[J_ARM] + dt * damp;
-            float u = motor_torque(tau[j], qd[j], tj[J_VLIM]) - dot(ax[j], pA.w) - damp * qd[j];
+            D = dot(ax[j], U[j].w) + tj[J_ARM] + dt * damp;
+            u = motor_torque(tau[j], qd[j], tj[J_VLIM]) - dot(ax[j], pA.w) - damp * qd[j];
             float lo = tj[J_LO], hi = tj[J_HI];
             LG_PROF_COUNT(3, lo <= hi && (q[j] + dt * qd[j] < lo || q[j] + dt * qd[j] > hi));
             LG_PROF_COUNT(4, vl[j] != 0.0f);
@@ -1013,6 +1074,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
                 float Bv = 100.0f * D / dt;
                 u += -Bv * (qd[j] - vl[j] * tj[J_VLIM]);
                 D += dt * Bv;
+            }
             }
             Dinv[j] = __builtin_amdgcn_rcpf(D); uu[j] = u;
             Ia = IA;
@@ -1058,7 +1120,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
             a.v = ap.v;
             uu[j] = qdd;
             if (more) {
-                float lim = tab[j * LG_JS + J_VLIM], qn = qd[j] + dt * qdd;
+                float lim = HELD ? jvlim[j] : tab[j * LG_JS + J_VLIM], qn = qd[j] + dt * qdd;
                 if (lim > 0.0f && vl[j] == 0.0f && fabsf(qn) > lim) vl[j] = qn > 0.0f ? 1.0f : -1.0f;
             }
 #pragma unroll
@@ -1072,7 +1134,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
 #pragma unroll
     for (int j = 0; j < L; j++) {
         float v = qd[j] + dt * uu[j];
-        float lim = tab[j * LG_JS + J_VLIM];
+        float lim = HELD ? jvlim[j] : tab[j * LG_JS + J_VLIM];
         if (lim > 0.0f) v = fminf(fmaxf(v, -lim), lim);
         qd[j] = v;
         q[j] += dt * v;

@@ -1,5 +1,5 @@
 import ctypes, os, sys
-ROOT="/root/repo"; sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.realpath(__file__))); sys.path.insert(0, ROOT)
 os.environ["LG_HIP_LIB"] = os.path.join(ROOT, "legged_games_gym_amd", "csrc", "liblegged_hip_prof.so")
 import numpy as np, torch
 from legged_games_gym_amd import capi
