@@ -29,6 +29,8 @@ ROLL, VARIANTS = "tests/test_gpu_rollout_oracle.py", "tests/test_gpu_step_varian
 A1_VARIANTS = f"{VARIANTS}::test_a1_step_variants_against_the_oracle"       # A1 (PD) x plane / height field x SC x NW 4 / 2 / 1
 HF = "tests/test_gpu_hf_contact.py"                                         # designed slopes, risers and map edges, N = 40 (NW = 4)
 HF_STEP, HF_SUBSTEP = f"{HF}::test_step_against_the_oracle", f"{HF}::test_substep_against_the_oracle"
+FALL = "tests/test_gpu_cassie_fall.py"                                      # Cassie through landing, stance, pelvis contact and the in-step reset
+FALL_EVERY, FALL_WAVES = f"{FALL}::test_every_step_of_the_fall_against_the_oracle", f"{FALL}::test_landing_stance_and_fall_with_fewer_helper_waves"
 HF_PHYSICS = [HF_SUBSTEP, f"{HF}::test_kernel_force_direction", f"{HF}::test_rotation_equivalence_on_the_device"]
 
 COVERAGE = {
@@ -44,10 +46,12 @@ COVERAGE = {
     k_step(A, 1, 1, 0, 4, 0): [f"{FULL}::test_config3_anymal_rough_4096_full_terrain", f"{FULL}::test_trimesh_vertical_faces_parity", HF_STEP],
     k_step(A, 1, 1, 0, 4, 1): [f"{VARIANTS}::test_anymal_rough_heightfield_with_self_collision", HF_STEP],
     # biped (cassie), PD control
-    k_step(C, 0, 0, 0, 4, 0): [f"{PARITY}::test_full_step_parity"],
-    k_step(C, 0, 0, 0, 2, 0): [f"{PARITY}::test_step_parity_with_fewer_helper_waves"],
-    k_step(C, 0, 0, 0, 1, 0): [f"{PARITY}::test_step_parity_with_fewer_helper_waves"],
-    **{k_step(C, 0, 1, 0, nw, 0): [f"{FULL}::test_cassie_heightfield_step_parity"] + ([HF_STEP] if nw == 4 else []) for nw in (1, 2, 4)},
+    # (plane: the two tests of test_gpu_parity.py compare the step straight after reset_idx, with the robot in free fall from z = 1; the
+    # fall tests are the ones with ground contact -- toes and pelvis -- a terminating env and a reset inside the step)
+    k_step(C, 0, 0, 0, 4, 0): [f"{PARITY}::test_full_step_parity", FALL_EVERY],
+    k_step(C, 0, 0, 0, 2, 0): [f"{PARITY}::test_step_parity_with_fewer_helper_waves", FALL_WAVES],
+    k_step(C, 0, 0, 0, 1, 0): [f"{PARITY}::test_step_parity_with_fewer_helper_waves", FALL_WAVES],
+    **{k_step(C, 0, 1, 0, nw, 0): [f"{FULL}::test_cassie_heightfield_step_parity"] + ([HF_STEP, FALL_EVERY] if nw == 4 else []) for nw in (1, 2, 4)},
     # one 5 ms rigid-body sub-step (lg_physics_substep)
     k_physics(A, 0, 0): [f"{PARITY}::test_physics_substep_parity"],
     k_physics(A, 0, 1): [f"{PARITY}::test_physics_substep_parity", f"{SELF}::test_substep_parity_with_crossed_legs"],
