@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from tests import wide_learner_check as wl
+from tests.wide_learner_check import loss_tables as _loss_tables, place_ratios_and_value_steps as _place_ratios_and_value_steps
 
 pytestmark = pytest.mark.gpu
 
@@ -85,32 +86,6 @@ def test_wide_kernels_match_float64_autograd_on_the_generic_path(spec, shared, m
         assert all(torch.equal(a, b) for a, b in zip(first, got + list(outs)))
     finally:
         lib.lg_mlp_wide_set_precision(old)
-
-
-def _loss_tables(A, R, g, dev="cuda"):
-    """Storage-like tables of R rows (float32, as RolloutStorage holds them): old_sigma varies per action and is the same in every row."""
-    r = lambda *s: torch.randn(*s, device=dev, generator=g)
-    old_sigma = (0.4 + 1.2 * torch.rand(A, device=dev, generator=g)).expand(R, A).contiguous()
-    old_mu = r(R, A) * 0.2
-    t = dict(old_sigma=old_sigma, old_mu=old_mu, actions=old_mu + old_sigma * r(R, A), adv=r(R, 1), old_val=r(R, 1) * 0.3)
-    t["ret"] = t["old_val"] + 0.5 * r(R, 1)
-    return t
-
-
-def _place_ratios_and_value_steps(t, ix, mu, std, val, g, clip):
-    """old_log_prob / old values of the mini-batch rows, set from the float64 reference's own log-probability and value so that the
-    ratio is uniform on [1 - 2 clip, 1 + 2 clip] and the value step on [-2 clip, 2 clip], nothing within 0.02 of a clip edge (a stored
-    log-probability under ANOTHER sigma would put every row of a 16-action policy far outside the range)."""
-    mb = ix.numel()
-    dist_ = torch.distributions.Normal(mu.double(), mu.double() * 0.0 + std.double())
-    lp = dist_.log_prob(t["actions"][ix].double()).sum(-1)
-    u = wl.spread(g, mb, 1 - 2 * clip, (1 - clip, 1 + clip), 1 + 2 * clip, 0.02, mu.device)
-    dv = wl.spread(g, mb, -2 * clip, (-clip, clip), 2 * clip, 0.02, mu.device)
-    old_lp = torch.zeros(t["adv"].shape[0], 1, device=mu.device)
-    old_lp[ix, 0] = (lp - torch.log(u)).float()
-    t["old_val"][ix, 0] = (val.double().squeeze(-1) - dv).float()
-    t["ret"][ix] = t["old_val"][ix] + 0.5 * torch.randn(mb, 1, device=mu.device, generator=g)
-    t["old_lp"] = old_lp
 
 
 def _lg_ppo_loss(lib, mu, std, val, ix, t, clip, vc, ec, clipped, d_mu, d_val):

@@ -13,13 +13,20 @@ RESOURCES = os.path.join(REPO, "legged_games_gym_amd", "csrc", "kernel_resources
 KERNELS = ("k_gemm_wide", "k_gemm_wide_bf16x3", "k_wide_prep", "k_wide_reduce", "k_wide_out_bwd",
            "k_mlp_chain_fwd64", "k_chain_pack", "k_mlp_train", "k_mlp_reduce", "k_ppo_loss")
 
-RL, WIDE = "tests/test_gpu_rl.py", "tests/test_gpu_wide_learner.py"
+RL, WIDE, FLAT64 = "tests/test_gpu_rl.py", "tests/test_gpu_wide_learner.py", "tests/test_gpu_flat_learner.py"
 ROUGH = f"{RL}::test_wide_mlp_kernels_match_autograd"                      # 235 / 169 inputs, 12 / 1 outputs, mb 24 576 / 1000 / 37, both precisions
 GENERIC = f"{WIDE}::test_wide_kernels_match_float64_autograd_on_the_generic_path"      # game shapes and the shapes around them, both precisions
 STEP = f"{WIDE}::test_composed_minibatch_step_matches_float64_autograd_at_the_game_shape"
 FLAT = f"{RL}::test_mlp_kernels_match_autograd"                            # 48-128-64-32 networks against autograd
 RAGGED = f"{RL}::test_mlp_kernels_ragged_widths_and_a_single_net"
-MINIBATCH = f"{RL}::test_fused_ppo_minibatch_equals_forward_loss_backward"  # in-kernel loss against forward -> lg_ppo_loss -> backward
+# compares two paths of the library (in-kernel loss against forward -> lg_ppo_loss -> backward): the float64 tests below are the reference tests
+MINIBATCH = f"{RL}::test_fused_ppo_minibatch_equals_forward_loss_backward"
+# 48-128-64-32 networks against float64 at the kernels' edges: widths, row-tile schedule and partial counts, gathers with repeated rows
+FLAT_FB = [f"{FLAT64}::test_forward_and_backward_match_float64_over_widths", f"{FLAT64}::test_forward_and_backward_match_float64_over_the_schedule",
+           f"{FLAT64}::test_gather_with_duplicates_and_table_ends"]
+# ... and the build with the PPO loss inside: 1 .. 16 actions, the schedule, ratios far outside the clip range
+FLAT_FUSED = [f"{FLAT64}::test_fused_minibatch_matches_float64_over_action_counts", f"{FLAT64}::test_fused_minibatch_matches_float64_over_the_schedule",
+              f"{FLAT64}::test_fused_minibatch_far_outside_the_clip_range"]
 LOSS = [f"{RL}::test_fused_ppo_loss_matches_autograd", f"{WIDE}::test_ppo_loss_kernel_matches_float64_at_the_games_action_counts", STEP]
 
 
@@ -51,10 +58,10 @@ COVERAGE = {
     "_ZN2lg17k_mlp_chain_fwd64ILi11EEEvNS_9ChainArgsE": [ROUGH],
     "_ZN2lg12k_chain_packENS_13ChainPackArgsE": [ROUGH],
     # LDS-resident trainer of the 48-128-64-32 networks: forward, backward, backward with the PPO loss inside
-    mlp_train(0, 4, 0): [FLAT, RAGGED],
-    mlp_train(1, 2, 0): [FLAT, RAGGED],
-    mlp_train(1, 2, 1): [MINIBATCH],
-    "_ZN2lg12k_mlp_reduceENS_13MlpReduceArgsE": [FLAT, RAGGED, MINIBATCH],
+    mlp_train(0, 4, 0): [FLAT, RAGGED] + FLAT_FB,
+    mlp_train(1, 2, 0): [FLAT, RAGGED] + FLAT_FB,
+    mlp_train(1, 2, 1): [MINIBATCH] + FLAT_FUSED,
+    "_ZN2lg12k_mlp_reduceENS_13MlpReduceArgsE": [FLAT, RAGGED, MINIBATCH] + FLAT_FB + FLAT_FUSED,
     "k_ppo_loss": LOSS,
 }
 
