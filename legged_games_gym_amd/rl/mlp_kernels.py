@@ -16,9 +16,15 @@ def _linears(seq: nn.Sequential) -> List[nn.Linear]:
     return [m for m in seq if isinstance(m, nn.Linear)]
 
 
+def _is_elu_mlp(net: nn.Sequential) -> bool:
+    """Exactly Linear-ELU-Linear-ELU-Linear-ELU-Linear with the default ELU (alpha = 1): what the kernels compute."""
+    return len(net) == 7 and all(isinstance(m, nn.Linear if i % 2 == 0 else nn.ELU) and (i % 2 == 0 or m.alpha == 1.0) for i, m in enumerate(net))
+
+
 class MlpTrainer:
     """Forward / backward of up to two ``nn.Sequential`` MLPs (actor, critic) over a mini-batch of storage rows."""
     has_fused_minibatch = True      # lg_ppo_minibatch: forward + PPO loss + backward in one kernel (48-128-64-32 shape)
+    max_width = None                # widths are checked by the forward probe: only the compiled-in shapes run
 
     def __init__(self, nets: Sequence[nn.Sequential], inputs: Sequence[torch.Tensor], mb: int, forward_only: bool = False):
         self.lib = capi.load_library()
@@ -27,10 +33,8 @@ class MlpTrainer:
         self.inputs = list(inputs)                 # flattened [R, in] row sources (rollout storage views)
         self.mb = int(mb)
         self.layers = [_linears(n) for n in self.nets]
-        # exactly Linear-ELU-Linear-ELU-Linear-ELU-Linear with the default ELU (alpha = 1): what the kernels compute
-        self.supported = all(len(l) == 4 for l in self.layers) and all(
-            len(n) == 7 and all(isinstance(m, nn.Linear if i % 2 == 0 else nn.ELU) and (i % 2 == 0 or m.alpha == 1.0) for i, m in enumerate(n))
-            for n in self.nets)
+        self.supported = all(_is_elu_mlp(n) for n in self.nets) and (
+            self.max_width is None or all(max(m.in_features, m.out_features) <= self.max_width for l in self.layers for m in l))
         if not self.supported:
             return
         dev = self.inputs[0].device
@@ -38,10 +42,15 @@ class MlpTrainer:
         self.grad_outputs = [] if forward_only else [torch.zeros_like(o) for o in self.outputs]
         self.desc = (capi.lg_mlp_net * len(self.nets))()
         self.refresh()
-        need = 0 if forward_only else self.lib.lg_mlp_workspace_bytes(self.desc, len(self.nets))
-        self.workspace = torch.empty(need // 4, device=dev)
-        probe = self.lib.lg_mlp_forward(self.desc, len(self.nets), None, self.mb, torch.cuda.current_stream(dev).cuda_stream)
-        self.supported = probe == 0                # -4: this MLP shape is not built
+        self.workspace = torch.empty(self._workspace_floats(), device=dev)
+        self.supported = self._probe()
+
+    def _workspace_floats(self) -> int:
+        return 0 if self.forward_only else self.lib.lg_mlp_workspace_bytes(self.desc, len(self.nets)) // 4
+
+    def _probe(self) -> bool:
+        """One forward launch: -4 says this MLP shape is not built."""
+        return self.lib.lg_mlp_forward(self.desc, len(self.nets), None, self.mb, torch.cuda.current_stream(self.inputs[0].device).cuda_stream) == 0
 
     def refresh(self):
         """(Re)read parameter / gradient / input addresses into the descriptors; allocates .grad where missing."""
@@ -100,24 +109,13 @@ class WideMlpTrainer(MlpTrainer):
     the workspace, the backward() that follows reads them; there is no single-kernel mini-batch step for these widths
     (``has_fused_minibatch``)."""
     has_fused_minibatch = False
+    max_width = 4096
 
-    def __init__(self, nets: Sequence[nn.Sequential], inputs: Sequence[torch.Tensor], mb: int, forward_only: bool = False):
-        self.lib = capi.load_library()
-        self.forward_only = forward_only
-        self.nets, self.inputs, self.mb = list(nets), list(inputs), int(mb)
-        self.layers = [_linears(n) for n in self.nets]
-        self.supported = all(len(l) == 4 for l in self.layers) and all(
-            len(n) == 7 and all(isinstance(m, nn.Linear if i % 2 == 0 else nn.ELU) and (i % 2 == 0 or m.alpha == 1.0) for i, m in enumerate(n))
-            for n in self.nets) and all(m.out_features <= 4096 and m.in_features <= 4096 for l in self.layers for m in l)
-        if not self.supported:
-            return
-        dev = self.inputs[0].device
-        self.outputs = [torch.empty(self.mb, l[-1].out_features, device=dev) for l in self.layers]
-        self.grad_outputs = [] if forward_only else [torch.zeros_like(o) for o in self.outputs]
-        self.desc = (capi.lg_mlp_net * len(self.nets))()
-        self.refresh()
-        need = self.lib.lg_mlp_wide_workspace_bytes(self.desc, len(self.nets), self.mb)
-        self.workspace = torch.empty(need // 4 + 4, device=dev)
+    def _workspace_floats(self) -> int:                 # (the forward pass needs it too: the activations live there)
+        return self.lib.lg_mlp_wide_workspace_bytes(self.desc, len(self.nets), self.mb) // 4 + 4
+
+    def _probe(self) -> bool:                           # any widths up to max_width run: nothing to probe
+        return True
 
     def _args(self, rows):
         dev = self.inputs[0].device

@@ -12,6 +12,16 @@ def _world():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+def _switch(name):
+    """An ``LG_*`` environment switch: on unless set to "0".  Read by the constructors only: a switch holds for the instance's life."""
+    return os.environ.get(name, "1") != "0"
+
+
+def gaussian_kl(mu, sig, old_mu, old_sig):
+    """KL(old || new) of diagonal Gaussians per row (rsl_rl's expression)."""
+    return torch.sum(torch.log(sig / old_sig + 1.0e-5) + (old_sig.square() + (old_mu - mu).square()) / (2.0 * sig.square()) - 0.5, dim=-1)
+
+
 class RolloutStorage:
     class Transition:
         def __init__(self):
@@ -31,6 +41,7 @@ class RolloutStorage:
         self.actions_log_prob, self.values, self.returns, self.advantages = z(1), z(1), z(1), z(1)
         self.num_transitions_per_env, self.num_envs, self.step = T, N, 0
         self.initial_hidden_a = self.initial_hidden_c = None      # recurrent policy: the state carried INTO the rollout, tuples of [layers, N, H]
+        self._lib = None                                          # the HIP extension, loaded by the first GAE scan on a GPU
 
     def add_transitions(self, t):
         if self.step >= self.num_transitions_per_env:
@@ -55,19 +66,19 @@ class RolloutStorage:
         """Recurrent policy: the (actor, critic) memory states at the first step of the rollout, ``None`` for a memory that has not stepped
         yet (zeros).  Stored once per rollout: every later trajectory of an env starts behind a done, i.e. from zeros, so rsl_rl's
         per-step copies (4 x T x N x H floats) carry nothing these 4 x N x H do not."""
-        for name, hid in zip(("initial_hidden_a", "initial_hidden_c"), hidden_states):
-            old = getattr(self, name)
+        def stored(old, hid):
             if hid is None:
-                if old is not None:
-                    for o in old:
-                        o.zero_()
-                continue
+                for o in old or ():
+                    o.zero_()
+                return old
             hid = hid if isinstance(hid, tuple) else (hid,)
             if old is None or len(old) != len(hid) or any(o.shape != h.shape for o, h in zip(old, hid)):
                 old = tuple(torch.zeros(h.shape, device=self.device) for h in hid)       # (fixed buffers: a captured rollout copies into them)
-                setattr(self, name, old)
             for o, h in zip(old, hid):
                 o.copy_(h)
+            return old
+        hid_a, hid_c = hidden_states
+        self.initial_hidden_a, self.initial_hidden_c = stored(self.initial_hidden_a, hid_a), stored(self.initial_hidden_c, hid_c)
 
     def recurrent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
         """rsl_rl's generator of the same name: mini-batches are contiguous env ranges; every env's rollout is cut behind each done into
@@ -106,9 +117,7 @@ class RolloutStorage:
     def compute_returns(self, last_values, gamma, lam):
         """GAE(gamma, lambda); advantages normalised over the GLOBAL batch: with several ranks
         the fused [returns || advantages] buffer is all-gathered once (RCCL over xGMI)."""
-        if self._gae_kernel(last_values, gamma, lam):
-            pass
-        else:
+        if not self._gae_kernel(last_values, gamma, lam):
             self._gae_torch(last_values, gamma, lam)
         self._normalise_advantages()
 
@@ -116,7 +125,7 @@ class RolloutStorage:
         """One launch of the HIP scan (``lg_gae_returns``) instead of ~6 torch kernels per rollout step; GPU only."""
         if not self.values.is_cuda:
             return False
-        if getattr(self, "_lib", None) is None:
+        if self._lib is None:
             from .. import capi
             self._lib = capi.load_library()        # on a GPU the extension is the product path: a missing build fails loudly here
         T, N = self.num_transitions_per_env, self.num_envs
@@ -158,20 +167,24 @@ class RolloutStorage:
         lens = idx[1:] - idx[:-1]
         return lens.float().mean(), self.rewards.mean()
 
+    def flat_views(self):
+        """The stored rollout as [T * N, .] views, in the order the mini-batch tuples use: obs, critic obs (the SAME view as obs when no
+        privileged observations are stored), actions, values, advantages, returns, log-probabilities, mu, sigma."""
+        obs = self.observations.flatten(0, 1)
+        cobs = self.privileged_observations.flatten(0, 1) if self.privileged_observations is not None else obs
+        return (obs, cobs, self.actions.flatten(0, 1), self.values.flatten(0, 1), self.advantages.flatten(0, 1), self.returns.flatten(0, 1),
+                self.actions_log_prob.flatten(0, 1), self.mu.flatten(0, 1), self.sigma.flatten(0, 1))
+
     def mini_batch_generator(self, num_mini_batches, num_epochs=8, perm=None):
         B = self.num_envs * self.num_transitions_per_env
         mb = B // num_mini_batches
         if perm is None:
             perm = torch.randperm(num_mini_batches * mb, requires_grad=False, device=self.device)
-        obs = self.observations.flatten(0, 1)
-        cobs = self.privileged_observations.flatten(0, 1) if self.privileged_observations is not None else obs
-        act, val, ret = self.actions.flatten(0, 1), self.values.flatten(0, 1), self.returns.flatten(0, 1)
-        lp, adv = self.actions_log_prob.flatten(0, 1), self.advantages.flatten(0, 1)
-        mu, sig = self.mu.flatten(0, 1), self.sigma.flatten(0, 1)
+        flat = self.flat_views()
         for _ in range(num_epochs):
             for i in range(num_mini_batches):
                 ix = perm[i * mb:(i + 1) * mb]
-                yield obs[ix], cobs[ix], act[ix], val[ix], adv[ix], ret[ix], lp[ix], mu[ix], sig[ix], (None, None), None
+                yield (*(t[ix] for t in flat), (None, None), None)
 
 
 class _LinearSplitK(torch.autograd.Function):
@@ -206,6 +219,10 @@ def _mlp_split_k(seq, x):
 
 
 class PPO:
+    """The ``LG_PPO_*`` switches and ``LG_DP_GRAPHS`` are read once, by the constructor: they hold per instance, so set them before
+    constructing ``PPO`` (``LG_DP_GRAPHS=0``: the data-parallel kernel update keeps its eager launches -- A/B, and what a refused capture
+    falls back to).  The structure of the device update is described in DESIGN.md ("The update's driver")."""
+
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
                  use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", graphed_update=True, fused_loss=True):
@@ -214,26 +231,37 @@ class PPO:
         # the adaptive-KL learning rate all on the device): the flat networks' update is launch-bound (~150 tiny kernels).
         # (a recurrent policy is updated by the eager loop of update(): back-propagation through time is autograd's)
         self._graph_ok = bool(graphed_update) and str(device).startswith("cuda") and not getattr(actor_critic, "is_recurrent", False)
-        self._graph, self._graph_key, self._graph_whole = None, None, False
-        self._updates_done = 0
         # ... and the surrogate / value / entropy losses with their gradients w.r.t. the network outputs come from ONE HIP kernel
         # (``lg_ppo_loss``) instead of ~100 small torch kernels; autograd only runs through the two MLPs.
-        import os as _os
-        self._fused_loss = bool(fused_loss) and self._graph_ok and _os.environ.get("LG_PPO_FUSED_LOSS", "1") != "0"
+        self._fused_loss = bool(fused_loss) and self._graph_ok and _switch("LG_PPO_FUSED_LOSS")
         # ... and for the MLP shape of the flat tasks the two networks' forward and backward run in the MFMA learner kernels
         # (lg_mlp_forward / lg_mlp_backward, rl/mlp_kernels.py): autograd is not involved at all.  LG_PPO_MLP_KERNELS=0 disables.
-        self._mlp_kernels = self._fused_loss and _os.environ.get("LG_PPO_MLP_KERNELS", "1") != "0"
-        self._mlp = None
+        self._mlp_kernels = self._fused_loss and _switch("LG_PPO_MLP_KERNELS")
         # ... and gradient clipping, the adaptive-KL learning-rate rule and Adam are two launches (lg_adam_step) instead of ~60
         # small torch kernels, updating torch.optim.Adam's own state tensors in place.  LG_PPO_ADAM_KERNEL=0 disables.
-        self._adam_kernel = self._fused_loss and _os.environ.get("LG_PPO_ADAM_KERNEL", "1") != "0"
-        self._fused_minibatch = _os.environ.get("LG_PPO_FUSED_MINIBATCH", "1") != "0"   # lg_ppo_minibatch instead of forward / loss / backward
-        self._wide_kernels = _os.environ.get("LG_PPO_WIDE_KERNELS", "1") != "0"         # lg_mlp_wide_* for widths the LDS-resident kernels do not cover
-        self._split_k = _os.environ.get("LG_PPO_SPLIT_K", "1") != "0"       # torch MLP path (wide networks): see _LinearSplitK
+        self._adam_kernel = self._fused_loss and _switch("LG_PPO_ADAM_KERNEL")
+        self._fused_minibatch = _switch("LG_PPO_FUSED_MINIBATCH")     # lg_ppo_minibatch instead of forward / loss / backward
+        self._wide_kernels = _switch("LG_PPO_WIDE_KERNELS")           # lg_mlp_wide_* for widths the LDS-resident kernels do not cover
+        self._split_k = _switch("LG_PPO_SPLIT_K")                     # torch MLP path (wide networks): see _LinearSplitK
+        self._dp_graphs_wanted = _switch("LG_DP_GRAPHS")              # world_size > 1: capture the two halves around the all-reduce
+        # What is captured over fixed addresses (_drop_captured lets go of all of it, and nothing else does):
+        self._graph, self._graph_whole = None, False     # one process: the update graph; whole = epochs x mini-batches in ONE graph
+        self._dp_graphs = None                           # several: ([pre graph per mini-batch slot], post graph); False = capture refused
+        self._mlp, self._mlp_key = None, None            # MlpTrainer (descriptors hold parameter / .grad / storage addresses)
+        self._dp_key = None                        # _capture_key() of the last update
+        self._updates_done = 0                           # 0: the next update is the eager warm-up, >= 1: capture may happen
+        self._dp_graph_error = "not attempted (LG_DP_GRAPHS=0 or the torch MLP path)"      # why the two graphs are not in use; None: they are
+        self.dp_launches = None
+        # Device buffers of an update (_ensure_buffers) and the flat gradient buffer of the data-parallel kernel path (_flat_grad_views):
+        self._buffers_key = None
+        self._perm_buf = self._ix_one = self._acc = self._stats = self._d_std = self._d_mu = self._d_val = None
+        self._adam_scratch = self._gstream = None
+        self._gflat, self._goffs = None, None
         self._lib = None
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.actor_critic = actor_critic.to(device)
         self.storage = None
+        self._prime = self._lr = None
         if self._graph_ok:
             # The CUDA generator allocates its graph-safe state tensors at the first capture in the process; if that happens
             # under torch.inference_mode (the rollout graph, rl/runner.py) they become inference tensors and a later capture
@@ -299,17 +327,58 @@ class PPO:
             ac.memory_c.hidden_states = carried
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
-    def _allreduce_grads(self):
-        if _world() == 1:
-            return
-        grads = [p.grad for p in self.actor_critic.parameters() if p.grad is not None]
-        flat = torch.cat([g.flatten() for g in grads])
-        dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-        flat /= _world()
-        o = 0
-        for g in grads:
-            g.copy_(flat[o:o + g.numel()].view_as(g))
-            o += g.numel()
+    # ------------------------------------------------------------------ one body per formula
+    @property
+    def _adaptive(self):
+        return self.desired_kl is not None and self.schedule == "adaptive"
+
+    def _loss(self, lp, old_lp, adv, val, tval, ret, entropy):
+        """(total loss, clipped surrogate, value loss) of a mini-batch; ``old_lp`` / ``adv`` arrive squeezed to the shape of ``lp``."""
+        ratio = torch.exp(lp - old_lp)
+        surrogate = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
+        if self.use_clipped_value_loss:
+            vclip = tval + (val - tval).clamp(-self.clip_param, self.clip_param)
+            vloss = torch.max((val - ret).pow(2), (vclip - ret).pow(2)).mean()
+        else:
+            vloss = (ret - val).pow(2).mean()
+        return surrogate + self.value_loss_coef * vloss - self.entropy_coef * entropy.mean(), surrogate, vloss
+
+    @torch.no_grad()
+    def _kl_rule(self, kl):
+        """The adaptive-KL rule on the DEVICE learning rate (no host decision: capturable).  The eager loop of update() applies the same
+        rule to Python floats and ``param_groups``: another mechanism, kept there."""
+        lr = self._lr
+        down, up = torch.clamp(lr / 1.5, min=1e-5), torch.clamp(lr * 1.5, max=1e-2)
+        self._lr.copy_(torch.where(kl > self.desired_kl * 2.0, down, torch.where((kl < self.desired_kl / 2.0) & (kl > 0.0), up, lr)))
+
+    def _loss_inputs(self):
+        """The seven storage tables and four coefficients of lg_ppo_loss and of struct lg_ppo_batch, in the order both take them."""
+        st, p = self.storage, lambda t: t.data_ptr()
+        return ((p(st.actions), p(st.actions_log_prob), p(st.mu), p(st.sigma), p(st.advantages), p(st.values), p(st.returns)),
+                (float(self.clip_param), float(self.value_loss_coef), float(self.entropy_coef), int(bool(self.use_clipped_value_loss))))
+
+    # ------------------------------------------------------------------ device state: buffers, flat gradients, what is captured
+    def _ensure_buffers(self, mb, nmb, num_actions):
+        """The device buffers an update works in, allocated together and again only when a size changes; True when that happened."""
+        key = (mb, nmb, num_actions)
+        if key == self._buffers_key:
+            return False
+        dev = self.device
+        # mini-batch i reads rows _perm_buf[i*mb : (i+1)*mb]: fixed addresses, so captured kernels need no index copies
+        self._perm_buf = torch.zeros(nmb * mb, dtype=torch.int64, device=dev)
+        self._ix_one = torch.zeros(mb, dtype=torch.int64, device=dev)          # row list of the one-step graph
+        self._acc = torch.zeros(2, device=dev)                                 # running sums of (value loss, surrogate) over the update
+        self._stats = torch.zeros(4, device=dev)                               # a step's (surrogate, value loss, KL, entropy)
+        # d loss / d (std, mu, value) from lg_ppo_loss.  _d_std is owned here; _flat_grad_views re-points it into the flat buffer.
+        self._d_std = torch.zeros(num_actions, device=dev)
+        self._d_mu, self._d_val = torch.empty(mb, num_actions, device=dev), torch.empty(mb, 1, device=dev)
+        if self._adam_kernel and self._adam_scratch is None:
+            from .. import capi
+            self._adam_scratch = torch.zeros(capi.LG_ADAM_SCRATCH_FLOATS, device=dev)
+        if self._gstream is None:
+            self._gstream = torch.cuda.Stream(device=dev)                      # warm-up and capture run on it
+        self._buffers_key = key
+        return True
 
     def _flat_grad_views(self):
         """Data-parallel kernel path: every parameter's ``.grad`` (and the policy-std gradient the loss kernel writes) becomes a
@@ -318,7 +387,7 @@ class PPO:
         n_params + 1 floats instead of a concatenation, an all-reduce, a scalar all-reduce and 17 copies back)."""
         params = list(self.actor_critic.parameters())
         n = sum(p.numel() for p in params)
-        buf = getattr(self, "_gflat", None)
+        buf = self._gflat
         if buf is None or buf.numel() != n + 1 or any(p.grad is None or p.grad.data_ptr() != buf[o].data_ptr() for p, o in zip(params, self._goffs)):
             buf = torch.zeros(n + 1, device=self.device)
             offs, o = [], 0
@@ -329,48 +398,40 @@ class PPO:
                 offs.append(o)
                 o += p.numel()
             self._gflat, self._goffs = buf, offs
-            std = self.actor_critic.std
-            self._d_std = std.grad                      # the loss kernels write d loss / d std here
-            self._mlp = None                            # descriptors hold the old .grad addresses
-            self._dp_graphs, self._dp_key = None, None  # ... and so do the captured data-parallel graphs
+            self._drop_captured(warm_up_again=False)     # descriptors and graphs hold the old .grad addresses
+        # The one writer of _d_std besides _ensure_buffers: on this path the loss kernels write d loss / d std into the buffer's std slot
+        # (on every call: _ensure_buffers hands out a fresh tensor when the storage changes size, the slot stays).
+        self._d_std = self.actor_critic.std.grad
         return self._gflat
 
-    def _allreduce_flat(self, adaptive):
-        """One collective per mini-batch step: mean gradient and (adaptive schedule) mean KL over the ranks."""
-        flat = self._gflat
-        if adaptive:
-            flat[-1:].copy_(self._stats[2:3])
-        dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-        flat.mul_(1.0 / _world())
-        if adaptive:
-            self._stats[2:3].copy_(flat[-1:])
-
-    def after_optimizer_load(self):
-        """The optimiser's tensors were replaced (checkpoint resume): re-link the device learning rate, drop the captured graphs
-        (the single-process update graph and the data-parallel "pre" / "post" graphs: their Adam launches hold the old state addresses)."""
-        if self._graph_ok:
-            for g in self.optimizer.param_groups:
-                self._lr.copy_(torch.as_tensor(g["lr"], device=self.device).float().reshape(()))
-                g["lr"] = self._lr
-            self._graph, self._updates_done = None, 0
-            self._dp_graphs, self._dp_key = None, None
-
     def _dp_state_key(self):
-        """Addresses the captured data-parallel graphs bake in besides the storage's: Adam's state tensors and the flat gradient buffer."""
+        """Addresses a captured update bakes in besides the storage's: Adam's state tensors and the flat gradient buffer."""
         ptrs = []
         for q in self.actor_critic.parameters():
             stt = self.optimizer.state.get(q) or {}
             ptrs += [stt[k].data_ptr() if torch.is_tensor(stt.get(k)) else 0 for k in ("exp_avg", "exp_avg_sq", "step")]
-        flat = getattr(self, "_gflat", None)
-        return tuple(ptrs) + (flat.data_ptr() if flat is not None else 0,)
+        return tuple(ptrs) + (self._gflat.data_ptr() if self._gflat is not None else 0,)
 
-    # ------------------------------------------------------------------ captured mini-batch step
-    def _flat(self):
+    def _capture_key(self, mb):
+        """The one key of everything captured: the storage's addresses, the mini-batch size and ``_dp_state_key``."""
         st = self.storage
-        obs = st.observations.flatten(0, 1)
-        cobs = st.privileged_observations.flatten(0, 1) if st.privileged_observations is not None else obs
-        return (obs, cobs, st.actions.flatten(0, 1), st.values.flatten(0, 1), st.advantages.flatten(0, 1), st.returns.flatten(0, 1),
-                st.actions_log_prob.flatten(0, 1), st.mu.flatten(0, 1), st.sigma.flatten(0, 1))
+        return (st.observations.data_ptr(), st.advantages.data_ptr(), st.returns.data_ptr(), mb) + self._dp_state_key()
+
+    def _drop_captured(self, warm_up_again):
+        """THE invalidation point: everything captured over addresses that are no longer the live ones goes -- both kinds of graphs, their
+        key, the MlpTrainer's descriptors.  ``warm_up_again``: the next update runs eagerly first (it re-creates what a capture must not)."""
+        self._graph, self._graph_whole, self._dp_graphs, self._dp_key, self._mlp = None, False, None, None, None
+        if warm_up_again:
+            self._updates_done = 0
+
+    def after_optimizer_load(self):
+        """The optimiser's tensors were replaced (checkpoint resume): re-link the device learning rate and drop what was captured
+        (the Adam launches of the graphs hold the old state addresses)."""
+        if self._graph_ok:
+            for g in self.optimizer.param_groups:
+                self._lr.copy_(torch.as_tensor(g["lr"], device=self.device).float().reshape(()))
+                g["lr"] = self._lr
+            self._drop_captured(warm_up_again=True)
 
     def _fused_ready(self):
         if not self._fused_loss:
@@ -381,27 +442,22 @@ class PPO:
         ac = self.actor_critic
         return bool(self._lib) and hasattr(ac, "actor") and hasattr(ac, "critic") and hasattr(ac, "std") and ac.std.numel() <= 16
 
-    def _mlp_trainer(self):
+    def _mlp_trainer(self, mb):
         """MlpTrainer for the current storage / mini-batch size, or None when the networks are not the kernels' shape."""
         if not self._mlp_kernels:
             return None
-        st, ac = self.storage, self.actor_critic
-        obs = st.observations.flatten(0, 1)
-        cobs = st.privileged_observations.flatten(0, 1) if st.privileged_observations is not None else obs
-        mb = self._ix.numel()
+        ac = self.actor_critic
+        obs, cobs = self.storage.flat_views()[:2]
         key = (obs.data_ptr(), cobs.data_ptr(), mb)
         if self._mlp is None or self._mlp_key != key:
-            from .mlp_kernels import MlpTrainer
-            if not (isinstance(ac.actor, nn.Sequential) and isinstance(ac.critic, nn.Sequential)):
-                self._mlp_kernels = False
-                return None
-            self._mlp, self._mlp_key = MlpTrainer([ac.actor, ac.critic], [obs, cobs], mb), key
-            if not self._mlp.supported:                  # not the LDS-resident shape: the layer-wise GEMM kernels take any widths
-                from .mlp_kernels import WideMlpTrainer
-                self._mlp = WideMlpTrainer([ac.actor, ac.critic], [obs, cobs], mb) if self._wide_kernels else None
-            if self._mlp is None or not self._mlp.supported:
-                self._mlp_kernels, self._mlp = False, None
-                return None
+            from .mlp_kernels import MlpTrainer, WideMlpTrainer
+            nets, tr = [ac.actor, ac.critic], None
+            if all(isinstance(n, nn.Sequential) for n in nets):
+                tr = MlpTrainer(nets, [obs, cobs], mb)
+                if not tr.supported and self._wide_kernels:      # not the LDS-resident shape: the layer-wise GEMM kernels take any widths
+                    tr = WideMlpTrainer(nets, [obs, cobs], mb)
+            self._mlp, self._mlp_key = (tr if tr is not None and tr.supported else None), key
+            self._mlp_kernels = self._mlp is not None            # no kernels for these networks: the torch MLP path from here on
         return self._mlp
 
     def _adam_table(self):
@@ -426,101 +482,81 @@ class PPO:
             t = table[i]
             t.param, t.grad, t.exp_avg, t.exp_avg_sq = q.data_ptr(), q.grad.data_ptr(), stt["exp_avg"].data_ptr(), stt["exp_avg_sq"].data_ptr()
             t.step, t.numel = stt["step"].data_ptr(), q.numel()
-        if getattr(self, "_adam_scratch", None) is None:
-            self._adam_scratch = torch.zeros(capi.LG_ADAM_SCRATCH_FLOATS, device=self.device)
         return table
 
-    def _mb_forward_loss_backward(self, tr):
-        """MLP forward -> lg_ppo_loss -> MLP backward as separate launches (learner kernels when ``tr`` is given, torch otherwise)."""
-        st, ac, ix = self.storage, self.actor_critic, self._ix
-        if tr is not None:
-            tr.refresh()                             # parameter / .grad addresses (stable in steady state)
-            mu, val = tr.forward(ix)
-        else:
-            obs_all = st.observations.flatten(0, 1)
-            obs = obs_all[ix]
-            cobs = st.privileged_observations.flatten(0, 1)[ix] if st.privileged_observations is not None else obs
-            if self._split_k and isinstance(ac.actor, nn.Sequential) and isinstance(ac.critic, nn.Sequential):
-                mu, val = _mlp_split_k(ac.actor, obs), _mlp_split_k(ac.critic, cobs)
-            else:
-                mu, val = ac.actor(obs), ac.critic(cobs)
-        mb, A = mu.shape
-        if getattr(self, "_d_mu", None) is None or self._d_mu.shape != mu.shape:
-            self._d_mu, self._d_val = torch.empty_like(mu), torch.empty(mb, 1, device=mu.device)
-            if getattr(self, "_d_std", None) is None or self._d_std.numel() != A:
-                self._d_std = torch.zeros(A, device=mu.device)
-            if getattr(self, "_stats", None) is None:
-                self._stats = torch.zeros(4, device=mu.device)
-        d_mu, d_val = (tr.grad_outputs if tr is not None else (self._d_mu, self._d_val))
-        p = lambda t: t.data_ptr()
-        rc = self._lib.lg_ppo_loss(p(mu), p(ac.std), p(val), p(ix), p(st.actions), p(st.actions_log_prob), p(st.mu), p(st.sigma), p(st.advantages),
-                                   p(st.values), p(st.returns), float(self.clip_param), float(self.value_loss_coef), float(self.entropy_coef),
-                                   int(bool(self.use_clipped_value_loss)), p(d_mu), p(self._d_std), p(d_val), p(self._stats), int(mb), int(A),
-                                   torch.cuda.current_stream(mu.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"lg_ppo_loss failed ({rc}): {self._lib.lg_last_error().decode()}")
-        if tr is not None:
-            tr.backward(ix)
-        else:
-            torch.autograd.backward([mu, val], [d_mu, d_val])
-
-    def _mb_step_fused(self, phase=None):
-        """Mini-batch step on the device kernels: [MLP forward -> PPO loss -> MLP backward] -> gradient clip + KL rule + Adam.
-        The bracket is ONE kernel (lg_ppo_minibatch) when the networks have the learner kernels' shape; otherwise torch MLP
-        passes (autograd) around lg_ppo_loss.  ``phase`` (data-parallel kernel path): "pre" = everything in front of the flat
-        all-reduce, "post" = everything behind it -- the two halves are captured as HIP graphs around the eager collective."""
-        st, ac, ix = self.storage, self.actor_critic, self._ix
-        if phase == "post":
-            return self._mb_step_fused_post(self.desired_kl is not None and self.schedule == "adaptive", self._dp_acc_done, True)
-        flat_dp = _world() > 1 and self._mlp_kernels
-        if flat_dp:
+    # ------------------------------------------------------------------ the mini-batch step, in three parts
+    def _gradients(self, ix):
+        """Part 1: MLP forward -> PPO loss -> MLP backward on the rows ``ix``.  ONE kernel (lg_ppo_minibatch) when the networks have the
+        learner kernels' shape; otherwise wide learner kernels or torch MLP passes (autograd) around lg_ppo_loss.  Returns (flat, acc_done):
+        the gradients lie in the data-parallel flat buffer (its last slot then carries the KL) / the kernel already summed the losses."""
+        st, ac = self.storage, self.actor_critic
+        if _world() > 1 and self._mlp_kernels:
             self._flat_grad_views()                  # .grad tensors = views of one buffer (before the descriptors read their addresses)
-        tr = self._mlp_trainer()
-        flat_dp = flat_dp and tr is not None         # (torch MLP path: autograd allocates its own .grad tensors)
+        tr = self._mlp_trainer(ix.numel())
+        flat = _world() > 1 and tr is not None       # (torch MLP path: autograd allocates its own .grad tensors)
         p = lambda t: t.data_ptr()
-        if tr is not None and self._fused_minibatch and tr.has_fused_minibatch:
-            # forward + loss + backward of both networks in ONE kernel (lg_ppo_minibatch): mu / value never reach HBM
-            mb, A = ix.numel(), ac.std.numel()
-            if getattr(self, "_d_std", None) is None or self._d_std.numel() != A:
-                self._d_std = torch.zeros(A, device=self.device)
-            if getattr(self, "_stats", None) is None:
-                self._stats = torch.zeros(4, device=self.device)
+        tables, coefs = self._loss_inputs()
+        acc_done = tr is not None and self._fused_minibatch and tr.has_fused_minibatch
+        if acc_done:
+            # forward + loss + backward of both networks in ONE kernel: mu / value never reach HBM, and it keeps the running loss sums
             tr.refresh()
             from .. import capi
-            b = capi.lg_ppo_batch()
-            b.actions, b.old_log_prob, b.old_mu, b.old_sigma = p(st.actions), p(st.actions_log_prob), p(st.mu), p(st.sigma)
-            b.advantages, b.old_values, b.returns, b.std = p(st.advantages), p(st.values), p(st.returns), p(ac.std)
-            b.clip, b.value_coef, b.entropy_coef = float(self.clip_param), float(self.value_loss_coef), float(self.entropy_coef)
-            b.use_clipped_value, b.d_std, b.stats = int(bool(self.use_clipped_value_loss)), p(self._d_std), p(self._stats)
-            b.loss_acc = p(self._acc)                # the kernel also keeps the update's running loss sums
-            tr.ppo_minibatch(ix, b)
-            acc_done = True
+            tr.ppo_minibatch(ix, capi.lg_ppo_batch(*tables, p(ac.std), *coefs, p(self._d_std), p(self._stats), p(self._acc)))
         else:
-            self._mb_forward_loss_backward(tr)
-            acc_done = False
+            if tr is not None:
+                tr.refresh()                         # parameter / .grad addresses (stable in steady state)
+                mu, val = tr.forward(ix)
+                d_mu, d_val = tr.grad_outputs
+            else:
+                obs_all, cobs_all = st.flat_views()[:2]
+                obs = obs_all[ix]
+                cobs = obs if cobs_all is obs_all else cobs_all[ix]
+                if self._split_k and isinstance(ac.actor, nn.Sequential) and isinstance(ac.critic, nn.Sequential):
+                    mu, val = _mlp_split_k(ac.actor, obs), _mlp_split_k(ac.critic, cobs)
+                else:
+                    mu, val = ac.actor(obs), ac.critic(cobs)
+                d_mu, d_val = self._d_mu, self._d_val
+            mb, A = mu.shape
+            rc = self._lib.lg_ppo_loss(p(mu), p(ac.std), p(val), p(ix), *tables, *coefs, p(d_mu), p(self._d_std), p(d_val), p(self._stats),
+                                       int(mb), int(A), torch.cuda.current_stream(mu.device).cuda_stream)
+            if rc != 0:
+                raise RuntimeError(f"lg_ppo_loss failed ({rc}): {self._lib.lg_last_error().decode()}")
+            if tr is not None:
+                tr.backward(ix)
+            else:
+                torch.autograd.backward([mu, val], [d_mu, d_val])
         ac.std.grad = self._d_std
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        if phase == "pre":
-            if not flat_dp:
-                raise RuntimeError("the two-graph data-parallel step needs the flat-gradient kernel path")
-            self._dp_acc_done = acc_done
-            if adaptive:
-                self._gflat[-1:].copy_(self._stats[2:3])
-            return
-        if flat_dp:                                  # data-parallel ranks: mean gradient and mean KL (rollout shards are equal-sized), ONE collective
-            self._allreduce_flat(adaptive)
+        if flat and self._adaptive:
+            self._gflat[-1:].copy_(self._stats[2:3])
+        return flat, acc_done
+
+    def _collective(self, flat):
+        """Part 2: sum over the ranks -- ONE all-reduce of the flat buffer (gradients + KL slot; ``_optimise`` takes the mean), or the
+        concatenate / all-reduce / copy-back of autograd's ``.grad`` tensors and a scalar all-reduce of the KL."""
+        if flat:
+            dist.all_reduce(self._gflat, op=dist.ReduceOp.SUM)
         elif _world() > 1:
             self._allreduce_grads()
-            if adaptive:
+            if self._adaptive:
                 dist.all_reduce(self._stats[2:3], op=dist.ReduceOp.SUM)
                 self._stats[2:3] /= _world()
-        self._mb_step_fused_post(adaptive, acc_done, False)
 
-    def _mb_step_fused_post(self, adaptive, acc_done, after_collective):
-        """Behind the gradients (and the collective): [mean over ranks] -> gradient clip + KL rule + Adam."""
-        ac = self.actor_critic
-        p = lambda t: t.data_ptr()
-        if after_collective:                         # the eager all-reduce summed the flat buffer (gradients + KL slot)
+    def _allreduce_grads(self):
+        if _world() == 1:
+            return
+        grads = [p.grad for p in self.actor_critic.parameters() if p.grad is not None]
+        flat = torch.cat([g.flatten() for g in grads])
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+        flat /= _world()
+        o = 0
+        for g in grads:
+            g.copy_(flat[o:o + g.numel()].view_as(g))
+            o += g.numel()
+
+    def _optimise(self, flat, acc_done):
+        """Part 3: [mean over the ranks of the all-reduced flat buffer] -> gradient clip + KL rule + Adam -> running loss sums."""
+        adaptive, p = self._adaptive, lambda t: t.data_ptr()
+        if flat:
             self._gflat.mul_(1.0 / _world())
             if adaptive:
                 self._stats[2:3].copy_(self._gflat[-1:])
@@ -535,48 +571,26 @@ class PPO:
                 raise RuntimeError(f"lg_adam_step failed ({rc}): {self._lib.lg_last_error().decode()}")
         else:
             if adaptive:
-                with torch.no_grad():
-                    kl, lr = self._stats[2], self._lr
-                    down, up = torch.clamp(lr / 1.5, min=1e-5), torch.clamp(lr * 1.5, max=1e-2)
-                    self._lr.copy_(torch.where(kl > self.desired_kl * 2.0, down, torch.where((kl < self.desired_kl / 2.0) & (kl > 0.0), up, lr)))
-            nn.utils.clip_grad_norm_(ac.parameters(), self.max_grad_norm)
+                self._kl_rule(self._stats[2])
+            nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
             self.optimizer.step()
         if not acc_done:
             with torch.no_grad():
                 self._acc[0] += self._stats[1]
                 self._acc[1] += self._stats[0]
 
-    def _zero_grad(self):
-        # the learner kernels overwrite persistent .grad tensors (their addresses are baked into the captured graph)
-        if not (self._mlp_kernels and self._mlp is not None):
-            self.optimizer.zero_grad(set_to_none=True)
-
-    def _mb_step(self):
-        """One mini-batch step on the rows listed in ``self._ix``; everything stays on the device (no host decisions)."""
-        if self._fused_ready():
-            return self._mb_step_fused()
-        ix = self._ix
-        obs, cobs, act, tval, adv, ret, old_lp, old_mu, old_sig = (t[ix] for t in self._flat())
+    def _mb_step_torch(self, ix):
+        """The step without the loss kernel (``fused_loss=False``; one process): torch's loss and autograd, still without host decisions."""
+        obs, cobs, act, tval, adv, ret, old_lp, old_mu, old_sig = (t[ix] for t in self.storage.flat_views())
         ac = self.actor_critic
         ac.update_distribution(obs)
         lp = ac.get_actions_log_prob(act)
         val = ac.evaluate(cobs)
         mu, sig, ent = ac.action_mean, ac.action_std, ac.entropy
-        if self.desired_kl is not None and self.schedule == "adaptive":
+        if self._adaptive:
             with torch.no_grad():
-                kl = torch.sum(torch.log(sig / old_sig + 1.0e-5) + (old_sig.square() + (old_mu - mu).square()) / (2.0 * sig.square()) - 0.5, dim=-1).mean()
-                lr = self._lr
-                down, up = torch.clamp(lr / 1.5, min=1e-5), torch.clamp(lr * 1.5, max=1e-2)
-                self._lr.copy_(torch.where(kl > self.desired_kl * 2.0, down, torch.where((kl < self.desired_kl / 2.0) & (kl > 0.0), up, lr)))
-        ratio = torch.exp(lp - torch.squeeze(old_lp))
-        a = torch.squeeze(adv)
-        surrogate = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
-        if self.use_clipped_value_loss:
-            vclip = tval + (val - tval).clamp(-self.clip_param, self.clip_param)
-            vloss = torch.max((val - ret).pow(2), (vclip - ret).pow(2)).mean()
-        else:
-            vloss = (ret - val).pow(2).mean()
-        loss = surrogate + self.value_loss_coef * vloss - self.entropy_coef * ent.mean()
+                self._kl_rule(gaussian_kl(mu, sig, old_mu, old_sig).mean())
+        loss, surrogate, vloss = self._loss(lp, torch.squeeze(old_lp), torch.squeeze(adv), val, tval, ret, ent)
         loss.backward()
         nn.utils.clip_grad_norm_(self.actor_critic.parameters(), self.max_grad_norm)
         self.optimizer.step()
@@ -584,156 +598,135 @@ class PPO:
             self._acc[0] += vloss.detach()
             self._acc[1] += surrogate.detach()
 
-    def _update_graphed(self, perm=None):
-        st = self.storage
-        B = st.num_envs * st.num_transitions_per_env
-        mb = B // self.num_mini_batches
-        key = (st.observations.data_ptr(), st.advantages.data_ptr(), st.returns.data_ptr(), mb)
-        if self._graph is not None and key != self._graph_key:
-            # the storage was re-allocated: the captured graph reads the old buffers; warm up eagerly again before re-capturing
-            self._graph, self._mlp, self._updates_done = None, None, 0
-        self._graph_key = key
-        if self._graph is None and (getattr(self, "_perm_buf", None) is None or self._perm_buf.numel() != self.num_mini_batches * mb):
-            # mini-batch i reads rows _perm_buf[i*mb : (i+1)*mb]: fixed addresses, so captured kernels need no index copies
-            self._perm_buf = torch.zeros(self.num_mini_batches * mb, dtype=torch.int64, device=self.device)
-            self._ix_one = torch.zeros(mb, dtype=torch.int64, device=self.device)      # row list of the one-step graph
-            self._ix = self._ix_one
-            self._acc = torch.zeros(2, device=self.device)
+    def _mb_step(self, ix):
+        """One mini-batch step on the rows ``ix``; everything stays on the device (no host decisions)."""
+        if not self._fused_ready():
+            return self._mb_step_torch(ix)
+        flat, acc_done = self._gradients(ix)
+        self._collective(flat)
+        self._optimise(flat, acc_done)
+
+    def _zero_grad(self):
+        # the learner kernels overwrite persistent .grad tensors (their addresses are baked into the captured graph)
+        if not (self._mlp_kernels and self._mlp is not None):
+            self.optimizer.zero_grad(set_to_none=True)
+
+    # ------------------------------------------------------------------ the schedule of a device update
+    def _begin_update(self, perm):
+        """Buffers, the check of what was captured, accumulator reset, permutation copy; returns each mini-batch's rows (views of ``_perm_buf``)."""
+        st, nmb = self.storage, self.num_mini_batches
+        mb = st.num_envs * st.num_transitions_per_env // nmb
+        resized = self._ensure_buffers(mb, nmb, st.actions.shape[-1])
+        key = self._capture_key(mb)
+        if (resized or key != self._dp_key) and (self._graph is not None or self._dp_graphs is not None):
+            # Captured over other addresses (the storage was re-allocated).  One process warms up eagerly again before re-capturing;
+            # the data-parallel capture prepares its trainer outside the graphs and captures again in this update.
+            # (a key that changes while nothing is captured -- Adam's state appears during update 0 -- restarts nothing)
+            self._drop_captured(warm_up_again=_world() == 1)
+        self._dp_key = key
         self._acc.zero_()
-        # The first update runs eagerly ON THE CAPTURE STREAM: it is the warm-up torch asks for before capturing autograd +
-        # optimiser work (library handles / workspaces and the optimiser state get created on that stream, outside capture).
-        if self._graph is None and not hasattr(self, "_gstream"):
-            self._gstream = torch.cuda.Stream(device=self.device)
-        cur = torch.cuda.current_stream(self.device)
         if perm is None:                             # one permutation per update, re-used by every epoch (rsl_rl)
-            perm = torch.randperm(self.num_mini_batches * mb, device=self.device)
-        self._perm_buf.copy_(perm[:self._perm_buf.numel()])
-        views = [self._perm_buf[i * mb:(i + 1) * mb] for i in range(self.num_mini_batches)]
-        if self._graph is not None and self._graph_whole:
-            self._graph.replay()                     # the whole update (epochs x mini-batches) is one graph
-        elif self._graph is not None:
-            for _ in range(self.num_learning_epochs):
-                for i in range(self.num_mini_batches):
-                    self._ix_one.copy_(views[i])     # one-step graph (torch MLP path): reads _ix_one
-                    self._graph.replay()
-        elif self._updates_done >= 1:
-            # Capture.  On the kernel path a mini-batch step is 5 launches, so all epochs x mini-batches go into ONE graph (each
-            # step reading its own slice of _perm_buf); the torch MLP path (~150 launches and fresh activations per step) keeps a
-            # one-step graph replayed 20 times.
-            self._graph_whole = self._mlp is not None and self._adam_kernel and (not self._mlp.has_fused_minibatch or self._fused_minibatch)
-            self._gstream.wait_stream(cur)
-            self._zero_grad()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=self._gstream, capture_error_mode="thread_local"):
-                if self._graph_whole:
-                    for _ in range(self.num_learning_epochs):
-                        for i in range(self.num_mini_batches):
-                            self._ix = views[i]
-                            self._mb_step()
-                else:
-                    self._ix = self._ix_one
-                    self._mb_step()
-            self._graph = g
-            self._ix = self._ix_one
-            if self._graph_whole:
-                g.replay()                           # the capture did not execute
-            else:
-                for _ in range(self.num_learning_epochs):
-                    for i in range(self.num_mini_batches):
-                        self._ix_one.copy_(views[i])
-                        g.replay()
-        else:
-            for _ in range(self.num_learning_epochs):
-                for i in range(self.num_mini_batches):
-                    self._gstream.wait_stream(cur)
-                    with torch.cuda.stream(self._gstream):
-                        self._ix = views[i]
-                        self._zero_grad()
-                        self._mb_step()
-                    cur.wait_stream(self._gstream)
-            self._ix = self._ix_one
+            perm = torch.randperm(nmb * mb, device=self.device)
+        self._perm_buf.copy_(perm[:nmb * mb])
+        return [self._perm_buf[i * mb:(i + 1) * mb] for i in range(nmb)]
+
+    def _steps(self, slots):
+        """epochs x mini-batches: every mini-batch slot (its rows, or its graph) once per epoch."""
+        return (slot for _ in range(self.num_learning_epochs) for slot in slots)
+
+    def _end_update(self):
         n = self.num_learning_epochs * self.num_mini_batches
         mean_v, mean_s, lr = (float(x) for x in torch.cat((self._acc / n, self._lr.view(1))).cpu())
         self.learning_rate = lr
         self._updates_done += 1
-        st.clear()
+        self.storage.clear()
         return mean_v, mean_s
 
-    def _update_fused_eager(self, perm=None):
-        """world_size > 1, kernel path.  A mini-batch step is [backward graph] -> flat all-reduce (RCCL, eager: one collective of all
+    def _capturing(self):
+        """(graph, context that captures into it on the capture stream)."""
+        g = torch.cuda.CUDAGraph()
+        return g, torch.cuda.graph(g, stream=self._gstream, capture_error_mode="thread_local")
+
+    def _run_single(self, views):
+        """One process: update 0 eager ON THE CAPTURE STREAM -- the warm-up torch asks for before capturing autograd + optimiser work
+        (library handles / workspaces and the optimiser state get created on that stream, outside capture) -- capture at update 1,
+        replay from then on."""
+        cur, gs = torch.cuda.current_stream(self.device), self._gstream
+        if self._graph is None and self._updates_done >= 1:
+            # On the kernel path a mini-batch step is 5 launches, so all epochs x mini-batches go into ONE graph (each step reading
+            # its own slice of _perm_buf); the torch MLP path (~150 launches and fresh activations per step) keeps a one-step graph
+            # that reads _ix_one.
+            self._graph_whole = self._mlp is not None and self._adam_kernel and (not self._mlp.has_fused_minibatch or self._fused_minibatch)
+            gs.wait_stream(cur)
+            self._zero_grad()
+            g, capture = self._capturing()
+            with capture:
+                for ix in self._steps(views) if self._graph_whole else [self._ix_one]:
+                    self._mb_step(ix)
+            self._graph = g                          # (the capture did not execute: this update replays it like every later one)
+        if self._graph is None:
+            for ix in self._steps(views):
+                gs.wait_stream(cur)
+                with torch.cuda.stream(gs):
+                    self._zero_grad()
+                    self._mb_step(ix)
+                cur.wait_stream(gs)
+        elif self._graph_whole:
+            self._graph.replay()
+        else:
+            for ix in self._steps(views):
+                self._ix_one.copy_(ix)
+                self._graph.replay()
+
+    def _run_data_parallel(self, views):
+        """world_size > 1, loss kernel path.  A mini-batch step is [backward graph] -> flat all-reduce (RCCL, eager: one collective of all
         gradients + the KL slot) -> [optimiser graph]: after an eager first update the two halves are captured once -- one "pre" graph
-        per mini-batch slot (each reads its own slice of the permutation buffer), one "post" graph (mean over ranks, clip, KL rule,
-        Adam) -- so an update is 2 x epochs x mini-batches graph replays + epochs x mini-batches collectives from the host, no kernel
-        launch of its own.  ``LG_DP_GRAPHS=0`` keeps the eager launches (A/B, and the fallback when capture is refused)."""
-        st = self.storage
-        B = st.num_envs * st.num_transitions_per_env
-        mb = B // self.num_mini_batches
-        nmb = self.num_mini_batches
-        if getattr(self, "_perm_buf", None) is None or self._perm_buf.numel() != nmb * mb:
-            self._perm_buf = torch.zeros(nmb * mb, dtype=torch.int64, device=self.device)
-            self._acc = torch.zeros(2, device=self.device)
-            self._dp_graphs = None
-        key = (st.observations.data_ptr(), st.advantages.data_ptr(), st.returns.data_ptr(), mb) + self._dp_state_key()
-        if getattr(self, "_dp_key", None) != key:
-            self._dp_key, self._dp_graphs = key, None
-        self._acc.zero_()
-        if perm is None:
-            perm = torch.randperm(nmb * mb, device=self.device)
-        self._perm_buf.copy_(perm[:nmb * mb])
-        views = [self._perm_buf[i * mb:(i + 1) * mb] for i in range(nmb)]
-        want_graphs = os.environ.get("LG_DP_GRAPHS", "1") != "0" and self._mlp_kernels and self._adam_kernel
+        per mini-batch slot (``_gradients`` on its own slice of the permutation buffer), one "post" graph (``_optimise``) -- so an update
+        is 2 x epochs x mini-batches graph replays + epochs x mini-batches collectives from the host, no kernel launch of its own."""
         self.dp_launches = None
-        if want_graphs and self._updates_done >= 1 and getattr(self, "_dp_graphs", None) is None:
+        if self._dp_graphs_wanted and self._mlp_kernels and self._adam_kernel and self._updates_done >= 1 and self._dp_graphs is None:
             try:
-                self._ix = views[0]
-                if self._mlp_trainer() is None:
+                if self._mlp_trainer(views[0].numel()) is None:
                     raise RuntimeError("no learner kernels for these networks")
-                if not hasattr(self, "_gstream"):
-                    self._gstream = torch.cuda.Stream(device=self.device)
                 self._gstream.wait_stream(torch.cuda.current_stream(self.device))
-                pre = []
-                for i in range(nmb):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=self._gstream, capture_error_mode="thread_local"):
-                        self._ix = views[i]
+                pre_graphs = []
+                for ix in views:
+                    g, capture = self._capturing()
+                    with capture:
                         self._zero_grad()
-                        self._mb_step_fused("pre")
-                    pre.append(g)
-                post = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(post, stream=self._gstream, capture_error_mode="thread_local"):
-                    self._mb_step_fused("post")
-                self._dp_graphs = (pre, post)
+                        flat, acc_done = self._gradients(ix)
+                        if not flat:
+                            raise RuntimeError("the two-graph data-parallel step needs the flat-gradient kernel path")
+                    pre_graphs.append(g)
+                post, capture = self._capturing()
+                with capture:
+                    self._optimise(True, acc_done)   # (the same for every slot: known here, at capture time)
+                self._dp_graphs, self._dp_graph_error = (pre_graphs, post), None
             except Exception as exc:                  # capture refused (e.g. the torch MLP path): stay eager, say so once
                 self._dp_graphs = False
                 self._dp_graph_error = f"{type(exc).__name__}: {exc}"
-        if getattr(self, "_dp_graphs", None):
-            pre, post = self._dp_graphs
-            for _ in range(self.num_learning_epochs):
-                for i in range(nmb):
-                    pre[i].replay()
-                    dist.all_reduce(self._gflat, op=dist.ReduceOp.SUM)
-                    post.replay()
-            n = self.num_learning_epochs * nmb
+        if self._dp_graphs:
+            pre_graphs, post = self._dp_graphs
+            for pre in self._steps(pre_graphs):
+                pre.replay()
+                self._collective(True)
+                post.replay()
+            n = self.num_learning_epochs * self.num_mini_batches
             self.dp_launches = {"graph_replays": 2 * n, "collectives": n, "kernel_launches_from_host": 0}
         else:
-            for _ in range(self.num_learning_epochs):
-                for i in range(nmb):
-                    self._ix = views[i]
-                    self._zero_grad()
-                    self._mb_step()
-        n = self.num_learning_epochs * nmb
-        mean_v, mean_s, lr = (float(x) for x in torch.cat((self._acc / n, self._lr.view(1))).cpu())
-        self.learning_rate = lr
-        self._updates_done += 1
-        st.clear()
-        return mean_v, mean_s
+            for ix in self._steps(views):
+                self._zero_grad()
+                self._mb_step(ix)
 
     def update(self, perm=None):
         """One PPO update over the stored rollout.  ``perm`` (optional) fixes the mini-batch permutation (tests)."""
-        if self._graph_ok and _world() == 1:
-            return self._update_graphed(perm)
-        if self._graph_ok and self._fused_ready():
-            return self._update_fused_eager(perm)
+        if self._graph_ok and (_world() == 1 or self._fused_ready()):
+            views = self._begin_update(perm)
+            if _world() == 1:
+                self._run_single(views)
+            else:
+                self._run_data_parallel(views)
+            return self._end_update()
         mean_v, mean_s = 0.0, 0.0
         if self.actor_critic.is_recurrent:
             gen = self.storage.recurrent_mini_batch_generator(self.num_mini_batches, self.num_learning_epochs)
@@ -744,10 +737,9 @@ class PPO:
             lp = self.actor_critic.get_actions_log_prob(act)
             val = self.actor_critic.evaluate(cobs, masks=masks, hidden_states=hid[1])
             mu, sig, ent = self.actor_critic.action_mean, self.actor_critic.action_std, self.actor_critic.entropy
-            if self.desired_kl is not None and self.schedule == "adaptive":
+            if self._adaptive:
                 with torch.inference_mode():
-                    kl = torch.sum(torch.log(sig / old_sig + 1.0e-5) + (old_sig.square() + (old_mu - mu).square()) / (2.0 * sig.square()) - 0.5, dim=-1)
-                    kl_mean = kl.mean()
+                    kl_mean = gaussian_kl(mu, sig, old_mu, old_sig).mean()
                     if _world() > 1:
                         dist.all_reduce(kl_mean, op=dist.ReduceOp.SUM)
                         kl_mean /= _world()
@@ -757,15 +749,7 @@ class PPO:
                         self.learning_rate = min(1e-2, self.learning_rate * 1.5)
                     for g in self.optimizer.param_groups:
                         g["lr"] = self.learning_rate
-            ratio = torch.exp(lp - old_lp.squeeze(-1))
-            a = adv.squeeze(-1)
-            surrogate = torch.max(-a * ratio, -a * torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param)).mean()
-            if self.use_clipped_value_loss:
-                vclip = tval + (val - tval).clamp(-self.clip_param, self.clip_param)
-                vloss = torch.max((val - ret).pow(2), (vclip - ret).pow(2)).mean()
-            else:
-                vloss = (ret - val).pow(2).mean()
-            loss = surrogate + self.value_loss_coef * vloss - self.entropy_coef * ent.mean()
+            loss, surrogate, vloss = self._loss(lp, old_lp.squeeze(-1), adv.squeeze(-1), val, tval, ret, ent)
             self.optimizer.zero_grad()
             loss.backward()
             self._allreduce_grads()

@@ -176,27 +176,49 @@ def test_composed_minibatch_step_matches_float64_autograd_at_the_game_shape(prec
         lib.lg_mlp_wide_set_precision(old)
 
 
-def test_after_optimizer_load_drops_the_data_parallel_graphs():
+def test_after_optimizer_load_drops_the_data_parallel_graphs(monkeypatch):
     """A checkpoint load replaces Adam's state tensors: the captured data-parallel "pre" / "post" graphs (which hold the old
-    addresses) and their key must go, like the single-process update graph."""
-    from legged_games_gym_amd.rl import ActorCritic, PPO
+    addresses) and their key must go, like the single-process update graph, its ``whole`` flag and the MlpTrainer's descriptors --
+    EVERYTHING captured, through the one invalidation point, from each of the four places that call it."""
+    from legged_games_gym_amd.rl import ActorCritic, PPO, ppo
     torch.manual_seed(0)
     ac = ActorCritic(19, 19, 6, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128])
     alg = PPO(ac, schedule="adaptive", desired_kl=0.01, learning_rate=1e-3, device="cuda:0")
+    alg.init_storage(16, 4, [19], [None], [6])
     sentinel = (["pre"], "post")
-    alg._graph, alg._dp_graphs, alg._dp_key, alg._updates_done = object(), sentinel, ("key",), 3
+
+    def seed():
+        alg._graph, alg._graph_whole, alg._dp_graphs, alg._dp_key, alg._mlp, alg._updates_done = object(), True, sentinel, ("key",), object(), 3
+
+    def dropped(updates_done):
+        return (alg._graph is None and alg._graph_whole is False and alg._dp_graphs is None and alg._dp_key is None and alg._mlp is None
+                and alg._updates_done == updates_done)
+    seed()
+    alg._drop_captured(warm_up_again=False)
+    assert dropped(3)
+    seed()                                                                  # 1. the checkpoint load: the warm-up starts again
     alg.optimizer.load_state_dict(alg.optimizer.state_dict())
     alg.after_optimizer_load()
-    assert alg._graph is None and alg._dp_graphs is None and alg._dp_key is None and alg._updates_done == 0
+    assert dropped(0)
     assert alg.optimizer.param_groups[0]["lr"] is alg._lr
-    # ... and so must a rebuild of the flat gradient buffer
-    alg._dp_graphs, alg._dp_key = sentinel, ("key",)
+    seed()                                                                  # 2. a rebuild of the flat gradient buffer
     flat = alg._flat_grad_views()
-    assert alg._dp_graphs is None and alg._dp_key is None
-    # steady state: the buffer is kept, and so are graphs captured over it; its address and Adam's state addresses are part of the key
-    alg._dp_graphs = sentinel
-    assert alg._flat_grad_views() is flat and alg._dp_graphs is sentinel
-    assert alg._dp_state_key()[-1] == flat.data_ptr()
+    assert dropped(3)
+    # steady state: the buffer is kept, and so is what was captured over it; its address and Adam's state addresses are part of the key
+    seed()
+    assert alg._flat_grad_views() is flat and alg._dp_graphs is sentinel and alg._graph is not None and alg._dp_key == ("key",)
+    assert alg._dp_state_key()[-1] == flat.data_ptr() and alg._capture_key(64)[4:] == alg._dp_state_key()
+    alg._begin_update(None)                                                 # 3. the key check of an update, one process: warm up again
+    assert alg._graph is None and alg._graph_whole is False and alg._dp_graphs is None and alg._mlp is None and alg._updates_done == 0
+    assert alg._dp_key == alg._capture_key(64)
+    seed()                                                                  # 4. ... and of a data-parallel update: captured again at once
+    monkeypatch.setattr(ppo, "_world", lambda: 2)
+    alg._begin_update(None)
+    assert alg._graph is None and alg._graph_whole is False and alg._dp_graphs is None and alg._mlp is None and alg._updates_done == 3
+    # nothing captured: a key that moves (Adam's state appears during the first update) restarts nothing
+    alg._dp_key, alg._updates_done = ("key",), 1
+    alg._begin_update(None)
+    assert alg._updates_done == 1 and alg._dp_key == alg._capture_key(64)
 
 
 def _dp_resume_worker(rank, world, port, out):
