@@ -659,6 +659,55 @@ def bind_all(lib):
     return lib
 
 
+# ---------------------------------------------------------------------------------------------------------------- legged_lstm_sequence.h
+# A library of its own (csrc/liblegged_lstm_seq.so, built by a second hipcc command): outside ABI / ALL_SYMBOLS / bind_all, which
+# describe liblegged_hip.so.
+LG_LSTM_SEQ_MAX_IN, LG_LSTM_SEQ_MAX_HIDDEN, LG_LSTM_SEQ_BLOCK_ROWS = 256, 256, 32
+LSTM_SEQ_ABI = {
+    "lg_lstm_seq_create": ([i32, i32, i32, _P(_vp)], _int),
+    "lg_lstm_seq_load_device": ([_vp, _vp, _vp, _vp, _vp, _vp], _int),
+    "lg_lstm_seq_destroy": ([_vp], _int),
+    "lg_lstm_seq_workspace_floats": ([i32, i32, i32], C.c_size_t),
+    "lg_lstm_seq_forward": ([_vp, _vp, i64, _vp, _vp, _vp, _vp, i32, i32, _vp], _int),
+    "lg_lstm_seq_backward": ([_vp, _vp, _vp, _vp, _vp, i32, i32, _vp], _int),
+    "lg_lstm_seq_last_error": ([], C.c_char_p),
+}
+LSTM_SEQ_SYMBOLS = list(LSTM_SEQ_ABI)
+_LSTM_SEQ_LIB_NAME = "liblegged_lstm_seq.so"
+_lstm_seq_lib = None
+
+
+def lstm_seq_supported(num_in: int, hidden: int) -> bool:
+    """The shapes ``lg_lstm_seq_create`` takes (the rollout cell's)."""
+    return 1 <= num_in <= LG_LSTM_SEQ_MAX_IN and 32 <= hidden <= LG_LSTM_SEQ_MAX_HIDDEN and hidden % 32 == 0
+
+
+def lstm_seq_library_path() -> str:
+    """In-tree liblegged_lstm_seq.so; LG_LSTM_SEQ_LIB selects another build of the same source."""
+    return os.environ.get("LG_LSTM_SEQ_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _LSTM_SEQ_LIB_NAME)
+
+
+def bind_lstm_seq(lib):
+    for symbol, (argtypes, restype) in LSTM_SEQ_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    return lib
+
+
+def load_lstm_seq_library():
+    """Load the LSTM sequence kernels or fail loudly -- never a CPU substitute."""
+    global _lstm_seq_lib
+    if _lstm_seq_lib is not None:
+        return _lstm_seq_lib
+    path = lstm_seq_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _lstm_seq_lib = bind_lstm_seq(C.CDLL(path))
+    return _lstm_seq_lib
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

@@ -99,12 +99,13 @@ class Memory(nn.Module):
             raise ValueError(f"rnn_type must be 'lstm' or 'gru', got {type!r}")
         self.rnn = (nn.GRU if kind == "gru" else nn.LSTM)(input_size=input_size, hidden_size=hidden_size, num_layers=num_layers)
         self.hidden_states = None
+        self.sequence = None                          # batch mode on the device kernels (rl.lstm_sequence.DeviceLstmSequence, attached by PPO(device_bptt=True)); no sub-module, no parameter
 
     def forward(self, input, masks=None, hidden_states=None):
         if masks is not None:                         # batch mode (policy update): padded trajectories from their stored initial states
             if hidden_states is None:
                 raise ValueError("Hidden states not passed to memory module during policy update")
-            out, _ = self.rnn(input, hidden_states)
+            out = self.sequence(input, hidden_states) if self.sequence is not None else self.rnn(input, hidden_states)[0]
             return unpad_trajectories(out, masks)
         self._own_states()
         out, states = self.rnn(input.unsqueeze(0), self.hidden_states)      # rollout mode: one step on the carried state

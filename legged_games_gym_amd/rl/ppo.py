@@ -225,7 +225,7 @@ class PPO:
 
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0,
-                 use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", graphed_update=True, fused_loss=True):
+                 use_clipped_value_loss=True, schedule="fixed", desired_kl=0.01, device="cpu", graphed_update=True, fused_loss=True, device_bptt=False):
         self.device = device
         # Single-GPU runs replay one captured HIP graph per mini-batch step (forward, losses, backward, grad clip, Adam and
         # the adaptive-KL learning rate all on the device): the flat networks' update is launch-bound (~150 tiny kernels).
@@ -260,6 +260,8 @@ class PPO:
         self._lib = None
         self.desired_kl, self.schedule, self.learning_rate = desired_kl, schedule, learning_rate
         self.actor_critic = actor_critic.to(device)
+        if device_bptt:
+            self._attach_device_bptt()
         self.storage = None
         self._prime = self._lr = None
         if self._graph_ok:
@@ -279,6 +281,24 @@ class PPO:
         self.value_loss_coef, self.entropy_coef = value_loss_coef, entropy_coef
         self.gamma, self.lam, self.max_grad_norm = gamma, lam, max_grad_norm
         self.use_clipped_value_loss = use_clipped_value_loss
+
+    def _attach_device_bptt(self):
+        """``device_bptt``: the recurrence of both memories' batch mode on the LSTM sequence kernels (rl/lstm_sequence.py) instead of
+        ``nn.LSTM`` and autograd's back-propagation through time; the update loop itself is the same.  Both memories or neither."""
+        ac = self.actor_critic
+        if not getattr(ac, "is_recurrent", False):
+            why = "the policy is not recurrent"
+        elif not str(self.device).startswith("cuda"):
+            why = f"the learner is on {self.device}"
+        else:
+            from .lstm_sequence import sequence_unsupported_reason
+            why = sequence_unsupported_reason(ac.memory_a.rnn) or sequence_unsupported_reason(ac.memory_c.rnn)
+        if why is not None:
+            print(f"[ppo] device BPTT unavailable ({why}); torch LSTM and autograd in the update")
+            return
+        from .lstm_sequence import DeviceLstmSequence
+        ac.memory_a.sequence = DeviceLstmSequence(ac.memory_a.rnn, self.device)
+        ac.memory_c.sequence = DeviceLstmSequence(ac.memory_c.rnn, self.device)
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)

@@ -27,7 +27,7 @@ class OnPolicyRunner:
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             for prm in actor_critic.parameters():       # replicas start from rank 0's weights (env seeds differ per rank)
                 dist.broadcast(prm.data, src=0)
-        self.alg = PPO(actor_critic, device=device, **self.alg_cfg)
+        self.alg = PPO(actor_critic, device=device, device_bptt=self.cfg.get("device_bptt", False), **self.alg_cfg)      # (device_bptt: a runner key like device_rollout, not a config field)
         self.num_steps_per_env = self.cfg["num_steps_per_env"]
         self.save_interval = self.cfg["save_interval"]
         self.alg.init_storage(env.num_envs, self.num_steps_per_env, [env.num_obs], [env.num_privileged_obs], [env.num_actions])

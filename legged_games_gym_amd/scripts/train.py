@@ -16,7 +16,9 @@ length, as ``Episode/outcome_*``.
 
 ``--policy_class_name ActorCriticRecurrent [--rnn_type lstm --rnn_hidden_size 256 --rnn_num_layers 1]`` trains an LSTM policy (rsl_rl's class
 of that name): on a locomotion task on the GPU the memories and the actor run on the device in the rollout (``lg_lstm_step``), the update is
-back-propagation through time in torch; the game tasks take the generic loop."""
+back-propagation through time in torch; the game tasks take the generic loop.  ``--device_bptt`` (off by default) moves the recurrence of
+that update onto the device as well: both memories' padded trajectories run through time in ``lg_lstm_seq_forward`` / ``lg_lstm_seq_backward``
+(one launch each way per memory and mini-batch); the MLPs, the loss and Adam stay in torch."""
 import os
 
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
@@ -56,6 +58,8 @@ def train(args):
     rank, world = _init_distributed(args)
     if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
         task_registry.get_cfgs(args.task)[1].runner.device_rollout = True
+    if args.device_bptt:                     # likewise a runner key
+        task_registry.get_cfgs(args.task)[1].runner.device_bptt = True
     apply_policy_args(task_registry.get_cfgs(args.task)[1], args)     # --policy_class_name ActorCriticRecurrent [--rnn_type / --rnn_hidden_size / --rnn_num_layers]
     if args.outcome_stats:                   # read with getattr() by the game tasks: no field of the registered config classes
         if args.task not in a1_game.TASKS + a1_game.SCRIPTED_TASKS:

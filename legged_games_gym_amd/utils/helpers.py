@@ -207,6 +207,9 @@ def get_args(argv=None):
     p.add_argument("--device_rollout", action="store_true", default=False,
                    help="high_level_game: train on the device rollout (runner key of the same name: MFMA high-level actor, three launches per step, one graph "
                         "replay per rollout); an actor shape the kernels refuse falls back to the generic loop with a message")
+    p.add_argument("--device_bptt", action="store_true", default=False,
+                   help="ActorCriticRecurrent on the GPU: run the LSTM recurrence of the PPO update, forward and backward through time, on the device sequence "
+                        "kernels (runner key of the same name); a memory they do not cover (GRU, several layers, more than 256 units) keeps torch with a message")
     p.add_argument("--outcome_stats", action="store_true", default=False,
                    help="the game tasks (dec_high_level_game: scripts/train_dec_game.py): count inside the post-step launch why episodes end (captured, left the arena, fell, "
                         "survived) and log the rates as Episode/outcome_*; the scripts set env.outcome_stats on the registration they use")
