@@ -3,7 +3,9 @@
 
 Wraps an ``ActorCritic`` (bundled or rsl_rl's: anything with ``.actor`` = Sequential of Linear/ELU and ``.std``).
 The torch module stays the owner of the parameters; call ``sync()`` after an optimiser step to re-upload them.
-Numerics: fp32 MFMA (exact fp32 FMA chains); tests compare against the torch fp32 forward.
+Numerics: fp32 MFMA (exact fp32 FMA chains), or split-bf16 products with fp32 accumulation for the 512-256-128 shapes at
+``lg_mlp_wide_set_precision(1)``, the default.  tests/test_gpu_actor_edges.py compares every kernel with a float64 forward of the
+module (2e-5 of the output scale for the exact kernels, 1e-4 for the split-bf16 ones); earlier tests compare with the torch fp32 forward.
 """
 import ctypes as C
 

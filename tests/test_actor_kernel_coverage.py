@@ -7,7 +7,9 @@ instantiation fails this test until a test for it is added to the table.  (CPU o
 
 Which call reaches which instantiation (lg_policy_act in csrc/lg_learner.hip): TILES0 = ceil(observations / 16).  The 48-128-64-32 actor
 always runs k_policy_act<3, 8, 4, 2>.  A 512-256-128 actor runs k_policy_act_wide<TILES0, 16, 8, 4> at lg_mlp_wide_set_precision(1), the
-default, and k_policy_act<TILES0, 32, 16, 8> at precision 0; the tests named for them are parametrised over both settings."""
+default, and k_policy_act<TILES0, 32, 16, 8> at precision 0; the tests named for them are parametrised over both settings.  The tests of
+tests/test_gpu_actor_edges.py take every one of the nine to the first and last observation width of its range, to env counts on every
+side of a workgroup and to 1 .. 16 actions against float64 (tests/actor_check.py holds the table and restates this dispatch)."""
 import ast
 import os
 import re
@@ -33,6 +35,12 @@ ACTOR_MEANS = f"{ACTOR}::test_means_match_float64_and_the_flags_do_what_they_say
 ACTOR_NOISE = f"{ACTOR}::test_noise_is_the_reference_stream_for_every_action_count_and_step_source"
 ACTOR_SYNC = f"{ACTOR}::test_sync_device_equals_a_fresh_handle"
 ROUGH_DEFAULT = f"{CELL}::test_default_policy_of_the_rough_task_through_the_wrapper"
+EDGES = "tests/test_gpu_actor_edges.py"                                    # tests/actor_check.py: every kernel at its width, env-count and action-count edges
+EDGE_MEANS = f"{EDGES}::test_means_match_float64_with_guard_rows_intact"   # float64, NaN guard rows; host pack, then lg_policy_load_device bit-equal
+EDGE_FLAGS = f"{EDGES}::test_flags_at_a_ragged_case"
+EDGE_NOISE = f"{EDGES}::test_noise_is_the_reference_stream_for_every_action_count"      # 19 observations, 1 .. 16 actions, both precisions
+EDGE_REPACK = f"{EDGES}::test_device_repack_equals_host_pack_at_the_padded_widths"      # sync_device() at each range's first and last width
+EDGE = [EDGE_MEANS, EDGE_FLAGS, EDGE_REPACK]
 
 
 def policy_act(t0, t1, t2, t3):
@@ -47,24 +55,24 @@ def policy_act_wide(t0):
 
 COVERAGE = {
     # exact-f32 actors: the flat shape at either precision, the 512-256-128 shapes at precision 0
-    policy_act(3, 8, 4, 2): [TORCH, NOISE, REPACK],
-    policy_act(15, 32, 16, 8): [TORCH, NOISE],                             # rough: 235 observations
-    policy_act(11, 32, 16, 8): [TORCH, NOISE],                             # cassie: 169
-    policy_act(2, 32, 16, 8): [GAME_SHAPE],                                # high_level_game: 19
-    policy_act(1, 32, 16, 8): [ONE_TILE],                                  # dec_high_level_game: 16 and 3
+    policy_act(3, 8, 4, 2): [TORCH, NOISE, REPACK] + EDGE,
+    policy_act(15, 32, 16, 8): [TORCH, NOISE] + EDGE,                      # rough: 235 observations
+    policy_act(11, 32, 16, 8): [TORCH, NOISE] + EDGE,                      # cassie: 169
+    policy_act(2, 32, 16, 8): [GAME_SHAPE, EDGE_NOISE] + EDGE,            # high_level_game: 19
+    policy_act(1, 32, 16, 8): [ONE_TILE] + EDGE,                          # dec_high_level_game: 16 and 3
     # split-bf16 actors: the same shapes at precision 1
-    policy_act_wide(15): [TORCH, NOISE, REPACK],
-    policy_act_wide(11): [TORCH, NOISE],
-    policy_act_wide(2): [GAME_SHAPE],
-    policy_act_wide(1): [ONE_TILE],
+    policy_act_wide(15): [TORCH, NOISE, REPACK] + EDGE,
+    policy_act_wide(11): [TORCH, NOISE] + EDGE,
+    policy_act_wide(2): [GAME_SHAPE, EDGE_NOISE] + EDGE,
+    policy_act_wide(1): [ONE_TILE] + EDGE,
     # the shared actor launches of the game tasks: float64 forwards of every role at n = 33
     "_ZN2lg10k_prey_actENS_11PreyActArgsE": [f"{GAME}::test_shared_actor_launch_matches_float64_forwards"],
     "_ZN2lg9k_dec_actENS_10DecActArgsE": [f"{DEC}::test_shared_actor_launch_matches_float64_forwards"],
     "_ZN2lg10k_pool_actENS_11PoolActArgsE": [f"{POOL}::test_pooled_launch_matches_float64_forwards_of_each_blocks_member"],
     # weight packing on the device (sync_device()): the f32 layout is read by the precision-0 kernels and the flat actor, the split-bf16
     # layout by the precision-1 kernels, whose handles pack it at creation too
-    "_Z13k_policy_packPKfS0_iiiiPfS1_": [REPACK, GAME_SHAPE, ONE_TILE],
-    "_ZN2lg18k_policy_pack_wideEPKfS1_iiiiiPDF16bPf": [TORCH, REPACK, GAME_SHAPE, ONE_TILE],
+    "_Z13k_policy_packPKfS0_iiiiPfS1_": [REPACK, GAME_SHAPE, ONE_TILE, EDGE_MEANS, EDGE_REPACK],
+    "_ZN2lg18k_policy_pack_wideEPKfS1_iiiiiPDF16bPf": [TORCH, REPACK, GAME_SHAPE, ONE_TILE, EDGE_MEANS, EDGE_REPACK],
     # the recurrent policy: the cell (lg_lstm_create packs on the device) and the actor behind it (every handle packs on the device)
     "_ZN2lg11k_lstm_cellENS_8LstmArgsE": CELL_TESTS + [ROUGH_DEFAULT],
     "_ZN2lg11k_lstm_packEPKfS1_S1_S1_P15HIP_vector_typeIfLj4EES4_iii": [CELL_STEP, f"{CELL}::test_load_device_equals_create"],
