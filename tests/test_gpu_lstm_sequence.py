@@ -8,7 +8,8 @@ Reference: a ``.double()`` copy of the ``nn.LSTM`` on the CPU, stepped through t
 bars are about the kernels and not about float32.
 
 Inputs: trajectory lengths in 1 .. T (trajectory 0 full), ``x`` and ``dh_out`` zero beyond each length (what ``split_and_pad_trajectories``
-and ``unpad_trajectories``' backward produce), ``h0`` / ``c0`` non-zero.  The float64 references are computed once per case and shared."""
+and ``unpad_trajectories``' backward produce), ``h0`` / ``c0`` non-zero: the recipe of tests/lstm_seq_check.make_inputs, which
+tests/test_gpu_lstm_sequence_edges.py runs at the kernels' shape edges.  The float64 references are computed once per case and shared."""
 import copy
 import ctypes as C
 import functools
@@ -18,7 +19,8 @@ import pytest
 import torch
 import torch.nn as nn
 
-from tests.recurrent_ref import lstm_params64, lstm_step64, saturating_bias
+from tests import lstm_seq_check as lc
+from tests.recurrent_ref import lstm_params64, lstm_step64
 from tests.wide_learner_check import GRAD_ABS, GRAD_TOL, compare
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +28,7 @@ TOL = 2e-5
 DEV = "cuda:0"
 # (T, B, I, H): the smallest at which each mechanism can go wrong -- one of everything | odd K = 51 and one row past a block | 2 waves |
 # the update's T | an exact block and 8 waves | the rough task's K = 491 (odd) | the largest LDS blocks, three workgroups
-SHAPES = [(1, 1, 1, 32), (2, 33, 19, 32), (3, 5, 17, 64), (24, 37, 48, 64), (24, 32, 48, 256), (5, 64, 235, 256), (24, 96, 256, 256)]
+SHAPES = list(lc.OLD_SHAPES)
 MID = (24, 37, 48, 64)
 PARAMS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
 
@@ -52,21 +54,7 @@ def _reference(rnn, x, h0, c0, dh, dtype):
 @functools.lru_cache(maxsize=None)
 def _case(shape, scale=1.0, saturate=False):
     """Inputs, the float64 reference and the float32 control of one case (all on the CPU; never modified afterwards)."""
-    T, B, I, H = shape
-    torch.manual_seed(1000 * T + 10 * B + I + H)
-    rnn = nn.LSTM(I, H)
-    with torch.no_grad():
-        for p in rnn.parameters():
-            p.mul_(scale)
-        if saturate:
-            rnn.bias_ih_l0.add_(torch.from_numpy(saturating_bias(H)).float())
-    gen = torch.Generator().manual_seed(7 * T + B)
-    lengths = torch.randint(1, T + 1, (B,), generator=gen)
-    lengths[0] = T
-    live = (torch.arange(T).unsqueeze(1) < lengths.unsqueeze(0)).float().unsqueeze(-1)          # [T, B, 1]
-    x = (torch.rand(T, B, I, generator=gen) * 6.0 - 3.0) * live
-    dh = torch.randn(T, B, H, generator=gen) * live
-    h0, c0 = torch.rand(B, H, generator=gen) * 2 - 1, torch.rand(B, H, generator=gen) * 2 - 1
+    rnn, x, h0, c0, dh, lengths = lc.make_inputs(shape, scale, saturate)
     want = _reference(rnn, x, h0, c0, dh, torch.float64)
     ctrl = _reference(rnn, x, h0, c0, dh, torch.float32)
     # the control: float32 torch is within a quarter of every bar
@@ -178,13 +166,10 @@ def test_forward_matches_the_explicit_float64_restatement():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. the rollout's cell
-@pytest.mark.parametrize("shape", SHAPES)
-def test_forward_matches_the_rollout_cell_stepped_through_time(shape):
-    """T launches of ``lg_lstm_step`` (actor role only) from the same (h0, c0): the update's first epoch evaluates the policy that acted,
-    so its probability ratio is 1 to the extent these two agree."""
+def _check_against_the_stepped_cell(case):
     from legged_games_gym_amd.rl.recurrent_actor import DeviceLstm, lstm_step
     from legged_games_gym_amd import capi
-    case = _case(shape)
+    shape = case["shape"]
     T, B, I, H = shape
     run = _forward(case)
     cell, lib = DeviceLstm(run["rnn"], DEV), capi.load_library()
@@ -201,6 +186,13 @@ def test_forward_matches_the_rollout_cell_stepped_through_time(shape):
     c_last = run["ws"][4 * T * B * H:].view(T, B, H)[-1]
     print(f"{shape}: sequence against the stepped cell: err {err:.3e}; bit-equal h {torch.equal(hs, run['h_out'])}, last c {torch.equal(c, c_last)}")
     assert err < TOL * scale
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_forward_matches_the_rollout_cell_stepped_through_time(shape):
+    """T launches of ``lg_lstm_step`` (actor role only) from the same (h0, c0): the update's first epoch evaluates the policy that acted,
+    so its probability ratio is 1 to the extent these two agree."""
+    _check_against_the_stepped_cell(_case(shape))
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. backward
