@@ -708,6 +708,63 @@ def load_lstm_seq_library():
     return _lstm_seq_lib
 
 
+# ---------------------------------------------------------------------------------------------------------------- legged_game_recurrent.h
+# The recurrent actor launch of the game tasks, a library of its own as well (csrc/liblegged_game_recurrent.so, a third hipcc command):
+# outside ABI / ALL_SYMBOLS / bind_all.  It reads the lg_policy / lg_lstm_actor handles liblegged_hip.so created.
+GAME_RECURRENT_ABI = {
+    "lg_game_lstm_act": ([_vp, _vp, _P(lg_game_params), _P(lg_game_buffers), _vp, _vp, _vp, _vp, _vp, u64, i64, _vp, i32, _vp, _vp, _vp, _vp, _vp], _int),
+    "lg_game_recurrent_last_error": ([], C.c_char_p),
+    "lg_game_recurrent_sizeof": _SIZEOF,
+}
+GAME_RECURRENT_SYMBOLS = list(GAME_RECURRENT_ABI)
+GAME_RECURRENT_STRUCTS = (lg_game_params, lg_game_buffers)          # what lg_game_recurrent_sizeof sizes by index (2, 3: the two handles, opaque here)
+_GAME_RECURRENT_LIB_NAME = "liblegged_game_recurrent.so"
+_game_recurrent_lib = None
+
+
+def game_recurrent_library_path() -> str:
+    """In-tree liblegged_game_recurrent.so; LG_GAME_RECURRENT_LIB selects another build of the same source."""
+    return os.environ.get("LG_GAME_RECURRENT_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _GAME_RECURRENT_LIB_NAME)
+
+
+def bind_game_recurrent(lib):
+    for symbol, (argtypes, restype) in GAME_RECURRENT_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    for which, st in enumerate(GAME_RECURRENT_STRUCTS):
+        size = lib.lg_game_recurrent_sizeof(which)
+        if size != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def load_game_recurrent_library():
+    """Load the recurrent actor launch of the game tasks or fail loudly -- never a CPU substitute."""
+    global _game_recurrent_lib
+    if _game_recurrent_lib is not None:
+        return _game_recurrent_lib
+    path = game_recurrent_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _game_recurrent_lib = bind_game_recurrent(C.CDLL(path))
+    return _game_recurrent_lib
+
+
+def game_lstm_act(hl_actor, ll_policy, params: lg_game_params, buffers: lg_game_buffers, h: int, hl_obs: Optional[int], ll_obs: int, ll_actions: int,
+                  mean: int, seed: int, step: int, step_counter: Optional[int], deterministic: bool, sample: Optional[int] = None,
+                  sigma: Optional[int] = None, log_prob: Optional[int] = None, obs_copy: Optional[int] = None, stream: int = 0) -> int:
+    """``lg_game_lstm_act``: ``lg_game_act`` for a recurrent high-level actor (an ``lg_lstm_actor`` handle on the actor memory's ``h``).
+    Returns 0, or -4 when the actor pair has no shared kernel (the caller then issues the separate launches); raises on any other error."""
+    lib = load_game_recurrent_library()
+    rc = lib.lg_game_lstm_act(hl_actor, ll_policy, C.byref(params), C.byref(buffers), h, hl_obs, ll_obs, ll_actions, mean, int(seed), int(step),
+                              step_counter, int(bool(deterministic)), sample, sigma, log_prob, obs_copy, stream)
+    if rc not in (0, -4):
+        raise RuntimeError(f"lg_game_lstm_act failed ({rc}): {lib.lg_game_recurrent_last_error().decode()}")
+    return rc
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

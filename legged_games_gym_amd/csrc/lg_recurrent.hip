@@ -6,6 +6,7 @@
 
 #include "lg_device.h"             // rand4: the Philox stream of the actor kernels
 #include "lg_recurrent.h"
+#include "lg_lstm_actor_body.h"      // the actor MLP of k_lstm_actor, shared with the game layer's recurrent actor launch
 #include "../../include/legged_recurrent.h"
 
 #define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return lg::fail(-10, "HIP error: %s", hipGetErrorString(_e)); } while (0)
@@ -122,72 +123,10 @@ __global__ void __launch_bounds__(256) k_lstm_actor_pack(const float *__restrict
     }
 }
 
-__device__ __forceinline__ float lstm_actor_elu(const float x) { return x > 0.0f ? x : (__builtin_amdgcn_exp2f(1.442695041f * x) - 1.0f); }
-
 __global__ void __launch_bounds__(64 * LG_LSTM_ACTOR_WAVES) k_lstm_actor(const LstmActorArgs A) {
     extern __shared__ float lds[];                    // two activation buffers [max_width][LG_LSTM_LD], then the noise [32][16]
     float *xa = lds, *xb = lds + (size_t)A.max_width * LG_LSTM_LD, *ns = xb + (size_t)A.max_width * LG_LSTM_LD;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, env0 = 32 * (int)blockIdx.x;
-    const int nA = A.dims[4];
-    {   // the memory's output of the 32 rows as xa[k][row]; rows past num_envs are zeros
-        const int H = A.dims[0];
-        for (int e = tid; e < 32 * H; e += 64 * LG_LSTM_ACTOR_WAVES) {
-            const int row = e / H, k = e - row * H, env = env0 + row;
-            xa[k * LG_LSTM_LD + row] = env < A.num_envs ? A.h[(size_t)env * H + k] : 0.0f;
-        }
-    }
-    if (tid < 128) {                                  // std * eps of actions 4 g .. 4 g + 3 of row tid >> 2 (0 when deterministic)
-        const int row = tid >> 2, g = tid & 3, env = env0 + row;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (4 * g < nA && !A.deterministic && env < A.num_envs) {
-            const int64_t step = A.step >= 0 ? A.step : (A.step_counter ? A.step_counter[0] + 1 : 0);
-            float u[4];
-            rand4(A.seed ^ 0x9E3779B97F4A7C15ull, env, step, 100 + g, 0, u);
-            const float rad0 = sqrtf(-2.0f * __logf(fmaxf(u[0], 1e-12f))), rad1 = sqrtf(-2.0f * __logf(fmaxf(u[2], 1e-12f)));
-            float s0, c0, s1, c1;
-            __sincosf(6.2831853f * u[1], &s0, &c0);
-            __sincosf(6.2831853f * u[3], &s1, &c1);
-            const float eps[4] = {rad0 * c0, rad0 * s0, rad1 * c1, rad1 * s1};
-#pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = (4 * g + r < nA) ? A.std[4 * g + r] * eps[r] : 0.0f;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) ns[row * 16 + 4 * g + r] = v[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int L = 0; L < 4; L++) {
-        const float *in = (L & 1) ? xb : xa;
-        float *out = (L & 1) ? xa : xb;
-        const int ks = A.dims[L] / 2, tiles = A.pad[L + 1] / 32;
-        const float *al = in + (lane >> 5) * LG_LSTM_LD + (lane & 31);
-        for (int o = wave; o < tiles; o += LG_LSTM_ACTOR_WAVES) {
-            const int unit = 32 * o + (lane & 31);
-            const float bias = A.p[A.b_off[L] + unit];
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[r] = bias;
-            const float *__restrict__ wp = A.p + A.w_off[L] + (size_t)o * ks * 64 + lane;
-            for (int s = 0; s < ks; s += 4) {         // (ks is a multiple of 16: the widths are multiples of 32)
-                const float w0 = wp[(size_t)s * 64], w1 = wp[(size_t)(s + 1) * 64], w2 = wp[(size_t)(s + 2) * 64], w3 = wp[(size_t)(s + 3) * 64];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(al[2 * s * LG_LSTM_LD], w0, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(al[(2 * s + 2) * LG_LSTM_LD], w1, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(al[(2 * s + 4) * LG_LSTM_LD], w2, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(al[(2 * s + 6) * LG_LSTM_LD], w3, acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (L < 3) out[unit * LG_LSTM_LD + row] = lstm_actor_elu(acc[r]);
-                else if (unit < nA && env0 + row < A.num_envs) {
-                    const size_t at = (size_t)(env0 + row) * nA + unit;
-                    if (A.mean) A.mean[at] = acc[r];
-                    A.actions[at] = acc[r] + ns[row * 16 + unit];
-                }
-            }
-        }
-        __syncthreads();
-    }
+    lstm_actor_body<LG_LSTM_ACTOR_WAVES, 4>(A, (int)blockIdx.x, xa, xb, ns, LstmActorStores{});      // lg_lstm_actor_body.h
 }
 
 static size_t actor_lds_bytes(const int max_width) { return ((size_t)2 * max_width * LG_LSTM_LD + 32 * 16) * sizeof(float); }

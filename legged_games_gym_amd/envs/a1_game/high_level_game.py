@@ -14,6 +14,9 @@ high-level actor on the device as well, in three launches:
 
     lg_game_act (both actors + the clip)  ->  lg_step  ->  lg_game_post
 
+With a recurrent policy (``rl.RecurrentFusedActor``) it is four: ``lg_lstm_step`` (both memories) and ``lg_game_lstm_act``
+(include/legged_game_recurrent.h: the low-level actor and the actor MLP on the actor memory's output, with the clip) take ``lg_game_act``'s place.
+
 The low-level policy acts on the observation buffer as the last low-level step left it, so a new command reaches its input one step
 late -- as in the reference (:177-178).  That is also what lets ``lg_game_act`` run both actors side by side.
 
@@ -115,6 +118,8 @@ class HighLevelGame(GameBase):
         self._check_output("sample", sample, n * self.num_actions)
         self._check_output("sigma", sigma, n * self.num_actions)
         self._check_output("log_prob", log_prob, n)
+        if getattr(fused_actor, "recurrent", False):
+            return self._act_recurrent(fused_actor, obs_in, obs_out, deterministic, sample, sigma, log_prob)
         command, mean = fused_actor.output_buffers(n)
         ll_actions = self._ll_fused.output_buffers(n)[0]
         B = self._bind_command(command, obs_out)
@@ -137,12 +142,67 @@ class HighLevelGame(GameBase):
         ll_actions = self.ll_policy(ll.obs_buf)
         return command, mean, ll_actions, B
 
-    def step_policy(self, fused_actor, deterministic=False, sample=None, sigma=None, log_prob=None):
+    def _recurrent_launch(self, fused_actor, say=True):
+        """The bound ``lg_game_lstm_act`` library when the recurrent actor launch can be used now, else None (with a one-line message the
+        first time for each reason): the low-level role is the split-bf16 kernel, so wide precision 0 takes the separate launches, and so
+        does a build without the library.  Decided per call: ``lg_mlp_wide_set_precision`` may change between calls."""
+        why = None
+        if fused_actor.lib.lg_mlp_wide_set_precision(-1) != 1:        # (an invalid mode changes nothing and returns the current one)
+            why = "wide precision 0"
+        else:
+            try:
+                return capi.load_game_recurrent_library()
+            except (RuntimeError, OSError) as exc:
+                why = f"{type(exc).__name__}: {exc}"
+        self._say_separate(why, say)
+        return None
+
+    def _say_separate(self, why, say=True):
+        said = self.__dict__.setdefault("_separate_said", set())
+        if say and why not in said:
+            said.add(why)
+            print(f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act + lg_game_pre + lg_policy_act")
+
+    def _act_recurrent(self, fused_actor, obs_in, obs_out, deterministic, sample, sigma, log_prob):
+        """``_act`` for a ``RecurrentFusedActor``: ``lg_lstm_step`` on ``obs_in`` (both memories; a deterministic evaluation advances only
+        the actor memory), rows that ``reset_buf`` of the previous step marks starting from a zero state, then ``lg_game_lstm_act`` on the
+        new ``h``.  The critic memory's output of the step is left in ``self._critic_out`` (None when it did not move).  Separate launches
+        (``lg_lstm_actor_act`` + ``lg_game_pre`` + low-level ``lg_policy_act``) on rc -4, at wide precision 0 or without the library."""
+        ll, n = self.ll_env, self.num_envs
+        command, mean = fused_actor.output_buffers(n)
+        ll_actions = self._ll_fused.output_buffers(n)[0]
+        B = self._bind_command(command, obs_out)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        ptr = lambda t: None if t is None else t.data_ptr()
+        copy = obs_out is not obs_in
+        lib = self._recurrent_launch(fused_actor)
+        h_a, self._critic_out = fused_actor.step_memories(obs_in, None if deterministic else obs_in, reset=self.reset_buf)
+        if lib is not None:
+            step, ctr = fused_actor.peek_step()
+            rc = capi.game_lstm_act(fused_actor.handle, self._ll_fused.handle, self._P, B, h_a.data_ptr(), obs_in.data_ptr(), ll.obs_buf.data_ptr(),
+                                    ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step, ctr, deterministic, ptr(sample), ptr(sigma),
+                                    ptr(log_prob), obs_out.data_ptr() if copy else None, stream)
+            if rc == 0:
+                fused_actor.next_step()                        # the launch used this step of the actor's noise stream
+                return command, mean, ll_actions, B
+            self._say_separate("no kernel for this actor pair")
+        command, mean = fused_actor.fused.act_with_mean(h_a, deterministic)
+        self._fill_optional_outputs({"sample": sample, "sigma": sigma, "log_prob": log_prob, "obs_copy": obs_out if copy else None}, n, command, mean,
+                                    fused_actor.ac.std.detach(), obs_in)
+        capi.game_pre(self._P, B, stream)
+        ll_actions = self.ll_policy(ll.obs_buf)
+        return command, mean, ll_actions, B
+
+    def step_policy(self, fused_actor, deterministic=False, sample=None, sigma=None, log_prob=None, with_critic_memory=False):
         """Rollout step with the high-level actor on the device: ``lg_game_act`` -> ``lg_step`` -> ``lg_game_post``, three launches.
         Returns ``(command, mean), (obs, privileged_obs, rew, dones, extras)``: ``command`` is the clipped command (what ``step`` leaves in the
         caller's tensor), ``mean`` the actor's output; both are ``fused_actor``'s buffers.  Optional float32 outputs: ``sample`` [N,6] (the
         unclipped sample), ``sigma`` [N,6] and ``log_prob`` [N] of that sample (what ``PPO.act`` stores).  The observations the actor read
-        stay in the tensor returned by the previous call, as with ``step``."""
+        stay in the tensor returned by the previous call, as with ``step``.
+
+        A ``RecurrentFusedActor`` makes it four launches, ``lg_lstm_step`` -> ``lg_game_lstm_act`` -> ``lg_step`` -> ``lg_game_post``: its memories
+        advance on the observations, rows whose episode ended in the previous step from a zero state.  ``with_critic_memory`` then returns
+        the critic memory's output of the step as a third value of the first tuple (the actor's buffer, re-used two steps later)."""
         ll = self.ll_env
         prev = self.obs_buf
         self._obs_flip ^= 1
@@ -155,7 +215,8 @@ class HighLevelGame(GameBase):
             raise
         ll.step(ll_actions)
         self._post(B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
-        return (command, mean), (self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras)
+        head = (command, mean, self._critic_out) if with_critic_memory and getattr(fused_actor, "recurrent", False) else (command, mean)
+        return head, (self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras)
 
     def shared_actor_launch(self, fused_actor):
         """Whether ``lg_game_act`` has a kernel for ``fused_actor`` next to the low-level actor at the current wide precision (rc 0, not -4).
@@ -166,6 +227,15 @@ class HighLevelGame(GameBase):
         ll_actions = self._ll_fused.output_buffers(n)[0]
         B = self._bind_command(command, self.obs_buf)
         step, ctr = fused_actor.peek_step()
+        if getattr(fused_actor, "recurrent", False):
+            # lg_game_lstm_act on the actor memory's current output: the memories do not move
+            lib = self._recurrent_launch(fused_actor, say=False)
+            if fused_actor.num_envs != n:
+                fused_actor._allocate(n)
+            h = fused_actor.hidden_states()[0][0][0]
+            return lib is not None and capi.game_lstm_act(fused_actor.handle, self._ll_fused.handle, self._P, B, h.data_ptr(), None,
+                                                          self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step,
+                                                          ctr, True, None, None, None, None, torch.cuda.current_stream(self.device).cuda_stream) == 0
         return capi.game_act(fused_actor.handle, self._ll_fused.handle, self._P, B, self.obs_buf.data_ptr(), self.ll_env.obs_buf.data_ptr(),
                              ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step, ctr, True, None, None, None, None,
                              torch.cuda.current_stream(self.device).cuda_stream) == 0
@@ -179,8 +249,13 @@ class HighLevelGame(GameBase):
         sim = self.ll_env._sim
         self._require_device_step_counter(fused_actor)
 
+        # a recurrent actor's memories alternate between two state slots: an odd number of steps per replay brings the state back after every step
+        hold = getattr(fused_actor, "recurrent", False) and steps_per_replay % 2 == 1
+
         def device_step():
             _, _, ll_actions, B = self._act(fused_actor, self.obs_buf, self.obs_buf, deterministic)
+            if hold:
+                fused_actor.hold_slot()
             sim.step(ll_actions, -1)
             self._post(B, -1, torch.cuda.current_stream(self.device).cuda_stream)
         self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)

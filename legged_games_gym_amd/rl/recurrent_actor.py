@@ -109,16 +109,30 @@ class DeviceLstmActor:
         if rc != 0:
             raise RuntimeError(f"lg_lstm_actor_load_device failed ({rc}): {self.lib.lg_last_error().decode()}")
 
-    def act_with_mean(self, h, deterministic=False):
-        n = h.shape[0]
+    # what HighLevelGame._act reads of a FusedActor (the shared actor launch writes into these buffers and counts its own launch)
+    def output_buffers(self, n):
+        """(actions, mean) tensors the kernels write into (re-used between calls; clone to keep a value)."""
         if self._out is None or self._out[0].shape[0] != n:
             self._out = (torch.empty(n, self.num_actions, device=self.device), torch.empty(n, self.num_actions, device=self.device))
-        actions, mean = self._out
+        return self._out
+
+    def peek_step(self):
+        """``(step, step_counter)`` the next launch will use, without counting it (``FusedActor.peek_step``)."""
         if self.step_counter is not None:
-            step, ctr = -1, self.step_counter.data_ptr()
-        else:
-            self._host_step += 1
-            step, ctr = self._host_step, None
+            return -1, self.step_counter.data_ptr()
+        return self._host_step + 1, None
+
+    def next_step(self):
+        """``peek_step`` and count the launch."""
+        step, ctr = self.peek_step()
+        if ctr is None:
+            self._host_step = step
+        return step, ctr
+
+    def act_with_mean(self, h, deterministic=False):
+        n = h.shape[0]
+        actions, mean = self.output_buffers(n)
+        step, ctr = self.next_step()
         rc = self.lib.lg_lstm_actor_act(self.handle, h.data_ptr(), actions.data_ptr(), mean.data_ptr(), n, self.seed, step, ctr, int(deterministic),
                                         torch.cuda.current_stream(self.device).cuda_stream)
         if rc != 0:
@@ -154,6 +168,18 @@ class RecurrentFusedActor:
     seed = property(lambda self: self.fused.seed)
     step_counter = property(lambda self: self.fused.step_counter)
     num_actions = property(lambda self: self.fused.num_actions)
+    # ... and what HighLevelGame._act reads: the actor MLP's handle, buffers and step count; the marker selects lg_game_lstm_act there
+    recurrent = True
+    handle = property(lambda self: self.fused.handle)
+
+    def output_buffers(self, n):
+        return self.fused.output_buffers(n)
+
+    def peek_step(self):
+        return self.fused.peek_step()
+
+    def next_step(self):
+        return self.fused.next_step()
 
     def _allocate(self, n):
         z = lambda h: torch.zeros(n, h, device=self.device)
@@ -195,6 +221,15 @@ class RecurrentFusedActor:
                 dst.copy_(src)
         self._flip = 1 - f
         return self.state_a[1 - f][0], (self.state_c[1 - f][0] if with_c else None)
+
+    def hold_slot(self):
+        """Bring the state the last ``step_memories`` wrote back into the slots it read, and read from there again: a captured graph with an
+        odd number of steps then starts every replay from the same addresses.  The returned outputs of that step stay valid."""
+        f = self._flip
+        for st in (self.state_a, self.state_c):
+            for dst, src in zip(st[1 - f], st[f]):
+                dst.copy_(src)
+        self._flip = 1 - f
 
     def peek_critic(self, critic_obs, reset=None):
         """The critic memory's output for ``critic_obs`` from the carried state, which stays where it is (the last value of a rollout)."""

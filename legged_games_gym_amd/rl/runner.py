@@ -75,12 +75,14 @@ class OnPolicyRunner:
 
     def _make_recurrent_fused_actor(self):
         """Recurrent policy: both memories in one ``lg_lstm_step`` launch, then the MFMA actor on the actor memory's output, per step
-        (``RecurrentFusedActor``); the critic MLP once per rollout on the critic memory's outputs of all T steps.  Locomotion envs only;
-        a memory the device cell does not cover (GRU, several layers, more than 256 units) or privileged observations take the torch loop."""
+        (``RecurrentFusedActor``); the critic MLP once per rollout on the critic memory's outputs of all T steps.  A memory the device cell
+        does not cover (GRU, several layers, more than 256 units) or privileged observations take the torch loop.  The single-policy game
+        tasks with ``device_rollout``: the same actor through ``env.step_policy`` (lg_lstm_step -> lg_game_lstm_act -> lg_step -> post)."""
         env, ac = self.env, self.alg.actor_critic
-        if self.cfg.get("device_rollout", False) and hasattr(env, "ll_env"):
-            print("[runner] device rollout unavailable (the game actor kernels have no recurrent policy); generic VecEnv loop")
-            return None
+        if hasattr(env, "ll_env"):
+            if not self.cfg.get("device_rollout", False):
+                return None
+            return self._make_recurrent_game_actor()
         if not (str(self.device).startswith("cuda") and self.cfg.get("fused_rollout", True) and hasattr(env, "_sim")):
             return None
         from .recurrent_actor import RecurrentFusedActor, lstm_unsupported_reason
@@ -100,6 +102,35 @@ class OnPolicyRunner:
         self._critic_features = torch.zeros(T, N, ac.memory_c.rnn.hidden_size, device=self.device)     # the critic memory's output of every step
         self._fused_step, self._rolled = False, False         # neither lg_step_policy nor lg_rollout_policy has a recurrent kernel
         self._recurrent_rollout = True
+        return fused
+
+    def _make_recurrent_game_actor(self):
+        """``device_rollout`` of ``high_level_game`` / ``scripted_predator_game`` with a recurrent policy; None (and why) where it cannot run."""
+        env, ac = self.env, self.alg.actor_critic
+        from .recurrent_actor import RecurrentFusedActor, lstm_unsupported_reason
+        why = None
+        if not str(self.device).startswith("cuda"):
+            why = f"the policy is on {self.device}, the game actor kernels run on a GPU"
+        elif not hasattr(env, "step_policy") or getattr(env, "dec_agent_view", False):
+            why = "the game actor kernels have no recurrent policy for this task"
+        elif env.num_privileged_obs is not None:
+            why = "privileged observations"
+        else:
+            why = lstm_unsupported_reason(ac.memory_a.rnn) or lstm_unsupported_reason(ac.memory_c.rnn)
+            why = why and f"no device LSTM cell for a {why}"
+        if why is None:
+            try:
+                fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
+                                            step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs)
+                env.shared_actor_launch(fused)                # raises the new kernel's LDS limit here, outside any capture; False = separate launches
+            except Exception as exc:
+                why = f"{type(exc).__name__}: {exc}"
+        if why is not None:
+            print(f"[runner] device rollout unavailable ({why}); generic VecEnv loop")
+            return None
+        T, N = self.num_steps_per_env, env.num_envs
+        self._critic_features = torch.zeros(T, N, ac.memory_c.rnn.hidden_size, device=self.device)     # the critic memory's output of every step
+        self._game_rollout = self._recurrent_rollout = True
         return fused
 
     def _recurrent_last_values(self, critic_obs):
@@ -263,9 +294,21 @@ class OnPolicyRunner:
         step.cur_return, step.cur_length, step.sums = p(stats["cur_rew"]), p(stats["cur_len"]), p(stats["_sums"])
         stream = torch.cuda.current_stream(self.device).cuda_stream
         step.std, step.time_outs, step.storage_time_outs = None, None, None
+        rec = self._recurrent_rollout
+        if rec:
+            # as _rollout_steps_fused: the state this rollout starts from, once; rows whose episode ended in the last step start from zeros
+            st.save_initial_hidden_states(fused.hidden_states())
+            keep = (env.reset_buf == 0).view(1, -1, 1)
+            for hid in st.initial_hidden_a + st.initial_hidden_c:
+                hid.mul_(keep)
         for t in range(T):
             prev_obs = obs
-            (command, mean), (obs, _, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t])
+            if rec:                                               # lg_lstm_step -> lg_game_lstm_act -> lg_step -> post
+                (command, mean, h_c), (obs, _, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t],
+                                                                                        with_critic_memory=True)
+                self._critic_features[t].copy_(h_c)
+            else:
+                (command, mean), (obs, _, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t])
             step.obs, step.actions, step.mean, step.rewards, step.dones = p(prev_obs), p(command), p(mean), p(rewards), p(dones)
             touts = infos.get("time_outs") if dec else None
             if touts is not None:                                 # (absent with env.send_timeouts = False: nothing is bootstrapped then)
@@ -278,7 +321,11 @@ class OnPolicyRunner:
             if rc != 0:
                 raise RuntimeError(f"lg_rollout_record failed ({rc}): {lib.lg_last_error().decode()}")
         st.step = T
-        st.values.copy_(self._critic_values(st).view(T, -1, 1))
+        if rec:
+            st.values.copy_(alg.actor_critic.critic(self._critic_features.flatten(0, 1)).view(T, -1, 1))      # critic MLP once on the memory's outputs of all steps
+            fused.publish_states(env.reset_buf)                                                              # the torch memories follow the device state
+        else:
+            st.values.copy_(self._critic_values(st).view(T, -1, 1))
         if dec:
             st.rewards.add_(alg.gamma * st.values * self._time_outs)                           # bootstrap on time-outs (PPO.process_env_step)
         return obs, obs

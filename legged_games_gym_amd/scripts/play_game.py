@@ -5,8 +5,9 @@
 
 The newest checkpoint of the task is loaded through the runner, as ``scripts/play.py`` does; the outcome statistics of the env are switched
 on (include/legged_game_outcome.h) and ``S`` high-level steps (default: 2 x ``max_episode_length``) are rolled out with the deterministic
-policy -- as replays of the graphed three-launch policy step where ``lg_game_act`` has a kernel for the actor pair, else through ``step()``
-with the runner's inference policy.  The totals are read ONCE, at the end.  A table is printed and ``outcomes_<iteration>.json`` is written
+policy -- as replays of the graphed three-launch policy step where ``lg_game_act`` has a kernel for the actor pair (four launches with a
+recurrent checkpoint, ``--policy_class_name ActorCriticRecurrent`` and the ``--rnn_*`` flags it was trained with: ``lg_lstm_step`` and
+``lg_game_lstm_act`` in front), else through ``step()`` with the runner's inference policy.  The totals are read ONCE, at the end.  A table is printed and ``outcomes_<iteration>.json`` is written
 next to the checkpoint: ``totals`` (the seven integers of ``env.outcome_totals()``; its ``steps`` is the summed length of the finished
 episodes), ``rates`` (the five flags over ``episodes``), ``mean_steps``, ``num_envs`` and ``steps`` (the ``S`` of the rollout).
 
@@ -22,7 +23,7 @@ import legged_games_gym_amd.utils.task_registry as registry_module
 from legged_games_gym_amd.envs import *  # noqa: F401,F403
 from legged_games_gym_amd.envs import a1_game
 from legged_games_gym_amd.utils import get_args
-from legged_games_gym_amd.utils.helpers import get_load_path
+from legged_games_gym_amd.utils.helpers import apply_policy_args, get_load_path
 from legged_games_gym_amd.utils.task_registry import task_registry
 
 COUNTS = ("episodes", "captured", "prey_out", "predator_out", "fell", "survived", "steps")
@@ -63,6 +64,7 @@ def play_game(args, steps=None):
     env_cfg.domain_rand.push_robots = False
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     train_cfg.runner.resume = True
+    apply_policy_args(train_cfg, args)      # --policy_class_name ActorCriticRecurrent [--rnn_*]: the flags the checkpoint was trained with
     runner, train_cfg = task_registry.make_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg)
     log_root = os.path.join(registry_module.LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name)
     checkpoint = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
@@ -74,9 +76,15 @@ def play_game(args, steps=None):
     if str(env.device).startswith("cuda"):
         from legged_games_gym_amd.rl import FusedActor
         try:
-            fused = FusedActor(runner.alg.actor_critic, env.device, seed=int(getattr(env.cfg, "seed", 1)), step_counter=env.ll_env._sim.buf["step_counter"])
+            ac, kw = runner.alg.actor_critic, dict(seed=int(getattr(env.cfg, "seed", 1)), step_counter=env.ll_env._sim.buf["step_counter"])
+            if ac.is_recurrent:             # memories from zero, lg_lstm_step -> lg_game_lstm_act -> lg_step -> post per step
+                from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor
+                fused = RecurrentFusedActor(ac, env.device, num_envs=env.num_envs, **kw)
+            else:
+                fused = FusedActor(ac, env.device, **kw)
             if env.shared_actor_launch(fused):
-                replay = env.make_graphed_policy_step(fused, deterministic=True)
+                with torch.inference_mode():        # as the runner captures its rollouts: torch's per-capture generator state may stem from such a capture
+                    replay = env.make_graphed_policy_step(fused, deterministic=True)
         except ValueError as exc:           # an actor the MFMA kernels have no shape for
             print(f"[play_game] device policy step unavailable ({exc}); stepping through the inference policy")
     env.reset_outcome_totals()              # (the capture's warm-up steps are not part of the evaluation)

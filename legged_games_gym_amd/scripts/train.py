@@ -16,7 +16,8 @@ length, as ``Episode/outcome_*``.
 
 ``--policy_class_name ActorCriticRecurrent [--rnn_type lstm --rnn_hidden_size 256 --rnn_num_layers 1]`` trains an LSTM policy (rsl_rl's class
 of that name): on a locomotion task on the GPU the memories and the actor run on the device in the rollout (``lg_lstm_step``), the update is
-back-propagation through time in torch; the game tasks take the generic loop.  ``--device_bptt`` (off by default) moves the recurrence of
+back-propagation through time in torch; ``high_level_game`` / ``scripted_predator_game`` take the generic loop, or with ``--device_rollout`` four
+launches per step (``lg_lstm_step`` -> ``lg_game_lstm_act`` -> ``lg_step`` -> the post kernel), the rollout one graph replay.  ``--device_bptt`` (off by default) moves the recurrence of
 that update onto the device as well: both memories' padded trajectories run through time in ``lg_lstm_seq_forward`` / ``lg_lstm_seq_backward``
 (one launch each way per memory and mini-batch); the MLPs, the loss and Adam stay in torch."""
 import os

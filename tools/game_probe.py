@@ -25,6 +25,16 @@ update, same seed and size).  With ``--trace`` it replays (p) only.
 policy step, alternating: k_outcome_post<false> against k_game_post and k_outcome_post<true> against k_pursuer_post in the same run; writes
 profiles/game_outcome_step.json.
 
+``--recurrent`` times the recurrent policy's device path (a random-init ``ActorCriticRecurrent``, ``--rnn-hidden`` units per memory, the
+512-256-128 actor behind it) and writes profiles/game_recurrent_step.json, per step of a two-step graph (the memories alternate between two
+state slots), alternating in one process:
+  (r) the four-launch step: lg_lstm_step, lg_game_lstm_act, k_step, k_game_post;
+  (s) the same graph with the policy stage as separate launches: lg_lstm_step, lg_lstm_actor_act, k_game_pre, lg_policy_act, k_step, k_game_post;
+  (f) the feed-forward three-launch step of the same env: lg_game_act, k_step, k_game_post;
+then, unless ``--train-iterations 0``, PPO training with ``ActorCriticRecurrent`` and the runner's ``device_rollout`` on and off: env-steps/s
+including the update, and the rollout's and the update's share of an iteration from synchronised stamps around every update.  With ``--trace``
+it replays (r) only.
+
 The low-level policy is a seeded random-init checkpoint written to a temporary directory: the kernels' cost does not depend on the weights."""
 import argparse
 import json
@@ -137,29 +147,53 @@ def graph_rollout_steps(env, fused, steps, separate_copy):
     return replay
 
 
-def train_steps_per_s(n, mesh, tmp, device_rollout, iterations, warm=2):
-    """env-steps/s of ``OnPolicyRunner.learn`` on high_level_game (rollout + update), after ``warm`` iterations that build graphs and workspaces."""
+def train_steps_per_s(n, mesh, tmp, device_rollout, iterations, warm=2, rnn_hidden=None):
+    """env-steps/s of ``OnPolicyRunner.learn`` on high_level_game (rollout + update), after ``warm`` iterations that build graphs and workspaces.
+    ``rnn_hidden``: train an ``ActorCriticRecurrent`` with that many units per memory."""
     import time
     from legged_games_gym_amd.envs import a1_game, task_registry
     from legged_games_gym_amd.utils import get_args
+    from legged_games_gym_amd.utils.helpers import apply_policy_args
     a1_game.register()
     try:
         env_cfg, train_cfg = task_registry.get_cfgs("high_level_game")
         env_cfg.env.ll_policy_path, env_cfg.terrain.mesh_type = os.path.join(tmp, "model_0.pt"), mesh
         if device_rollout:
             train_cfg.runner.device_rollout = True
-        args = get_args(["--task", "high_level_game", "--num_envs", str(n), "--headless", "--sim_device", "cuda:0", "--rl_device", "cuda:0", "--seed", "1"])
+        args = get_args(["--task", "high_level_game", "--num_envs", str(n), "--headless", "--sim_device", "cuda:0", "--rl_device", "cuda:0", "--seed", "1"]
+                        + (["--policy_class_name", "ActorCriticRecurrent", "--rnn_hidden_size", str(rnn_hidden)] if rnn_hidden else []))
+        apply_policy_args(train_cfg, args)
         env, _ = task_registry.make_env("high_level_game", args)
         torch.manual_seed(1)
         runner, _ = task_registry.make_alg_runner(env, "high_level_game", args, log_root=None)
+        marks = []
+        if rnn_hidden:                                 # where an iteration's time goes: synchronised stamps around every update
+            update = runner.alg.update
+
+            def stamped_update(*a, **k):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                out = update(*a, **k)
+                torch.cuda.synchronize()
+                marks.append((t, time.perf_counter()))
+                return out
+            runner.alg.update = stamped_update
         runner.learn(num_learning_iterations=warm)
         torch.cuda.synchronize()
+        del marks[:]
         t0 = time.perf_counter()
         runner.learn(num_learning_iterations=iterations)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         assert (runner._fused is not None) == bool(device_rollout)
-        return iterations * runner.num_steps_per_env * n / dt
+        rate = iterations * runner.num_steps_per_env * n / dt
+        if not rnn_hidden:
+            return rate
+        # rollout = from the end of one update to the start of the next (graph replay or the generic loop, returns, the actor's device repack)
+        rollouts = [1e3 * (marks[i][0] - marks[i - 1][1]) for i in range(1, len(marks))]
+        updates = [1e3 * (b - a) for a, b in marks]
+        return {"env_steps_per_s": rate, "rollout_ms": {"median": statistics.median(rollouts), "min": min(rollouts), "max": max(rollouts)},
+                "update_ms": {"median": statistics.median(updates), "min": min(updates), "max": max(updates)}}
     finally:
         a1_game.unregister()
 
@@ -215,6 +249,68 @@ def policy_step_main(args):
         with open(out, "w") as fh:
             json.dump(result, fh, indent=1)
         print("wrote", out)
+
+
+def recurrent_main(args):
+    """The recurrent policy's graphed step against the same graph with the policy stage as separate launches and against the feed-forward
+    three-launch step, per step of a two-step graph; then training with the runner's switch on and off."""
+    from legged_games_gym_amd.rl import ActorCriticRecurrent
+    from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.replays, "repeats": args.repeats,
+              "rnn_hidden_size": args.rnn_hidden, "steps_per_replay": 2, "envs": {}, "training": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            env, _ = make_env(n, args.mesh, tmp)
+            torch.manual_seed(1)
+            ac = ActorCriticRecurrent(env.num_obs, env.num_obs, env.num_actions, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128],
+                                      rnn_hidden_size=args.rnn_hidden).to("cuda:0").eval()
+            counter = env.ll_env._sim.buf["step_counter"]
+            one = RecurrentFusedActor(ac, "cuda:0", seed=7, step_counter=counter, num_envs=n)
+            assert env.shared_actor_launch(one), "lg_game_lstm_act refused the probe's actor pair"
+            four = env.make_graphed_policy_step(one, steps_per_replay=2)
+            if args.trace:
+                for _ in range(200):
+                    four()
+                torch.cuda.synchronize()
+                continue
+            apart = RecurrentFusedActor(ac, "cuda:0", seed=7, step_counter=counter, num_envs=n)
+            env._recurrent_launch = lambda *a, **k: None           # the policy stage as separate launches, for this capture only
+            try:
+                six = env.make_graphed_policy_step(apart, steps_per_replay=2)
+            finally:
+                del env._recurrent_launch
+            three = env.make_graphed_policy_step(fused_high_level_actor(env), steps_per_replay=2)
+            for fn in (four, six, three):
+                timed(fn, 100)
+            r, s, f = [], [], []
+            for _ in range(args.repeats):              # alternating: other work shares the machine
+                r.append(timed(four, args.replays // 2) / 2)
+                s.append(timed(six, args.replays // 2) / 2)
+                f.append(timed(three, args.replays // 2) / 2)
+            gain = [y - x for x, y in zip(r, s)]
+            result["envs"][str(n)] = {"recurrent_four_launch_step": spread(r), "recurrent_separate_policy_launches": spread(s),
+                                      "feed_forward_three_launch_step": spread(f), "separate_minus_one_launch": spread(gain),
+                                      "env_steps_per_s_recurrent_four_launch_step": n / (statistics.median(r) * 1e-6)}
+            assert torch.isfinite(env.obs_buf).all() and torch.isfinite(env.ll_env.root_states).all()
+            assert all(bool(torch.isfinite(t).all()) for pair in one.hidden_states() for t in pair)
+            print(f"{n} envs, per step: four launches {statistics.median(r):.1f} us ({min(r):.1f} .. {max(r):.1f}), separate policy launches "
+                  f"{statistics.median(s):.1f} us ({min(s):.1f} .. {max(s):.1f}), difference {statistics.median(gain):+.2f} us ({min(gain):+.2f} .. "
+                  f"{max(gain):+.2f}), feed-forward three launches {statistics.median(f):.1f} us ({min(f):.1f} .. {max(f):.1f})", flush=True)
+        if args.trace:
+            return
+        if args.train_iterations > 0:
+            n = args.envs[0]
+            for key, on in (("device_rollout_off", False), ("device_rollout_on", True)):
+                t = train_steps_per_s(n, args.mesh, tmp, on, args.train_iterations, rnn_hidden=args.rnn_hidden)
+                result["training"][key] = dict({"envs": n, "iterations": args.train_iterations}, **t)
+                print(f"training, recurrent policy, {n} envs, {key}: {t['env_steps_per_s']:.0f} env-steps/s; per iteration: rollout of 24 steps "
+                      f"{t['rollout_ms']['median']:.2f} ms ({t['rollout_ms']['min']:.2f} .. {t['rollout_ms']['max']:.2f}), update "
+                      f"{t['update_ms']['median']:.1f} ms ({t['update_ms']['min']:.1f} .. {t['update_ms']['max']:.1f})", flush=True)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "game_recurrent_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
 
 
 def scripted_main(args):
@@ -319,10 +415,14 @@ def main():
     ap.add_argument("--train-iterations", type=int, default=10, help="--policy-step: timed PPO iterations per setting of the runner switch (0: skip)")
     ap.add_argument("--scripted", action="store_true", help="time scripted_predator_game's graphed policy step beside high_level_game's; writes profiles/pursuer_step.json")
     ap.add_argument("--outcome", action="store_true", help="time the graphed policy step of both tasks with the outcome statistics off and on; writes profiles/game_outcome_step.json")
+    ap.add_argument("--recurrent", action="store_true", help="time the recurrent policy's graphed step against separate policy launches and the feed-forward step; writes profiles/game_recurrent_step.json")
+    ap.add_argument("--rnn-hidden", type=int, default=256, help="--recurrent: units per memory")
     ap.add_argument("--trace", action="store_true", help="a short loop of graph replays only (for a kernel trace)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("game_probe needs an AMD GPU: there is nothing to time on the CPU")
+    if args.recurrent:
+        return recurrent_main(args)
     if args.outcome:
         return outcome_main(args)
     if args.scripted:
