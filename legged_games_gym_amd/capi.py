@@ -765,6 +765,97 @@ def game_lstm_act(hl_actor, ll_policy, params: lg_game_params, buffers: lg_game_
     return rc
 
 
+# ---------------------------------------------------------------------------------------------------------------- legged_dec_game_recurrent.h
+# The recurrent policy stage of dec_high_level_game, a fourth library (csrc/liblegged_dec_game_recurrent.so): outside ABI / ALL_SYMBOLS /
+# bind_all.  It reads the lg_lstm / lg_lstm_actor / lg_policy handles liblegged_hip.so created.
+class lg_dec_lstm_role(C.Structure):
+    """include/legged_dec_game_recurrent.h: lg_dec_lstm_role (one memory of the cell launch: handle or None, device addresses)."""
+    _fields_ = [("l", C.c_void_p), ("x", C.c_void_p), ("h_in", C.c_void_p), ("c_in", C.c_void_p), ("h_out", C.c_void_p), ("c_out", C.c_void_p)]
+
+
+DEC_GAME_RECURRENT_ABI = {
+    "lg_dec_lstm_step": ([_P(lg_dec_lstm_role), _vp, i32, _vp], _int),
+    "lg_dec_game_lstm_act": ([_vp, _vp, _vp, _P(lg_dec_game_params), _P(lg_dec_game_buffers), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, u64, u64, i64, _vp,
+                              i32, i32, _P(lg_dec_act_outputs), _P(lg_dec_act_outputs), _vp], _int),
+    "lg_dec_game_recurrent_last_error": ([], C.c_char_p),
+    "lg_dec_game_recurrent_sizeof": _SIZEOF,
+}
+DEC_GAME_RECURRENT_SYMBOLS = list(DEC_GAME_RECURRENT_ABI)
+# what lg_dec_game_recurrent_sizeof sizes by index (3, 4, 5: the three handles, opaque here)
+DEC_GAME_RECURRENT_STRUCTS = {0: lg_dec_game_params, 1: lg_dec_game_buffers, 2: lg_dec_act_outputs, 6: lg_dec_lstm_role}
+DEC_LSTM_ROLES = ("pred_actor", "pred_critic", "prey_actor", "prey_critic")      # the order of lg_dec_lstm_step's roles
+_DEC_GAME_RECURRENT_LIB_NAME = "liblegged_dec_game_recurrent.so"
+_dec_game_recurrent_lib = None
+
+
+def dec_game_recurrent_library_path() -> str:
+    """In-tree liblegged_dec_game_recurrent.so; LG_DEC_GAME_RECURRENT_LIB selects another build of the same source."""
+    return os.environ.get("LG_DEC_GAME_RECURRENT_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_GAME_RECURRENT_LIB_NAME)
+
+
+def bind_dec_game_recurrent(lib):
+    for symbol, (argtypes, restype) in DEC_GAME_RECURRENT_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    for which, st in DEC_GAME_RECURRENT_STRUCTS.items():
+        size = lib.lg_dec_game_recurrent_sizeof(which)
+        if size != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def load_dec_game_recurrent_library():
+    """Load the recurrent policy stage of dec_high_level_game or fail loudly -- never a CPU substitute."""
+    global _dec_game_recurrent_lib
+    if _dec_game_recurrent_lib is not None:
+        return _dec_game_recurrent_lib
+    path = dec_game_recurrent_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _dec_game_recurrent_lib = bind_dec_game_recurrent(C.CDLL(path))
+    return _dec_game_recurrent_lib
+
+
+def dec_lstm_roles(roles) -> "C.Array":
+    """``lg_dec_lstm_role[4]`` from four entries in the order of ``DEC_LSTM_ROLES``: None (absent), or
+    ``(handle, x, h_in, c_in, h_out, c_out)`` with device addresses."""
+    if len(roles) != 4:
+        raise ValueError("lg_dec_lstm_step takes four roles (None = absent)")
+    arr = (lg_dec_lstm_role * 4)()
+    for slot, role in zip(arr, roles):
+        if role is not None:
+            slot.l, slot.x, slot.h_in, slot.c_in, slot.h_out, slot.c_out = (getattr(v, "value", v) for v in role)
+    return arr
+
+
+def dec_lstm_step(roles, reset: Optional[int], num_envs: int, stream: int = 0) -> None:
+    """``lg_dec_lstm_step``: up to four memories advanced in one launch.  ``roles``: what ``dec_lstm_roles`` takes, or its result (kept by
+    a caller that replays the same launch)."""
+    lib = load_dec_game_recurrent_library()
+    arr = roles if isinstance(roles, C.Array) else dec_lstm_roles(roles)
+    rc = lib.lg_dec_lstm_step(arr, reset, int(num_envs), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_lstm_step failed ({rc}): {lib.lg_dec_game_recurrent_last_error().decode()}")
+
+
+def dec_game_lstm_act(pred_actor, prey_actor, ll_policy, params: lg_dec_game_params, buffers: lg_dec_game_buffers, h_pred: int, h_prey: int,
+                      pred_obs: Optional[int], prey_obs: Optional[int], ll_obs: int, ll_actions: int, mean_pred: int, mean_prey: int, seed_pred: int,
+                      seed_prey: int, step: int, step_counter: Optional[int], deterministic_pred: bool, deterministic_prey: bool,
+                      out_pred: Optional[lg_dec_act_outputs] = None, out_prey: Optional[lg_dec_act_outputs] = None, stream: int = 0) -> int:
+    """``lg_dec_game_lstm_act``: ``lg_dec_game_act`` for recurrent agents (``lg_lstm_actor`` handles on the actor memories' ``h``).
+    Returns 0, or -4 when the actors have no shared kernel (the caller then issues the separate launches); raises on any other error."""
+    lib = load_dec_game_recurrent_library()
+    rc = lib.lg_dec_game_lstm_act(pred_actor, prey_actor, ll_policy, C.byref(params), C.byref(buffers), h_pred, h_prey, pred_obs, prey_obs, ll_obs, ll_actions,
+                                  mean_pred, mean_prey, int(seed_pred), int(seed_prey), int(step), step_counter, int(bool(deterministic_pred)),
+                                  int(bool(deterministic_prey)), C.byref(out_pred) if out_pred is not None else None,
+                                  C.byref(out_prey) if out_prey is not None else None, stream)
+    if rc not in (0, -4):
+        raise RuntimeError(f"lg_dec_game_lstm_act failed ({rc}): {lib.lg_dec_game_recurrent_last_error().decode()}")
+    return rc
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

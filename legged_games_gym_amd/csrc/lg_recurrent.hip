@@ -7,6 +7,7 @@
 #include "lg_device.h"             // rand4: the Philox stream of the actor kernels
 #include "lg_recurrent.h"
 #include "lg_lstm_actor_body.h"      // the actor MLP of k_lstm_actor, shared with the game layer's recurrent actor launch
+#include "lg_lstm_cell_body.h"       // the cell of k_lstm_cell, shared with the cell launch of the decentralised game
 #include "../../include/legged_recurrent.h"
 
 #define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return lg::fail(-10, "HIP error: %s", hipGetErrorString(_e)); } while (0)
@@ -34,68 +35,6 @@ __global__ void __launch_bounds__(256) k_lstm_pack(const float *__restrict__ w_i
         const int unit = idx - n_w;
         bp[unit] = make_float4(b_ih[unit] + b_hh[unit], b_ih[hidden + unit] + b_hh[hidden + unit],
                                b_ih[2 * hidden + unit] + b_hh[2 * hidden + unit], b_ih[3 * hidden + unit] + b_hh[3 * hidden + unit]);
-    }
-}
-
-// 1-ulp v_exp_f32 / v_rcp_f32 (the build's fast-math convention): sigma saturates to exactly 0 / 1 and tanh to -1 / 1 through inf
-__device__ __forceinline__ float lstm_sigmoid(const float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(-1.44269504088896341f * x)); }
-__device__ __forceinline__ float lstm_tanh(const float x) { return 1.0f - 2.0f / (1.0f + __builtin_amdgcn_exp2f(2.88539008177792681f * x)); }
-
-// One role's workgroup: env rows 32 blk .. 32 blk + 31, all hidden units (hidden / 32 waves).
-__device__ __forceinline__ void lstm_cell_role(const LstmRole &R, const uint8_t *__restrict__ reset, const int num_envs, const int blk, float *xs) {
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int I = R.num_in, H = R.hidden, K = I + H, nthreads = 2 * H;            // 64 threads per 32 hidden units
-    const bool active = wave < H / 32;                                            // (the launch is sized for the wider role: the
-    const int env0 = 32 * blk;
-    if (active) {                                                                 //  narrower one's surplus waves only meet the barrier)
-        // stage [x | h_in] of the 32 rows as xs[k][row]; rows past num_envs and the pad row k = K are zeros, a reset row's h is zero
-        for (int e = tid; e < 32 * I; e += nthreads) {
-            const int row = e / I, k = e - row * I, env = env0 + row;
-            xs[k * LG_LSTM_LD + row] = env < num_envs ? R.x[(size_t)env * I + k] : 0.0f;
-        }
-        for (int e = tid; e < 32 * H; e += nthreads) {
-            const int row = e / H, k = e - row * H, env = env0 + row;
-            const bool live = env < num_envs && !(reset && reset[env]);
-            xs[(I + k) * LG_LSTM_LD + row] = live ? R.h_in[(size_t)env * H + k] : 0.0f;
-        }
-        if ((K & 1) && tid < 32) xs[K * LG_LSTM_LD + tid] = 0.0f;                     // the pad row of an odd K (the buffer holds 2 ksteps = K + 1 rows then)
-    }
-    __syncthreads();
-    if (!active) return;
-
-    const int unit = 32 * wave + (lane & 31);
-    const float4 b = ((const float4 *)R.bp)[unit];
-    f32x16 acc_i, acc_f, acc_g, acc_o;
-#pragma unroll
-    for (int r = 0; r < 16; r++) { acc_i[r] = b.x; acc_f[r] = b.y; acc_g[r] = b.z; acc_o[r] = b.w; }
-    const float4 *__restrict__ wp = (const float4 *)R.wp + (size_t)wave * R.ksteps * 64 + lane;
-    const float *xl = xs + (lane >> 5) * LG_LSTM_LD + (lane & 31);
-#define LG_LSTM_KSTEP(W_, A_) \
-    acc_i = __builtin_amdgcn_mfma_f32_32x32x2f32(A_, W_.x, acc_i, 0, 0, 0); acc_f = __builtin_amdgcn_mfma_f32_32x32x2f32(A_, W_.y, acc_f, 0, 0, 0); \
-    acc_g = __builtin_amdgcn_mfma_f32_32x32x2f32(A_, W_.z, acc_g, 0, 0, 0); acc_o = __builtin_amdgcn_mfma_f32_32x32x2f32(A_, W_.w, acc_o, 0, 0, 0);
-    int s = 0;
-    for (; s + 4 <= R.ksteps; s += 4) {           // four k-steps' operands in flight: 4 KB of weights per wave and trip
-        const float4 w0 = wp[(size_t)s * 64], w1 = wp[(size_t)(s + 1) * 64], w2 = wp[(size_t)(s + 2) * 64], w3 = wp[(size_t)(s + 3) * 64];
-        const float a0 = xl[2 * s * LG_LSTM_LD], a1 = xl[(2 * s + 2) * LG_LSTM_LD], a2 = xl[(2 * s + 4) * LG_LSTM_LD], a3 = xl[(2 * s + 6) * LG_LSTM_LD];
-        LG_LSTM_KSTEP(w0, a0) LG_LSTM_KSTEP(w1, a1) LG_LSTM_KSTEP(w2, a2) LG_LSTM_KSTEP(w3, a3)
-    }
-    for (; s < R.ksteps; s++) {
-        const float4 w = wp[(size_t)s * 64];
-        const float a = xl[2 * s * LG_LSTM_LD];
-        LG_LSTM_KSTEP(w, a)
-    }
-#undef LG_LSTM_KSTEP
-    // cell update straight from the accumulators: register r is env row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column = unit
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int env = env0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (env < num_envs) {
-            const size_t o = (size_t)env * H + unit;
-            const float c_prev = (reset && reset[env]) ? 0.0f : R.c_in[o];
-            const float c = lstm_sigmoid(acc_f[r]) * c_prev + lstm_sigmoid(acc_i[r]) * lstm_tanh(acc_g[r]);
-            R.c_out[o] = c;
-            R.h_out[o] = lstm_sigmoid(acc_o[r]) * lstm_tanh(c);
-        }
     }
 }
 

@@ -14,6 +14,10 @@ positions, four visibility flags) to its command ``(lin_vel_x, lin_vel_y, ang_ve
 
     lg_dec_game_act (three actors + the clips)  ->  lg_step  ->  lg_dec_game_post
 
+With recurrent policies (two ``rl.RecurrentFusedActor``) it is four, ``lg_dec_lstm_step`` (the actor memories of both agents and the critic
+memories the caller asks for, one launch) and ``lg_dec_game_lstm_act`` (include/legged_dec_game_recurrent.h: the three actors on the actor
+memories' outputs, with the clips) taking ``lg_dec_game_act``'s place.
+
 Outcome statistics (off by default; ``env.outcome_stats = True`` on the config object or ``enable_outcome_stats()``): the last launch of
 every step path becomes ``lg_dec_outcome_post`` (include/legged_dec_game_outcome.h), which writes what ``lg_dec_game_post`` writes, bit for
 bit, and also counts inside the launch why the done envs' episodes ended.  ``extras["episode"]`` then additionally holds five device scalars
@@ -156,7 +160,8 @@ class DecHighLevelGame(GameBase):
         return replay
 
     # ------------------------------------------------------------------ hot path with both actors on the device
-    def _act(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_pred_out, obs_prey_out, deterministic_pred, deterministic_prey, out_pred=None, out_prey=None):
+    def _act(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_pred_out, obs_prey_out, deterministic_pred, deterministic_prey, out_pred=None, out_prey=None,
+             with_critic_memory=()):
         """``lg_dec_game_act``: both commands = clip(actor(obs) + noise), the prey's into the low-level commands, the low-level actions, and
         the prey's observations copied to ``obs_prey_out`` (where ``lg_dec_game_post`` then shifts the history in place) -- one launch.
         Separate launches when the actor triple or the wide precision has no shared kernel (rc -4).  ``out_*``: dicts of optional float32
@@ -165,10 +170,12 @@ class DecHighLevelGame(GameBase):
         (include/legged_dec_game_pool.h), which takes that role's weights, biases and std per 32-env block from the pool member its slot table
         names; the pool's ``live`` actor supplies seed, step source and output buffers.  Its rc -4 path is one ``lg_policy_act`` on all envs
         per member in use, rows selected by block.
+        Two ``RecurrentFusedActor`` s take ``_act_recurrent`` (``with_critic_memory``: the agents whose critic memory moves too).
         Returns ``(command_pred, mean_pred), (command_prey, mean_prey), ll_actions, buffers``."""
         ll, n = self.ll_env, self.num_envs
         pool_pred, pool_prey = (f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey))
         fused_pred, fused_prey = _live(fused_pred), _live(fused_prey)
+        recurrent = self._recurrent_pair(fused_pred, fused_prey, pool_pred, pool_prey)
         for name, t, width in (("predator", obs_pred_in, self.num_obs_pred), ("prey", obs_prey_in, self.num_obs_prey)):
             if t.shape != (n, width) or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError(f"{name} observations must be a contiguous float32 [{n},{width}] tensor")
@@ -202,6 +209,9 @@ class DecHighLevelGame(GameBase):
             raise ValueError("the two FusedActors must count their noise steps alike (both on the low-level sim's device step counter, or both on the host)")
         if fused_pred.seed == fused_prey.seed:
             raise ValueError("the two FusedActors need different seeds: they draw their noise under the same purposes")
+        if recurrent:
+            return self._act_recurrent(fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
+                                       outputs, B, with_critic_memory)
         if pool_pred is None and pool_prey is None:
             rc = capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, obs_pred_in.data_ptr(), obs_prey_in.data_ptr(),
                                    ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed,
@@ -233,41 +243,190 @@ class DecHighLevelGame(GameBase):
         ll_actions = self.ll_policy(ll.obs_buf)
         return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
 
-    def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None):
+    # ------------------------------------------------------------------ recurrent policies
+    @staticmethod
+    def _recurrent_pair(fused_pred, fused_prey, pool_pred=None, pool_prey=None):
+        """Whether both actors are ``RecurrentFusedActor`` s.  Both agents are recurrent or neither (one train cfg builds both), and the
+        opponent pool holds feed-forward snapshots only."""
+        rec = [bool(getattr(f, "recurrent", False)) for f in (fused_pred, fused_prey)]
+        if any(rec) and (pool_pred is not None or pool_prey is not None):
+            raise ValueError("the opponent pool is feed-forward: lg_dec_pool_act has no recurrent role, so an OpponentPool cannot stand next to a "
+                             "RecurrentFusedActor")
+        if rec[0] != rec[1]:
+            raise ValueError("both agents of dec_high_level_game are recurrent (RecurrentFusedActor) or neither: lg_dec_game_lstm_act has no mixed pair")
+        return rec[0]
+
+    def _recurrent_library(self, fused, say=True):
+        """``(library or None, whether lg_dec_game_lstm_act can be used now)``: the low-level role is the split-bf16 kernel, so wide precision
+        0 takes the separate actor launches, and a build without the library takes separate launches throughout (a one-line message the
+        first time for each reason).  Decided per call: ``lg_mlp_wide_set_precision`` may change between calls."""
+        try:
+            lib = capi.load_dec_game_recurrent_library()
+        except (RuntimeError, OSError) as exc:
+            self._say_separate(f"{type(exc).__name__}: {exc}", say)
+            return None, False
+        if fused.lib.lg_mlp_wide_set_precision(-1) != 1:              # (an invalid mode changes nothing and returns the current one)
+            self._say_separate("wide precision 0", say)
+            return lib, False
+        return lib, True
+
+    def _say_separate(self, why, say=True):
+        said = self.__dict__.setdefault("_separate_said", set())
+        if say and why not in said:
+            said.add(why)
+            print(f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act x 2 + lg_dec_game_pre + lg_policy_act")
+
+    def _act_recurrent(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
+                       outputs, B, with_critic_memory):
+        """``_act`` for two ``RecurrentFusedActor`` s (arguments already checked there).  ``lg_dec_lstm_step``: both actor memories on the
+        observations they read, and the critic memory of every agent in ``with_critic_memory``, in one launch on the actors' own ``(h, c)``
+        slots (read ``[flip]``, write ``[1 - flip]``); rows that ``reset_buf`` of the previous step marks start from a zero state.  Then
+        ``lg_dec_game_lstm_act`` on the two new ``h``.  The critic memories' outputs are left in ``self._critic_out`` (agent -> tensor, None
+        when it did not move).  Separate launches (``lg_lstm_actor_act`` x 2 + ``lg_dec_game_pre`` + low-level ``lg_policy_act``) on rc -4, at wide
+        precision 0 or without the library (then ``lg_lstm_step`` per agent as well)."""
+        ll, n = self.ll_env, self.num_envs
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        agents = (("pred", fused_pred, obs_pred_in), ("prey", fused_prey, obs_prey_in))
+        critics = {a: a in with_critic_memory for a in AGENTS}
+        lib, shared = self._recurrent_library(fused_pred)
+        h, self._critic_out = {}, {}
+        if lib is not None:
+            roles = []
+            for a, fused, obs in agents:
+                if fused.num_envs != n:
+                    fused._allocate(n)
+                f = fused._flip
+                for lstm, state, present in ((fused.lstm_a, fused.state_a, True), (fused.lstm_c, fused.state_c, critics[a])):
+                    roles.append((lstm.handle, obs.data_ptr(), state[f][0].data_ptr(), state[f][1].data_ptr(), state[1 - f][0].data_ptr(),
+                                  state[1 - f][1].data_ptr()) if present else None)
+                h[a], self._critic_out[a] = fused.state_a[1 - f][0], (fused.state_c[1 - f][0] if critics[a] else None)
+            capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
+            for a, fused, _ in agents:
+                fused.advance_slots(critics[a])
+        else:
+            for a, fused, obs in agents:
+                h[a], self._critic_out[a] = fused.step_memories(obs, obs if critics[a] else None, reset=self.reset_buf)
+        command_pred, mean_pred = fused_pred.output_buffers(n)
+        command_prey, mean_prey = fused_prey.output_buffers(n)
+        ll_actions = self._ll_fused.output_buffers(n)[0]
+        carry = obs_prey_out is not obs_prey_in
+        want_prey_copy = out_prey.get("obs_copy") is not None
+        if shared:
+            step, ctr = fused_prey.peek_step()
+            rc = capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, h["pred"].data_ptr(), h["prey"].data_ptr(),
+                                        obs_pred_in.data_ptr(), obs_prey_in.data_ptr(), ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
+                                        mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, deterministic_pred, deterministic_prey,
+                                        outputs(out_pred, None), outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
+            self.last_act_rc = rc
+            if rc == 0:
+                fused_pred.next_step(); fused_prey.next_step()     # the launch used this step of both noise streams
+                if carry and want_prey_copy:
+                    obs_prey_out.copy_(obs_prey_in)
+                return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
+            self._say_separate("no kernel for this actor pair")
+        else:
+            self.last_act_rc = -4
+        for a, fused, obs, det, out in (("pred", fused_pred, obs_pred_in, deterministic_pred, out_pred), ("prey", fused_prey, obs_prey_in, deterministic_prey, out_prey)):
+            command, mean = fused.fused.act_with_mean(h[a], det)
+            self._fill_optional_outputs(out, n, command, mean, fused.ac.std.detach(), obs)
+        if carry:
+            obs_prey_out.copy_(obs_prey_in)
+        capi.dec_game_pre(self._P, B, stream)
+        ll_actions = self.ll_policy(ll.obs_buf)
+        return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
+
+    def shared_actor_launch(self, fused_pred, fused_prey):
+        """Whether the actor launch of a step has a kernel for this pair next to the low-level actor at the current wide precision (rc 0, not
+        -4).  Issues it once, deterministically, on the current observations when it has: commands, means, low-level commands and actions
+        are overwritten (every step path rewrites them before reading them), no noise stream is advanced and no memory moves.  With two
+        ``RecurrentFusedActor`` s the warm-up call that raises the LDS limits of both kernels of liblegged_dec_game_recurrent.so outside
+        any capture: one ``lg_dec_lstm_step`` of the two actor memories into the slots the next step overwrites, then
+        ``lg_dec_game_lstm_act`` on the actor memories' current outputs."""
+        n = self.num_envs
+        fused_pred, fused_prey = _live(fused_pred), _live(fused_prey)
+        recurrent = self._recurrent_pair(fused_pred, fused_prey)
+        command_pred, mean_pred = fused_pred.output_buffers(n)
+        command_prey, mean_prey = fused_prey.output_buffers(n)
+        ll_actions = self._ll_fused.output_buffers(n)[0]
+        B = self._bind(command_pred, command_prey, self.obs_buf_pred, self.obs_buf_prey)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        step, ctr = fused_prey.peek_step()
+        if not recurrent:
+            return capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, self.obs_buf_pred.data_ptr(),
+                                     self.obs_buf_prey.data_ptr(), self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
+                                     mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream) == 0
+        lib, shared = self._recurrent_library(fused_pred, say=False)
+        if lib is None:
+            return False
+        roles, h = [], []
+        for fused, obs in ((fused_pred, self.obs_buf_pred), (fused_prey, self.obs_buf_prey)):
+            if fused.num_envs != n:
+                fused._allocate(n)
+            f, st = fused._flip, fused.state_a
+            roles += [(fused.lstm_a.handle, obs.data_ptr(), st[f][0].data_ptr(), st[f][1].data_ptr(), st[1 - f][0].data_ptr(), st[1 - f][1].data_ptr()), None]
+            h.append(st[f][0])
+        capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
+        return shared and capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, h[0].data_ptr(), h[1].data_ptr(), None,
+                                                 None, self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(),
+                                                 fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream) == 0
+
+    def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None, with_critic_memory=()):
         """Rollout step with both agents' actors on the device: ``lg_dec_game_act`` -> ``lg_step`` -> ``lg_dec_game_post``, three launches.
         Returns ``(command_pred, mean_pred), (command_prey, mean_prey), step result``: the clipped commands (what ``step`` leaves in the
         caller's tensors) and the actors' outputs, all in the ``FusedActor`` buffers.  ``out_pred`` / ``out_prey``: dicts of optional float32
         outputs -- ``sample`` (the unclipped sample), ``sigma``, ``log_prob`` of that sample (what ``PPO.act`` stores), ``obs_copy`` (the
-        observations the actor read).  The observations the actors read stay in the tensors returned by the previous call, as with ``step``."""
+        observations the actor read).  The observations the actors read stay in the tensors returned by the previous call, as with ``step``.
+
+        Two ``RecurrentFusedActor`` s make it four launches, ``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act`` -> ``lg_step`` -> ``lg_dec_game_post``:
+        both actor memories advance on their observations, rows whose episode ended in the previous step from a zero state.
+        ``with_critic_memory``: the agents ("pred", "prey") whose critic memory advances in the same launch; such an agent's tuple gets the
+        critic memory's output of the step as a third value (the actor's buffer, re-used two steps later).  A critic memory that is not
+        named stays where it is."""
         ll = self.ll_env
+        with_critic_memory = (with_critic_memory,) if isinstance(with_critic_memory, str) else tuple(with_critic_memory or ())
+        unknown = set(with_critic_memory) - set(AGENTS)
+        if unknown:
+            raise ValueError(f"with_critic_memory names agents of {AGENTS}, got {sorted(unknown)}")
         prev_pred = self.obs_buf_pred
         prev_prey = self._flip_observations(carry=False)
         try:
             pred, prey, ll_actions, B = self._act(fused_pred, fused_prey, prev_pred, prev_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
-                                                  deterministic_prey, out_pred, out_prey)
+                                                  deterministic_prey, out_pred, out_prey, with_critic_memory)
         except Exception:
             self._unflip_observations()
             raise
         ll.step(ll_actions)
         self._post(B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
+        if with_critic_memory and getattr(_live(fused_pred), "recurrent", False):
+            pred = pred + (self._critic_out["pred"],) if "pred" in with_critic_memory else pred
+            prey = prey + (self._critic_out["prey"],) if "prey" in with_critic_memory else prey
         return pred, prey, self._step_result()
 
-    def make_graphed_policy_step(self, fused_pred, fused_prey, warmup=3, steps_per_replay=1, deterministic_pred=False, deterministic_prey=False):
+    def make_graphed_policy_step(self, fused_pred, fused_prey, warmup=3, steps_per_replay=1, deterministic_pred=False, deterministic_prey=False,
+                                 with_critic_memory=()):
         """``make_graphed_step`` with both actors on the device: the graph is ``lg_dec_game_act`` -> ``lg_step`` -> ``lg_dec_game_post`` per
         step, the observations stay in one buffer per agent.  Both ``FusedActor`` s must draw their noise stream from the low-level sim's
         device step counter (``FusedActor(..., step_counter=env.ll_env._sim.buf["step_counter"])``).  Returns a zero-argument callable that
         replays the graph; the actors' ``output_buffers(num_envs)`` then hold the commands and the means of the last step.
-        ``deterministic_pred`` / ``deterministic_prey``: that agent's command is its clipped mean (evaluation)."""
+        ``deterministic_pred`` / ``deterministic_prey``: that agent's command is its clipped mean (evaluation).
+        Two ``RecurrentFusedActor`` s: only the actor memories are in the cell launch, and the critic memories of the agents named in
+        ``with_critic_memory``; with an odd number of steps per replay the slots of BOTH actors are held (``hold_slot``), so that every
+        replay starts from the same addresses."""
         sim = self.ll_env._sim
         for fused in (_live(fused_pred), _live(fused_prey)):
             self._require_device_step_counter(fused)
+        hold = self._recurrent_pair(_live(fused_pred), _live(fused_prey)) and steps_per_replay % 2 == 1
+        with_critic_memory = (with_critic_memory,) if isinstance(with_critic_memory, str) else tuple(with_critic_memory or ())
 
         def device_step():
             _, _, ll_actions, B = self._act(fused_pred, fused_prey, self.obs_buf_pred, self.obs_buf_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
-                                            deterministic_prey)
+                                            deterministic_prey, with_critic_memory=with_critic_memory)
+            if hold:
+                fused_pred.hold_slot(); fused_prey.hold_slot()
             sim.step(ll_actions, -1)
             self._post(B, -1, torch.cuda.current_stream(self.device).cuda_stream)
         self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)
+        self._policy_step_actors = (fused_pred, fused_prey)      # the graph reads their weights and memories where they are: they live as long as it does
         return replay
 
     # ------------------------------------------------------------------ resets and observations
@@ -503,12 +662,22 @@ class AgentView:
             return self._result(self.env.step(actions, other))
         return self._result(self.env.step(other, actions))
 
-    def step_policy(self, fused, deterministic=False, sample=None, sigma=None, log_prob=None, obs_copy=None):
+    def step_policy(self, fused, deterministic=False, sample=None, sigma=None, log_prob=None, obs_copy=None, with_critic_memory=False):
         """Device path: ``opponent`` is a ``FusedActor`` or an ``rl.OpponentPool`` (a mixture of opponents by 32-env block).  Returns ``(command, mean), (obs, None, rew, dones, extras)`` of this agent, the
-        contract of ``HighLevelGame.step_policy``."""
+        contract of ``HighLevelGame.step_policy``.  Recurrent policies (``fused`` and ``opponent`` both ``RecurrentFusedActor`` s):
+        ``with_critic_memory`` advances this agent's critic memory too and returns its output as a third value of the first tuple; of the
+        opponent only the actor memory advances."""
         mine = {k: v for k, v in (("sample", sample), ("sigma", sigma), ("log_prob", log_prob), ("obs_copy", obs_copy)) if v is not None}
+        critic = (self.agent,) if with_critic_memory else ()
         if self.agent == "pred":
-            pred, _, out = self.env.step_policy(fused, self.opponent, deterministic_pred=deterministic, out_pred=mine)
+            pred, _, out = self.env.step_policy(fused, self.opponent, deterministic_pred=deterministic, out_pred=mine, with_critic_memory=critic)
             return pred, self._result(out)
-        _, prey, out = self.env.step_policy(self.opponent, fused, deterministic_prey=deterministic, out_prey=mine)
+        _, prey, out = self.env.step_policy(self.opponent, fused, deterministic_prey=deterministic, out_prey=mine, with_critic_memory=critic)
         return prey, self._result(out)
+
+    def shared_actor_launch(self, fused):
+        """``DecHighLevelGame.shared_actor_launch`` with the opponent; None while the view has no opponent yet (``DecGamePolicyRunner`` sets
+        it once both agents' actors exist and makes the call then)."""
+        if self.opponent is None:
+            return None
+        return self.env.shared_actor_launch(fused, self.opponent) if self.agent == "pred" else self.env.shared_actor_launch(self.opponent, fused)

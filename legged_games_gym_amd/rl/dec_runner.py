@@ -24,7 +24,14 @@ Outcomes per pool member and prioritised opponents.  
 ``<log_dir>/opponents.csv`` gets one row per member of that pool: its blocks, the six counts OF THIS EVOLUTION and the learner's win rate.
 Runner key ``opponent_priority`` (a float power, default 0 = off; read with ``.get()``; ``--opponent_priority``): above 0 the non-live blocks
 are dealt in proportion to ``pfsp_weights`` of the pool's running counts -- a past opponent the learner loses to gets more envs -- instead of
-round-robin; it needs ``opponent_pool_size > 0`` and the outcome statistics.  With priority 0 the calls to ``assign`` are unchanged."""
+round-robin; it needs ``opponent_pool_size > 0`` and the outcome statistics.  With priority 0 the calls to ``assign`` are unchanged.
+
+Recurrent policies (``policy_class_name = "ActorCriticRecurrent"``) train on the device path only: the runner key ``device_rollout`` is
+required, and so are a GPU, memories the device cell covers and no opponent pool -- there is no generic loop for two recurrent agents, so
+each of these raises with its reason instead of falling back.  A step is ``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act`` -> ``lg_step`` ->
+post.  The opponent samples and only its actor memory advances; the learner's critic memory advances with it.  All actor memories carry on
+across evolutions; at the start of an evolution the agent that becomes the learner zeroes its CRITIC memory's state, which did not move while
+it was the opponent."""
 import os
 import re
 
@@ -54,9 +61,7 @@ class DecGamePolicyRunner:
     def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
         self.env, self.cfg, self.device, self.log_dir = env, train_cfg["runner"], device, log_dir
         self.priority = opponent_priority_of(self.cfg, env)       # before anything is built
-        if self.cfg.get("policy_class_name", "ActorCritic") != "ActorCritic":
-            raise NotImplementedError(f"DecGamePolicyRunner trains two feed-forward ActorCritic policies; policy class {self.cfg['policy_class_name']!r} "
-                                      "is not supported for the decentralised game")
+        self.recurrent = self._check_policy_class(train_cfg, device)     # before anything is built, too
         self.views = {a: env.agent_view(a, None) for a in AGENTS}
         self.runners = {}
         for a in AGENTS:
@@ -71,6 +76,11 @@ class DecGamePolicyRunner:
             else:                                         # generic path for both: a view cannot mix a device learner with a torch opponent
                 self.runners[a]._fused, self.runners[a]._game_rollout = None, False
                 self.views[a].opponent = self._sampling_policy(other)
+        if self.recurrent and not device_path:                # (an actor shape the kernels refuse: the per-agent runner has said which)
+            raise NotImplementedError("ActorCriticRecurrent on dec_high_level_game runs on the device rollout only and it is unavailable (see the "
+                                      "[runner] message above); there is no generic loop for two recurrent agents")
+        if self.recurrent:
+            env.shared_actor_launch(fused["pred"], fused["prey"])     # raises the LDS limits of the recurrent kernels here, outside any capture
         self.device_path = device_path
         self.pool_size = int(self.cfg.get("opponent_pool_size", 0) or 0)
         self.latest_share = float(self.cfg.get("opponent_latest_share", 0.5))
@@ -95,6 +105,35 @@ class DecGamePolicyRunner:
         if log_dir is not None:
             for a in AGENTS:
                 self._follow(a)
+
+    def _check_policy_class(self, train_cfg, device):
+        """Whether the policies are recurrent.  ``ActorCriticRecurrent`` is taken only where the device path can run it; every other case
+        raises with its reason before anything is built."""
+        name = self.cfg.get("policy_class_name", "ActorCritic")
+        if name == "ActorCritic":
+            return False
+        if name != "ActorCriticRecurrent" or not self.cfg.get("device_rollout", False):
+            raise NotImplementedError(f"DecGamePolicyRunner trains two feed-forward ActorCritic policies, or two ActorCriticRecurrent policies with the "
+                                      f"runner key device_rollout (--device_rollout); policy class {name!r} is not supported for the decentralised game "
+                                      "without it: there is no generic loop for two recurrent agents")
+        if not str(device).startswith("cuda"):
+            raise ValueError(f"ActorCriticRecurrent on dec_high_level_game needs a GPU: the policies are on {device}, the recurrent game kernels run on "
+                             "the device and there is no generic loop for two recurrent agents")
+        if int(self.cfg.get("opponent_pool_size", 0) or 0) > 0:
+            raise ValueError("opponent_pool_size > 0 with ActorCriticRecurrent: the opponent pool is feed-forward (lg_dec_pool_act has no recurrent role)")
+        import torch.nn as nn
+        from .recurrent_actor import lstm_unsupported_reason
+        policy = train_cfg["policy"]
+        kind = str(policy.get("rnn_type", "lstm")).lower()
+        if kind not in ("lstm", "gru"):
+            raise ValueError(f"rnn_type must be 'lstm' or 'gru', got {kind!r}")
+        probe = (nn.GRU if kind == "gru" else nn.LSTM)(input_size=3, hidden_size=int(policy.get("rnn_hidden_size", 256)),
+                                                       num_layers=int(policy.get("rnn_num_layers", 1)))      # (the predator's memory; both have these units)
+        why = lstm_unsupported_reason(probe)
+        if why is not None:
+            raise ValueError(f"ActorCriticRecurrent on dec_high_level_game: no device LSTM cell for a {why}, and there is no generic loop for two "
+                             "recurrent agents")
+        return True
 
     def _follow(self, agent):
         """Keep the combined files current while ``agent`` 's runner trains: whenever it saves ``model_<it>.pt`` (``runner.save_interval`` and the end
@@ -150,9 +189,11 @@ class DecGamePolicyRunner:
                 if getattr(self.env, "_outcome", None) is not None:
                     self.env.enable_member_outcomes(self.pools[other])             # before learn captures its graph, too
                     counted = (self.pools[other], self.pools[other].member_totals_host())
+            if self.recurrent:
+                runner._fused.reset_critic_state()         # the critic memory did not move while this agent was the opponent (G21)
             runner.learn(num_learning_iterations=num_learning_iterations, init_at_random_ep_len=False)
             if runner._fused is not None:
-                runner._fused.sync_device()                # the other view's opponent: this agent's new weights, repacked in place
+                runner._fused.sync_device()                # the other view's opponent: this agent's new weights (both LSTMs and the actor), repacked in place
             if counted is not None and self.log_dir is not None:
                 self._log_opponents(e, agent, *counted)
             self.current_evolution = e + 1

@@ -188,11 +188,21 @@ class RecurrentFusedActor:
         self.state_c = [(z(Hc), z(Hc)), (z(Hc), z(Hc))]
         self.scratch_c = (z(Hc), z(Hc))                        # outputs of a critic-only step that must not move the carried state
         self.num_envs, self._flip = n, 0
+        self._critic_slots_equal = True                        # both slots of the critic memory hold the carried state (see advance_slots)
 
     def reset_states(self):
         for pair in self.state_a + self.state_c:
             for t in pair:
                 t.zero_()
+        self._critic_slots_equal = True
+
+    def reset_critic_state(self):
+        """Zero the critic memory's state in both slots (``DecGamePolicyRunner``: the agent that becomes the learner; the memory did not move
+        while it was the opponent).  The actor memory carries on."""
+        for pair in self.state_c:
+            for t in pair:
+                t.zero_()
+        self._critic_slots_equal = True
 
     def hidden_states(self):
         """((h_a, c_a), (h_c, c_c)) the next step starts from, as ``[1, N, H]`` views (``ActorCriticRecurrent.get_hidden_states``)."""
@@ -219,8 +229,22 @@ class RecurrentFusedActor:
         if not with_c:                                       # the critic memory did not move: keep both of its slots current
             for dst, src in zip(self.state_c[1 - f], self.state_c[f]):
                 dst.copy_(src)
+        self._critic_slots_equal = not with_c
         self._flip = 1 - f
         return self.state_a[1 - f][0], (self.state_c[1 - f][0] if with_c else None)
+
+    def advance_slots(self, with_critic):
+        """What ``step_memories`` does after its launch, for a caller that issued the launch itself on this actor's slots (``lg_dec_lstm_step``
+        of ``dec_high_level_game``: read ``[flip]``, write ``[1 - flip]``).  A critic memory that did not move needs both of its slots
+        current; they are copied only when the last step that moved it left them different, so a memory that never moves costs no copy."""
+        f = self._flip
+        if with_critic:
+            self._critic_slots_equal = False
+        elif not self._critic_slots_equal:
+            for dst, src in zip(self.state_c[1 - f], self.state_c[f]):
+                dst.copy_(src)
+            self._critic_slots_equal = True
+        self._flip = 1 - f
 
     def hold_slot(self):
         """Bring the state the last ``step_memories`` wrote back into the slots it read, and read from there again: a captured graph with an
@@ -229,6 +253,7 @@ class RecurrentFusedActor:
         for st in (self.state_a, self.state_c):
             for dst, src in zip(st[1 - f], st[f]):
                 dst.copy_(src)
+        self._critic_slots_equal = True
         self._flip = 1 - f
 
     def peek_critic(self, critic_obs, reset=None):

@@ -105,13 +105,14 @@ class OnPolicyRunner:
         return fused
 
     def _make_recurrent_game_actor(self):
-        """``device_rollout`` of ``high_level_game`` / ``scripted_predator_game`` with a recurrent policy; None (and why) where it cannot run."""
+        """``device_rollout`` of ``high_level_game`` / ``scripted_predator_game`` / an agent view of ``dec_high_level_game`` with a recurrent
+        policy; None (and why) where it cannot run."""
         env, ac = self.env, self.alg.actor_critic
         from .recurrent_actor import RecurrentFusedActor, lstm_unsupported_reason
         why = None
         if not str(self.device).startswith("cuda"):
             why = f"the policy is on {self.device}, the game actor kernels run on a GPU"
-        elif not hasattr(env, "step_policy") or getattr(env, "dec_agent_view", False):
+        elif not hasattr(env, "step_policy"):
             why = "the game actor kernels have no recurrent policy for this task"
         elif env.num_privileged_obs is not None:
             why = "privileged observations"
@@ -123,6 +124,7 @@ class OnPolicyRunner:
                 fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
                                             step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs)
                 env.shared_actor_launch(fused)                # raises the new kernel's LDS limit here, outside any capture; False = separate launches
+                                                              # (an agent view has no opponent yet: DecGamePolicyRunner makes the call)
             except Exception as exc:
                 why = f"{type(exc).__name__}: {exc}"
         if why is not None:
@@ -373,6 +375,8 @@ class OnPolicyRunner:
         ll_flip0 = getattr(getattr(env, "ll_env", None), "_obs_flip", 0)
         captured = False
         mem_flip0 = getattr(self._fused, "_flip", None)       # (recurrent policy: the (h, c) ping-pong of its memories)
+        opponent = getattr(env, "opponent", None)             # (an agent view of dec_high_level_game: the other agent's memories move in every step too)
+        opp_flip0 = getattr(opponent, "_flip", None)
         try:
             N, dev = env.num_envs, self.device
             sums = torch.zeros(3, device=dev)             # {sum of finished-episode returns, of their lengths, their count}
@@ -387,6 +391,7 @@ class OnPolicyRunner:
                 flip0, counter0 = env._obs_flip, env.common_step_counter
                 ll_flip0 = getattr(getattr(env, "ll_env", None), "_obs_flip", 0)
                 mem_flip0 = getattr(self._fused, "_flip", None)
+                opp_flip0 = getattr(opponent, "_flip", None)
                 env.begin_graph_capture()
                 captured = True
                 graph = torch.cuda.CUDAGraph()
@@ -419,6 +424,8 @@ class OnPolicyRunner:
                 env.common_step_counter = counter0
                 if mem_flip0 is not None:
                     self._fused._flip = mem_flip0
+                if opp_flip0 is not None:
+                    opponent._flip = opp_flip0
             self.alg.storage.clear()
             return None
 

@@ -6,7 +6,9 @@ the newest ``dec_high_level_game`` checkpoint is loaded and both agents' inferen
 of the env are switched on (include/legged_dec_game_outcome.h) and ``S`` high-level steps (default: 2 x ``max_episode_length``) are rolled
 out with BOTH agents deterministic -- as replays of the graphed three-launch policy step where ``lg_dec_game_act`` has a kernel for the actor
 triple, else through ``step_policy`` (separate actor launches), else through ``step`` with the runner's inference policies.  The totals are
-read ONCE, at the end.  A table is printed and ``outcomes_<iteration>.json`` is written next to the checkpoint: ``totals`` (the six
+read ONCE, at the end.  A recurrent checkpoint (``--policy_class_name ActorCriticRecurrent`` and the ``--rnn_*`` flags it was trained with) goes
+through the graphed policy step as well: ``lg_dec_lstm_step`` with the two actor memories only, starting from zero states, then
+``lg_dec_game_lstm_act``.  A table is printed and ``outcomes_<iteration>.json`` is written next to the checkpoint: ``totals`` (the six
 integers of ``env.outcome_totals()``; its ``steps`` is the summed length of the finished episodes), ``rates`` (the four flags over
 ``episodes``), ``mean_steps``, ``num_envs``, ``steps`` (the ``S`` of the rollout), ``task``, ``iteration`` and ``path``.
 
@@ -22,7 +24,7 @@ import torch
 from legged_games_gym_amd.envs import *  # noqa: F401,F403
 import legged_games_gym_amd.utils.task_registry as registry_module
 from legged_games_gym_amd.envs import a1_game
-from legged_games_gym_amd.utils.helpers import get_load_path
+from legged_games_gym_amd.utils.helpers import apply_policy_args, get_load_path
 from legged_games_gym_amd.utils.task_registry import task_registry
 
 from .train_dec_game import _args as _train_args
@@ -45,6 +47,9 @@ def play(args, steps=None):
     env_cfg.domain_rand.push_robots = False
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     train_cfg.runner.resume = True
+    apply_policy_args(train_cfg, args)
+    if getattr(train_cfg.runner, "policy_class_name", "ActorCritic") == "ActorCriticRecurrent":
+        train_cfg.runner.device_rollout = True      # what the runner builds two recurrent policies for
     runner, train_cfg = task_registry.make_dec_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root="default")
     policy_pred = runner.get_inference_policy("pred", device=env.device)
     policy_prey = runner.get_inference_policy("prey", device=env.device)
@@ -88,9 +93,12 @@ class DecEvaluation:
     ENV_STATE = ("rew_buf_prey", "rew_buf_pred", "reset_buf", "time_out_buf", "episode_length_buf", "curr_episode_step", "predator_pos", "_episode_sums",
                  "_episode_means", "_extras_accum", "_extras_ticket")
 
-    def __init__(self, args):
+    def __init__(self, args, allow_recurrent=True):
         if args.task not in a1_game.DEC_TASKS:
             raise SystemExit(f"play_dec_game plays {a1_game.DEC_TASKS}; use scripts.play_game for --task={args.task}")
+        if not allow_recurrent and getattr(args, "policy_class_name", None) == "ActorCriticRecurrent":
+            raise SystemExit("cross-play of recurrent checkpoints is not supported: weights swapped underneath one graph would meet the memories of "
+                             "another policy; use play_dec_game --outcomes per checkpoint")
         a1_game.register_dec()
         env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
         env_cfg, train_cfg = copy.deepcopy(env_cfg), copy.deepcopy(train_cfg)      # the registered objects keep their values (--num_envs lands on a copy)
@@ -105,6 +113,10 @@ class DecEvaluation:
         for key in ("device_rollout", "graphed_rollout"):        # the runner only holds the two ActorCritics here
             if hasattr(train_cfg.runner, key):
                 delattr(train_cfg.runner, key)
+        apply_policy_args(train_cfg, args)      # --policy_class_name ActorCriticRecurrent [--rnn_*]: the flags the checkpoint was trained with
+        self.recurrent = getattr(train_cfg.runner, "policy_class_name", "ActorCritic") == "ActorCriticRecurrent"
+        if self.recurrent:                      # ... and the two RecurrentFusedActors: the runner builds them on the device path only
+            train_cfg.runner.device_rollout, train_cfg.runner.graphed_rollout = True, False
         runner, train_cfg = task_registry.make_dec_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root=None)
         log_root = os.path.join(registry_module.LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name)
         self.checkpoint = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
@@ -118,7 +130,9 @@ class DecEvaluation:
         env.reset()
         self._start = self._snapshot()
         self.fused, self._replay, self.path = None, None, "step() with the inference policies"
-        if str(env.device).startswith("cuda"):
+        if self.recurrent:                      # the runners' own actors: on the device step counter, seeds apart
+            self.fused = {a: runner.runners[a]._fused for a in ("pred", "prey")}
+        elif str(env.device).startswith("cuda"):
             from legged_games_gym_amd.envs.a1_game.dec_high_level_game import SEED_OFFSET_PRED, SEED_OFFSET_PREY
             from legged_games_gym_amd.rl import FusedActor
             try:
@@ -152,6 +166,9 @@ class DecEvaluation:
             t.copy_(v)
         ll.common_step_counter = snap["counter"]
         ll._sim.buf["step_counter"].fill_(snap["counter"])
+        if self.recurrent and self.fused is not None:
+            for fused in self.fused.values():   # memories start from zero
+                fused.reset_states()
 
     def load(self, state_pred, state_prey):
         """Put the ``model_state_dict`` halves of two checkpoints under the step path (the captured graph is NOT re-captured)."""

@@ -10,10 +10,14 @@ falls and low-level time-outs among the finished episodes and their mean length,
 in the share F (default 0.5) of the 32-env blocks, up to K frozen earlier versions of it in the rest (``rl.OpponentPool``, DESIGN.md G19);
 the checkpoints then carry the pools.  With ``--outcome_stats`` as well, the outcomes are also counted per pool member and logged to
 ``opponents.csv``, and ``--opponent_priority P`` (P > 0) deals the non-live blocks by prioritised fictitious self-play: a past opponent the
-learner loses to gets more envs.  Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
+learner loses to gets more envs.  ``--policy_class_name ActorCriticRecurrent [--rnn_hidden_size H]`` with ``--device_rollout``
+trains two LSTM policies (four launches per step: ``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act`` -> ``lg_step`` -> post); without
+``--device_rollout``, on the CPU, with a GRU / several layers / more than 256 units or with ``--opponent_pool`` the runner stops and says why.
+Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
 from legged_games_gym_amd.envs import a1_game
 from legged_games_gym_amd.utils import get_args
+from legged_games_gym_amd.utils.helpers import apply_policy_args
 from legged_games_gym_amd.utils.task_registry import task_registry
 
 DEFAULT_TASK = "dec_high_level_game"
@@ -23,6 +27,7 @@ def train(args):
     if args.task not in a1_game.DEC_TASKS:
         raise SystemExit(f"train_dec_game trains {a1_game.DEC_TASKS}; use scripts.train for --task={args.task}")
     a1_game.register_dec()
+    apply_policy_args(task_registry.get_cfgs(args.task)[1], args)     # --policy_class_name ActorCriticRecurrent [--rnn_type / --rnn_hidden_size / --rnn_num_layers]
     if args.device_rollout:                  # a runner key, read with .get(): the config classes stay value for value the reference's
         task_registry.get_cfgs(args.task)[1].runner.device_rollout = True
     if args.opponent_pool:                   # runner keys, read with .get() as well

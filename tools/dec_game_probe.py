@@ -29,7 +29,17 @@ legged_dec_game_member_outcome.h: the counts kept per pool member as well), by t
 alternating repeats, HIP events, median and min .. max per variant and of the difference repeat by repeat ->
 profiles/dec_member_outcome_step.json.
 
-    python tools/dec_game_probe.py --member-outcome [--envs 2000 4096] [--step-replays 2000] [--repeats 5]"""
+    python tools/dec_game_probe.py --member-outcome [--envs 2000 4096] [--step-replays 2000] [--repeats 5]
+
+``--recurrent`` times the graphed policy step with two recurrent policies (``ActorCriticRecurrent``, ``--rnn-hidden-size`` units, default 256;
+the predator is the learner, so its critic memory moves too, the prey the opponent): the four-launch step (``lg_dec_lstm_step`` ->
+``lg_dec_game_lstm_act`` -> k_step -> post) against the same graph with the policy stage as the eight launches of the older entry points
+(``lg_lstm_step`` x 2, ``lg_lstm_actor_act`` x 2, ``lg_dec_game_pre``, ``lg_policy_act``, k_step, post) and against the feed-forward
+three-launch step, by the method of ``--outcome``: one process, two-step graphs, alternating repeats, HIP events, median and min .. max per
+step -> profiles/dec_recurrent_step.json.  ``--trace`` replays the four-launch graph only, for a kernel table in a run of its own:
+``rocprofv3 --kernel-trace --stats -- python tools/dec_game_probe.py --recurrent --trace --envs 4096``.
+
+    python tools/dec_game_probe.py --recurrent [--envs 2000 4096] [--step-replays 2000] [--repeats 5]"""
 import argparse
 import json
 import os
@@ -336,6 +346,110 @@ def member_outcome_main(args):
     print("wrote", out)
 
 
+def recurrent_pair(env, units):
+    """Two ``RecurrentFusedActor`` s of the task's default actor widths on the env's device step counter (seeded random-init policies: the
+    time does not depend on the weights)."""
+    from legged_games_gym_amd.rl import ActorCriticRecurrent
+    from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor
+    ctr = env.ll_env._sim.buf["step_counter"]
+    torch.manual_seed(1)
+    return [RecurrentFusedActor(ActorCriticRecurrent(no, no, na, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN, rnn_hidden_size=units).to(DEV), DEV,
+                                seed=seed, step_counter=ctr, num_envs=env.num_envs) for no, na, seed in ((3, 2, 1 + 7919 + 104729), (16, 4, 1 + 7919))]
+
+
+def separate_recurrent_step(env, pred, prey):
+    """The eight-launch step of the older entry points on the actors' own slots: ``lg_lstm_step`` with the learner's (predator's) actor and
+    critic memory, ``lg_lstm_step`` with the opponent's (prey's) actor memory, ``lg_lstm_actor_act`` x 2, ``lg_dec_game_pre``, the low-level
+    ``lg_policy_act``, k_step, the post kernel.  No copy kernels: the opponent's critic memory rests in both of its slots."""
+    from legged_games_gym_amd.rl.recurrent_actor import lstm_step
+    n, lib = env.num_envs, pred.lib
+
+    def device_step():
+        stream = torch.cuda.current_stream().cuda_stream
+        h = []
+        for fused, obs, with_c in ((pred, env.obs_buf_pred, True), (prey, env.obs_buf_prey, False)):
+            f = fused._flip
+            lstm_step(lib, fused.lstm_a, fused.lstm_c if with_c else None, obs, obs if with_c else None, env.reset_buf, fused.state_a[f], fused.state_a[1 - f],
+                      fused.state_c[f], fused.state_c[1 - f], n, stream)
+            h.append(fused.state_a[1 - f][0])
+            fused._flip = 1 - f
+        (cp, _), (cy, _) = pred.fused.act_with_mean(h[0]), prey.fused.act_with_mean(h[1])
+        B = env._bind(cp, cy, env.obs_buf_pred, env.obs_buf_prey)
+        capi.dec_game_pre(env._P, B, stream)
+        ll_actions = env.ll_policy(env.ll_env.obs_buf)
+        env.ll_env._sim.step(ll_actions, -1)
+        env._post(B, -1, stream)
+    return device_step
+
+
+def recurrent_main(args):
+    """Two-step graphs of the policy step: recurrent in four launches, recurrent with the policy stage as separate launches, feed-forward in
+    three launches; same process, same sizes, alternating repeats; microseconds per STEP."""
+    S = 2
+    names = ("recurrent_four_launch_step", "recurrent_separate_policy_launches", "feed_forward_three_launch_step")
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.step_replays, "repeats": args.repeats,
+              "rnn_hidden_size": args.rnn_hidden_size, "steps_per_replay": S, "learner": "pred (its critic memory moves)", "unit": "us per policy step", "envs": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            envs, steps, actors = [], [], []                     # (a graph reads its actors' weights and memories where they are: all kept until the size is done)
+            env = make_env(n, args.mesh, tmp)
+            pred, prey = recurrent_pair(env, args.rnn_hidden_size)
+            actors.append((pred, prey))
+            if env.shared_actor_launch(pred, prey) is not True:          # raises the LDS limits outside the capture
+                raise RuntimeError("lg_dec_game_lstm_act refused the actors")
+            steps.append(env.make_graphed_policy_step(pred, prey, steps_per_replay=S, with_critic_memory=("pred",)))
+            assert env.last_act_rc == 0
+            envs.append(env)
+            if args.trace:
+                for _ in range(args.step_replays // S):
+                    steps[0]()
+                torch.cuda.synchronize()
+                assert torch.isfinite(env.obs_buf_prey).all()
+                print(f"{n} envs: {args.step_replays} steps of the four-launch graph replayed")
+                continue
+            env = make_env(n, args.mesh, tmp)
+            pred, prey = recurrent_pair(env, args.rnn_hidden_size)
+            actors.append((pred, prey))
+            env._policy_step_graph, replay = env._capture(separate_recurrent_step(env, pred, prey), 3, S, env._step_result)
+            steps.append(replay)
+            envs.append(env)
+            env = make_env(n, args.mesh, tmp)
+            ctr = env.ll_env._sim.buf["step_counter"]
+            torch.manual_seed(1)
+            fused = [FusedActor(ActorCritic(no, no, na, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV), DEV, seed=seed, step_counter=ctr)
+                     for no, na, seed in ((3, 2, 1 + 7919 + 104729), (16, 4, 1 + 7919))]
+            actors.append(fused)
+            steps.append(env.make_graphed_policy_step(*fused, steps_per_replay=S))
+            assert env.last_act_rc == 0
+            envs.append(env)
+            for fn in steps:
+                timed(fn, args.step_replays // (4 * S))          # warm every graph before the first timed window
+            t = [[] for _ in steps]
+            for _ in range(args.repeats):
+                for i, fn in enumerate(steps):
+                    t[i].append(timed(fn, args.step_replays // S) / S)
+            row = {name: spread(x) for name, x in zip(names, t)}
+            row["separate_minus_four_launch"] = spread([y - x for x, y in zip(t[0], t[1])])
+            row["four_launch_minus_feed_forward"] = spread([x - z for x, z in zip(t[0], t[2])])
+            row["env_steps_per_s_recurrent_four_launch_step"] = n / (statistics.median(t[0]) * 1e-6)
+            for env in envs:
+                assert torch.isfinite(env.obs_buf_prey).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            result["envs"][str(n)] = row
+            print(f"{n} envs, per step of a two-step graph: " + "; ".join(f"{name} {statistics.median(x):.1f} us ({min(x):.1f} .. {max(x):.1f})" for name, x in zip(names, t)),
+                  flush=True)
+            d = row["separate_minus_four_launch"]
+            print(f"  separate - four launches {d['median_us']:+.2f} us ({d['min_us']:+.2f} .. {d['max_us']:+.2f})", flush=True)
+            torch.cuda.synchronize()
+            del steps, envs, actors
+    if args.trace:
+        return
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_recurrent_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 DEFAULT_OUT = os.path.join(REPO, "profiles", "dec_game_act.json")
 
 
@@ -355,7 +469,13 @@ def main():
     ap.add_argument("--members", type=int, nargs="+", default=[1, 4, 8], help="--pool: pool sizes to time")
     ap.add_argument("--member-outcome", action="store_true", help="time the graphed policy step against a 4-member prey pool with lg_dec_outcome_post and with "
                     "lg_dec_member_outcome_post as the last launch; writes profiles/dec_member_outcome_step.json")
+    ap.add_argument("--recurrent", action="store_true", help="time the graphed policy step with two recurrent policies in four launches, with the policy stage as "
+                    "separate launches, and the feed-forward three-launch step; writes profiles/dec_recurrent_step.json")
+    ap.add_argument("--rnn-hidden-size", type=int, default=256, help="--recurrent: units of every memory")
+    ap.add_argument("--trace", action="store_true", help="--recurrent: replay the four-launch graph only and write nothing (for a rocprofv3 kernel table)")
     args = ap.parse_args()
+    if args.recurrent:
+        return recurrent_main(args)
     if args.outcome:
         return outcome_main(args)
     if args.member_outcome:
