@@ -856,6 +856,122 @@ def dec_game_lstm_act(pred_actor, prey_actor, ll_policy, params: lg_dec_game_par
     return rc
 
 
+# ---------------------------------------------------------------------------------------------------------------- legged_dec_pool_recurrent.h
+# The recurrent policy stage of dec_high_level_game with an opponent pool, a fifth library (csrc/liblegged_dec_pool_recurrent.so): outside
+# ABI / ALL_SYMBOLS / bind_all.  It reads the lg_lstm / lg_lstm_actor / lg_policy handles liblegged_hip.so created.
+class lg_dec_rpool_info(C.Structure):
+    """include/legged_dec_pool_recurrent.h: lg_dec_rpool_info (what ``lg_dec_rpool_query`` reports)."""
+    _fields_ = [("count", i32), ("role", i32), ("device", i32), ("num_in", i32), ("hidden", i32), ("ksteps", i32), ("dims", i32 * 5), ("max_width", i32),
+                ("table", C.c_void_p)]
+
+
+DEC_POOL_RECURRENT_ABI = {
+    "lg_dec_rpool_create": ([_P(_vp), _P(_vp), i32, i32, i32, _P(_vp)], _int),
+    "lg_dec_rpool_destroy": ([_vp], _int),
+    "lg_dec_rpool_query": ([_vp, _P(lg_dec_rpool_info)], _int),
+    "lg_dec_pool_lstm_step": ([_P(lg_dec_lstm_role), _vp, _vp, _vp, _vp, _vp, i32, _vp], _int),
+    "lg_dec_pool_lstm_act": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(lg_dec_game_params), _P(lg_dec_game_buffers), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              u64, u64, i64, _vp, i32, i32, _P(lg_dec_act_outputs), _P(lg_dec_act_outputs), _vp], _int),
+    "lg_dec_pool_recurrent_last_error": ([], C.c_char_p),
+    "lg_dec_pool_recurrent_sizeof": _SIZEOF,
+}
+DEC_POOL_RECURRENT_SYMBOLS = list(DEC_POOL_RECURRENT_ABI)
+# what lg_dec_pool_recurrent_sizeof sizes by index (3, 4, 5: the three handles, opaque here)
+DEC_POOL_RECURRENT_STRUCTS = {0: lg_dec_game_params, 1: lg_dec_game_buffers, 2: lg_dec_act_outputs, 6: lg_dec_lstm_role, 7: lg_dec_rpool_info}
+_DEC_POOL_RECURRENT_LIB_NAME = "liblegged_dec_pool_recurrent.so"
+_dec_pool_recurrent_lib = None
+
+
+def dec_pool_recurrent_library_path() -> str:
+    """In-tree liblegged_dec_pool_recurrent.so; LG_DEC_POOL_RECURRENT_LIB selects another build of the same source."""
+    return os.environ.get("LG_DEC_POOL_RECURRENT_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_POOL_RECURRENT_LIB_NAME)
+
+
+def bind_dec_pool_recurrent(lib):
+    for symbol, (argtypes, restype) in DEC_POOL_RECURRENT_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    for which, st in DEC_POOL_RECURRENT_STRUCTS.items():
+        size = lib.lg_dec_pool_recurrent_sizeof(which)
+        if size != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def load_dec_pool_recurrent_library():
+    """Load the pooled recurrent policy stage of dec_high_level_game or fail loudly -- never a CPU substitute."""
+    global _dec_pool_recurrent_lib
+    if _dec_pool_recurrent_lib is not None:
+        return _dec_pool_recurrent_lib
+    path = dec_pool_recurrent_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _dec_pool_recurrent_lib = bind_dec_pool_recurrent(C.CDLL(path))
+    return _dec_pool_recurrent_lib
+
+
+def _dec_pool_recurrent_call(name, *args, ok=(0,)):
+    lib = load_dec_pool_recurrent_library()
+    rc = getattr(lib, name)(*args)
+    if rc not in ok:
+        raise RuntimeError(f"{name} failed ({rc}): {lib.lg_dec_pool_recurrent_last_error().decode()}")
+    return rc
+
+
+def dec_rpool_create(lstm_handles, actor_handles, role: str, device: int = 0) -> C.c_void_p:
+    """``lg_dec_rpool_create`` over the members' ``lg_lstm`` (ACTOR memory) and ``lg_lstm_actor`` handles; ``role`` is "prey" or "pred".  The
+    handles must outlive the pool and must not be re-created (``load_device`` / ``sync_device`` repack in place, which the pool follows)."""
+    if len(lstm_handles) != len(actor_handles):
+        raise ValueError("one lg_lstm and one lg_lstm_actor handle per member")
+    arrays = [(C.c_void_p * len(hs))(*[getattr(h, "value", h) for h in hs]) for hs in (lstm_handles, actor_handles)]
+    out = C.c_void_p()
+    _dec_pool_recurrent_call("lg_dec_rpool_create", arrays[0], arrays[1], len(lstm_handles), DEC_POOL_ROLES[role], int(device), C.byref(out))
+    return out
+
+
+def dec_rpool_destroy(pool):
+    if pool:
+        load_dec_pool_recurrent_library().lg_dec_rpool_destroy(pool)
+
+
+def dec_rpool_query(pool) -> lg_dec_rpool_info:
+    info = lg_dec_rpool_info()
+    _dec_pool_recurrent_call("lg_dec_rpool_query", pool, C.byref(info))
+    return info
+
+
+def dec_pool_lstm_step(roles, pool_pred, block_slot_pred: Optional[int], pool_prey, block_slot_prey: Optional[int], reset: Optional[int], num_envs: int,
+                       stream: int = 0) -> None:
+    """``lg_dec_pool_lstm_step``: ``lg_dec_lstm_step`` with the weights of a pooled ACTOR memory chosen per 32-env block.  ``roles`` as for
+    ``dec_lstm_step`` (a pooled role's handle may be None: give its five buffers); ``pool_*``: an ``lg_dec_rpool`` handle or None,
+    ``block_slot_*``: the device address of its int32 slot table."""
+    if not isinstance(roles, C.Array):
+        if len(roles) != 4:
+            raise ValueError("lg_dec_pool_lstm_step takes four roles (None = absent)")
+        arr = (lg_dec_lstm_role * 4)()
+        for slot, role in zip(arr, roles):
+            if role is not None:
+                slot.l, slot.x, slot.h_in, slot.c_in, slot.h_out, slot.c_out = (getattr(v, "value", v) for v in role)
+        roles = arr
+    _dec_pool_recurrent_call("lg_dec_pool_lstm_step", roles, pool_pred, block_slot_pred, pool_prey, block_slot_prey, reset, int(num_envs), stream)
+
+
+def dec_pool_lstm_act(pred_actor, prey_actor, ll_policy, pool_pred, block_slot_pred: Optional[int], pool_prey, block_slot_prey: Optional[int],
+                      params: lg_dec_game_params, buffers: lg_dec_game_buffers, h_pred: int, h_prey: int, pred_obs: Optional[int], prey_obs: Optional[int],
+                      ll_obs: int, ll_actions: int, mean_pred: int, mean_prey: int, seed_pred: int, seed_prey: int, step: int, step_counter: Optional[int],
+                      deterministic_pred: bool, deterministic_prey: bool, out_pred: Optional[lg_dec_act_outputs] = None,
+                      out_prey: Optional[lg_dec_act_outputs] = None, stream: int = 0) -> int:
+    """``lg_dec_pool_lstm_act``: ``lg_dec_game_lstm_act`` with the actor MLP of a pooled role chosen per 32-env block.  Returns 0, or -4 when
+    the actors have no shared kernel (the caller then issues the separate launches); raises on any other error."""
+    return _dec_pool_recurrent_call("lg_dec_pool_lstm_act", pred_actor, prey_actor, ll_policy, pool_pred, block_slot_pred, pool_prey, block_slot_prey,
+                                    C.byref(params), C.byref(buffers), h_pred, h_prey, pred_obs, prey_obs, ll_obs, ll_actions, mean_pred, mean_prey,
+                                    int(seed_pred), int(seed_prey), int(step), step_counter, int(bool(deterministic_pred)), int(bool(deterministic_prey)),
+                                    C.byref(out_pred) if out_pred is not None else None, C.byref(out_prey) if out_prey is not None else None, stream,
+                                    ok=(0, -4))
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

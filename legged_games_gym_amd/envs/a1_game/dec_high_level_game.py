@@ -27,6 +27,9 @@ and ``outcome_totals()`` the running integer sums.  A step is still three launch
 ``step_policy`` / ``make_graphed_policy_step`` take an ``rl.OpponentPool`` in place of either ``FusedActor``: the actor launch is then
 ``lg_dec_pool_act`` (include/legged_dec_game_pool.h), the same launch with that role's weights chosen per 32-env block from the pool.
 
+With recurrent policies the pool is an ``rl.RecurrentOpponentPool`` and the two launches of the policy stage are ``lg_dec_pool_lstm_step`` /
+``lg_dec_pool_lstm_act`` (include/legged_dec_pool_recurrent.h): the weights of that role's actor memory and actor MLP chosen per block.
+
 Outcomes per pool member (off by default; ``enable_member_outcomes(pool)``, needs the outcome statistics): the last launch becomes
 ``lg_dec_member_outcome_post`` (include/legged_dec_game_member_outcome.h), ``lg_dec_outcome_post`` that also keeps the six counts per member
 of that pool, read back with ``pool.member_totals_host()``.  Everything else comes out bit-identical.
@@ -211,7 +214,7 @@ class DecHighLevelGame(GameBase):
             raise ValueError("the two FusedActors need different seeds: they draw their noise under the same purposes")
         if recurrent:
             return self._act_recurrent(fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
-                                       outputs, B, with_critic_memory)
+                                       outputs, B, with_critic_memory, pool_pred, pool_prey)
         if pool_pred is None and pool_prey is None:
             rc = capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, obs_pred_in.data_ptr(), obs_prey_in.data_ptr(),
                                    ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed,
@@ -246,49 +249,60 @@ class DecHighLevelGame(GameBase):
     # ------------------------------------------------------------------ recurrent policies
     @staticmethod
     def _recurrent_pair(fused_pred, fused_prey, pool_pred=None, pool_prey=None):
-        """Whether both actors are ``RecurrentFusedActor`` s.  Both agents are recurrent or neither (one train cfg builds both), and the
-        opponent pool holds feed-forward snapshots only."""
+        """Whether both actors are ``RecurrentFusedActor`` s.  Both agents are recurrent or neither (one train cfg builds both), and next to a
+        recurrent actor a pool must be recurrent too (``rl.RecurrentOpponentPool``): an ``OpponentPool`` holds feed-forward snapshots only."""
         rec = [bool(getattr(f, "recurrent", False)) for f in (fused_pred, fused_prey)]
-        if any(rec) and (pool_pred is not None or pool_prey is not None):
+        if any(rec) and any(pool is not None and not getattr(pool, "recurrent", False) for pool in (pool_pred, pool_prey)):
             raise ValueError("the opponent pool is feed-forward: lg_dec_pool_act has no recurrent role, so an OpponentPool cannot stand next to a "
                              "RecurrentFusedActor")
         if rec[0] != rec[1]:
             raise ValueError("both agents of dec_high_level_game are recurrent (RecurrentFusedActor) or neither: lg_dec_game_lstm_act has no mixed pair")
         return rec[0]
 
-    def _recurrent_library(self, fused, say=True):
+    def _recurrent_library(self, fused, say=True, pooled=False):
         """``(library or None, whether lg_dec_game_lstm_act can be used now)``: the low-level role is the split-bf16 kernel, so wide precision
         0 takes the separate actor launches, and a build without the library takes separate launches throughout (a one-line message the
-        first time for each reason).  Decided per call: ``lg_mlp_wide_set_precision`` may change between calls."""
+        first time for each reason).  Decided per call: ``lg_mlp_wide_set_precision`` may change between calls.  ``pooled``: the library of
+        the pooled launches (``lg_dec_pool_lstm_step`` / ``lg_dec_pool_lstm_act``) instead."""
         try:
-            lib = capi.load_dec_game_recurrent_library()
+            lib = capi.load_dec_pool_recurrent_library() if pooled else capi.load_dec_game_recurrent_library()
         except (RuntimeError, OSError) as exc:
-            self._say_separate(f"{type(exc).__name__}: {exc}", say)
+            self._say_separate(f"{type(exc).__name__}: {exc}", say, pooled)
             return None, False
         if fused.lib.lg_mlp_wide_set_precision(-1) != 1:              # (an invalid mode changes nothing and returns the current one)
-            self._say_separate("wide precision 0", say)
+            self._say_separate("wide precision 0", say, pooled)
             return lib, False
         return lib, True
 
-    def _say_separate(self, why, say=True):
+    def _say_separate(self, why, say=True, pooled=False):
         said = self.__dict__.setdefault("_separate_said", set())
-        if say and why not in said:
-            said.add(why)
-            print(f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act x 2 + lg_dec_game_pre + lg_policy_act")
+        if say and (why, pooled) not in said:
+            said.add((why, pooled))
+            if pooled:
+                print(f"[{self.TASK}] pooled recurrent actor launch unavailable ({why}); lg_lstm_actor_act per member + lg_dec_game_pre + lg_policy_act")
+            else:
+                print(f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act x 2 + lg_dec_game_pre + lg_policy_act")
 
     def _act_recurrent(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
-                       outputs, B, with_critic_memory):
+                       outputs, B, with_critic_memory, pool_pred=None, pool_prey=None):
         """``_act`` for two ``RecurrentFusedActor`` s (arguments already checked there).  ``lg_dec_lstm_step``: both actor memories on the
         observations they read, and the critic memory of every agent in ``with_critic_memory``, in one launch on the actors' own ``(h, c)``
         slots (read ``[flip]``, write ``[1 - flip]``); rows that ``reset_buf`` of the previous step marks start from a zero state.  Then
         ``lg_dec_game_lstm_act`` on the two new ``h``.  The critic memories' outputs are left in ``self._critic_out`` (agent -> tensor, None
         when it did not move).  Separate launches (``lg_lstm_actor_act`` x 2 + ``lg_dec_game_pre`` + low-level ``lg_policy_act``) on rc -4, at wide
-        precision 0 or without the library (then ``lg_lstm_step`` per agent as well)."""
+        precision 0 or without the library (then ``lg_lstm_step`` per agent as well).
+        ``pool_pred`` / ``pool_prey``: an ``rl.RecurrentOpponentPool`` whose live actor that agent's ``fused_*`` is.  The two launches are then
+        ``lg_dec_pool_lstm_step`` / ``lg_dec_pool_lstm_act`` (include/legged_dec_pool_recurrent.h), which take that role's weights per 32-env
+        block from the pool member its slot table names; the state is the live actor's.  Their separate launches are one ``lg_lstm_step`` /
+        ``lg_lstm_actor_act`` per member in use on all envs, rows selected by block (``step_memory_separate`` / ``act_separate``)."""
         ll, n = self.ll_env, self.num_envs
         stream = torch.cuda.current_stream(self.device).cuda_stream
         agents = (("pred", fused_pred, obs_pred_in), ("prey", fused_prey, obs_prey_in))
         critics = {a: a in with_critic_memory for a in AGENTS}
-        lib, shared = self._recurrent_library(fused_pred)
+        pools = {"pred": pool_pred, "prey": pool_prey}
+        pooled = pool_pred is not None or pool_prey is not None
+        slots = {a: (pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None) for a, pool in pools.items()}
+        lib, shared = self._recurrent_library(fused_pred, pooled=pooled)
         h, self._critic_out = {}, {}
         if lib is not None:
             roles = []
@@ -300,12 +314,21 @@ class DecHighLevelGame(GameBase):
                     roles.append((lstm.handle, obs.data_ptr(), state[f][0].data_ptr(), state[f][1].data_ptr(), state[1 - f][0].data_ptr(),
                                   state[1 - f][1].data_ptr()) if present else None)
                 h[a], self._critic_out[a] = fused.state_a[1 - f][0], (fused.state_c[1 - f][0] if critics[a] else None)
-            capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
+            if pooled:
+                capi.dec_pool_lstm_step(roles, *slots["pred"], *slots["prey"], self.reset_buf.data_ptr(), n, stream)
+            else:
+                capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
             for a, fused, _ in agents:
                 fused.advance_slots(critics[a])
         else:
             for a, fused, obs in agents:
-                h[a], self._critic_out[a] = fused.step_memories(obs, obs if critics[a] else None, reset=self.reset_buf)
+                if pools[a] is None:
+                    h[a], self._critic_out[a] = fused.step_memories(obs, obs if critics[a] else None, reset=self.reset_buf)
+                    continue
+                h[a], self._critic_out[a] = pools[a].step_memory_separate(obs, reset=self.reset_buf), None
+                if critics[a]:                                   # the critic memory is never pooled: the live actor's, alone
+                    self._critic_out[a] = fused.step_critic_memory(obs, reset=self.reset_buf)
+                fused.advance_slots(critics[a])
         command_pred, mean_pred = fused_pred.output_buffers(n)
         command_prey, mean_prey = fused_prey.output_buffers(n)
         ll_actions = self._ll_fused.output_buffers(n)[0]
@@ -313,22 +336,28 @@ class DecHighLevelGame(GameBase):
         want_prey_copy = out_prey.get("obs_copy") is not None
         if shared:
             step, ctr = fused_prey.peek_step()
-            rc = capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, h["pred"].data_ptr(), h["prey"].data_ptr(),
-                                        obs_pred_in.data_ptr(), obs_prey_in.data_ptr(), ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
-                                        mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, deterministic_pred, deterministic_prey,
-                                        outputs(out_pred, None), outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
+            tail = (self._P, B, h["pred"].data_ptr(), h["prey"].data_ptr(), obs_pred_in.data_ptr(), obs_prey_in.data_ptr(), ll.obs_buf.data_ptr(),
+                    ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, deterministic_pred,
+                    deterministic_prey, outputs(out_pred, None), outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
+            if pooled:
+                rc = capi.dec_pool_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *slots["pred"], *slots["prey"], *tail)
+            else:
+                rc = capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *tail)
             self.last_act_rc = rc
             if rc == 0:
                 fused_pred.next_step(); fused_prey.next_step()     # the launch used this step of both noise streams
                 if carry and want_prey_copy:
                     obs_prey_out.copy_(obs_prey_in)
                 return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
-            self._say_separate("no kernel for this actor pair")
+            self._say_separate("no kernel for this actor pair", pooled=pooled)
         else:
             self.last_act_rc = -4
         for a, fused, obs, det, out in (("pred", fused_pred, obs_pred_in, deterministic_pred, out_pred), ("prey", fused_prey, obs_prey_in, deterministic_prey, out_prey)):
-            command, mean = fused.fused.act_with_mean(h[a], det)
-            self._fill_optional_outputs(out, n, command, mean, fused.ac.std.detach(), obs)
+            if pools[a] is None:
+                (command, mean), std = fused.fused.act_with_mean(h[a], det), fused.ac.std.detach()
+            else:
+                command, mean, std = pools[a].act_separate(h[a], det)        # per member in use, rows by block; std [n, actions] of the rows' members
+            self._fill_optional_outputs(out, n, command, mean, std, obs)
         if carry:
             obs_prey_out.copy_(obs_prey_in)
         capi.dec_game_pre(self._P, B, stream)
@@ -341,10 +370,12 @@ class DecHighLevelGame(GameBase):
         are overwritten (every step path rewrites them before reading them), no noise stream is advanced and no memory moves.  With two
         ``RecurrentFusedActor`` s the warm-up call that raises the LDS limits of both kernels of liblegged_dec_game_recurrent.so outside
         any capture: one ``lg_dec_lstm_step`` of the two actor memories into the slots the next step overwrites, then
-        ``lg_dec_game_lstm_act`` on the actor memories' current outputs."""
+        ``lg_dec_game_lstm_act`` on the actor memories' current outputs.  Given an ``rl.RecurrentOpponentPool`` for an agent, the pooled
+        kernels of liblegged_dec_pool_recurrent.so are warmed up the same way (``lg_dec_pool_lstm_step``, ``lg_dec_pool_lstm_act``)."""
         n = self.num_envs
+        pool_pred, pool_prey = (f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey))
         fused_pred, fused_prey = _live(fused_pred), _live(fused_prey)
-        recurrent = self._recurrent_pair(fused_pred, fused_prey)
+        recurrent = self._recurrent_pair(fused_pred, fused_prey, pool_pred, pool_prey)
         command_pred, mean_pred = fused_pred.output_buffers(n)
         command_prey, mean_prey = fused_prey.output_buffers(n)
         ll_actions = self._ll_fused.output_buffers(n)[0]
@@ -355,7 +386,8 @@ class DecHighLevelGame(GameBase):
             return capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, self.obs_buf_pred.data_ptr(),
                                      self.obs_buf_prey.data_ptr(), self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
                                      mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream) == 0
-        lib, shared = self._recurrent_library(fused_pred, say=False)
+        pooled = pool_pred is not None or pool_prey is not None
+        lib, shared = self._recurrent_library(fused_pred, say=False, pooled=pooled)
         if lib is None:
             return False
         roles, h = [], []
@@ -365,10 +397,14 @@ class DecHighLevelGame(GameBase):
             f, st = fused._flip, fused.state_a
             roles += [(fused.lstm_a.handle, obs.data_ptr(), st[f][0].data_ptr(), st[f][1].data_ptr(), st[1 - f][0].data_ptr(), st[1 - f][1].data_ptr()), None]
             h.append(st[f][0])
+        tail = (self._P, B, h[0].data_ptr(), h[1].data_ptr(), None, None, self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
+                mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream)
+        if pooled:
+            slots = [a for pool in (pool_pred, pool_prey) for a in ((pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None))]
+            capi.dec_pool_lstm_step(roles, *slots, self.reset_buf.data_ptr(), n, stream)
+            return shared and capi.dec_pool_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *slots, *tail) == 0
         capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
-        return shared and capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, h[0].data_ptr(), h[1].data_ptr(), None,
-                                                 None, self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(),
-                                                 fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream) == 0
+        return shared and capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *tail) == 0
 
     def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None, with_critic_memory=()):
         """Rollout step with both agents' actors on the device: ``lg_dec_game_act`` -> ``lg_step`` -> ``lg_dec_game_post``, three launches.
@@ -415,14 +451,15 @@ class DecHighLevelGame(GameBase):
         sim = self.ll_env._sim
         for fused in (_live(fused_pred), _live(fused_prey)):
             self._require_device_step_counter(fused)
-        hold = self._recurrent_pair(_live(fused_pred), _live(fused_prey)) and steps_per_replay % 2 == 1
+        pools = [f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey)]
+        hold = self._recurrent_pair(_live(fused_pred), _live(fused_prey), *pools) and steps_per_replay % 2 == 1
         with_critic_memory = (with_critic_memory,) if isinstance(with_critic_memory, str) else tuple(with_critic_memory or ())
 
         def device_step():
             _, _, ll_actions, B = self._act(fused_pred, fused_prey, self.obs_buf_pred, self.obs_buf_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
                                             deterministic_prey, with_critic_memory=with_critic_memory)
             if hold:
-                fused_pred.hold_slot(); fused_prey.hold_slot()
+                _live(fused_pred).hold_slot(); _live(fused_prey).hold_slot()      # (a pool's state is its live actor's)
             sim.step(ll_actions, -1)
             self._post(B, -1, torch.cuda.current_stream(self.device).cuda_stream)
         self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)

@@ -14,7 +14,7 @@ from .actor_critic import ActorCritic, ActorCriticRecurrent, Memory
 from .ppo import PPO, RolloutStorage
 from .runner import OnPolicyRunner
 from .dec_runner import DecGamePolicyRunner
-from .opponent_pool import OpponentPool, apportion, assign_blocks, assign_blocks_weighted, learner_win_rate, pfsp_weights
+from .opponent_pool import OpponentPool, RecurrentOpponentPool, stale_blocks, apportion, assign_blocks, assign_blocks_weighted, learner_win_rate, pfsp_weights
 
 
 
@@ -30,5 +30,5 @@ def RecurrentFusedActor(*args, **kwargs):
     return _F(*args, **kwargs)
 
 
-__all__ = ["RecurrentFusedActor", "ActorCritic", "ActorCriticRecurrent", "Memory", "PPO", "RolloutStorage", "OnPolicyRunner", "DecGamePolicyRunner", "FusedActor", "OpponentPool", "assign_blocks", "assign_blocks_weighted",
+__all__ = ["RecurrentFusedActor", "ActorCritic", "ActorCriticRecurrent", "Memory", "PPO", "RolloutStorage", "OnPolicyRunner", "DecGamePolicyRunner", "FusedActor", "OpponentPool", "RecurrentOpponentPool", "stale_blocks", "assign_blocks", "assign_blocks_weighted",
            "apportion", "learner_win_rate", "pfsp_weights"]

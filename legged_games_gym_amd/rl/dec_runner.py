@@ -27,11 +27,19 @@ are dealt in proportion to ``pfsp_weights`` of the pool's running counts -- a pa
 round-robin; it needs ``opponent_pool_size > 0`` and the outcome statistics.  With priority 0 the calls to ``assign`` are unchanged.
 
 Recurrent policies (``policy_class_name = "ActorCriticRecurrent"``) train on the device path only: the runner key ``device_rollout`` is
-required, and so are a GPU, memories the device cell covers and no opponent pool -- there is no generic loop for two recurrent agents, so
-each of these raises with its reason instead of falling back.  A step is ``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act`` -> ``lg_step`` ->
+required, and so are a GPU, memories the device cell covers and no feed-forward opponent pool -- there is no generic loop for two recurrent
+agents, so each of these raises with its reason instead of falling back.  A step is ``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act`` -> ``lg_step`` ->
 post.  The opponent samples and only its actor memory advances; the learner's critic memory advances with it.  All actor memories carry on
 across evolutions; at the start of an evolution the agent that becomes the learner zeroes its CRITIC memory's state, which did not move while
-it was the opponent."""
+it was the opponent.
+
+Opponent pool for recurrent policies (runner key ``opponent_pool_recurrent``, default False; read with ``.get()``; ``--opponent_pool_recurrent``).
+With it, ``ActorCriticRecurrent`` and ``opponent_pool_size > 0`` the two pools are ``RecurrentOpponentPool`` s over ``ActorCriticRecurrent``
+copies of the agent's own shape, a step is ``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_lstm_act`` -> ``lg_step`` -> post, and the evolution loop is
+the one above: push at the start, seeded ``assign`` or PFSP weights, member outcomes, ``opponents.csv``, pools in the checkpoints.  A pooled
+role has ONE ``(h, c)`` state, the live opponent's; ``assign`` zeroes the rows of the blocks whose member changed or was overwritten, before
+``runner.learn`` captures its graph.  The key is an explicit opt-in, like every device feature: without it the
+combination keeps its refusal, and the key with feed-forward policies or without a pool raises with its reason."""
 import os
 import re
 
@@ -62,6 +70,7 @@ class DecGamePolicyRunner:
         self.env, self.cfg, self.device, self.log_dir = env, train_cfg["runner"], device, log_dir
         self.priority = opponent_priority_of(self.cfg, env)       # before anything is built
         self.recurrent = self._check_policy_class(train_cfg, device)     # before anything is built, too
+        self.pool_recurrent = bool(self.cfg.get("opponent_pool_recurrent", False))
         self.views = {a: env.agent_view(a, None) for a in AGENTS}
         self.runners = {}
         for a in AGENTS:
@@ -90,17 +99,20 @@ class DecGamePolicyRunner:
             if not device_path:
                 raise ValueError("opponent_pool_size > 0 needs device_rollout (runner key / --device_rollout): the pool is one actor launch with the weights "
                                  "chosen per 32-env block, which only the device path has")
-            from .opponent_pool import OpponentPool
-            from .actor_critic import ActorCritic
+            from .opponent_pool import OpponentPool, RecurrentOpponentPool
+            from .actor_critic import ActorCritic, ActorCriticRecurrent
+            module, pool = (ActorCriticRecurrent, RecurrentOpponentPool) if self.recurrent else (ActorCritic, OpponentPool)
             for a in AGENTS:
                 view, policy_cfg = self.views[a], self.runners[a].policy_cfg
 
                 def make_actor_critic(view=view, policy_cfg=policy_cfg):      # the private module of one snapshot member: the shapes of the agent's own
-                    return ActorCritic(view.num_obs, view.num_obs, view.num_actions, **policy_cfg).to(device)
-                self.pools[a] = OpponentPool(fused[a], make_actor_critic, self.pool_size, a, seed=self.seed, latest_share=self.latest_share,
-                                             num_envs=env.num_envs)
+                    return module(view.num_obs, view.num_obs, view.num_actions, **policy_cfg).to(device)
+                self.pools[a] = pool(fused[a], make_actor_critic, self.pool_size, a, seed=self.seed, latest_share=self.latest_share,
+                                     num_envs=env.num_envs)
             for a in AGENTS:                              # a view's opponent: the pool of the OTHER agent's versions
                 self.views[a].opponent = self.pools["prey" if a == "pred" else "pred"]
+            if self.recurrent:                            # raises the LDS limits of the pooled recurrent kernels here, outside any capture
+                env.shared_actor_launch(fused["pred"], self.pools["prey"])
         self.current_evolution = 0
         if log_dir is not None:
             for a in AGENTS:
@@ -110,6 +122,12 @@ class DecGamePolicyRunner:
         """Whether the policies are recurrent.  ``ActorCriticRecurrent`` is taken only where the device path can run it; every other case
         raises with its reason before anything is built."""
         name = self.cfg.get("policy_class_name", "ActorCritic")
+        pool_recurrent, pool_size = bool(self.cfg.get("opponent_pool_recurrent", False)), int(self.cfg.get("opponent_pool_size", 0) or 0)
+        if pool_recurrent and name == "ActorCritic":
+            raise ValueError("opponent_pool_recurrent with feed-forward policies: the key makes the pools of two ActorCriticRecurrent policies "
+                             "(--policy_class_name ActorCriticRecurrent); a feed-forward pool needs opponent_pool_size alone")
+        if pool_recurrent and pool_size <= 0:
+            raise ValueError("opponent_pool_recurrent without an opponent pool: set the runner key opponent_pool_size > 0 (--opponent_pool K)")
         if name == "ActorCritic":
             return False
         if name != "ActorCriticRecurrent" or not self.cfg.get("device_rollout", False):
@@ -119,8 +137,9 @@ class DecGamePolicyRunner:
         if not str(device).startswith("cuda"):
             raise ValueError(f"ActorCriticRecurrent on dec_high_level_game needs a GPU: the policies are on {device}, the recurrent game kernels run on "
                              "the device and there is no generic loop for two recurrent agents")
-        if int(self.cfg.get("opponent_pool_size", 0) or 0) > 0:
-            raise ValueError("opponent_pool_size > 0 with ActorCriticRecurrent: the opponent pool is feed-forward (lg_dec_pool_act has no recurrent role)")
+        if pool_size > 0 and not pool_recurrent:
+            raise ValueError("opponent_pool_size > 0 with ActorCriticRecurrent: the opponent pool is feed-forward (lg_dec_pool_act has no recurrent role); "
+                             "set the runner key opponent_pool_recurrent (--opponent_pool_recurrent) for pools of recurrent snapshots")
         import torch.nn as nn
         from .recurrent_actor import lstm_unsupported_reason
         policy = train_cfg["policy"]

@@ -233,6 +233,14 @@ class RecurrentFusedActor:
         self._flip = 1 - f
         return self.state_a[1 - f][0], (self.state_c[1 - f][0] if with_c else None)
 
+    def step_critic_memory(self, critic_obs, reset=None):
+        """Advance the critic memory alone on this actor's slots (read ``[flip]``, write ``[1 - flip]``) and return its new output; the caller
+        then calls ``advance_slots(True)`` (the separate launches of a pooled role, whose actor memory ``rl.RecurrentOpponentPool`` advances)."""
+        f = self._flip
+        lstm_step(self.lib, None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[f], self.state_c[1 - f],
+                  critic_obs.shape[0], torch.cuda.current_stream(self.device).cuda_stream)
+        return self.state_c[1 - f][0]
+
     def advance_slots(self, with_critic):
         """What ``step_memories`` does after its launch, for a caller that issued the launch itself on this actor's slots (``lg_dec_lstm_step``
         of ``dec_high_level_game``: read ``[flip]``, write ``[1 - flip]``).  A critic memory that did not move needs both of its slots

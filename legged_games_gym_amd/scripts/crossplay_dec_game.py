@@ -12,7 +12,9 @@ cells of ``S`` replays of a ~100 us step take seconds, so the envs of a launch a
 
 ``crossplay_<i0>_..._<ik>.json`` in the run directory holds the K x K tables ``capture_rate``, ``timed_out_rate`` (the predator failed in
 time) and ``mean_steps`` -- rows are predators, columns are preys -- and the raw totals of every cell.  As with ``play_dec_game --outcomes``,
-episodes still running after ``S`` steps are not counted.  Recurrent checkpoints (``--policy_class_name ActorCriticRecurrent``) are refused."""
+episodes still running after ``S`` steps are not counted.  Recurrent checkpoints (``--policy_class_name ActorCriticRecurrent`` and the
+``--rnn_*`` flags of the run): both ``RecurrentFusedActor`` s are repacked in place per cell, and every cell starts with all memories at zero
+from the same start state as a feed-forward cell."""
 import json
 import os
 
@@ -41,7 +43,7 @@ def crossplay(args, checkpoints, steps=None):
     if not checkpoints:
         raise SystemExit("--checkpoints needs at least one iteration, e.g. --checkpoints 0,200,400")
     args.checkpoint = checkpoints[0]             # the env, the actors and the graph are built on the first checkpoint
-    ev = DecEvaluation(args, allow_recurrent=False)      # (a recurrent checkpoint: one line and out)
+    ev = DecEvaluation(args)
     run_dir = os.path.dirname(ev.checkpoint)
     halves = {}
     for c in dict.fromkeys(checkpoints):

@@ -89,16 +89,15 @@ class DecEvaluation:
     """One env, one pair of device actors and one deterministic step path of ``dec_high_level_game`` for evaluation rollouts that all begin
     at the SAME start: ``torch.manual_seed(seed)``, ``env.reset()``, and a copy of everything on the device taken right there, which
     ``run`` puts back -- with the low-level step counter, which keys every reset draw -- before it rolls out.  On the device path the step is
-    captured ONCE; ``load`` swaps weights underneath the graph (``FusedActor.sync_device`` repacks in place)."""
+    captured ONCE; ``load`` swaps weights underneath the graph (``FusedActor.sync_device`` repacks in place; for a recurrent run
+    ``RecurrentFusedActor.sync_device`` repacks both memories and the actor), and ``run`` starts all memories from zero, so a cell never meets
+    the state another pair of policies left."""
     ENV_STATE = ("rew_buf_prey", "rew_buf_pred", "reset_buf", "time_out_buf", "episode_length_buf", "curr_episode_step", "predator_pos", "_episode_sums",
                  "_episode_means", "_extras_accum", "_extras_ticket")
 
-    def __init__(self, args, allow_recurrent=True):
+    def __init__(self, args):
         if args.task not in a1_game.DEC_TASKS:
             raise SystemExit(f"play_dec_game plays {a1_game.DEC_TASKS}; use scripts.play_game for --task={args.task}")
-        if not allow_recurrent and getattr(args, "policy_class_name", None) == "ActorCriticRecurrent":
-            raise SystemExit("cross-play of recurrent checkpoints is not supported: weights swapped underneath one graph would meet the memories of "
-                             "another policy; use play_dec_game --outcomes per checkpoint")
         a1_game.register_dec()
         env_cfg, train_cfg = task_registry.get_cfgs(name=args.task)
         env_cfg, train_cfg = copy.deepcopy(env_cfg), copy.deepcopy(train_cfg)      # the registered objects keep their values (--num_envs lands on a copy)
@@ -171,7 +170,8 @@ class DecEvaluation:
                 fused.reset_states()
 
     def load(self, state_pred, state_prey):
-        """Put the ``model_state_dict`` halves of two checkpoints under the step path (the captured graph is NOT re-captured)."""
+        """Put the ``model_state_dict`` halves of two checkpoints under the step path (the captured graph is NOT re-captured): both
+        ``FusedActor`` s, or both ``RecurrentFusedActor`` s, are repacked in place."""
         self.modules["pred"].load_state_dict(state_pred)
         self.modules["prey"].load_state_dict(state_prey)
         if self.fused is not None:

@@ -12,7 +12,9 @@ the checkpoints then carry the pools.  With ``--outcome_stats`` as well, the out
 ``opponents.csv``, and ``--opponent_priority P`` (P > 0) deals the non-live blocks by prioritised fictitious self-play: a past opponent the
 learner loses to gets more envs.  ``--policy_class_name ActorCriticRecurrent [--rnn_hidden_size H]`` with ``--device_rollout``
 trains two LSTM policies (four launches per step: ``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act`` -> ``lg_step`` -> post); without
-``--device_rollout``, on the CPU, with a GRU / several layers / more than 256 units or with ``--opponent_pool`` the runner stops and says why.
+``--device_rollout``, on the CPU, with a GRU / several layers / more than 256 units or with ``--opponent_pool`` alone the runner stops and says
+why.  ``--opponent_pool K --opponent_pool_recurrent`` gives two recurrent policies their pools (``rl.RecurrentOpponentPool``: the launches are
+``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_lstm_act``, the weights of a block's actor memory and actor MLP its pool member's).
 Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
 from legged_games_gym_amd.envs import a1_game
@@ -33,6 +35,8 @@ def train(args):
     if args.opponent_pool:                   # runner keys, read with .get() as well
         runner_cfg = task_registry.get_cfgs(args.task)[1].runner
         runner_cfg.opponent_pool_size, runner_cfg.opponent_latest_share = args.opponent_pool, args.opponent_latest_share
+    if args.opponent_pool_recurrent:         # a runner key as well; the runner refuses it without the pool or with feed-forward policies
+        task_registry.get_cfgs(args.task)[1].runner.opponent_pool_recurrent = True
     if args.opponent_priority:               # a runner key as well; the runner refuses it without the pool or the outcome statistics
         task_registry.get_cfgs(args.task)[1].runner.opponent_priority = args.opponent_priority
     if args.outcome_stats:                   # read with getattr() by the env: no field of the registered config classes

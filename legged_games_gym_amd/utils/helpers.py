@@ -226,6 +226,9 @@ def get_args(argv=None):
     p.add_argument("--opponent_priority", type=float, default=0.0,
                    help="with --opponent_pool and --outcome_stats: deal the non-live blocks in proportion to (1 - learner's win rate against the member) ** P "
                         "instead of round-robin (runner key opponent_priority; 0 = off)")
+    p.add_argument("--opponent_pool_recurrent", action="store_true", default=False,
+                   help="with --opponent_pool and --policy_class_name ActorCriticRecurrent: the pools hold recurrent snapshots (runner key "
+                        "opponent_pool_recurrent; the actor memory and the actor MLP of a 32-env block are its pool member's)")
     # flags gymutil.parse_arguments contributes
     p.add_argument("--sim_device", type=str, default="cuda:0")
     p.add_argument("--pipeline", type=str, default="gpu")

@@ -39,7 +39,14 @@ three-launch step, by the method of ``--outcome``: one process, two-step graphs,
 step -> profiles/dec_recurrent_step.json.  ``--trace`` replays the four-launch graph only, for a kernel table in a run of its own:
 ``rocprofv3 --kernel-trace --stats -- python tools/dec_game_probe.py --recurrent --trace --envs 4096``.
 
-    python tools/dec_game_probe.py --recurrent [--envs 2000 4096] [--step-replays 2000] [--repeats 5]"""
+    python tools/dec_game_probe.py --recurrent [--envs 2000 4096] [--step-replays 2000] [--repeats 5]
+
+``--recurrent-pool`` times that four-launch recurrent step with the plain launches against the pooled launches of
+include/legged_dec_pool_recurrent.h (``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_lstm_act`` -> k_step -> post) with 1, 4 and 8 members (``--members``) of
+an ``rl.RecurrentOpponentPool`` on the prey role, the 32-env blocks dealt round-robin over the members, by the same method ->
+profiles/dec_recurrent_pool_step.json.
+
+    python tools/dec_game_probe.py --recurrent-pool [--envs 2000 4096] [--members 1 4 8] [--step-replays 2000] [--repeats 5]"""
 import argparse
 import json
 import os
@@ -450,6 +457,57 @@ def recurrent_main(args):
     print("wrote", out)
 
 
+def recurrent_pool_main(args):
+    """Two-step graphs of the four-launch recurrent policy step: the plain launches (``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act``) against the
+    pooled launches (``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_lstm_act``) with --members members on the prey role, the blocks dealt round-robin;
+    same process, same sizes, alternating repeats; microseconds per STEP."""
+    from legged_games_gym_amd.rl import ActorCriticRecurrent, RecurrentOpponentPool
+    S, units = 2, args.rnn_hidden_size
+    names = ["plain_four_launch_step"] + [f"pooled_{m}_members" for m in args.members]
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.step_replays, "repeats": args.repeats, "rnn_hidden_size": units,
+              "steps_per_replay": S, "pool_role": "prey", "learner": "pred (its critic memory moves)", "unit": "us per policy step", "envs": {}}
+    module = lambda: ActorCriticRecurrent(16, 16, 4, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN, rnn_hidden_size=units).to(DEV)
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            envs, steps, actors = [], [], []                     # (a graph reads its actors' weights and memories where they are: all kept until the size is done)
+            for members in [0] + list(args.members):
+                env = make_env(n, args.mesh, tmp)
+                pred, prey = recurrent_pair(env, units)
+                opponent = prey
+                if members:
+                    opponent = RecurrentOpponentPool(prey, module, max(1, members - 1), "prey", seed=1, num_envs=n)
+                    for k in range(members - 1):
+                        torch.manual_seed(10 + k)
+                        opponent.push(module().state_dict(), pushed_at=k)
+                    opponent.set_slots(torch.arange(opponent.slot_table(n).shape[0]) % members)      # round-robin: all members in flight
+                if env.shared_actor_launch(pred, opponent) is not True:      # raises the LDS limits outside the capture
+                    raise RuntimeError("the recurrent actor launch refused the actors")
+                steps.append(env.make_graphed_policy_step(pred, opponent, steps_per_replay=S, with_critic_memory=("pred",)))
+                assert env.last_act_rc == 0
+                envs.append(env); actors.append((pred, opponent))
+            for fn in steps:
+                timed(fn, args.step_replays // (4 * S))          # warm every graph before the first timed window
+            t = [[] for _ in steps]
+            for _ in range(args.repeats):
+                for i, fn in enumerate(steps):
+                    t[i].append(timed(fn, args.step_replays // S) / S)
+            row = {name: spread(x) for name, x in zip(names, t)}
+            for name, x in zip(names[1:], t[1:]):
+                row[f"{name}_minus_plain"] = spread([y - z for z, y in zip(t[0], x)])
+            for env in envs:
+                assert torch.isfinite(env.obs_buf_prey).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            result["envs"][str(n)] = row
+            print(f"{n} envs, per step of a two-step graph: " + "; ".join(f"{name} {statistics.median(x):.1f} us ({min(x):.1f} .. {max(x):.1f})" for name, x in zip(names, t)),
+                  flush=True)
+            torch.cuda.synchronize()
+            del steps, envs, actors
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_recurrent_pool_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 DEFAULT_OUT = os.path.join(REPO, "profiles", "dec_game_act.json")
 
 
@@ -473,7 +531,11 @@ def main():
                     "separate launches, and the feed-forward three-launch step; writes profiles/dec_recurrent_step.json")
     ap.add_argument("--rnn-hidden-size", type=int, default=256, help="--recurrent: units of every memory")
     ap.add_argument("--trace", action="store_true", help="--recurrent: replay the four-launch graph only and write nothing (for a rocprofv3 kernel table)")
+    ap.add_argument("--recurrent-pool", action="store_true", help="time the four-launch recurrent policy step with the plain launches against the pooled launches "
+                    "with --members members on the prey role; writes profiles/dec_recurrent_pool_step.json")
     args = ap.parse_args()
+    if args.recurrent_pool:
+        return recurrent_pool_main(args)
     if args.recurrent:
         return recurrent_main(args)
     if args.outcome:
