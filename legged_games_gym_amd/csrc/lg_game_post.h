@@ -28,6 +28,9 @@ LG_DEV GamePose game_load_pose(const float *pp, const float *root) {            
 // then differs from n / d by |r / d| * 2^-22 < 2^-21 ulp(q) before its single rounding.  n / d with d <= 2^20 is either a float
 // or at least ulp / 2^21 away from every rounding boundary (a boundary is a 25-bit number m / 2^k, and |n / d - m / 2^k| >= 1 / (d 2^k)),
 // so that rounding lands on the nearest float of the true quotient.  tests/test_gpu_pursuer_game.py checks every ep in 0 .. 2L.
+// For any finite floats with a normal d the same step leaves |q - n / d| far below an ulp before the rounding, so n = +-d gives exactly +-1:
+// game_observe needs that of the acos argument of a predator dead ahead or dead behind (the plain division, d's mantissa times its 1-ulp
+// reciprocal, returns a neighbour of 1 for some d: a predator dead behind at 3 m came out 3.5e-4 rad short of pi).  0 / 0 stays NaN (0 * inf).
 LG_DEV float game_quotient(float n, float d) {
     const float y = __builtin_amdgcn_rcpf(d);
     const float q0 = n * y;
@@ -107,8 +110,8 @@ LG_DEV void game_observe(const float half_fov, const GamePose &s, const GameHist
     const float fx = 1.0f - yz * tz, fy = yw * tz;
     const float dotv = fx * rx + fy * ry;
     const float denom = sqrtf(fx * fx + fy * fy) * sqrtf((rx * rx + ry * ry) + rz * rz);
-    const float angle = game_wrap_to_pi(acosf(dotv / denom));
-    const bool visible = fabsf(angle) <= half_fov;                                            // NaN (0/0) compares false: occluded
+    const float angle = game_wrap_to_pi(acosf(game_quotient(dotv, denom)));                   // no clamp: the reference has none
+    const bool visible = fabsf(angle) <= half_fov;                                            // NaN (0/0, an argument past 1) compares false: occluded
     obs[0] = k.h[0]; obs[1] = k.h[1]; obs[2] = k.h[2]; obs[3] = k.h[3]; obs[4] = k.h[4]; obs[5] = k.h[5];
     obs[6] = k.o[0]; obs[7] = k.o[1]; obs[8] = k.o[2];
     obs[9] = visible ? rx : k.o[0]; obs[10] = visible ? ry : k.o[1]; obs[11] = visible ? rz : k.o[2];

@@ -4,7 +4,8 @@ joints, both observations, the episode means).
 
 Written like tests/game_twin.py, whose pieces it imports: every expression in the kernel's operation order, rounding once per operation,
 so everything copied, added, subtracted or multiplied is bit-comparable with the device; values behind ``sqrt`` / ``acos`` (the rewards'
-distance, the flags) are not, which is why the tests keep their inputs away from the thresholds (``game_twin.margins``).  The episode
+distance, the flags) are not, which is why the tests keep their inputs away from the thresholds (``game_twin.margins``; the decisions AT
+the thresholds are pinned against float64 on designed inputs by tests/game_edges.py).  The episode
 means are a sum over envs whose order neither torch nor the device fixes: ``means_bound`` is their tolerance."""
 import numpy as np
 

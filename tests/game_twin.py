@@ -3,7 +3,8 @@ k_game_post (episode step, predator integration, reward, dones, root-state reset
 
 Every expression is written in the kernel's operation order and rounds once per operation (the kernels are compiled with floating-point
 contraction off), so everything that is copied, added, subtracted or multiplied is bit-comparable with the device; values behind ``sqrt`` /
-``acos`` (the reward's distance, the three flags) are not, which is why the tests keep their inputs away from the thresholds (``margins``).
+``acos`` (the reward's distance, the three flags) are not, which is why the tests keep their inputs away from the thresholds (``margins``);
+the decisions AT the thresholds are pinned against float64 on designed inputs by tests/game_edges.py.
 Draws come from tests/philox_np.py under the two game purposes, or are passed in (fixtures record the draws the reference consumed)."""
 import numpy as np
 
