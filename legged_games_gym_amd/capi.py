@@ -972,6 +972,61 @@ def dec_pool_lstm_act(pred_actor, prey_actor, ll_policy, pool_pred, block_slot_p
                                     ok=(0, -4))
 
 
+# ---------------------------------------------------------------------------------------------------------------- legged_dec_game_privileged.h
+# The privileged (critic-only) observations of dec_high_level_game, a sixth library (csrc/liblegged_dec_game_privileged.so): outside ABI /
+# ALL_SYMBOLS / bind_all.  It reads lg_dec_game_params / lg_dec_game_buffers and no handle of the other libraries.
+LG_DEC_NUM_PRIV_PREY, LG_DEC_NUM_PRIV_PRED = 22, 10
+DEC_GAME_PRIVILEGED_ABI = {
+    "lg_dec_game_privileged_obs": ([_P(lg_dec_game_params), _P(lg_dec_game_buffers), _vp, _vp, _vp], _int),
+    "lg_dec_game_privileged_last_error": ([], C.c_char_p),
+    "lg_dec_game_privileged_sizeof": _SIZEOF,
+}
+DEC_GAME_PRIVILEGED_SYMBOLS = list(DEC_GAME_PRIVILEGED_ABI)
+DEC_GAME_PRIVILEGED_STRUCTS = {0: lg_dec_game_params, 1: lg_dec_game_buffers}      # what lg_dec_game_privileged_sizeof sizes by index
+_DEC_GAME_PRIVILEGED_LIB_NAME = "liblegged_dec_game_privileged.so"
+_dec_game_privileged_lib = None
+
+
+def dec_game_privileged_library_path() -> str:
+    """In-tree liblegged_dec_game_privileged.so; LG_DEC_GAME_PRIVILEGED_LIB selects another build of the same source."""
+    return os.environ.get("LG_DEC_GAME_PRIVILEGED_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_GAME_PRIVILEGED_LIB_NAME)
+
+
+def bind_dec_game_privileged(lib):
+    for symbol, (argtypes, restype) in DEC_GAME_PRIVILEGED_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    for which, st in DEC_GAME_PRIVILEGED_STRUCTS.items():
+        size = lib.lg_dec_game_privileged_sizeof(which)
+        if size != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def load_dec_game_privileged_library():
+    """Load the privileged observations of dec_high_level_game or fail loudly -- never a CPU substitute."""
+    global _dec_game_privileged_lib
+    if _dec_game_privileged_lib is not None:
+        return _dec_game_privileged_lib
+    path = dec_game_privileged_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _dec_game_privileged_lib = bind_dec_game_privileged(C.CDLL(path))
+    return _dec_game_privileged_lib
+
+
+def dec_game_privileged_obs(params: lg_dec_game_params, buffers: lg_dec_game_buffers, priv_pred: Optional[int], priv_prey: Optional[int],
+                            stream: int = 0) -> None:
+    """``lg_dec_game_privileged_obs``: the critic-only rows of either agent ([N,10] / [N,22] device addresses, None = not written) from the
+    state the post launch left."""
+    lib = load_dec_game_privileged_library()
+    rc = lib.lg_dec_game_privileged_obs(C.byref(params), C.byref(buffers), priv_pred, priv_prey, stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_game_privileged_obs failed ({rc}): {lib.lg_dec_game_privileged_last_error().decode()}")
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

@@ -34,6 +34,14 @@ Outcomes per pool member (off by default; ``enable_member_outcomes(pool)``, need
 ``lg_dec_member_outcome_post`` (include/legged_dec_game_member_outcome.h), ``lg_dec_outcome_post`` that also keeps the six counts per member
 of that pool, read back with ``pool.member_totals_host()``.  Everything else comes out bit-identical.
 
+Privileged observations (off by default; ``cfg.env.num_privileged_obs_prey = 22`` and / or ``num_privileged_obs_predator = 10``): an
+asymmetric critic.  The critic exists during training only, so it may read what the prey's sensor hides: ``_post`` then issues one more
+launch, ``lg_dec_game_privileged_obs`` (include/legged_dec_game_privileged.h), right behind the post launch on every step path, which writes
+the agent's critic row from the post-reset state -- the observations, the true relative position, the prey's yaw-forward vector and the
+episode clock; for the predator the prey's velocity and current visibility flag as well.  The buffers alternate
+with the observation pair, ``step_policy(privileged_out=...)`` lets the launch write straight into a caller's storage, and with both fields
+``None`` no library is loaded and no launch is added.
+
 ``agent_view(agent, opponent)`` gives one agent's single-agent surface (what ``rl.OnPolicyRunner`` drives) with the other agent acting
 inside every step.  Deliberate differences from the reference are listed in DESIGN.md section 8 ("Quirks", G10 onward)."""
 import torch
@@ -47,6 +55,18 @@ SEED_OFFSET_PREY = 7919                      # noise seeds of the two sampled ac
 SEED_OFFSET_PRED = 7919 + 104729
 SUMS = ("evasion", "pursuit", "termination")     # rows of the device episode sums / entries of episode_means (include/legged_dec_game.h)
 AGENTS = ("pred", "prey")
+PRIVILEGED_WIDTHS = {"pred": capi.LG_DEC_NUM_PRIV_PRED, "prey": capi.LG_DEC_NUM_PRIV_PREY}     # include/legged_dec_game_privileged.h
+
+
+def check_privileged_widths(num_privileged_obs_prey, num_privileged_obs_predator):
+    """The two config fields ``env.num_privileged_obs_prey`` / ``env.num_privileged_obs_predator``: each ``None`` (that agent's critic reads its
+    observations) or the one width ``lg_dec_game_privileged_obs`` is compiled for.  Returns the agents that are on."""
+    want = (capi.LG_DEC_NUM_PRIV_PREY, capi.LG_DEC_NUM_PRIV_PRED)
+    got = (num_privileged_obs_prey, num_privileged_obs_predator)
+    if any(g is not None and (isinstance(g, bool) or g != w) for g, w in zip(got, want)):
+        raise ValueError(f"dec_high_level_game is compiled for {want[0]} prey and {want[1]} predator privileged observations (or None for either), "
+                         f"got {got}")
+    return tuple(a for a, g in (("pred", num_privileged_obs_predator), ("prey", num_privileged_obs_prey)) if g is not None)
 
 
 class DecHighLevelGame(GameBase):
@@ -68,11 +88,13 @@ class DecHighLevelGame(GameBase):
         sizes = (self.num_obs_prey, self.num_actions_prey, self.num_obs_pred, self.num_actions_pred)
         if sizes != (capi.LG_DEC_NUM_OBS_PREY, capi.LG_DEC_NUM_ACTIONS_PREY, capi.LG_DEC_NUM_OBS_PRED, capi.LG_DEC_NUM_ACTIONS_PRED):
             raise ValueError(f"dec_high_level_game is compiled for 16 / 4 prey and 3 / 2 predator observations / actions, got {sizes}")
-        if self.num_privileged_obs_prey is not None or self.num_privileged_obs_pred is not None:
-            raise NotImplementedError("the reference's dec_high_level_game has no privileged observations")
+        self._privileged = check_privileged_widths(self.num_privileged_obs_prey, self.num_privileged_obs_pred)
+        if self._privileged:
+            capi.load_dec_game_privileged_library()            # raises when it is not built: no launch is quietly left out
         if self.ll_env.num_dof != capi.LG_MAX_DOF:
             raise ValueError("dec_high_level_game resets the 12 joints of the low-level robot")
         self.privileged_obs_buf_prey = self.privileged_obs_buf_pred = None
+        self._priv_pair = {a: None for a in AGENTS}
         self.extras = {}
         self.enable_viewer_sync = True
         self.viewer = None
@@ -83,6 +105,8 @@ class DecHighLevelGame(GameBase):
         self._member_pool = self._member_outcome = None
         if getattr(cfg.env, "outcome_stats", False):           # no field of the registered config classes: they stay value for value the reference's
             self.enable_outcome_stats()
+        if self._privileged:
+            self._write_privileged()                           # valid from construction on
         self.init_done = True
 
     # ------------------------------------------------------------------ hot path
@@ -93,6 +117,7 @@ class DecHighLevelGame(GameBase):
         self._obs_flip ^= 1
         self.obs_buf_prey = self._obs_pair_prey[self._obs_flip]
         self.obs_buf_pred = self._obs_pair_pred[self._obs_flip]
+        self._select_privileged()
         if carry:
             self.obs_buf_prey.copy_(prev)
         return prev
@@ -101,6 +126,40 @@ class DecHighLevelGame(GameBase):
         self._obs_flip ^= 1
         self.obs_buf_prey = self._obs_pair_prey[self._obs_flip]
         self.obs_buf_pred = self._obs_pair_pred[self._obs_flip]
+        self._select_privileged()
+
+    def _select_privileged(self):
+        """The privileged buffers alternate with the observations, for the same reason: ``PPO.act`` keeps the critic observations until
+        ``process_env_step``."""
+        for a in self._privileged:
+            setattr(self, f"privileged_obs_buf_{a}", self._priv_pair[a][self._obs_flip])
+
+    def refresh_privileged_observations(self):
+        """Write the privileged rows again from the current state, after the caller edited what they are taken from (a runner that
+        randomises ``episode_length_buf`` at start).  Nothing to do with both config fields ``None``."""
+        if self._privileged:
+            self._write_privileged()
+
+    def _own_privileged(self):
+        """Before a capture: the privileged rows back in the env's own pair when the last ``step_policy`` left them in a caller's tensor."""
+        for a in self._privileged:
+            last = getattr(self, f"privileged_obs_buf_{a}")
+            if last is not self._priv_pair[a][self._obs_flip]:
+                self._priv_pair[a][self._obs_flip].copy_(last)
+        self._select_privileged()
+
+    def _write_privileged(self, B=None, stream=None, out=None):
+        """``lg_dec_game_privileged_obs`` on the current state: the rows of the agents that are on, into the env's current buffers or into
+        the caller's tensors ``out`` (agent -> tensor), which the env then hands out as that agent's privileged observations."""
+        if B is None:                                          # from the host (construction, reset_idx): into the env's own pair
+            self._select_privileged()
+            B = capi.dec_game_buffers(dict(self._pointers, obs_pred=self.obs_buf_pred.data_ptr(), obs_prey=self.obs_buf_prey.data_ptr()))
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        for a, t in (out or {}).items():
+            setattr(self, f"privileged_obs_buf_{a}", t)
+        dst = {a: getattr(self, f"privileged_obs_buf_{a}") for a in AGENTS}
+        capi.dec_game_privileged_obs(self._P, B, *(None if dst[a] is None else dst[a].data_ptr() for a in AGENTS), stream)
 
     def step(self, command_pred, command_prey):
         """Apply both agents' commands, run one low-level policy step, advance the predator (reference :169-210).  ``command_pred`` [num_envs, 2]
@@ -115,15 +174,18 @@ class DecHighLevelGame(GameBase):
         self._post(B, ll.common_step_counter, stream)
         return self._step_result()
 
-    def _post(self, B, common_step_counter, stream):
-        """The last launch of every step path: ``lg_dec_game_post``, or ``lg_dec_outcome_post`` with the outcome statistics on, or
-        ``lg_dec_member_outcome_post`` with them on and a pool bound (``enable_member_outcomes``)."""
+    def _post(self, B, common_step_counter, stream, privileged_out=None):
+        """The post stage of every step path: ``lg_dec_game_post``, or ``lg_dec_outcome_post`` with the outcome statistics on, or
+        ``lg_dec_member_outcome_post`` with them on and a pool bound (``enable_member_outcomes``); with privileged observations on,
+        ``lg_dec_game_privileged_obs`` right behind whichever ran."""
         if self._outcome is None:
             capi.dec_game_post(self._P, B, common_step_counter, stream)
         elif self._member_outcome is None:
             capi.dec_outcome_post(self._P, B, self._outcome, common_step_counter, stream)
         else:
             capi.dec_member_outcome_post(self._P, B, self._outcome, self._member_outcome, common_step_counter, stream)
+        if self._privileged:
+            self._write_privileged(B, stream, privileged_out)
 
     # ------------------------------------------------------------------ outcome statistics
     def enable_member_outcomes(self, pool):
@@ -159,12 +221,13 @@ class DecHighLevelGame(GameBase):
         """Capture ``step(policy_pred(obs_buf_pred), policy_prey(obs_buf_prey))`` into one HIP graph and return a zero-argument callable that
         replays it: both policies, ``lg_dec_game_pre``, low-level actor, ``lg_step``, ``lg_dec_game_post`` -- no host in between.  The
         policies must be capturable and read ``self.obs_buf_pred`` / ``self.obs_buf_prey``."""
+        self._own_privileged()
         self._step_graph, replay = self._capture(lambda: self._device_step(policy_pred(self.obs_buf_pred), policy_prey(self.obs_buf_prey)), warmup, steps_per_replay, self._step_result)
         return replay
 
     # ------------------------------------------------------------------ hot path with both actors on the device
     def _act(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_pred_out, obs_prey_out, deterministic_pred, deterministic_prey, out_pred=None, out_prey=None,
-             with_critic_memory=()):
+             with_critic_memory=(), critic_obs=None):
         """``lg_dec_game_act``: both commands = clip(actor(obs) + noise), the prey's into the low-level commands, the low-level actions, and
         the prey's observations copied to ``obs_prey_out`` (where ``lg_dec_game_post`` then shifts the history in place) -- one launch.
         Separate launches when the actor triple or the wide precision has no shared kernel (rc -4).  ``out_*``: dicts of optional float32
@@ -173,7 +236,8 @@ class DecHighLevelGame(GameBase):
         (include/legged_dec_game_pool.h), which takes that role's weights, biases and std per 32-env block from the pool member its slot table
         names; the pool's ``live`` actor supplies seed, step source and output buffers.  Its rc -4 path is one ``lg_policy_act`` on all envs
         per member in use, rows selected by block.
-        Two ``RecurrentFusedActor`` s take ``_act_recurrent`` (``with_critic_memory``: the agents whose critic memory moves too).
+        Two ``RecurrentFusedActor`` s take ``_act_recurrent`` (``with_critic_memory``: the agents whose critic memory moves too;
+        ``critic_obs``: agent -> what that memory reads, None = the agent's observations).
         Returns ``(command_pred, mean_pred), (command_prey, mean_prey), ll_actions, buffers``."""
         ll, n = self.ll_env, self.num_envs
         pool_pred, pool_prey = (f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey))
@@ -214,7 +278,7 @@ class DecHighLevelGame(GameBase):
             raise ValueError("the two FusedActors need different seeds: they draw their noise under the same purposes")
         if recurrent:
             return self._act_recurrent(fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
-                                       outputs, B, with_critic_memory, pool_pred, pool_prey)
+                                       outputs, B, with_critic_memory, pool_pred, pool_prey, critic_obs)
         if pool_pred is None and pool_prey is None:
             rc = capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, obs_pred_in.data_ptr(), obs_prey_in.data_ptr(),
                                    ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed,
@@ -284,7 +348,7 @@ class DecHighLevelGame(GameBase):
                 print(f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act x 2 + lg_dec_game_pre + lg_policy_act")
 
     def _act_recurrent(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
-                       outputs, B, with_critic_memory, pool_pred=None, pool_prey=None):
+                       outputs, B, with_critic_memory, pool_pred=None, pool_prey=None, critic_obs=None):
         """``_act`` for two ``RecurrentFusedActor`` s (arguments already checked there).  ``lg_dec_lstm_step``: both actor memories on the
         observations they read, and the critic memory of every agent in ``with_critic_memory``, in one launch on the actors' own ``(h, c)``
         slots (read ``[flip]``, write ``[1 - flip]``); rows that ``reset_buf`` of the previous step marks start from a zero state.  Then
@@ -294,10 +358,13 @@ class DecHighLevelGame(GameBase):
         ``pool_pred`` / ``pool_prey``: an ``rl.RecurrentOpponentPool`` whose live actor that agent's ``fused_*`` is.  The two launches are then
         ``lg_dec_pool_lstm_step`` / ``lg_dec_pool_lstm_act`` (include/legged_dec_pool_recurrent.h), which take that role's weights per 32-env
         block from the pool member its slot table names; the state is the live actor's.  Their separate launches are one ``lg_lstm_step`` /
-        ``lg_lstm_actor_act`` per member in use on all envs, rows selected by block (``step_memory_separate`` / ``act_separate``)."""
+        ``lg_lstm_actor_act`` per member in use on all envs, rows selected by block (``step_memory_separate`` / ``act_separate``).
+        ``critic_obs``: agent -> the input of its critic memory (the privileged observations that belong to the observations read), None or
+        absent = the observations themselves."""
         ll, n = self.ll_env, self.num_envs
         stream = torch.cuda.current_stream(self.device).cuda_stream
         agents = (("pred", fused_pred, obs_pred_in), ("prey", fused_prey, obs_prey_in))
+        cobs = {a: obs if (critic_obs or {}).get(a) is None else critic_obs[a] for a, _, obs in agents}
         critics = {a: a in with_critic_memory for a in AGENTS}
         pools = {"pred": pool_pred, "prey": pool_prey}
         pooled = pool_pred is not None or pool_prey is not None
@@ -310,8 +377,11 @@ class DecHighLevelGame(GameBase):
                 if fused.num_envs != n:
                     fused._allocate(n)
                 f = fused._flip
-                for lstm, state, present in ((fused.lstm_a, fused.state_a, True), (fused.lstm_c, fused.state_c, critics[a])):
-                    roles.append((lstm.handle, obs.data_ptr(), state[f][0].data_ptr(), state[f][1].data_ptr(), state[1 - f][0].data_ptr(),
+                for lstm, state, present, x in ((fused.lstm_a, fused.state_a, True, obs), (fused.lstm_c, fused.state_c, critics[a], cobs[a])):
+                    if present and x.shape[-1] != lstm.num_in:
+                        raise ValueError(f"the {a} agent's memory reads {lstm.num_in} inputs, its input here has {x.shape[-1]} (a critic memory reads "
+                                         "the privileged observations where they are on)")
+                    roles.append((lstm.handle, x.data_ptr(), state[f][0].data_ptr(), state[f][1].data_ptr(), state[1 - f][0].data_ptr(),
                                   state[1 - f][1].data_ptr()) if present else None)
                 h[a], self._critic_out[a] = fused.state_a[1 - f][0], (fused.state_c[1 - f][0] if critics[a] else None)
             if pooled:
@@ -323,11 +393,11 @@ class DecHighLevelGame(GameBase):
         else:
             for a, fused, obs in agents:
                 if pools[a] is None:
-                    h[a], self._critic_out[a] = fused.step_memories(obs, obs if critics[a] else None, reset=self.reset_buf)
+                    h[a], self._critic_out[a] = fused.step_memories(obs, cobs[a] if critics[a] else None, reset=self.reset_buf)
                     continue
                 h[a], self._critic_out[a] = pools[a].step_memory_separate(obs, reset=self.reset_buf), None
                 if critics[a]:                                   # the critic memory is never pooled: the live actor's, alone
-                    self._critic_out[a] = fused.step_critic_memory(obs, reset=self.reset_buf)
+                    self._critic_out[a] = fused.step_critic_memory(cobs[a], reset=self.reset_buf)
                 fused.advance_slots(critics[a])
         command_pred, mean_pred = fused_pred.output_buffers(n)
         command_prey, mean_prey = fused_prey.output_buffers(n)
@@ -406,7 +476,8 @@ class DecHighLevelGame(GameBase):
         capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
         return shared and capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *tail) == 0
 
-    def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None, with_critic_memory=()):
+    def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None, with_critic_memory=(),
+                    privileged_out=None):
         """Rollout step with both agents' actors on the device: ``lg_dec_game_act`` -> ``lg_step`` -> ``lg_dec_game_post``, three launches.
         Returns ``(command_pred, mean_pred), (command_prey, mean_prey), step result``: the clipped commands (what ``step`` leaves in the
         caller's tensors) and the actors' outputs, all in the ``FusedActor`` buffers.  ``out_pred`` / ``out_prey``: dicts of optional float32
@@ -417,26 +488,46 @@ class DecHighLevelGame(GameBase):
         both actor memories advance on their observations, rows whose episode ended in the previous step from a zero state.
         ``with_critic_memory``: the agents ("pred", "prey") whose critic memory advances in the same launch; such an agent's tuple gets the
         critic memory's output of the step as a third value (the actor's buffer, re-used two steps later).  A critic memory that is not
-        named stays where it is."""
+        named stays where it is; a critic memory that moves reads the agent's privileged observations where those are on.
+
+        ``privileged_out``: an optional dict ``{"pred": tensor, "prey": tensor}`` (either key may be absent) of contiguous float32
+        ``[num_envs, 10]`` / ``[num_envs, 22]`` destinations for THIS step's new privileged rows: ``lg_dec_game_privileged_obs`` writes there
+        instead of into the env's pair, and the step result's privileged slots are those tensors (a runner's rollout storage)."""
         ll = self.ll_env
+        privileged_out = self._check_privileged_out(privileged_out)
         with_critic_memory = (with_critic_memory,) if isinstance(with_critic_memory, str) else tuple(with_critic_memory or ())
         unknown = set(with_critic_memory) - set(AGENTS)
         if unknown:
             raise ValueError(f"with_critic_memory names agents of {AGENTS}, got {sorted(unknown)}")
         prev_pred = self.obs_buf_pred
+        prev_priv = {a: getattr(self, f"privileged_obs_buf_{a}") for a in AGENTS}
         prev_prey = self._flip_observations(carry=False)
         try:
             pred, prey, ll_actions, B = self._act(fused_pred, fused_prey, prev_pred, prev_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
-                                                  deterministic_prey, out_pred, out_prey, with_critic_memory)
+                                                  deterministic_prey, out_pred, out_prey, with_critic_memory, critic_obs=prev_priv)
         except Exception:
             self._unflip_observations()
+            for a in self._privileged:
+                setattr(self, f"privileged_obs_buf_{a}", prev_priv[a])
             raise
         ll.step(ll_actions)
-        self._post(B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream)
+        self._post(B, -1 if ll._capturing else ll.common_step_counter, torch.cuda.current_stream(self.device).cuda_stream, privileged_out)
         if with_critic_memory and getattr(_live(fused_pred), "recurrent", False):
             pred = pred + (self._critic_out["pred"],) if "pred" in with_critic_memory else pred
             prey = prey + (self._critic_out["prey"],) if "prey" in with_critic_memory else prey
         return pred, prey, self._step_result()
+
+    def _check_privileged_out(self, privileged_out):
+        privileged_out = dict(privileged_out or {})
+        for a, t in privileged_out.items():
+            if a not in AGENTS:
+                raise ValueError(f"privileged_out names agents of {AGENTS}, got {a!r}")
+            if a not in self._privileged:
+                raise ValueError(f"privileged_out[{a!r}]: the privileged observations of this agent are off (cfg.env.num_privileged_obs_*)")
+            n, w = self.num_envs, PRIVILEGED_WIDTHS[a]
+            if t.shape != (n, w) or t.dtype != torch.float32 or not t.is_contiguous() or str(t.device) != str(self.device):
+                raise ValueError(f"privileged_out[{a!r}] must be a contiguous float32 [{n},{w}] tensor on {self.device}")
+        return privileged_out
 
     def make_graphed_policy_step(self, fused_pred, fused_prey, warmup=3, steps_per_replay=1, deterministic_pred=False, deterministic_prey=False,
                                  with_critic_memory=()):
@@ -451,13 +542,15 @@ class DecHighLevelGame(GameBase):
         sim = self.ll_env._sim
         for fused in (_live(fused_pred), _live(fused_prey)):
             self._require_device_step_counter(fused)
+        self._own_privileged()
         pools = [f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey)]
         hold = self._recurrent_pair(_live(fused_pred), _live(fused_prey), *pools) and steps_per_replay % 2 == 1
         with_critic_memory = (with_critic_memory,) if isinstance(with_critic_memory, str) else tuple(with_critic_memory or ())
 
         def device_step():
             _, _, ll_actions, B = self._act(fused_pred, fused_prey, self.obs_buf_pred, self.obs_buf_prey, self.obs_buf_pred, self.obs_buf_prey, deterministic_pred,
-                                            deterministic_prey, with_critic_memory=with_critic_memory)
+                                            deterministic_prey, with_critic_memory=with_critic_memory,
+                                            critic_obs={a: getattr(self, f"privileged_obs_buf_{a}") for a in AGENTS})
             if hold:
                 _live(fused_pred).hold_slot(); _live(fused_prey).hold_slot()      # (a pool's state is its live actor's)
             sim.step(ll_actions, -1)
@@ -488,6 +581,8 @@ class DecHighLevelGame(GameBase):
         means = self._episode_sums[:, ids].mean(dim=1) / self.max_episode_length_s                        # (:298-305)
         self._episode_means.copy_(means)
         self._episode_sums[:, ids] = 0.
+        if self._privileged:
+            self._write_privileged()
 
     def reset(self):
         """Reset all envs, then one zero-command step (:313-319)."""
@@ -527,6 +622,9 @@ class DecHighLevelGame(GameBase):
                                self.MAX_REL_POS * torch.ones(N, self.num_obs_pred, device=dev, dtype=torch.float))
         self._obs_flip = 0
         self.obs_buf_prey, self.obs_buf_pred = self._obs_pair_prey[0], self._obs_pair_pred[0]
+        for a in self._privileged:                                            # written by lg_dec_game_privileged_obs before anyone reads them
+            self._priv_pair[a] = tuple(torch.zeros(N, PRIVILEGED_WIDTHS[a], device=dev, dtype=torch.float) for _ in range(2))
+        self._select_privileged()
         self.rew_buf_prey = torch.zeros(N, device=dev, dtype=torch.float)
         self.rew_buf_pred = torch.zeros(N, device=dev, dtype=torch.float)
         self.reset_buf = torch.ones(N, device=dev, dtype=torch.bool)          # persistent bool tensors, like the low-level env's (quirk Q1)
@@ -625,7 +723,7 @@ class AgentView:
         self.num_envs, self.cfg, self.device, self.ll_env = env.num_envs, env.cfg, env.device, env.ll_env
         self.num_obs = getattr(env, f"num_obs_{agent}")
         self.num_actions = getattr(env, f"num_actions_{agent}")
-        self.num_privileged_obs = None
+        self.num_privileged_obs = getattr(env, f"num_privileged_obs_{agent}")
         self.max_episode_length = env.max_episode_length
         self.fused_seed_offset = SEED_OFFSET_PRED if agent == "pred" else SEED_OFFSET_PREY     # noise seed of this agent's FusedActor: cfg.seed + this
 
@@ -646,6 +744,7 @@ class AgentView:
     def _obs_flip(self, value):          # (the runner puts the ping-pong back after a capture that failed part-way)
         self.env._obs_flip = value
         self.env.obs_buf_prey, self.env.obs_buf_pred = self.env._obs_pair_prey[value], self.env._obs_pair_pred[value]
+        self.env._select_privileged()
 
     @obs_buf.setter
     def obs_buf(self, value):            # (same path, after the _obs_flip setter: only the current buffer of the pair can be "assigned")
@@ -678,18 +777,21 @@ class AgentView:
         self.env.end_graph_capture(steps_captured)
 
     def reset(self):
-        obs_pred, obs_prey, _, _ = self.env.reset()
-        return (obs_pred if self.agent == "pred" else obs_prey), None
+        obs_pred, obs_prey, priv_pred, priv_prey = self.env.reset()
+        return (obs_pred, priv_pred) if self.agent == "pred" else (obs_prey, priv_prey)
 
     def get_observations(self):
         return self.obs_buf
 
     def get_privileged_observations(self):
-        return None
+        return getattr(self.env, f"privileged_obs_buf_{self.agent}")
+
+    def refresh_privileged_observations(self):
+        self.env.refresh_privileged_observations()
 
     def _result(self, out):
-        obs_pred, obs_prey, _, _, rew_pred, rew_prey, dones, extras = out
-        return (obs_pred, None, rew_pred, dones, extras) if self.agent == "pred" else (obs_prey, None, rew_prey, dones, extras)
+        obs_pred, obs_prey, priv_pred, priv_prey, rew_pred, rew_prey, dones, extras = out
+        return (obs_pred, priv_pred, rew_pred, dones, extras) if self.agent == "pred" else (obs_prey, priv_prey, rew_prey, dones, extras)
 
     def step(self, actions):
         """Generic path: ``opponent`` is a torch policy ``obs -> sampled actions``.  ``actions`` is clipped in place, as by ``env.step``."""
@@ -699,17 +801,19 @@ class AgentView:
             return self._result(self.env.step(actions, other))
         return self._result(self.env.step(other, actions))
 
-    def step_policy(self, fused, deterministic=False, sample=None, sigma=None, log_prob=None, obs_copy=None, with_critic_memory=False):
+    def step_policy(self, fused, deterministic=False, sample=None, sigma=None, log_prob=None, obs_copy=None, with_critic_memory=False, privileged_out=None):
         """Device path: ``opponent`` is a ``FusedActor`` or an ``rl.OpponentPool`` (a mixture of opponents by 32-env block).  Returns ``(command, mean), (obs, None, rew, dones, extras)`` of this agent, the
         contract of ``HighLevelGame.step_policy``.  Recurrent policies (``fused`` and ``opponent`` both ``RecurrentFusedActor`` s):
         ``with_critic_memory`` advances this agent's critic memory too and returns its output as a third value of the first tuple; of the
-        opponent only the actor memory advances."""
+        opponent only the actor memory advances.  ``privileged_out``: a tensor for this agent's new privileged rows of the step (the
+        env's ``step_policy``), returned in the result's second slot."""
         mine = {k: v for k, v in (("sample", sample), ("sigma", sigma), ("log_prob", log_prob), ("obs_copy", obs_copy)) if v is not None}
         critic = (self.agent,) if with_critic_memory else ()
+        priv = None if privileged_out is None else {self.agent: privileged_out}
         if self.agent == "pred":
-            pred, _, out = self.env.step_policy(fused, self.opponent, deterministic_pred=deterministic, out_pred=mine, with_critic_memory=critic)
+            pred, _, out = self.env.step_policy(fused, self.opponent, deterministic_pred=deterministic, out_pred=mine, with_critic_memory=critic, privileged_out=priv)
             return pred, self._result(out)
-        _, prey, out = self.env.step_policy(self.opponent, fused, deterministic_prey=deterministic, out_prey=mine, with_critic_memory=critic)
+        _, prey, out = self.env.step_policy(self.opponent, fused, deterministic_prey=deterministic, out_prey=mine, with_critic_memory=critic, privileged_out=priv)
         return prey, self._result(out)
 
     def shared_actor_launch(self, fused):

@@ -47,7 +47,9 @@ class HighLevelGame(GameBase):
         if (self.num_obs, self.num_actions) != (capi.LG_GAME_NUM_OBS, capi.LG_GAME_NUM_ACTIONS):
             raise ValueError("high_level_game is compiled for 19 observations and 6 actions")
         if self.num_privileged_obs is not None:
-            raise NotImplementedError("the reference's high_level_game has no privileged observations")
+            raise NotImplementedError(f"{self.TASK} has no privileged observations: its one policy already reads the true relative position in obs[16:19], "
+                                      "so a privileged critic would add a heading and a clock only (the asymmetric critic is dec_high_level_game's: "
+                                      "env.num_privileged_obs_prey / env.num_privileged_obs_predator)")
         self.privileged_obs_buf = None
         self.extras = {}
         self.enable_viewer_sync = True

@@ -45,7 +45,7 @@ import re
 
 import torch
 
-from .runner import OnPolicyRunner
+from .runner import OnPolicyRunner, check_critic_width
 
 AGENTS = ("pred", "prey")
 OPPONENT_COLUMNS = ("evolution", "agent", "member", "pushed_at", "blocks", "episodes", "captured", "timed_out", "fell", "ll_timed_out", "steps", "learner_win_rate")
@@ -106,7 +106,8 @@ class DecGamePolicyRunner:
                 view, policy_cfg = self.views[a], self.runners[a].policy_cfg
 
                 def make_actor_critic(view=view, policy_cfg=policy_cfg):      # the private module of one snapshot member: the shapes of the agent's own
-                    return module(view.num_obs, view.num_obs, view.num_actions, **policy_cfg).to(device)
+                    critic_obs = view.num_privileged_obs if view.num_privileged_obs is not None else view.num_obs      # (push(state_dict) loads the critic too)
+                    return module(view.num_obs, critic_obs, view.num_actions, **policy_cfg).to(device)
                 self.pools[a] = pool(fused[a], make_actor_critic, self.pool_size, a, seed=self.seed, latest_share=self.latest_share,
                                      num_envs=env.num_envs)
             for a in AGENTS:                              # a view's opponent: the pool of the OTHER agent's versions
@@ -193,6 +194,8 @@ class DecGamePolicyRunner:
     def learn(self, max_num_evolutions, num_learning_iterations, init_at_random_ep_len=False):
         if init_at_random_ep_len:                          # once, before the first evolution
             self.env.episode_length_buf[:] = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
+            if hasattr(self.env, "refresh_privileged_observations"):
+                self.env.refresh_privileged_observations()        # (the privileged rows hold the episode clock)
         for e in range(self.current_evolution, self.current_evolution + max_num_evolutions):
             agent = self.agent_of(e)
             runner = self.runners[agent]
@@ -279,6 +282,7 @@ class DecGamePolicyRunner:
         d = torch.load(path, map_location=self.device, weights_only=True)
         for a in AGENTS:
             r, half = self.runners[a], d[a]
+            check_critic_width(r.alg.actor_critic, half["model_state_dict"], a)
             r.alg.actor_critic.load_state_dict(half["model_state_dict"])
             if load_optimizer:
                 r.alg.optimizer.load_state_dict(half["optimizer_state_dict"])

@@ -13,6 +13,25 @@ from .actor_critic import ActorCritic, ActorCriticRecurrent
 from .ppo import PPO
 
 
+def critic_input_width(state_dict):
+    """The input width of the critic in an ``ActorCritic`` / ``ActorCriticRecurrent`` state dict: of the critic memory where there is one, of
+    the critic MLP's first layer otherwise; None when it has neither."""
+    for key in ("memory_c.rnn.weight_ih_l0", "critic.0.weight"):
+        if key in state_dict:
+            return int(state_dict[key].shape[1])
+    return None
+
+
+def check_critic_width(actor_critic, state_dict, agent=None):
+    """Refuse a checkpoint whose critic reads another number of inputs than ``actor_critic`` 's with an error that names the switch, instead of
+    ``load_state_dict`` 's size-mismatch trace: the privileged critic of dec_high_level_game (``--privileged_critic {prey,pred,both}``)."""
+    have, want = critic_input_width(state_dict), critic_input_width(actor_critic.state_dict())
+    if have is not None and want is not None and have != want:
+        who = f"the {agent} agent's " if agent else "the "
+        raise ValueError(f"{who}checkpoint has a critic with {have} inputs, this runner's critic has {want}: the critic's input width follows the privileged "
+                         "observations, so run with the --privileged_critic {prey,pred,both} the checkpoint was trained with (or without it)")
+
+
 class OnPolicyRunner:
     def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
         self.cfg, self.alg_cfg, self.policy_cfg = train_cfg["runner"], train_cfg["algorithm"], train_cfg["policy"]
@@ -46,8 +65,8 @@ class OnPolicyRunner:
         if alg is not None and alg.actor_critic.is_recurrent:
             return self._make_recurrent_fused_actor()
         if (self.cfg.get("device_rollout", False) and str(self.device).startswith("cuda") and hasattr(env, "ll_env")
-                and hasattr(env, "step_policy") and env.num_privileged_obs is None):
-            # high_level_game, opt-in: the high-level actor on the noise stream of the low-level sim's device step counter
+                and hasattr(env, "step_policy") and (env.num_privileged_obs is None or getattr(env, "dec_agent_view", False))):
+            # high_level_game, opt-in (an agent view of dec_high_level_game may have privileged observations: _rollout_steps_game): the high-level actor on the noise stream of the low-level sim's device step counter
             from .fused_actor import FusedActor
             try:
                 fused = FusedActor(self.alg.actor_critic, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
@@ -114,9 +133,9 @@ class OnPolicyRunner:
             why = f"the policy is on {self.device}, the game actor kernels run on a GPU"
         elif not hasattr(env, "step_policy"):
             why = "the game actor kernels have no recurrent policy for this task"
-        elif env.num_privileged_obs is not None:
+        elif env.num_privileged_obs is not None and not getattr(env, "dec_agent_view", False):
             why = "privileged observations"
-        else:
+        else:                                                     # (an agent view: the critic memory reads the privileged buffer)
             why = lstm_unsupported_reason(ac.memory_a.rnn) or lstm_unsupported_reason(ac.memory_c.rnn)
             why = why and f"no device LSTM cell for a {why}"
         if why is None:
@@ -283,10 +302,18 @@ class OnPolicyRunner:
         caller's tensor after ``PPO.act`` took the log-prob, so ``actions[t]`` is the clipped command while ``actions_log_prob[t]`` (and
         ``sigma[t]``, both written by the actor launch straight into the storage) belong to the unclipped sample.  The game sends no
         time-outs: nothing is bootstrapped.  An agent view of ``dec_high_level_game`` does send them (``dec_agent_view``): they are recorded
-        per step and bootstrapped as ``_rollout_steps_fused`` does."""
+        per step and bootstrapped as ``_rollout_steps_fused`` does.  With privileged observations on that view the critic observations of
+        step ``t`` are ``st.privileged_observations[t]``: one copy of the carried rows into slot 0, then the env's privileged launch of step
+        ``t`` writes slot ``t + 1`` itself (the last step a carry buffer) -- no copy launch per step.  Returns ``(obs, critic obs)`` behind
+        the last step."""
         env, alg, fused = self.env, self.alg, self._fused
         st, T = alg.storage, self.num_steps_per_env
         dec = getattr(env, "dec_agent_view", False)
+        priv = dec and env.num_privileged_obs is not None
+        if priv:
+            if getattr(self, "_priv_carry", None) is None:
+                self._priv_carry = torch.zeros(env.num_envs, env.num_privileged_obs, device=self.device)
+            st.privileged_observations[0].copy_(env.get_privileged_observations())      # (the carry of the last rollout, or the env's own after a reset / the other agent's steps)
         if dec and getattr(self, "_time_outs", None) is None:
             self._time_outs = torch.zeros(T, env.num_envs, 1, device=self.device)
         obs = env.get_observations()
@@ -303,14 +330,16 @@ class OnPolicyRunner:
             keep = (env.reset_buf == 0).view(1, -1, 1)
             for hid in st.initial_hidden_a + st.initial_hidden_c:
                 hid.mul_(keep)
+        cobs = None
         for t in range(T):
             prev_obs = obs
+            more = {"privileged_out": st.privileged_observations[t + 1] if t < T - 1 else self._priv_carry} if priv else {}
             if rec:                                               # lg_lstm_step -> lg_game_lstm_act -> lg_step -> post
-                (command, mean, h_c), (obs, _, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t],
-                                                                                        with_critic_memory=True)
+                (command, mean, h_c), (obs, cobs, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t],
+                                                                                           with_critic_memory=True, **more)
                 self._critic_features[t].copy_(h_c)
             else:
-                (command, mean), (obs, _, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t])
+                (command, mean), (obs, cobs, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t], **more)
             step.obs, step.actions, step.mean, step.rewards, step.dones = p(prev_obs), p(command), p(mean), p(rewards), p(dones)
             touts = infos.get("time_outs") if dec else None
             if touts is not None:                                 # (absent with env.send_timeouts = False: nothing is bootstrapped then)
@@ -330,7 +359,7 @@ class OnPolicyRunner:
             st.values.copy_(self._critic_values(st).view(T, -1, 1))
         if dec:
             st.rewards.add_(alg.gamma * st.values * self._time_outs)                           # bootstrap on time-outs (PPO.process_env_step)
-        return obs, obs
+        return obs, (cobs if priv else obs)
 
     # ------------------------------------------------------------------ graphed rollout
     def _rollout_steps(self, stats):
@@ -432,6 +461,8 @@ class OnPolicyRunner:
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
         if init_at_random_ep_len:
             self.env.episode_length_buf[:] = torch.randint_like(self.env.episode_length_buf, high=int(self.env.max_episode_length))
+            if hasattr(self.env, "refresh_privileged_observations"):
+                self.env.refresh_privileged_observations()        # (the episode clock of dec_high_level_game's privileged rows)
         obs = self.env.get_observations()
         pobs = self.env.get_privileged_observations()
         cobs = pobs if pobs is not None else obs
@@ -546,6 +577,7 @@ class OnPolicyRunner:
 
     def load(self, path, load_optimizer=True):
         d = torch.load(path, map_location=self.device, weights_only=True)
+        check_critic_width(self.alg.actor_critic, d["model_state_dict"], getattr(self.env, "agent", None))
         self.alg.actor_critic.load_state_dict(d["model_state_dict"])
         if load_optimizer:
             self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])

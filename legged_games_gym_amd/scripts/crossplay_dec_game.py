@@ -14,7 +14,8 @@ cells of ``S`` replays of a ~100 us step take seconds, so the envs of a launch a
 time) and ``mean_steps`` -- rows are predators, columns are preys -- and the raw totals of every cell.  As with ``play_dec_game --outcomes``,
 episodes still running after ``S`` steps are not counted.  Recurrent checkpoints (``--policy_class_name ActorCriticRecurrent`` and the
 ``--rnn_*`` flags of the run): both ``RecurrentFusedActor`` s are repacked in place per cell, and every cell starts with all memories at zero
-from the same start state as a feed-forward cell."""
+from the same start state as a feed-forward cell.  ``--privileged_critic {prey,pred,both}``: the flag of the run, so that the critics the
+checkpoints are loaded into have their shape (``scripts.play_dec_game``)."""
 import json
 import os
 

@@ -14,6 +14,8 @@ integers of ``env.outcome_totals()``; its ``steps`` is the summed length of the 
 
 Episodes still running when the rollout ends are NOT counted, which favours short episodes: with few steps the capture rate is overstated.
 The flags are not exclusive (an env may be captured in the step its low-level episode runs out), so the rates need not add up to one.
+``--privileged_critic {prey,pred,both}``: the flag the checkpoint was trained with; only the critic's shape depends on it, and a checkpoint
+whose critic has another input width is refused with an error that names the flag.
 ``DecEvaluation`` is what ``play_outcomes`` and ``scripts/crossplay_dec_game.py`` share."""
 import copy
 import json
@@ -45,6 +47,7 @@ def play(args, steps=None):
     env_cfg.noise.add_noise = False
     env_cfg.domain_rand.randomize_friction = False
     env_cfg.domain_rand.push_robots = False
+    a1_game.set_privileged_critic(env_cfg, getattr(args, "privileged_critic", None))     # only to rebuild a critic of the checkpoint's shape
     env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
     train_cfg.runner.resume = True
     apply_policy_args(train_cfg, args)
@@ -107,6 +110,7 @@ class DecEvaluation:
         env_cfg.noise.add_noise = False
         env_cfg.domain_rand.randomize_friction = False
         env_cfg.domain_rand.push_robots = False
+        a1_game.set_privileged_critic(env_cfg, getattr(args, "privileged_critic", None))     # only to rebuild a critic of the checkpoint's shape
         env, _ = task_registry.make_env(name=args.task, args=args, env_cfg=env_cfg)
         train_cfg.runner.resume = True
         for key in ("device_rollout", "graphed_rollout"):        # the runner only holds the two ActorCritics here
@@ -172,6 +176,9 @@ class DecEvaluation:
     def load(self, state_pred, state_prey):
         """Put the ``model_state_dict`` halves of two checkpoints under the step path (the captured graph is NOT re-captured): both
         ``FusedActor`` s, or both ``RecurrentFusedActor`` s, are repacked in place."""
+        from legged_games_gym_amd.rl.runner import check_critic_width
+        for a, state in (("pred", state_pred), ("prey", state_prey)):
+            check_critic_width(self.modules[a], state, a)
         self.modules["pred"].load_state_dict(state_pred)
         self.modules["prey"].load_state_dict(state_prey)
         if self.fused is not None:

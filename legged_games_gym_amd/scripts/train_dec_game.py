@@ -15,6 +15,9 @@ trains two LSTM policies (four launches per step: ``lg_dec_lstm_step`` -> ``lg_d
 ``--device_rollout``, on the CPU, with a GRU / several layers / more than 256 units or with ``--opponent_pool`` alone the runner stops and says
 why.  ``--opponent_pool K --opponent_pool_recurrent`` gives two recurrent policies their pools (``rl.RecurrentOpponentPool``: the launches are
 ``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_lstm_act``, the weights of a block's actor memory and actor MLP its pool member's).
+``--privileged_critic {prey,pred,both}`` gives that agent an asymmetric critic: it reads the true relative position, the prey's heading and
+the episode clock (the predator's: the prey's velocity and whether the prey sees it), written by one more launch per step,
+``lg_dec_game_privileged_obs``; the actor keeps the sensor's view.  The play scripts take the same flag to rebuild the critic.
 Needs a trained ``a1`` checkpoint, like ``high_level_game``."""
 from legged_games_gym_amd.envs import *  # noqa: F401,F403  (registers the locomotion tasks)
 from legged_games_gym_amd.envs import a1_game
@@ -41,6 +44,7 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].runner.opponent_priority = args.opponent_priority
     if args.outcome_stats:                   # read with getattr() by the env: no field of the registered config classes
         task_registry.get_cfgs(args.task)[0].env.outcome_stats = True
+    a1_game.set_privileged_critic(task_registry.get_cfgs(args.task)[0], getattr(args, "privileged_critic", None))     # before the env is made
     env, env_cfg = task_registry.make_env(name=args.task, args=args)
     runner, train_cfg = task_registry.make_dec_alg_runner(env=env, name=args.task, args=args)
     runner.learn(max_num_evolutions=train_cfg.runner.max_evolutions, num_learning_iterations=train_cfg.runner.max_iterations, init_at_random_ep_len=True)

@@ -229,6 +229,10 @@ def get_args(argv=None):
     p.add_argument("--opponent_pool_recurrent", action="store_true", default=False,
                    help="with --opponent_pool and --policy_class_name ActorCriticRecurrent: the pools hold recurrent snapshots (runner key "
                         "opponent_pool_recurrent; the actor memory and the actor MLP of a 32-env block are its pool member's)")
+    p.add_argument("--privileged_critic", type=str, default=None, choices=("prey", "pred", "both"),
+                   help="dec_high_level_game (scripts/train_dec_game.py, play_dec_game.py, crossplay_dec_game.py): an asymmetric critic for that agent -- it reads "
+                        "the simulator's true state (env.num_privileged_obs_prey = 22 / env.num_privileged_obs_predator = 10), the actor keeps the sensor's view; "
+                        "the play scripts need it to rebuild a critic of the checkpoint's shape")
     # flags gymutil.parse_arguments contributes
     p.add_argument("--sim_device", type=str, default="cuda:0")
     p.add_argument("--pipeline", type=str, default="gpu")

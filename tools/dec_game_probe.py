@@ -46,7 +46,14 @@ include/legged_dec_pool_recurrent.h (``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_
 an ``rl.RecurrentOpponentPool`` on the prey role, the 32-env blocks dealt round-robin over the members, by the same method ->
 profiles/dec_recurrent_pool_step.json.
 
-    python tools/dec_game_probe.py --recurrent-pool [--envs 2000 4096] [--members 1 4 8] [--step-replays 2000] [--repeats 5]"""
+    python tools/dec_game_probe.py --recurrent-pool [--envs 2000 4096] [--members 1 4 8] [--step-replays 2000] [--repeats 5]
+
+``--privileged`` times the graphed feed-forward policy step with the prey's privileged vector off (three launches) and on (a fourth,
+``lg_dec_game_privileged_obs``, include/legged_dec_game_privileged.h, behind the post launch), by the method of ``--outcome``: one process,
+alternating repeats, median [min .. max] per variant and of the difference on - off repeat by repeat -> profiles/dec_privileged_step.json.
+Whether the difference is outside the spread of the repeats decides whether the writer is worth fusing into the post kernels.
+
+    python tools/dec_game_probe.py --privileged [--envs 2000 4096] [--step-replays 2000] [--repeats 5]"""
 import argparse
 import json
 import os
@@ -219,7 +226,7 @@ def pool_main(args):
     print("wrote", path)
 
 
-def make_env(n, mesh, tmp):
+def make_env(n, mesh, tmp, tweak=None):
     from legged_games_gym_amd.envs import task_registry
     from legged_games_gym_amd.envs.a1_game import DecHighLevelGame, DecHighLevelGameCfg as Cfg
     from legged_games_gym_amd.utils import get_args, set_seed
@@ -231,6 +238,8 @@ def make_env(n, mesh, tmp):
     torch.save({"model_state_dict": ac.state_dict(), "optimizer_state_dict": {}, "iter": 0, "infos": None}, ckpt)
     cfg = Cfg()
     cfg.env.num_envs, cfg.env.ll_policy_path, cfg.terrain.mesh_type, cfg.seed = n, ckpt, mesh, 1
+    if tweak is not None:
+        tweak(cfg)
     args = get_args(["--headless", "--sim_device", DEV, "--rl_device", DEV])
     set_seed(1)
     env = DecHighLevelGame(cfg, parse_sim_params(args, {"sim": class_to_dict(cfg.sim)}), args.physics_engine, DEV, True)
@@ -293,6 +302,51 @@ def outcome_main(args):
             d = row["outcome_minus_plain"]
             print(f"  statistics on - off {d['median_us']:+.2f} us ({d['min_us']:+.2f} .. {d['max_us']:+.2f})", flush=True)
     out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_outcome_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
+def privileged_main(args):
+    """The graphed feed-forward policy step with the prey's privileged vector off (three launches) and on (a fourth,
+    lg_dec_game_privileged_obs / k_privileged_obs, behind the post launch): same process, same sizes, alternating repeats; the difference
+    on - off repeat by repeat, to be read against the spread of the repeats."""
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.step_replays, "repeats": args.repeats,
+              "unit": "us per graphed policy step (three launches; four with the prey's privileged vector)", "envs": {}}
+    names = ("privileged_off", "privileged_prey")
+
+    def prey_vector(cfg):
+        cfg.env.num_privileged_obs_prey = 22
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            envs, steps = [], []
+            for on in (False, True):
+                env = make_env(n, args.mesh, tmp, prey_vector if on else None)
+                ctr = env.ll_env._sim.buf["step_counter"]
+                torch.manual_seed(1)
+                fused = [FusedActor(ActorCritic(no, no, na, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN).to(DEV), DEV, seed=seed, step_counter=ctr)
+                         for no, na, seed in ((3, 2, 1 + 7919 + 104729), (16, 4, 1 + 7919))]
+                envs.append(env)
+                steps.append(env.make_graphed_policy_step(*fused))
+                assert env.last_act_rc == 0
+            for fn in steps:
+                timed(fn, args.step_replays // 4)                # warm both graphs before the first timed window
+            t = [[], []]
+            for _ in range(args.repeats):
+                for i, fn in enumerate(steps):
+                    t[i].append(timed(fn, args.step_replays))
+            row = {f"{name}_policy_step": spread(x) for name, x in zip(names, t)}
+            row["on_minus_off"] = spread([y - x for x, y in zip(t[0], t[1])])
+            for env in envs:
+                assert torch.isfinite(env.obs_buf_prey).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            assert envs[0].privileged_obs_buf_prey is None and torch.equal(envs[1].privileged_obs_buf_prey[:, :16], envs[1].obs_buf_prey)
+            result["envs"][str(n)] = row
+            print(f"{n} envs, graphed policy step: " + "; ".join(
+                f"{name} {statistics.median(x):.1f} us [{min(x):.1f} .. {max(x):.1f}]" for name, x in zip(names, t)), flush=True)
+            d = row["on_minus_off"]
+            print(f"  privileged on - off {d['median_us']:+.2f} us [{d['min_us']:+.2f} .. {d['max_us']:+.2f}]", flush=True)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_privileged_step.json")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(result, fh, indent=1)
@@ -533,7 +587,11 @@ def main():
     ap.add_argument("--trace", action="store_true", help="--recurrent: replay the four-launch graph only and write nothing (for a rocprofv3 kernel table)")
     ap.add_argument("--recurrent-pool", action="store_true", help="time the four-launch recurrent policy step with the plain launches against the pooled launches "
                     "with --members members on the prey role; writes profiles/dec_recurrent_pool_step.json")
+    ap.add_argument("--privileged", action="store_true", help="time the graphed policy step with the prey's privileged vector off and on (one more launch, "
+                    "lg_dec_game_privileged_obs); writes profiles/dec_privileged_step.json")
     args = ap.parse_args()
+    if args.privileged:
+        return privileged_main(args)
     if args.recurrent_pool:
         return recurrent_pool_main(args)
     if args.recurrent:
