@@ -27,6 +27,14 @@ FLAT_FB = [f"{FLAT64}::test_forward_and_backward_match_float64_over_widths", f"{
 # ... and the build with the PPO loss inside: 1 .. 16 actions, the schedule, ratios far outside the clip range
 FLAT_FUSED = [f"{FLAT64}::test_fused_minibatch_matches_float64_over_action_counts", f"{FLAT64}::test_fused_minibatch_matches_float64_over_the_schedule",
               f"{FLAT64}::test_fused_minibatch_far_outside_the_clip_range"]
+# the chain forward against float64 over tests/chain_check.py's table (precision 1), what each takes to the kernel:
+CHAIN = "tests/test_gpu_chain_forward_edges.py"
+CHAIN_EDGES = [f"{CHAIN}::test_outputs_match_float64_element_by_element_with_guards",     # every case: outputs element by element, NaN workspace, NaN guard rows
+               f"{CHAIN}::test_parameter_gradients_match_float64",                         # every case: the saved activations through the backward pass
+               f"{CHAIN}::test_saved_activations_row_by_row",                              # mb 33 / 65 / 1025: act[0..2] one row at a time at the half / workgroup edges
+               f"{CHAIN}::test_designed_pre_activations",                                  # pre-activations of exactly 0, -1e-6, -30, -100, -1e4, 8 in every hidden layer
+               f"{CHAIN}::test_bit_identical_from_run_to_run"]                             # 17 workgroups twice: the same bits
+CHAIN_REPACK = f"{CHAIN}::test_the_forward_follows_an_in_place_parameter_step"             # a forward pass after an in-place parameter change, no refresh()
 LOSS = [f"{RL}::test_fused_ppo_loss_matches_autograd", f"{WIDE}::test_ppo_loss_kernel_matches_float64_at_the_games_action_counts", STEP]
 
 
@@ -53,10 +61,12 @@ COVERAGE = {
     "_ZN2lg11k_wide_prepENS_12WidePrepArgsE": [ROUGH, GENERIC, STEP],
     "_ZN2lg13k_wide_reduceENS_14WideReduceArgsE": [ROUGH, GENERIC, STEP],
     "_ZN2lg14k_wide_out_bwdILi16EEEvNS_10OutBwdArgsE": [ROUGH, GENERIC, STEP],
-    # chain forward (precision 1, both nets 235 or both 169 wide) and its weight packing
-    "_ZN2lg17k_mlp_chain_fwd64ILi15EEEvNS_9ChainArgsE": [ROUGH],
-    "_ZN2lg17k_mlp_chain_fwd64ILi11EEEvNS_9ChainArgsE": [ROUGH],
-    "_ZN2lg12k_chain_packENS_13ChainPackArgsE": [ROUGH],
+    # chain forward (precision 1, both nets 235 or both 169 wide) and its weight packing; CHAIN_EDGES takes each of <15> and <11> to the
+    # ends of its width range and every quad boundary of the last k-step, 1 .. 16 outputs, one net / two nets / two ldx, mb 1 .. 1025
+    "_ZN2lg17k_mlp_chain_fwd64ILi15EEEvNS_9ChainArgsE": [ROUGH] + CHAIN_EDGES,
+    "_ZN2lg17k_mlp_chain_fwd64ILi11EEEvNS_9ChainArgsE": [ROUGH] + CHAIN_EDGES,
+    # ... the packing with them: every width's zeroed columns past in_dim, the biases padded to 32 per tile, and CHAIN_REPACK
+    "_ZN2lg12k_chain_packENS_13ChainPackArgsE": [ROUGH] + CHAIN_EDGES + [CHAIN_REPACK],
     # LDS-resident trainer of the 48-128-64-32 networks: forward, backward, backward with the PPO loss inside
     mlp_train(0, 4, 0): [FLAT, RAGGED] + FLAT_FB,
     mlp_train(1, 2, 0): [FLAT, RAGGED] + FLAT_FB,
