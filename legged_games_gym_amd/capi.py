@@ -1027,6 +1027,57 @@ def dec_game_privileged_obs(params: lg_dec_game_params, buffers: lg_dec_game_buf
         raise RuntimeError(f"lg_dec_game_privileged_obs failed ({rc}): {lib.lg_dec_game_privileged_last_error().decode()}")
 
 
+# ---------------------------------------------------------------------------------------------------------------- legged_recurrent_wide.h
+# The LSTM cell and actor MLP of memories with up to 512 units, a seventh library (csrc/liblegged_lstm_wide.so): outside ABI / ALL_SYMBOLS /
+# bind_all.  Its handles are its own; the signatures are those of the lg_lstm_* entries of legged_recurrent.h.
+LG_LSTM_WIDE_MAX_IN, LG_LSTM_WIDE_MAX_HIDDEN, LG_LSTM_WIDE_GROUP_UNITS, LG_LSTM_WIDE_BLOCK_ENVS = 256, 512, 256, 32
+LSTM_WIDE_ABI = {
+    "lg_lstm_wide_create": ([i32, i32, _vp, _vp, _vp, _vp, i32, _P(_vp)], _int),
+    "lg_lstm_wide_load_device": ([_vp, _vp, _vp, _vp, _vp, _vp], _int),
+    "lg_lstm_wide_destroy": ([_vp], _int),
+    "lg_lstm_wide_step": ([_vp] * 13 + [i32, _vp], _int),
+    "lg_lstm_wide_actor_create": ([_P(i32), i32, _P(_vp)], _int),
+    "lg_lstm_wide_actor_load_device": ([_vp, _P(_vp), _P(_vp), _vp, _vp], _int),
+    "lg_lstm_wide_actor_destroy": ([_vp], _int),
+    "lg_lstm_wide_actor_act": ([_vp, _vp, _vp, _vp, i32, u64, i64, _vp, i32, _vp], _int),
+    "lg_lstm_wide_last_error": ([], C.c_char_p),
+}
+LSTM_WIDE_SYMBOLS = list(LSTM_WIDE_ABI)
+_LSTM_WIDE_LIB_NAME = "liblegged_lstm_wide.so"
+_lstm_wide_lib = None
+
+
+def lstm_wide_supported(num_in: int, hidden: int) -> bool:
+    """The shapes ``lg_lstm_wide_create`` takes."""
+    return 1 <= num_in <= LG_LSTM_WIDE_MAX_IN and 32 <= hidden <= LG_LSTM_WIDE_MAX_HIDDEN and hidden % 32 == 0
+
+
+def lstm_wide_library_path() -> str:
+    """In-tree liblegged_lstm_wide.so; LG_LSTM_WIDE_LIB selects another build of the same source."""
+    return os.environ.get("LG_LSTM_WIDE_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _LSTM_WIDE_LIB_NAME)
+
+
+def bind_lstm_wide(lib):
+    for symbol, (argtypes, restype) in LSTM_WIDE_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    return lib
+
+
+def load_lstm_wide_library():
+    """Load the wide LSTM cell and actor or fail loudly -- never a CPU substitute."""
+    global _lstm_wide_lib
+    if _lstm_wide_lib is not None:
+        return _lstm_wide_lib
+    path = lstm_wide_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _lstm_wide_lib = bind_lstm_wide(C.CDLL(path))
+    return _lstm_wide_lib
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

@@ -338,6 +338,14 @@ class DecHighLevelGame(GameBase):
             return lib, False
         return lib, True
 
+    def _recurrent_launches(self, fused_pred, fused_prey, say=True, pooled=False):
+        """``_recurrent_library`` for a pair of actors.  An actor with ``wide`` memories (``RecurrentFusedActor(wide=True)`` above 256 units) holds
+        handles of liblegged_lstm_wide.so, which none of the shared launches reads: separate launches throughout, said once."""
+        if getattr(fused_pred, "wide", False) or getattr(fused_prey, "wide", False):
+            self._say_separate("wide memory", say, pooled)
+            return None, False
+        return self._recurrent_library(fused_pred, say=say, pooled=pooled)
+
     def _say_separate(self, why, say=True, pooled=False):
         said = self.__dict__.setdefault("_separate_said", set())
         if say and (why, pooled) not in said:
@@ -369,7 +377,7 @@ class DecHighLevelGame(GameBase):
         pools = {"pred": pool_pred, "prey": pool_prey}
         pooled = pool_pred is not None or pool_prey is not None
         slots = {a: (pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None) for a, pool in pools.items()}
-        lib, shared = self._recurrent_library(fused_pred, pooled=pooled)
+        lib, shared = self._recurrent_launches(fused_pred, fused_prey, pooled=pooled)
         h, self._critic_out = {}, {}
         if lib is not None:
             roles = []
@@ -457,7 +465,7 @@ class DecHighLevelGame(GameBase):
                                      self.obs_buf_prey.data_ptr(), self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
                                      mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream) == 0
         pooled = pool_pred is not None or pool_prey is not None
-        lib, shared = self._recurrent_library(fused_pred, say=False, pooled=pooled)
+        lib, shared = self._recurrent_launches(fused_pred, fused_prey, say=False, pooled=pooled)
         if lib is None:
             return False
         roles, h = [], []

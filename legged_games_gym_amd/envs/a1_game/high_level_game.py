@@ -149,7 +149,9 @@ class HighLevelGame(GameBase):
         first time for each reason): the low-level role is the split-bf16 kernel, so wide precision 0 takes the separate launches, and so
         does a build without the library.  Decided per call: ``lg_mlp_wide_set_precision`` may change between calls."""
         why = None
-        if fused_actor.lib.lg_mlp_wide_set_precision(-1) != 1:        # (an invalid mode changes nothing and returns the current one)
+        if getattr(fused_actor, "wide", False):                       # handles of liblegged_lstm_wide.so: lg_game_lstm_act reads main-library ones
+            why = "wide memory"
+        elif fused_actor.lib.lg_mlp_wide_set_precision(-1) != 1:      # (an invalid mode changes nothing and returns the current one)
             why = "wide precision 0"
         else:
             try:

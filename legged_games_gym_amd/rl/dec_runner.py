@@ -142,17 +142,22 @@ class DecGamePolicyRunner:
             raise ValueError("opponent_pool_size > 0 with ActorCriticRecurrent: the opponent pool is feed-forward (lg_dec_pool_act has no recurrent role); "
                              "set the runner key opponent_pool_recurrent (--opponent_pool_recurrent) for pools of recurrent snapshots")
         import torch.nn as nn
-        from .recurrent_actor import lstm_unsupported_reason
+        from .recurrent_actor import lstm_unsupported_reason, wide_memory_would_help
+        wide = bool(self.cfg.get("wide_memory", False))
+        if wide and pool_recurrent:
+            raise ValueError("wide_memory with opponent_pool_recurrent: the pooled launches (lg_dec_pool_lstm_step / lg_dec_pool_lstm_act) stop at "
+                             "256 units and read main-library handles; a wide recurrent opponent pool does not exist")
         policy = train_cfg["policy"]
         kind = str(policy.get("rnn_type", "lstm")).lower()
         if kind not in ("lstm", "gru"):
             raise ValueError(f"rnn_type must be 'lstm' or 'gru', got {kind!r}")
         probe = (nn.GRU if kind == "gru" else nn.LSTM)(input_size=3, hidden_size=int(policy.get("rnn_hidden_size", 256)),
                                                        num_layers=int(policy.get("rnn_num_layers", 1)))      # (the predator's memory; both have these units)
-        why = lstm_unsupported_reason(probe)
+        why = lstm_unsupported_reason(probe, wide)
         if why is not None:
+            hint = " (the runner key wide_memory / --wide_memory covers up to 512 units)" if not wide and wide_memory_would_help(probe) else ""
             raise ValueError(f"ActorCriticRecurrent on dec_high_level_game: no device LSTM cell for a {why}, and there is no generic loop for two "
-                             "recurrent agents")
+                             f"recurrent agents{hint}")
         return True
 
     def _follow(self, agent):

@@ -11,32 +11,47 @@ import torch.nn as nn
 from .. import capi
 
 
-def lstm_unsupported_reason(rnn):
-    """Why ``lg_lstm_create`` does not take this ``nn.LSTM`` / ``nn.GRU``, or None."""
+def lstm_unsupported_reason(rnn, wide=False):
+    """Why ``lg_lstm_create`` (``wide``: ``lg_lstm_wide_create``) does not take this ``nn.LSTM`` / ``nn.GRU``, or None."""
     if not isinstance(rnn, nn.LSTM):
         return f"{type(rnn).__name__} memory (the device cell is an LSTM)"
     if rnn.num_layers != 1 or rnn.bidirectional or getattr(rnn, "proj_size", 0) or not rnn.bias:
         return f"{rnn.num_layers}-layer memory (the device cell is one plain layer)"
+    if wide:
+        if not capi.lstm_wide_supported(rnn.input_size, rnn.hidden_size):
+            return (f"memory of {rnn.input_size} inputs and {rnn.hidden_size} units (the wide device cell takes 1 .. {capi.LG_LSTM_WIDE_MAX_IN} "
+                    f"inputs and a multiple of 32 units up to {capi.LG_LSTM_WIDE_MAX_HIDDEN})")
+        return None
     if not capi.lstm_supported(rnn.input_size, rnn.hidden_size):
         return (f"memory of {rnn.input_size} inputs and {rnn.hidden_size} units (the device cell takes 1 .. {capi.LG_LSTM_MAX_IN} inputs and "
                 f"a multiple of 32 units up to {capi.LG_LSTM_MAX_HIDDEN})")
     return None
 
 
-class DeviceLstm:
-    """One ``lg_lstm`` handle over a one-layer ``nn.LSTM``."""
+def wide_memory_would_help(rnn):
+    """Whether the key ``wide_memory`` turns a refusal of this memory into an acceptance (the fall-back messages then name it)."""
+    return lstm_unsupported_reason(rnn) is not None and lstm_unsupported_reason(rnn, wide=True) is None
 
-    def __init__(self, rnn, device):
-        why = lstm_unsupported_reason(rnn)
+
+class DeviceLstm:
+    """One ``lg_lstm`` handle over a one-layer ``nn.LSTM``; with ``wide`` one ``lg_lstm_wide`` handle of liblegged_lstm_wide.so (up to 512
+    units), whose entry points have the same signatures."""
+
+    def __init__(self, rnn, device, wide=False):
+        why = lstm_unsupported_reason(rnn, wide)
         if why is not None:
             raise ValueError(f"no device LSTM cell for a {why}")
-        self.lib, self.rnn, self.device = capi.load_library(), rnn, torch.device(device)
+        self.wide = bool(wide)
+        self.lib, self.rnn, self.device = (capi.load_lstm_wide_library() if wide else capi.load_library()), rnn, torch.device(device)
+        self._pre = "lg_lstm_wide" if wide else "lg_lstm"
+        self._last_error = self.lib.lg_lstm_wide_last_error if wide else self.lib.lg_last_error
         self.num_in, self.hidden = rnn.input_size, rnn.hidden_size
         self.handle = C.c_void_p()
         host = [np.ascontiguousarray(p.detach().float().cpu().numpy()) for p in self._params()]
-        rc = self.lib.lg_lstm_create(self.num_in, self.hidden, *[a.ctypes.data for a in host], self.device.index or 0, C.byref(self.handle))
+        rc = getattr(self.lib, self._pre + "_create")(self.num_in, self.hidden, *[a.ctypes.data for a in host], self.device.index or 0,
+                                                      C.byref(self.handle))
         if rc != 0:
-            raise RuntimeError(f"lg_lstm_create failed ({rc}): {self.lib.lg_last_error().decode()}")
+            raise RuntimeError(f"{self._pre}_create failed ({rc}): {self._last_error().decode()}")
 
     def _params(self):
         r = self.rnn
@@ -48,47 +63,55 @@ class DeviceLstm:
         for p in ps:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 raise ValueError("DeviceLstm.load_device needs contiguous float32 CUDA parameters")
-        rc = self.lib.lg_lstm_load_device(self.handle, *[p.data_ptr() for p in ps], torch.cuda.current_stream(self.device).cuda_stream)
+        rc = getattr(self.lib, self._pre + "_load_device")(self.handle, *[p.data_ptr() for p in ps], torch.cuda.current_stream(self.device).cuda_stream)
         if rc != 0:
-            raise RuntimeError(f"lg_lstm_load_device failed ({rc}): {self.lib.lg_last_error().decode()}")
+            raise RuntimeError(f"{self._pre}_load_device failed ({rc}): {self._last_error().decode()}")
 
     def __del__(self):
         try:
             if self.handle:
-                self.lib.lg_lstm_destroy(self.handle)
+                getattr(self.lib, self._pre + "_destroy")(self.handle)
                 self.handle = C.c_void_p()
         except Exception:
             pass
 
 
 def lstm_step(lib, lstm_a, lstm_c, x_a, x_c, reset, state_in_a, state_out_a, state_in_c, state_out_c, num_envs, stream):
-    """``lg_lstm_step`` on tensors; a role is absent when its ``DeviceLstm`` is None.  ``state_*`` are ``(h, c)`` pairs."""
+    """``lg_lstm_step`` on tensors; a role is absent when its ``DeviceLstm`` is None.  ``state_*`` are ``(h, c)`` pairs.  ``lib`` is the
+    library of the handles: with ``wide`` memories (liblegged_lstm_wide.so) the launch is ``lg_lstm_wide_step``."""
+    wide = getattr(lstm_a if lstm_a is not None else lstm_c, "wide", False)
+    step, last_error, name = ((lib.lg_lstm_wide_step, lib.lg_lstm_wide_last_error, "lg_lstm_wide_step") if wide
+                              else (lib.lg_lstm_step, lib.lg_last_error, "lg_lstm_step"))
     p = lambda t: None if t is None else t.data_ptr()
     ha, ca = state_in_a if lstm_a is not None else (None, None)
     hoa, coa = state_out_a if lstm_a is not None else (None, None)
     hc, cc = state_in_c if lstm_c is not None else (None, None)
     hoc, coc = state_out_c if lstm_c is not None else (None, None)
-    rc = lib.lg_lstm_step(lstm_a.handle if lstm_a is not None else None, lstm_c.handle if lstm_c is not None else None,
-                          p(x_a) if lstm_a is not None else None, p(x_c) if lstm_c is not None else None, p(reset),
-                          p(ha), p(ca), p(hoa), p(coa), p(hc), p(cc), p(hoc), p(coc), int(num_envs), stream)
+    rc = step(lstm_a.handle if lstm_a is not None else None, lstm_c.handle if lstm_c is not None else None,
+              p(x_a) if lstm_a is not None else None, p(x_c) if lstm_c is not None else None, p(reset),
+              p(ha), p(ca), p(hoa), p(coa), p(hc), p(cc), p(hoc), p(coc), int(num_envs), stream)
     if rc != 0:
-        raise RuntimeError(f"lg_lstm_step failed ({rc}): {lib.lg_last_error().decode()}")
+        raise RuntimeError(f"{name} failed ({rc}): {last_error().decode()}")
 
 
 class DeviceLstmActor:
     """One ``lg_lstm_actor`` handle over ``actor_critic.actor`` (Linear / ELU x 3 / Linear) and ``actor_critic.std``; the step bookkeeping
-    of ``FusedActor``: the env's device step counter when given, a host count otherwise."""
+    of ``FusedActor``: the env's device step counter when given, a host count otherwise.  With ``wide`` the handle is an
+    ``lg_lstm_wide_actor`` of liblegged_lstm_wide.so (an input width up to 512)."""
 
-    def __init__(self, actor_critic, device, seed=1, step_counter=None):
-        self.lib, self.ac, self.device = capi.load_library(), actor_critic, torch.device(device)
+    def __init__(self, actor_critic, device, seed=1, step_counter=None, wide=False):
+        self.wide = bool(wide)
+        self.lib, self.ac, self.device = (capi.load_lstm_wide_library() if wide else capi.load_library()), actor_critic, torch.device(device)
+        self._pre = "lg_lstm_wide_actor" if wide else "lg_lstm_actor"
+        self._last_error = self.lib.lg_lstm_wide_last_error if wide else self.lib.lg_last_error
         self.seed, self.step_counter, self._host_step, self._out = int(seed), step_counter, 0, None
         lin = self._layers()
         dims = (C.c_int32 * 5)(lin[0].in_features, *[m.out_features for m in lin])
         self.num_actions = lin[3].out_features
         self.handle = C.c_void_p()
-        rc = self.lib.lg_lstm_actor_create(dims, self.device.index or 0, C.byref(self.handle))
+        rc = getattr(self.lib, self._pre + "_create")(dims, self.device.index or 0, C.byref(self.handle))
         if rc != 0:
-            raise RuntimeError(f"lg_lstm_actor_create failed ({rc}): {self.lib.lg_last_error().decode()}")
+            raise RuntimeError(f"{self._pre}_create failed ({rc}): {self._last_error().decode()}")
         self.sync_device()
 
     def _layers(self):
@@ -104,10 +127,10 @@ class DeviceLstmActor:
             if not (m.weight.is_cuda and m.weight.dtype == torch.float32 and m.weight.is_contiguous()):
                 raise ValueError("DeviceLstmActor needs contiguous float32 CUDA parameters")
         ptr = C.c_void_p * 4
-        rc = self.lib.lg_lstm_actor_load_device(self.handle, ptr(*[m.weight.data_ptr() for m in lin]), ptr(*[m.bias.data_ptr() for m in lin]),
-                                                self.ac.std.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        rc = getattr(self.lib, self._pre + "_load_device")(self.handle, ptr(*[m.weight.data_ptr() for m in lin]), ptr(*[m.bias.data_ptr() for m in lin]),
+                                                           self.ac.std.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         if rc != 0:
-            raise RuntimeError(f"lg_lstm_actor_load_device failed ({rc}): {self.lib.lg_last_error().decode()}")
+            raise RuntimeError(f"{self._pre}_load_device failed ({rc}): {self._last_error().decode()}")
 
     # what HighLevelGame._act reads of a FusedActor (the shared actor launch writes into these buffers and counts its own launch)
     def output_buffers(self, n):
@@ -133,16 +156,16 @@ class DeviceLstmActor:
         n = h.shape[0]
         actions, mean = self.output_buffers(n)
         step, ctr = self.next_step()
-        rc = self.lib.lg_lstm_actor_act(self.handle, h.data_ptr(), actions.data_ptr(), mean.data_ptr(), n, self.seed, step, ctr, int(deterministic),
-                                        torch.cuda.current_stream(self.device).cuda_stream)
+        rc = getattr(self.lib, self._pre + "_act")(self.handle, h.data_ptr(), actions.data_ptr(), mean.data_ptr(), n, self.seed, step, ctr,
+                                                   int(deterministic), torch.cuda.current_stream(self.device).cuda_stream)
         if rc != 0:
-            raise RuntimeError(f"lg_lstm_actor_act failed ({rc}): {self.lib.lg_last_error().decode()}")
+            raise RuntimeError(f"{self._pre}_act failed ({rc}): {self._last_error().decode()}")
         return actions, mean
 
     def __del__(self):
         try:
             if self.handle:
-                self.lib.lg_lstm_actor_destroy(self.handle)
+                getattr(self.lib, self._pre + "_destroy")(self.handle)
                 self.handle = C.c_void_p()
         except Exception:
             pass
@@ -150,16 +173,24 @@ class DeviceLstmActor:
 
 class RecurrentFusedActor:
     """``FusedActor`` for an ``ActorCriticRecurrent``: owns the two ``lg_lstm`` handles, the ``(h, c)`` ping-pong buffers of both memories
-    and the device actor MLP over ``actor_critic.actor`` (whose input width is ``rnn_hidden_size``)."""
+    and the device actor MLP over ``actor_critic.actor`` (whose input width is ``rnn_hidden_size``).
 
-    def __init__(self, actor_critic, device, seed: int = 1, step_counter: torch.Tensor = None, num_envs: int = None):
+    ``wide`` (the runner key ``wide_memory``): when either memory has more than 256 units, both memories and the actor take the handles of
+    liblegged_lstm_wide.so (up to 512 units; one launch still advances both memories) and the attribute ``wide`` is True.  The game envs
+    then issue the separate launches, because their shared kernels read main-library handles.  With both memories within 256 units
+    nothing wide is created."""
+
+    def __init__(self, actor_critic, device, seed: int = 1, step_counter: torch.Tensor = None, num_envs: int = None, wide: bool = False):
         if not getattr(actor_critic, "is_recurrent", False):
             raise ValueError("RecurrentFusedActor wraps an ActorCriticRecurrent")
         self.ac, self.device = actor_critic, torch.device(device)
-        self.lstm_a = DeviceLstm(actor_critic.memory_a.rnn, device)
-        self.lstm_c = DeviceLstm(actor_critic.memory_c.rnn, device)
-        self.fused = DeviceLstmActor(actor_critic, device, seed=seed, step_counter=step_counter)
-        self.lib = self.fused.lib
+        rnns = (actor_critic.memory_a.rnn, actor_critic.memory_c.rnn)
+        self.wide = bool(wide) and any(getattr(r, "hidden_size", 0) > capi.LG_LSTM_MAX_HIDDEN for r in rnns)
+        self.lstm_a = DeviceLstm(rnns[0], device, wide=self.wide)
+        self.lstm_c = DeviceLstm(rnns[1], device, wide=self.wide)
+        self.fused = DeviceLstmActor(actor_critic, device, seed=seed, step_counter=step_counter, wide=self.wide)
+        self.lib = capi.load_library()                          # the FusedActor surface: the main library (the runner's rollout bookkeeping)
+        self.cell_lib = self.lstm_a.lib                         # the library of the three handles: the main one, or liblegged_lstm_wide.so
         self.num_envs, self._flip = None, 0
         if num_envs is not None:
             self._allocate(num_envs)
@@ -224,7 +255,7 @@ class RecurrentFusedActor:
             self._allocate(n)
         f = self._flip
         with_c = critic_obs is not None
-        lstm_step(self.lib, self.lstm_a, self.lstm_c if with_c else None, self._f32(obs), self._f32(critic_obs) if with_c else None, self._flags(reset),
+        lstm_step(self.cell_lib, self.lstm_a, self.lstm_c if with_c else None, self._f32(obs), self._f32(critic_obs) if with_c else None, self._flags(reset),
                   self.state_a[f], self.state_a[1 - f], self.state_c[f], self.state_c[1 - f], n, torch.cuda.current_stream(self.device).cuda_stream)
         if not with_c:                                       # the critic memory did not move: keep both of its slots current
             for dst, src in zip(self.state_c[1 - f], self.state_c[f]):
@@ -237,7 +268,7 @@ class RecurrentFusedActor:
         """Advance the critic memory alone on this actor's slots (read ``[flip]``, write ``[1 - flip]``) and return its new output; the caller
         then calls ``advance_slots(True)`` (the separate launches of a pooled role, whose actor memory ``rl.RecurrentOpponentPool`` advances)."""
         f = self._flip
-        lstm_step(self.lib, None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[f], self.state_c[1 - f],
+        lstm_step(self.cell_lib, None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[f], self.state_c[1 - f],
                   critic_obs.shape[0], torch.cuda.current_stream(self.device).cuda_stream)
         return self.state_c[1 - f][0]
 
@@ -267,7 +298,7 @@ class RecurrentFusedActor:
     def peek_critic(self, critic_obs, reset=None):
         """The critic memory's output for ``critic_obs`` from the carried state, which stays where it is (the last value of a rollout)."""
         n = critic_obs.shape[0]
-        lstm_step(self.lib, None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[self._flip], self.scratch_c, n,
+        lstm_step(self.cell_lib, None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[self._flip], self.scratch_c, n,
                   torch.cuda.current_stream(self.device).cuda_stream)
         return self.scratch_c[0]
 

@@ -105,14 +105,15 @@ class OnPolicyRunner:
         if not (str(self.device).startswith("cuda") and self.cfg.get("fused_rollout", True) and hasattr(env, "_sim")):
             return None
         from .recurrent_actor import RecurrentFusedActor, lstm_unsupported_reason
+        wide = bool(self.cfg.get("wide_memory", False))       # opt-in: memories of up to 512 units on liblegged_lstm_wide.so
         why = "privileged observations" if env.num_privileged_obs is not None else (
-            lstm_unsupported_reason(ac.memory_a.rnn) or lstm_unsupported_reason(ac.memory_c.rnn))
+            lstm_unsupported_reason(ac.memory_a.rnn, wide) or lstm_unsupported_reason(ac.memory_c.rnn, wide))
         if why is not None:
-            print(f"[runner] device LSTM cell unavailable ({why}); torch policy in the rollout")
+            print(f"[runner] device LSTM cell unavailable ({why}); torch policy in the rollout{self._wide_memory_hint(ac, wide)}")
             return None
         try:
             fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + 7919, step_counter=env._sim.buf["step_counter"],
-                                        num_envs=env.num_envs)
+                                        num_envs=env.num_envs, wide=wide)
         except Exception as exc:                              # unsupported actor shape: torch rollouts
             print(f"[runner] MFMA actor unavailable ({type(exc).__name__}: {exc}); torch policy in the rollout")
             return None
@@ -123,12 +124,22 @@ class OnPolicyRunner:
         self._recurrent_rollout = True
         return fused
 
+    @staticmethod
+    def _wide_memory_hint(ac, wide):
+        """What a fall-back message adds when the key ``wide_memory`` would have kept the policy on the device."""
+        from .recurrent_actor import lstm_unsupported_reason, wide_memory_would_help
+        rnns = (ac.memory_a.rnn, ac.memory_c.rnn)
+        if wide or not any(wide_memory_would_help(r) for r in rnns) or any(lstm_unsupported_reason(r, wide=True) for r in rnns):
+            return ""
+        return " (the runner key wide_memory / --wide_memory covers up to 512 units)"
+
     def _make_recurrent_game_actor(self):
         """``device_rollout`` of ``high_level_game`` / ``scripted_predator_game`` / an agent view of ``dec_high_level_game`` with a recurrent
         policy; None (and why) where it cannot run."""
         env, ac = self.env, self.alg.actor_critic
         from .recurrent_actor import RecurrentFusedActor, lstm_unsupported_reason
-        why = None
+        why, hint = None, ""
+        wide = bool(self.cfg.get("wide_memory", False))
         if not str(self.device).startswith("cuda"):
             why = f"the policy is on {self.device}, the game actor kernels run on a GPU"
         elif not hasattr(env, "step_policy"):
@@ -136,18 +147,19 @@ class OnPolicyRunner:
         elif env.num_privileged_obs is not None and not getattr(env, "dec_agent_view", False):
             why = "privileged observations"
         else:                                                     # (an agent view: the critic memory reads the privileged buffer)
-            why = lstm_unsupported_reason(ac.memory_a.rnn) or lstm_unsupported_reason(ac.memory_c.rnn)
+            why = lstm_unsupported_reason(ac.memory_a.rnn, wide) or lstm_unsupported_reason(ac.memory_c.rnn, wide)
             why = why and f"no device LSTM cell for a {why}"
+            hint = self._wide_memory_hint(ac, wide) if why else ""
         if why is None:
             try:
                 fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
-                                            step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs)
+                                            step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs, wide=wide)
                 env.shared_actor_launch(fused)                # raises the new kernel's LDS limit here, outside any capture; False = separate launches
                                                               # (an agent view has no opponent yet: DecGamePolicyRunner makes the call)
             except Exception as exc:
                 why = f"{type(exc).__name__}: {exc}"
         if why is not None:
-            print(f"[runner] device rollout unavailable ({why}); generic VecEnv loop")
+            print(f"[runner] device rollout unavailable ({why}); generic VecEnv loop{hint}")
             return None
         T, N = self.num_steps_per_env, env.num_envs
         self._critic_features = torch.zeros(T, N, ac.memory_c.rnn.hidden_size, device=self.device)     # the critic memory's output of every step

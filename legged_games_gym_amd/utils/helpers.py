@@ -210,12 +210,15 @@ def get_args(argv=None):
     p.add_argument("--device_bptt", action="store_true", default=False,
                    help="ActorCriticRecurrent on the GPU: run the LSTM recurrence of the PPO update, forward and backward through time, on the device sequence "
                         "kernels (runner key of the same name); a memory they do not cover (GRU, several layers, more than 256 units) keeps torch with a message")
+    p.add_argument("--wide_memory", action="store_true", default=False,
+                   help="ActorCriticRecurrent on the GPU: run LSTM memories of 288 .. 512 units on the device rollout (runner key of the same name: the cell "
+                        "and actor kernels of liblegged_lstm_wide.so; the game tasks then issue separate launches); off, such a memory falls back or is refused")
     p.add_argument("--outcome_stats", action="store_true", default=False,
                    help="the game tasks (dec_high_level_game: scripts/train_dec_game.py): count inside the post-step launch why episodes end (captured, left the arena, fell, "
                         "survived) and log the rates as Episode/outcome_*; the scripts set env.outcome_stats on the registration they use")
     p.add_argument("--policy_class_name", type=str, help="ActorCritic or ActorCriticRecurrent (runner key of the same name)")
     p.add_argument("--rnn_type", type=str, help="ActorCriticRecurrent: lstm or gru")
-    p.add_argument("--rnn_hidden_size", type=int, help="ActorCriticRecurrent: units of each memory (the device rollout covers multiples of 32 up to 256)")
+    p.add_argument("--rnn_hidden_size", type=int, help="ActorCriticRecurrent: units of each memory (the device rollout covers multiples of 32 up to 256, with --wide_memory up to 512)")
     p.add_argument("--rnn_num_layers", type=int, help="ActorCriticRecurrent: layers of each memory (the device rollout covers 1)")
     p.add_argument("--max_evolutions", type=int, help="dec_high_level_game: how often predator and prey alternate (scripts/train_dec_game.py)")
     p.add_argument("--opponent_pool", type=int, default=0,

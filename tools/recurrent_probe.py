@@ -16,7 +16,11 @@ Run on the GPU: ``python tools/recurrent_probe.py [--train]``.
 The kernel's own time, independent of the event timing above, comes from a profiler run of its own:
 ``rocprofv3 --kernel-trace --stats -d <dir> -- python tools/recurrent_probe.py --cell-only`` launches ``lg_lstm_step`` (both memories,
 4096 envs, 48 inputs, 256 units) 200 times eagerly and nothing else; the ``k_lstm_cell`` row of the kernel statistics against
-``flop`` / 155 TF is its share of the f32-MFMA peak."""
+``flop`` / 155 TF is its share of the f32-MFMA peak.
+
+``--wide`` measures the wide library instead (include/legged_recurrent_wide.h, the runner key ``wide_memory``) -> profiles/recurrent_wide_step.json:
+the same three variants at 512 units (``lg_lstm_wide_step`` + ``lg_lstm_wide_actor_act`` against torch, the cell against its FLOP count), and at
+256 units ``lg_lstm_wide_step`` against ``lg_lstm_step`` on the same memories, all in one process."""
 import argparse
 import json
 import os
@@ -72,12 +76,12 @@ def alternate(variants, stages, replays, pairs, discard):
             for k, v in times.items()}
 
 
-def measure(n, hidden, args):
+def measure(n, hidden, args, wide=False):
     from legged_games_gym_amd.rl import ActorCriticRecurrent
     from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor, lstm_step
     torch.manual_seed(1)
     ac = ActorCriticRecurrent(48, 48, 12, actor_hidden_dims=[128, 64, 32], critic_hidden_dims=[128, 64, 32], rnn_hidden_size=hidden).to(DEV)
-    rfa = RecurrentFusedActor(ac, DEV, seed=3, num_envs=n)
+    rfa = RecurrentFusedActor(ac, DEV, seed=3, num_envs=n, wide=wide)
     obs = torch.rand(n, 48, device=DEV) * 6.0 - 3.0
     reset = (torch.rand(n, device=DEV) < 0.02)
 
@@ -86,7 +90,7 @@ def measure(n, hidden, args):
 
     def cell():
         f = rfa._flip
-        lstm_step(rfa.lib, rfa.lstm_a, rfa.lstm_c, obs, obs, reset, rfa.state_a[f], rfa.state_a[1 - f], rfa.state_c[f], rfa.state_c[1 - f], n,
+        lstm_step(rfa.cell_lib, rfa.lstm_a, rfa.lstm_c, obs, obs, reset, rfa.state_a[f], rfa.state_a[1 - f], rfa.state_c[f], rfa.state_c[1 - f], n,
                   torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
         rfa._flip = 1 - f
 
@@ -113,6 +117,28 @@ def measure(n, hidden, args):
     r["cell"]["flop"] = flop
     r["cell"]["share_of_f32_mfma_peak"] = flop / (r["cell"]["median_us"] * 1e-6) / PEAK_F32_MFMA
     return r
+
+
+def wide_against_narrow_cell(n, hidden, args):
+    """``lg_lstm_wide_step`` against ``lg_lstm_step`` on the same two memories at a width both take."""
+    from legged_games_gym_amd.rl import ActorCriticRecurrent
+    from legged_games_gym_amd.rl.recurrent_actor import DeviceLstm, lstm_step
+    torch.manual_seed(1)
+    ac = ActorCriticRecurrent(48, 48, 12, actor_hidden_dims=[128, 64, 32], critic_hidden_dims=[128, 64, 32], rnn_hidden_size=hidden).to(DEV)
+    obs = torch.rand(n, 48, device=DEV) * 6.0 - 3.0
+    reset = (torch.rand(n, device=DEV) < 0.02).to(torch.uint8)
+    variants = {}
+    for name, wide in (("lg_lstm_wide_step", True), ("lg_lstm_step", False)):
+        la, lc = DeviceLstm(ac.memory_a.rnn, DEV, wide=wide), DeviceLstm(ac.memory_c.rnn, DEV, wide=wide)
+        st = [[(torch.zeros(n, hidden, device=DEV), torch.zeros(n, hidden, device=DEV)) for _ in range(2)] for _ in range(2)]
+        flip = [0]
+
+        def cell(la=la, lc=lc, st=st, flip=flip):
+            f = flip[0]
+            lstm_step(la.lib, la, lc, obs, obs, reset, st[0][f], st[0][1 - f], st[1][f], st[1][1 - f], n, torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
+            flip[0] = 1 - f
+        variants[name] = (capture(cell, args.graph_steps), cell)
+    return alternate(variants, args.graph_steps, args.replays, args.pairs, args.discard)
 
 
 def cell_only(n, hidden, launches):
@@ -160,8 +186,13 @@ def main():
     ap.add_argument("--train", action="store_true")
     ap.add_argument("--cell-only", action="store_true", help="launch the cell 200 times and exit (for a rocprofv3 kernel trace)")
     ap.add_argument("--train-iterations", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "recurrent_step.json"))
+    ap.add_argument("--wide", action="store_true", help="measure liblegged_lstm_wide.so: 512 units, and the wide cell against lg_lstm_step at 256")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "recurrent_wide_step.json" if args.wide else "recurrent_step.json")
+    if args.wide:
+        args.hidden, args.train = [512], False
     if args.cell_only:
         return cell_only(4096, 256, 200)
     prime = torch.cuda.CUDAGraph()                      # the generator's graph-safe state, created outside inference_mode (rl/ppo.py)
@@ -170,10 +201,15 @@ def main():
     out = {"device_name": torch.cuda.get_device_name(0), "graph_steps": args.graph_steps, "replays": args.replays, "pairs": args.pairs, "stage": {}}
     for n in args.envs:
         for h in args.hidden:
-            r = measure(n, h, args)
+            r = measure(n, h, args, wide=args.wide)
             out["stage"][f"{n}x{h}"] = r
             print(f"{n} envs, {h} units: " + "; ".join(f"{k} {v['median_us']:.1f} us [{v['min_us']:.1f} .. {v['max_us']:.1f}]" for k, v in r.items())
                   + f"; cell at {100 * r['cell']['share_of_f32_mfma_peak']:.1f} % of the f32-MFMA peak", flush=True)
+    if args.wide:
+        out["cell_at_256_units"] = {}
+        for n in args.envs:
+            out["cell_at_256_units"][f"{n}x256"] = r = wide_against_narrow_cell(n, 256, args)
+            print(f"{n} envs, 256 units: " + "; ".join(f"{k} {v['median_us']:.1f} us [{v['min_us']:.1f} .. {v['max_us']:.1f}]" for k, v in r.items()), flush=True)
     if args.train:
         out["train"] = {}
         for fused in (True, False):
