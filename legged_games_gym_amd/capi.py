@@ -1078,6 +1078,53 @@ def load_lstm_wide_library():
     return _lstm_wide_lib
 
 
+# ----------------------------------------------------------------------------------------------------------------- legged_recurrent_gru.h
+# The GRU cell of a recurrent policy, an eighth library (csrc/liblegged_gru.so): outside ABI / ALL_SYMBOLS / bind_all.  Its handles are its
+# own; the actor MLP behind a GRU memory is the main library's lg_lstm_actor.
+LG_GRU_MAX_IN, LG_GRU_MAX_HIDDEN, LG_GRU_BLOCK_ENVS = 256, 256, 32
+GRU_ABI = {
+    "lg_gru_create": ([i32, i32, _vp, _vp, _vp, _vp, i32, _P(_vp)], _int),
+    "lg_gru_load_device": ([_vp, _vp, _vp, _vp, _vp, _vp], _int),
+    "lg_gru_destroy": ([_vp], _int),
+    "lg_gru_step": ([_vp] * 9 + [i32, _vp], _int),
+    "lg_gru_last_error": ([], C.c_char_p),
+}
+GRU_SYMBOLS = list(GRU_ABI)
+_GRU_LIB_NAME = "liblegged_gru.so"
+_gru_lib = None
+
+
+def gru_supported(num_in: int, hidden: int) -> bool:
+    """The shapes ``lg_gru_create`` takes."""
+    return 1 <= num_in <= LG_GRU_MAX_IN and 32 <= hidden <= LG_GRU_MAX_HIDDEN and hidden % 32 == 0
+
+
+def gru_library_path() -> str:
+    """In-tree liblegged_gru.so; LG_GRU_LIB selects another build of the same source."""
+    return os.environ.get("LG_GRU_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _GRU_LIB_NAME)
+
+
+def bind_gru(lib):
+    for symbol, (argtypes, restype) in GRU_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    return lib
+
+
+def load_gru_library():
+    """Load the GRU cell or fail loudly -- never a CPU substitute."""
+    global _gru_lib
+    if _gru_lib is not None:
+        return _gru_lib
+    path = gru_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _gru_lib = bind_gru(C.CDLL(path))
+    return _gru_lib
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

@@ -340,9 +340,13 @@ class DecHighLevelGame(GameBase):
 
     def _recurrent_launches(self, fused_pred, fused_prey, say=True, pooled=False):
         """``_recurrent_library`` for a pair of actors.  An actor with ``wide`` memories (``RecurrentFusedActor(wide=True)`` above 256 units) holds
-        handles of liblegged_lstm_wide.so, which none of the shared launches reads: separate launches throughout, said once."""
+        handles of liblegged_lstm_wide.so, which none of the shared launches reads: separate launches throughout, said once.  Likewise an
+        actor with ``gru`` memories (``RecurrentFusedActor(gru=True)``, handles of liblegged_gru.so): ``lg_dec_lstm_step`` reads ``lg_lstm`` handles."""
         if getattr(fused_pred, "wide", False) or getattr(fused_prey, "wide", False):
             self._say_separate("wide memory", say, pooled)
+            return None, False
+        if getattr(fused_pred, "gru", False) or getattr(fused_prey, "gru", False):
+            self._say_separate("GRU memory", say, pooled)
             return None, False
         return self._recurrent_library(fused_pred, say=say, pooled=pooled)
 

@@ -142,7 +142,7 @@ class DecGamePolicyRunner:
             raise ValueError("opponent_pool_size > 0 with ActorCriticRecurrent: the opponent pool is feed-forward (lg_dec_pool_act has no recurrent role); "
                              "set the runner key opponent_pool_recurrent (--opponent_pool_recurrent) for pools of recurrent snapshots")
         import torch.nn as nn
-        from .recurrent_actor import lstm_unsupported_reason, wide_memory_would_help
+        from .recurrent_actor import gru_unsupported_reason, lstm_unsupported_reason, wide_memory_would_help
         wide = bool(self.cfg.get("wide_memory", False))
         if wide and pool_recurrent:
             raise ValueError("wide_memory with opponent_pool_recurrent: the pooled launches (lg_dec_pool_lstm_step / lg_dec_pool_lstm_act) stop at "
@@ -153,6 +153,15 @@ class DecGamePolicyRunner:
             raise ValueError(f"rnn_type must be 'lstm' or 'gru', got {kind!r}")
         probe = (nn.GRU if kind == "gru" else nn.LSTM)(input_size=3, hidden_size=int(policy.get("rnn_hidden_size", 256)),
                                                        num_layers=int(policy.get("rnn_num_layers", 1)))      # (the predator's memory; both have these units)
+        if kind == "gru" and bool(self.cfg.get("device_gru", False)):          # opt-in: GRU memories on liblegged_gru.so, separate launches
+            if pool_recurrent:
+                raise ValueError("device_gru with opponent_pool_recurrent: the pooled launches (lg_dec_pool_lstm_step / lg_dec_pool_lstm_act) read "
+                                 "lg_lstm handles; a recurrent opponent pool of GRU policies does not exist")
+            why = gru_unsupported_reason(probe)
+            if why is not None:
+                raise ValueError(f"ActorCriticRecurrent on dec_high_level_game with device_gru: no device GRU cell for a {why} (wide_memory does not "
+                                 "cover a GRU), and there is no generic loop for two recurrent agents")
+            return True
         why = lstm_unsupported_reason(probe, wide)
         if why is not None:
             hint = " (the runner key wide_memory / --wide_memory covers up to 512 units)" if not wide and wide_memory_would_help(probe) else ""

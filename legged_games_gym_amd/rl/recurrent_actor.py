@@ -28,6 +28,23 @@ def lstm_unsupported_reason(rnn, wide=False):
     return None
 
 
+def gru_unsupported_reason(rnn):
+    """Why ``lg_gru_create`` (the runner key ``device_gru``) does not take this ``nn.GRU`` / ``nn.LSTM``, or None."""
+    if not isinstance(rnn, nn.GRU):
+        return f"{type(rnn).__name__} memory (the device GRU cell is a GRU)"
+    if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias:
+        return f"{rnn.num_layers}-layer memory (the device GRU cell is one plain layer)"
+    if not capi.gru_supported(rnn.input_size, rnn.hidden_size):
+        return (f"memory of {rnn.input_size} inputs and {rnn.hidden_size} units (the device GRU cell takes 1 .. {capi.LG_GRU_MAX_IN} inputs and "
+                f"a multiple of 32 units up to {capi.LG_GRU_MAX_HIDDEN})")
+    return None
+
+
+def device_gru_would_help(rnn):
+    """Whether the key ``device_gru`` turns a refusal of this memory into an acceptance (the fall-back messages then name it)."""
+    return lstm_unsupported_reason(rnn) is not None and gru_unsupported_reason(rnn) is None
+
+
 def wide_memory_would_help(rnn):
     """Whether the key ``wide_memory`` turns a refusal of this memory into an acceptance (the fall-back messages then name it)."""
     return lstm_unsupported_reason(rnn) is not None and lstm_unsupported_reason(rnn, wide=True) is None
@@ -74,6 +91,56 @@ class DeviceLstm:
                 self.handle = C.c_void_p()
         except Exception:
             pass
+
+
+class DeviceGru:
+    """One ``lg_gru`` handle of liblegged_gru.so over a one-layer ``nn.GRU``: ``DeviceLstm``'s twin."""
+
+    wide, gru = False, True
+
+    def __init__(self, rnn, device):
+        why = gru_unsupported_reason(rnn)
+        if why is not None:
+            raise ValueError(f"no device GRU cell for a {why}")
+        self.lib, self.rnn, self.device = capi.load_gru_library(), rnn, torch.device(device)
+        self.num_in, self.hidden = rnn.input_size, rnn.hidden_size
+        self.handle = C.c_void_p()
+        host = [np.ascontiguousarray(p.detach().float().cpu().numpy()) for p in self._params()]
+        rc = self.lib.lg_gru_create(self.num_in, self.hidden, *[a.ctypes.data for a in host], self.device.index or 0, C.byref(self.handle))
+        if rc != 0:
+            raise RuntimeError(f"lg_gru_create failed ({rc}): {self.lib.lg_gru_last_error().decode()}")
+
+    def _params(self):
+        r = self.rnn
+        return r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0
+
+    def load_device(self):
+        """Repack from the module's CUDA parameters (``lg_gru_load_device``): one launch on the current stream, no host copy."""
+        ps = self._params()
+        for p in ps:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise ValueError("DeviceGru.load_device needs contiguous float32 CUDA parameters")
+        rc = self.lib.lg_gru_load_device(self.handle, *[p.data_ptr() for p in ps], torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"lg_gru_load_device failed ({rc}): {self.lib.lg_gru_last_error().decode()}")
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.lg_gru_destroy(self.handle)
+                self.handle = C.c_void_p()
+        except Exception:
+            pass
+
+
+def gru_step(lib, gru_a, gru_c, x_a, x_c, reset, h_in_a, h_out_a, h_in_c, h_out_c, num_envs, stream):
+    """``lg_gru_step`` on tensors; a role is absent when its ``DeviceGru`` is None.  ``lib`` is liblegged_gru.so."""
+    p = lambda t, present: None if (t is None or not present) else t.data_ptr()
+    a, c = gru_a is not None, gru_c is not None
+    rc = lib.lg_gru_step(gru_a.handle if a else None, gru_c.handle if c else None, p(x_a, a), p(x_c, c), p(reset, True),
+                         p(h_in_a, a), p(h_out_a, a), p(h_in_c, c), p(h_out_c, c), int(num_envs), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_gru_step failed ({rc}): {lib.lg_gru_last_error().decode()}")
 
 
 def lstm_step(lib, lstm_a, lstm_c, x_a, x_c, reset, state_in_a, state_out_a, state_in_c, state_out_c, num_envs, stream):
@@ -178,19 +245,29 @@ class RecurrentFusedActor:
     ``wide`` (the runner key ``wide_memory``): when either memory has more than 256 units, both memories and the actor take the handles of
     liblegged_lstm_wide.so (up to 512 units; one launch still advances both memories) and the attribute ``wide`` is True.  The game envs
     then issue the separate launches, because their shared kernels read main-library handles.  With both memories within 256 units
-    nothing wide is created."""
+    nothing wide is created.
 
-    def __init__(self, actor_critic, device, seed: int = 1, step_counter: torch.Tensor = None, num_envs: int = None, wide: bool = False):
+    ``gru`` (the runner key ``device_gru``): both memories are ``nn.GRU``; the cell handles are ``DeviceGru`` of liblegged_gru.so, the actor is
+    the main library's and the attribute ``gru`` is True.  A GRU has one state tensor per memory: the slots hold 1-tuples ``(h,)`` where an
+    LSTM's hold ``(h, c)``, and every method does for the one tensor what it does for the two.  ``dec_high_level_game`` then issues the
+    separate launches, because its cell launch reads ``lg_lstm`` handles.  Without ``gru`` a GRU memory is refused as before."""
+
+    def __init__(self, actor_critic, device, seed: int = 1, step_counter: torch.Tensor = None, num_envs: int = None, wide: bool = False,
+                 gru: bool = False):
         if not getattr(actor_critic, "is_recurrent", False):
             raise ValueError("RecurrentFusedActor wraps an ActorCriticRecurrent")
         self.ac, self.device = actor_critic, torch.device(device)
         rnns = (actor_critic.memory_a.rnn, actor_critic.memory_c.rnn)
-        self.wide = bool(wide) and any(getattr(r, "hidden_size", 0) > capi.LG_LSTM_MAX_HIDDEN for r in rnns)
-        self.lstm_a = DeviceLstm(rnns[0], device, wide=self.wide)
-        self.lstm_c = DeviceLstm(rnns[1], device, wide=self.wide)
+        self.gru = bool(gru) and all(isinstance(r, nn.GRU) for r in rnns)
+        self.wide = not self.gru and bool(wide) and any(getattr(r, "hidden_size", 0) > capi.LG_LSTM_MAX_HIDDEN for r in rnns)
+        if self.gru:
+            self.lstm_a, self.lstm_c = DeviceGru(rnns[0], device), DeviceGru(rnns[1], device)
+        else:
+            self.lstm_a = DeviceLstm(rnns[0], device, wide=self.wide)
+            self.lstm_c = DeviceLstm(rnns[1], device, wide=self.wide)
         self.fused = DeviceLstmActor(actor_critic, device, seed=seed, step_counter=step_counter, wide=self.wide)
         self.lib = capi.load_library()                          # the FusedActor surface: the main library (the runner's rollout bookkeeping)
-        self.cell_lib = self.lstm_a.lib                         # the library of the three handles: the main one, or liblegged_lstm_wide.so
+        self.cell_lib = self.lstm_a.lib                         # the library of the cell handles: the main one, liblegged_lstm_wide.so or liblegged_gru.so
         self.num_envs, self._flip = None, 0
         if num_envs is not None:
             self._allocate(num_envs)
@@ -201,6 +278,7 @@ class RecurrentFusedActor:
     num_actions = property(lambda self: self.fused.num_actions)
     # ... and what HighLevelGame._act reads: the actor MLP's handle, buffers and step count; the marker selects lg_game_lstm_act there
     recurrent = True
+    gru = False                                                 # (the instance's, set by __init__: liblegged_gru.so handles, one state tensor per memory)
     handle = property(lambda self: self.fused.handle)
 
     def output_buffers(self, n):
@@ -215,9 +293,10 @@ class RecurrentFusedActor:
     def _allocate(self, n):
         z = lambda h: torch.zeros(n, h, device=self.device)
         Ha, Hc = self.lstm_a.hidden, self.lstm_c.hidden
-        self.state_a = [(z(Ha), z(Ha)), (z(Ha), z(Ha))]         # [flip] -> (h, c): the launch reads [flip] and writes [1 - flip]
-        self.state_c = [(z(Hc), z(Hc)), (z(Hc), z(Hc))]
-        self.scratch_c = (z(Hc), z(Hc))                        # outputs of a critic-only step that must not move the carried state
+        st = (lambda h: (z(h),)) if self.gru else (lambda h: (z(h), z(h)))
+        self.state_a = [st(Ha), st(Ha)]                        # [flip] -> (h, c), a GRU's (h,): the launch reads [flip] and writes [1 - flip]
+        self.state_c = [st(Hc), st(Hc)]
+        self.scratch_c = st(Hc)                                # outputs of a critic-only step that must not move the carried state
         self.num_envs, self._flip = n, 0
         self._critic_slots_equal = True                        # both slots of the critic memory hold the carried state (see advance_slots)
 
@@ -236,16 +315,29 @@ class RecurrentFusedActor:
         self._critic_slots_equal = True
 
     def hidden_states(self):
-        """((h_a, c_a), (h_c, c_c)) the next step starts from, as ``[1, N, H]`` views (``ActorCriticRecurrent.get_hidden_states``)."""
+        """((h_a, c_a), (h_c, c_c)), a GRU's ((h_a,), (h_c,)), the next step starts from, as ``[1, N, H]`` views
+        (``ActorCriticRecurrent.get_hidden_states``)."""
         return tuple(tuple(t.unsqueeze(0) for t in st[self._flip]) for st in (self.state_a, self.state_c))
 
     def publish_states(self, reset=None):
         """Point the torch module's memories at copies of the device state: the torch-side update and a later play start from the truth.
         ``reset``: the flags the next step would be given; the torch memories zero such rows at once (``Memory.reset``)."""
-        (ha, ca), (hc, cc) = self.hidden_states()
+        st_a, st_c = self.hidden_states()
         keep = 1.0 if reset is None else (reset == 0).view(1, -1, 1).float()
-        self.ac.memory_a.hidden_states = (ha * keep, ca * keep)
-        self.ac.memory_c.hidden_states = (hc * keep, cc * keep)
+        if self.gru:                                         # nn.GRU's state is the tensor, not a tuple
+            self.ac.memory_a.hidden_states, self.ac.memory_c.hidden_states = st_a[0] * keep, st_c[0] * keep
+            return
+        self.ac.memory_a.hidden_states = tuple(t * keep for t in st_a)
+        self.ac.memory_c.hidden_states = tuple(t * keep for t in st_c)
+
+    def _cell_step(self, cell_a, cell_c, x_a, x_c, reset, in_a, out_a, in_c, out_c, n):
+        """``lstm_step`` on ``(h, c)`` pairs or ``gru_step`` on the 1-tuples' tensors, on the current stream."""
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.gru:
+            only = lambda st: None if st is None else st[0]
+            gru_step(self.cell_lib, cell_a, cell_c, x_a, x_c, reset, only(in_a), only(out_a), only(in_c), only(out_c), n, stream)
+        else:
+            lstm_step(self.cell_lib, cell_a, cell_c, x_a, x_c, reset, in_a, out_a, in_c, out_c, n, stream)
 
     def step_memories(self, obs, critic_obs=None, reset=None):
         """Advance the actor memory (and, with ``critic_obs``, the critic memory) by one step; returns ``(h_a, h_c or None)``, the new
@@ -255,8 +347,8 @@ class RecurrentFusedActor:
             self._allocate(n)
         f = self._flip
         with_c = critic_obs is not None
-        lstm_step(self.cell_lib, self.lstm_a, self.lstm_c if with_c else None, self._f32(obs), self._f32(critic_obs) if with_c else None, self._flags(reset),
-                  self.state_a[f], self.state_a[1 - f], self.state_c[f], self.state_c[1 - f], n, torch.cuda.current_stream(self.device).cuda_stream)
+        self._cell_step(self.lstm_a, self.lstm_c if with_c else None, self._f32(obs), self._f32(critic_obs) if with_c else None, self._flags(reset),
+                        self.state_a[f], self.state_a[1 - f], self.state_c[f], self.state_c[1 - f], n)
         if not with_c:                                       # the critic memory did not move: keep both of its slots current
             for dst, src in zip(self.state_c[1 - f], self.state_c[f]):
                 dst.copy_(src)
@@ -268,8 +360,8 @@ class RecurrentFusedActor:
         """Advance the critic memory alone on this actor's slots (read ``[flip]``, write ``[1 - flip]``) and return its new output; the caller
         then calls ``advance_slots(True)`` (the separate launches of a pooled role, whose actor memory ``rl.RecurrentOpponentPool`` advances)."""
         f = self._flip
-        lstm_step(self.cell_lib, None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[f], self.state_c[1 - f],
-                  critic_obs.shape[0], torch.cuda.current_stream(self.device).cuda_stream)
+        self._cell_step(None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[f], self.state_c[1 - f],
+                        critic_obs.shape[0])
         return self.state_c[1 - f][0]
 
     def advance_slots(self, with_critic):
@@ -298,8 +390,7 @@ class RecurrentFusedActor:
     def peek_critic(self, critic_obs, reset=None):
         """The critic memory's output for ``critic_obs`` from the carried state, which stays where it is (the last value of a rollout)."""
         n = critic_obs.shape[0]
-        lstm_step(self.cell_lib, None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[self._flip], self.scratch_c, n,
-                  torch.cuda.current_stream(self.device).cuda_stream)
+        self._cell_step(None, self.lstm_c, None, self._f32(critic_obs), self._flags(reset), None, None, self.state_c[self._flip], self.scratch_c, n)
         return self.scratch_c[0]
 
     @staticmethod
@@ -327,7 +418,7 @@ class RecurrentFusedActor:
         return self.act_with_mean(obs, reset=reset, deterministic=True)[0]
 
     def sync_device(self):
-        """Refresh both LSTMs and the actor from the torch parameters on the device; call after every optimiser step."""
+        """Refresh both memories and the actor from the torch parameters on the device; call after every optimiser step."""
         self.lstm_a.load_device()
         self.lstm_c.load_device()
         self.fused.sync_device()

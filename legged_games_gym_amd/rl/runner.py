@@ -95,7 +95,7 @@ class OnPolicyRunner:
     def _make_recurrent_fused_actor(self):
         """Recurrent policy: both memories in one ``lg_lstm_step`` launch, then the MFMA actor on the actor memory's output, per step
         (``RecurrentFusedActor``); the critic MLP once per rollout on the critic memory's outputs of all T steps.  A memory the device cell
-        does not cover (GRU, several layers, more than 256 units) or privileged observations take the torch loop.  The single-policy game
+        does not cover (a GRU without the key ``device_gru``, several layers, more than 256 units) or privileged observations take the torch loop.  The single-policy game
         tasks with ``device_rollout``: the same actor through ``env.step_policy`` (lg_lstm_step -> lg_game_lstm_act -> lg_step -> post)."""
         env, ac = self.env, self.alg.actor_critic
         if hasattr(env, "ll_env"):
@@ -104,16 +104,16 @@ class OnPolicyRunner:
             return self._make_recurrent_game_actor()
         if not (str(self.device).startswith("cuda") and self.cfg.get("fused_rollout", True) and hasattr(env, "_sim")):
             return None
-        from .recurrent_actor import RecurrentFusedActor, lstm_unsupported_reason
+        from .recurrent_actor import RecurrentFusedActor
         wide = bool(self.cfg.get("wide_memory", False))       # opt-in: memories of up to 512 units on liblegged_lstm_wide.so
-        why = "privileged observations" if env.num_privileged_obs is not None else (
-            lstm_unsupported_reason(ac.memory_a.rnn, wide) or lstm_unsupported_reason(ac.memory_c.rnn, wide))
+        gru, cell_why, hint = self._recurrent_cell_reason(ac, wide)       # opt-in: GRU memories on liblegged_gru.so (the key device_gru)
+        why = "privileged observations" if env.num_privileged_obs is not None else cell_why
         if why is not None:
-            print(f"[runner] device LSTM cell unavailable ({why}); torch policy in the rollout{self._wide_memory_hint(ac, wide)}")
+            print(f"[runner] device {'GRU' if gru else 'LSTM'} cell unavailable ({why}); torch policy in the rollout{hint}")
             return None
         try:
             fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + 7919, step_counter=env._sim.buf["step_counter"],
-                                        num_envs=env.num_envs, wide=wide)
+                                        num_envs=env.num_envs, wide=wide, **({"gru": True} if gru else {}))
         except Exception as exc:                              # unsupported actor shape: torch rollouts
             print(f"[runner] MFMA actor unavailable ({type(exc).__name__}: {exc}); torch policy in the rollout")
             return None
@@ -133,12 +133,26 @@ class OnPolicyRunner:
             return ""
         return " (the runner key wide_memory / --wide_memory covers up to 512 units)"
 
+    def _recurrent_cell_reason(self, ac, wide):
+        """``(gru, why, hint)``: whether the key ``device_gru`` applies (it is set and both memories are ``nn.GRU``), why the device cell does
+        not take the memories (None: it does) and what the fall-back message adds on the same line."""
+        import torch.nn as nn
+        from .recurrent_actor import device_gru_would_help, gru_unsupported_reason, lstm_unsupported_reason
+        rnns = (ac.memory_a.rnn, ac.memory_c.rnn)
+        if bool(self.cfg.get("device_gru", False)) and all(isinstance(r, nn.GRU) for r in rnns):
+            return True, gru_unsupported_reason(rnns[0]) or gru_unsupported_reason(rnns[1]), ""
+        why = lstm_unsupported_reason(rnns[0], wide) or lstm_unsupported_reason(rnns[1], wide)
+        hint = self._wide_memory_hint(ac, wide)
+        if why is not None and all(device_gru_would_help(r) for r in rnns):
+            hint += " (the runner key device_gru / --device_gru runs GRU memories on the device)"
+        return False, why, hint
+
     def _make_recurrent_game_actor(self):
         """``device_rollout`` of ``high_level_game`` / ``scripted_predator_game`` / an agent view of ``dec_high_level_game`` with a recurrent
         policy; None (and why) where it cannot run."""
         env, ac = self.env, self.alg.actor_critic
-        from .recurrent_actor import RecurrentFusedActor, lstm_unsupported_reason
-        why, hint = None, ""
+        from .recurrent_actor import RecurrentFusedActor
+        why, hint, gru = None, "", False
         wide = bool(self.cfg.get("wide_memory", False))
         if not str(self.device).startswith("cuda"):
             why = f"the policy is on {self.device}, the game actor kernels run on a GPU"
@@ -147,13 +161,14 @@ class OnPolicyRunner:
         elif env.num_privileged_obs is not None and not getattr(env, "dec_agent_view", False):
             why = "privileged observations"
         else:                                                     # (an agent view: the critic memory reads the privileged buffer)
-            why = lstm_unsupported_reason(ac.memory_a.rnn, wide) or lstm_unsupported_reason(ac.memory_c.rnn, wide)
-            why = why and f"no device LSTM cell for a {why}"
-            hint = self._wide_memory_hint(ac, wide) if why else ""
+            gru, why, hint = self._recurrent_cell_reason(ac, wide)
+            why = why and f"no device {'GRU' if gru else 'LSTM'} cell for a {why}"
+            hint = hint if why else ""
         if why is None:
             try:
                 fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
-                                            step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs, wide=wide)
+                                            step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs, wide=wide,
+                                            **({"gru": True} if gru else {}))
                 env.shared_actor_launch(fused)                # raises the new kernel's LDS limit here, outside any capture; False = separate launches
                                                               # (an agent view has no opponent yet: DecGamePolicyRunner makes the call)
             except Exception as exc:

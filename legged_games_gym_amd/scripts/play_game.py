@@ -79,7 +79,8 @@ def play_game(args, steps=None):
             ac, kw = runner.alg.actor_critic, dict(seed=int(getattr(env.cfg, "seed", 1)), step_counter=env.ll_env._sim.buf["step_counter"])
             if ac.is_recurrent:             # memories from zero, lg_lstm_step -> lg_game_lstm_act -> lg_step -> post per step
                 from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor
-                fused = RecurrentFusedActor(ac, env.device, num_envs=env.num_envs, wide=getattr(args, "wide_memory", False), **kw)
+                fused = RecurrentFusedActor(ac, env.device, num_envs=env.num_envs, wide=getattr(args, "wide_memory", False),
+                                            gru=getattr(args, "device_gru", False), **kw)
             else:
                 fused = FusedActor(ac, env.device, **kw)
             if env.shared_actor_launch(fused) or getattr(fused, "wide", False):     # (a wide memory: the graph holds the separate launches)

@@ -63,6 +63,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].runner.device_bptt = True
     if args.wide_memory:                     # likewise: memories of up to 512 units on the device rollout
         task_registry.get_cfgs(args.task)[1].runner.wide_memory = True
+    if args.device_gru:                      # likewise: GRU memories on the device rollout
+        task_registry.get_cfgs(args.task)[1].runner.device_gru = True
     apply_policy_args(task_registry.get_cfgs(args.task)[1], args)     # --policy_class_name ActorCriticRecurrent [--rnn_type / --rnn_hidden_size / --rnn_num_layers]
     if args.outcome_stats:                   # read with getattr() by the game tasks: no field of the registered config classes
         if args.task not in a1_game.TASKS + a1_game.SCRIPTED_TASKS:

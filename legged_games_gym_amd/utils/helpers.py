@@ -213,6 +213,9 @@ def get_args(argv=None):
     p.add_argument("--wide_memory", action="store_true", default=False,
                    help="ActorCriticRecurrent on the GPU: run LSTM memories of 288 .. 512 units on the device rollout (runner key of the same name: the cell "
                         "and actor kernels of liblegged_lstm_wide.so; the game tasks then issue separate launches); off, such a memory falls back or is refused")
+    p.add_argument("--device_gru", action="store_true", default=False,
+                   help="ActorCriticRecurrent with --rnn_type gru on the GPU: run the GRU memories (one layer, up to 256 units) on the device rollout (runner key "
+                        "of the same name: the cell kernel of liblegged_gru.so; dec_high_level_game then issues separate launches); off, a GRU falls back or is refused")
     p.add_argument("--outcome_stats", action="store_true", default=False,
                    help="the game tasks (dec_high_level_game: scripts/train_dec_game.py): count inside the post-step launch why episodes end (captured, left the arena, fell, "
                         "survived) and log the rates as Episode/outcome_*; the scripts set env.outcome_stats on the registration they use")

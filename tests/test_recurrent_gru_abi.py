@@ -1,0 +1,284 @@
+"""The GRU cell (include/legged_recurrent_gru.h, liblegged_gru.so) without a GPU: the header's functions are ``capi.GRU_SYMBOLS``, a library
+of their own exports them and refuses bad shapes and null arguments before any launch, its kernel resource rows,
+``gru_unsupported_reason``, and what the runners and the scripts do with the key ``device_gru``."""
+import ctypes
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch.nn as nn
+
+from legged_games_gym_amd import capi
+
+REPO = os.path.dirname(os.path.dirname(os.path.realpath(__file__)))
+CSRC = os.path.join(REPO, "legged_games_gym_amd", "csrc")
+RESOURCES = os.path.join(CSRC, "kernel_resources_gru.txt")
+HEADER = "legged_recurrent_gru.h"
+KERNELS = ("k_gru_cell", "k_gru_pack")
+# substrings by which existing tests count kernel rows across all resource tables
+COUNTED = ("lstm_wide", "k_dec_", "k_game_", "k_prey_act", "k_policy_act", "k_pool_act", "k_pursuer_post", "k_outcome_post", "k_member_outcome",
+           "k_privileged_obs", "k_step", "k_physics")
+
+
+def _declared(header):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
+    return re.findall(r"\b(lg_[a-z_0-9]+)\s*\(", text)
+
+
+@pytest.fixture(scope="module")
+def libs():
+    if not (os.path.isfile(capi.gru_library_path()) and os.path.isfile(capi.library_path())):
+        import __graft_entry__ as entry
+        entry.build()
+    return capi.bind_gru(ctypes.CDLL(capi.gru_library_path())), ctypes.CDLL(capi.library_path())
+
+
+def test_header_symbol_list_matches_binding_and_is_disjoint_from_the_other_libraries():
+    assert sorted(_declared(HEADER)) == sorted(capi.GRU_SYMBOLS)
+    assert capi.GRU_SYMBOLS == ["lg_gru_create", "lg_gru_load_device", "lg_gru_destroy", "lg_gru_step", "lg_gru_last_error"]
+    for other in (capi.ALL_SYMBOLS, capi.LSTM_SEQ_SYMBOLS, capi.GAME_RECURRENT_SYMBOLS, capi.DEC_GAME_RECURRENT_SYMBOLS, capi.DEC_POOL_RECURRENT_SYMBOLS,
+                  capi.DEC_GAME_PRIVILEGED_SYMBOLS, capi.LSTM_WIDE_SYMBOLS):
+        assert not set(capi.GRU_SYMBOLS) & set(other)
+    assert HEADER not in capi.ABI
+    text = open(os.path.join(REPO, "include", HEADER)).read()
+    for name, value in (("LG_GRU_MAX_IN", capi.LG_GRU_MAX_IN), ("LG_GRU_MAX_HIDDEN", capi.LG_GRU_MAX_HIDDEN), ("LG_GRU_BLOCK_ENVS", capi.LG_GRU_BLOCK_ENVS)):
+        assert re.search(rf"#define {name} {value}\b", text), name
+    assert (capi.LG_GRU_MAX_IN, capi.LG_GRU_MAX_HIDDEN, capi.LG_GRU_BLOCK_ENVS) == (256, 256, 32)
+    # create / load_device / destroy have the signatures of the lg_lstm_* entries; the step has one state tensor per role where they have two
+    main = capi.ABI["legged_recurrent.h"][0]
+    for gru, lstm in (("lg_gru_create", "lg_lstm_create"), ("lg_gru_load_device", "lg_lstm_load_device"), ("lg_gru_destroy", "lg_lstm_destroy")):
+        assert capi.GRU_ABI[gru] == main[lstm], gru
+    assert len(capi.GRU_ABI["lg_gru_step"][0]) == len(main["lg_lstm_step"][0]) - 4
+
+
+def test_the_new_library_exports_the_symbols_and_the_main_library_does_not(libs, monkeypatch):
+    gru, main = libs
+    for sym in capi.GRU_SYMBOLS:
+        assert hasattr(gru, sym), sym
+        assert not hasattr(main, sym), sym
+    import __graft_entry__ as entry
+    assert entry.GRU_SOURCE == "lg_gru.hip" and entry.GRU_SOURCE not in entry.HIP_SOURCES
+    assert os.path.basename(entry.GRU_LIB) == "liblegged_gru.so" and os.path.basename(entry.GRU_RESOURCES) == "kernel_resources_gru.txt"
+    assert not any("gru" in os.path.basename(h) for h in entry.HIP_HEADERS)
+    included = set(re.findall(r'#include\s+"([^"]+)"', open(os.path.join(CSRC, entry.GRU_SOURCE)).read()))
+    assert {os.path.basename(i) for i in included} == {os.path.basename(h) for h in entry.GRU_HEADERS}, included
+    assert {os.path.basename(h) for h in entry.GRU_OWN_HEADERS} == {"lg_gru_cell_body.h", HEADER}
+    monkeypatch.setenv("LG_GRU_LIB", "/nonexistent/liblegged_gru.so")
+    assert capi.gru_library_path() == "/nonexistent/liblegged_gru.so"
+    monkeypatch.setattr(capi, "_gru_lib", None)
+    with pytest.raises(RuntimeError, match="not built; run"):
+        capi.load_gru_library()
+
+
+def test_supported_shapes():
+    ok = [(1, 32), (256, 256), (3, 64), (48, 96), (235, 256), (16, 160), (22, 128), (256, 224)]
+    bad = [(0, 64), (257, 64), (48, 0), (48, 48), (48, 288), (48, 512), (48, 16), (-1, 64)]
+    assert all(capi.gru_supported(*s) for s in ok) and not any(capi.gru_supported(*s) for s in bad)
+
+
+def test_bad_shapes_and_null_arguments_are_refused_before_any_launch(libs):
+    gru, _ = libs
+    err = gru.lg_gru_last_error
+    out = ctypes.c_void_p()
+    w = np.zeros(8, np.float32).ctypes.data                        # never read: every call below returns before the upload
+    for num_in, hidden in ((0, 64), (257, 64), (48, 0), (48, 48), (48, 288)):
+        assert gru.lg_gru_create(num_in, hidden, w, w, w, w, 0, ctypes.byref(out)) == -4, (num_in, hidden)
+        assert (b"hidden" in err() or b"num_in" in err()) and not out.value
+    for k in range(4):
+        args = [w, w, w, w]
+        args[k] = None
+        assert gru.lg_gru_create(48, 64, *args, 0, ctypes.byref(out)) == -1 and b"null" in err()
+    assert gru.lg_gru_create(48, 64, w, w, w, w, 0, None) == -1 and b"null" in err()
+    assert gru.lg_gru_load_device(None, w, w, w, w, None) == -1 and b"null" in err()
+    assert gru.lg_gru_destroy(None) == -1 and b"null" in err()
+    MB = 1 << 20
+    assert gru.lg_gru_step(None, None, MB, MB, None, MB, MB, MB, MB, 32, None) == -1 and b"both handles" in err()
+
+    class _Gru(ctypes.Structure):                                  # struct lg_gru in host memory: the refusals below come before the launch
+        _fields_ = [("num_in", ctypes.c_int32), ("hidden", ctypes.c_int32), ("ksteps", ctypes.c_int32), ("device", ctypes.c_int32),
+                    ("d_wp", ctypes.c_void_p), ("d_bp", ctypes.c_void_p)]
+    l = _Gru(48, 64, 56, 0, None, None)
+    h = ctypes.addressof(l)
+    for k in range(4):                                             # load_device with a handle: each null tensor
+        args = [w, w, w, w]
+        args[k] = None
+        assert gru.lg_gru_load_device(h, *args, None) == -1 and b"null" in err()
+    bufs = [1 * MB, 2 * MB]                                        # h_in, h_out
+    step = lambda la, lc, xa, xc, a, c, n: gru.lg_gru_step(la, lc, xa, xc, None, *a, *c, n, None)
+    none2 = [None] * 2
+    assert step(h, None, None, None, bufs, none2, 32) == -1 and b"actor memory" in err()
+    assert step(None, h, None, None, none2, bufs, 32) == -1 and b"critic memory" in err()
+    for k in range(2):
+        b = list(bufs)
+        b[k] = None
+        assert step(h, None, 5 * MB, None, b, none2, 32) == -1 and b"actor memory" in err()
+        assert step(None, h, None, 5 * MB, none2, b, 32) == -1 and b"critic memory" in err()
+        assert step(h, h, 5 * MB, 5 * MB, bufs, b, 32) == -1 and b"critic memory" in err()
+    for n in (0, -4):
+        assert step(h, None, 5 * MB, None, bufs, none2, n) == -2 and b"num_envs" in err()
+        assert step(None, h, None, 5 * MB, none2, bufs, n) == -2 and b"num_envs" in err()
+    assert step(h, None, 5 * MB, None, [MB, MB], none2, 32) == -2 and b"alias" in err()
+    assert step(None, h, None, 5 * MB, none2, [MB, MB], 32) == -2 and b"alias" in err()
+    assert step(h, h, 5 * MB, 5 * MB, bufs, [3 * MB, 3 * MB], 32) == -2 and b"alias" in err()
+    l2 = _Gru(48, 64, 56, 1, None, None)
+    assert step(h, ctypes.addressof(l2), 5 * MB, 5 * MB, bufs, [6 * MB, 7 * MB], 32) == -2 and b"devices" in err()
+
+
+def test_kernel_resource_rows_are_the_two_kernels_without_spill():
+    rows = [l.split() for l in open(RESOURCES) if not l.startswith("#")]
+    assert len(rows) == len(KERNELS) == 2, rows
+    for k in KERNELS:
+        assert sum(bool(re.match(rf"_ZN2lg{len(k)}{k}E", r[0])) for r in rows) == 1, k
+    for r in rows:
+        f = dict(zip(r[1::2], r[2::2]))
+        assert f["spill"] == "0" and f["scratch"] == "0", r
+        assert int(f["VGPRs"]) + int(f["AGPRs"]) <= 256, r             # 512 threads: two waves per SIMD
+        assert not any(word in r[0] for word in COUNTED), r            # the names stay out of the other tables' row counts
+    for other in os.listdir(CSRC):
+        if other.startswith("kernel_resources") and other != os.path.basename(RESOURCES):
+            assert "gru" not in open(os.path.join(CSRC, other)).read().lower(), other
+
+
+def test_gru_unsupported_reason():
+    from legged_games_gym_amd.rl.recurrent_actor import device_gru_would_help, gru_unsupported_reason, lstm_unsupported_reason
+    for i, h in ((48, 64), (1, 32), (256, 256), (235, 224)):
+        rnn = nn.GRU(i, h)
+        assert gru_unsupported_reason(rnn) is None and device_gru_would_help(rnn)
+        assert "GRU" in lstm_unsupported_reason(rnn)
+    for rnn, word in ((nn.GRU(48, 64, num_layers=2), "2-layer"), (nn.GRU(48, 64, bidirectional=True), "one plain layer"),
+                      (nn.GRU(48, 64, bias=False), "one plain layer"), (nn.GRU(48, 288), "288"), (nn.GRU(48, 288), "up to 256"),
+                      (nn.GRU(257, 64), "257"), (nn.GRU(48, 48), "multiple of 32"), (nn.LSTM(48, 64), "LSTM")):
+        why = gru_unsupported_reason(rnn)
+        assert why is not None and word in why, (word, why)
+        assert not device_gru_would_help(rnn)
+
+
+class _Fake:                                                       # stands in for the device objects: the key logic is what is tested here
+    made = []
+
+    def __init__(self, ac, device, **kw):
+        _Fake.made.append(kw)
+        self.wide, self.gru = kw.get("wide", False), kw.get("gru", False)
+
+
+def test_the_runner_reads_the_key(capsys, monkeypatch):
+    from legged_games_gym_amd.rl import OnPolicyRunner
+    from legged_games_gym_amd.rl import recurrent_actor
+    from legged_games_gym_amd.rl.actor_critic import ActorCriticRecurrent
+    made = _Fake.made
+    del made[:]
+    monkeypatch.setattr(recurrent_actor, "RecurrentFusedActor", _Fake)
+    policy = lambda **kw: ActorCriticRecurrent(48, 48, 12, [32, 32, 32], [32, 32, 32], **kw)
+    gru64, gru512, lstm64 = policy(rnn_type="gru", rnn_hidden_size=64), policy(rnn_type="gru", rnn_hidden_size=512), policy(rnn_hidden_size=64)
+    counter = types.SimpleNamespace(buf={"step_counter": None})
+    loco = types.SimpleNamespace(_sim=counter, num_privileged_obs=None, num_envs=4, cfg=types.SimpleNamespace(seed=1))
+    game = types.SimpleNamespace(ll_env=types.SimpleNamespace(_sim=counter), step_policy=lambda *a, **k: None, num_privileged_obs=None, num_envs=4,
+                                 cfg=types.SimpleNamespace(seed=1), shared_actor_launch=lambda fused: True)
+
+    def make(cfg, env, ac):
+        r = OnPolicyRunner.__new__(OnPolicyRunner)
+        r.cfg, r.device, r.env, r.alg, r.num_steps_per_env = cfg, "cuda:0", env, types.SimpleNamespace(actor_critic=ac), 4
+        capsys.readouterr()
+        try:
+            fused = r._make_fused_actor()
+        except Exception as exc:                                   # (torch.zeros on cuda without a GPU, after the decision was taken)
+            fused = exc
+        return fused, capsys.readouterr().out
+
+    # locomotion env: without the key today's message on one line (it may name the key behind it), nothing built
+    fused, out = make({}, loco, gru64)
+    assert fused is None and not made and out.startswith("[runner] device LSTM cell unavailable (GRU memory (the device cell is an LSTM)); torch policy in the rollout")
+    assert "device_gru" in out and "--device_gru" in out and "wide_memory" not in out and out.count("\n") == 1
+    fused, out = make({"device_gru": True}, loco, gru64)
+    assert made and made[-1]["gru"] is True and made[-1]["wide"] is False and "unavailable" not in out
+    del made[:]
+    # the game env with device_rollout
+    fused, out = make({"device_rollout": True}, game, gru64)
+    assert fused is None and not made and out.startswith("[runner] device rollout unavailable (no device LSTM cell for a GRU memory (the device cell is an LSTM)); "
+                                                         "generic VecEnv loop")
+    assert "device_gru" in out and out.count("\n") == 1
+    fused, out = make({"device_rollout": True, "device_gru": True}, game, gru64)
+    assert made and made[-1]["gru"] is True and "unavailable" not in out
+    del made[:]
+    # 512 units: no hint without the key, its own reason with it; wide_memory does not cover a GRU
+    for env, cfg in ((loco, {}), (loco, {"wide_memory": True}), (game, {"device_rollout": True})):
+        fused, out = make(cfg, env, gru512)
+        assert fused is None and not made and "unavailable" in out and "GRU memory" in out and "device_gru" not in out and "wide_memory" not in out, out
+    for env, cfg in ((loco, {"device_gru": True}), (game, {"device_rollout": True, "device_gru": True}), (loco, {"device_gru": True, "wide_memory": True})):
+        fused, out = make(cfg, env, gru512)
+        assert fused is None and not made and "unavailable" in out and "512" in out and "up to 256" in out and out.count("\n") == 1, out
+    # an LSTM policy: the key changes nothing
+    fused, out = make({"device_gru": True}, loco, lstm64)
+    assert made and "gru" not in made[-1] and made[-1]["wide"] is False and "unavailable" not in out
+
+
+def _dec_cfg(units, kind="gru", **runner):
+    return {"runner": dict(policy_class_name="ActorCriticRecurrent", device_rollout=True, **runner),
+            "policy": dict(rnn_type=kind, rnn_hidden_size=units, rnn_num_layers=1), "algorithm": {}}
+
+
+def test_the_dec_runner_accepts_a_gru_with_the_key_only():
+    from legged_games_gym_amd.rl import DecGamePolicyRunner
+    r = DecGamePolicyRunner.__new__(DecGamePolicyRunner)
+
+    def check(units, kind="gru", **runner):
+        cfg = _dec_cfg(units, kind, **runner)
+        r.cfg = cfg["runner"]
+        return r._check_policy_class(cfg, "cuda:0")
+    today = ("ActorCriticRecurrent on dec_high_level_game: no device LSTM cell for a GRU memory (the device cell is an LSTM), and there is no generic loop "
+             "for two recurrent agents")
+    for units in (64, 256, 512):
+        for keys in ({}, {"wide_memory": True}):
+            with pytest.raises(ValueError) as e:
+                check(units, **keys)
+            assert str(e.value) == today                               # without the key: today's text, byte for byte
+    for units in (32, 64, 256):
+        assert check(units, device_gru=True) is True
+    for units in (288, 512):
+        for keys in ({}, {"wide_memory": True}):
+            with pytest.raises(ValueError, match=f"device_gru.*no device GRU cell.*{units}.*up to 256.*no generic loop"):
+                check(units, device_gru=True, **keys)
+    with pytest.raises(ValueError, match="device_gru.*opponent_pool_recurrent.*lg_lstm handles"):
+        check(64, device_gru=True, opponent_pool_size=2, opponent_pool_recurrent=True)
+    # LSTM policies: the key changes nothing
+    assert check(256, "lstm", device_gru=True) is True
+    assert check(256, "lstm", device_gru=True, opponent_pool_size=2, opponent_pool_recurrent=True) is True
+    with pytest.raises(ValueError, match="no device LSTM cell.*512.*up to 256.*wide_memory"):
+        check(512, "lstm", device_gru=True)
+
+
+def test_the_wrapper_takes_gru_handles_only_for_gru_memories(monkeypatch):
+    """``RecurrentFusedActor(gru=True)``: which handles it asks for, decided before any is made."""
+    from legged_games_gym_amd.rl import recurrent_actor
+    from legged_games_gym_amd.rl.actor_critic import ActorCriticRecurrent
+    asked = []
+    monkeypatch.setattr(recurrent_actor, "DeviceGru", lambda rnn, device: asked.append("gru") or types.SimpleNamespace(hidden=rnn.hidden_size, lib="gru-lib"))
+    monkeypatch.setattr(recurrent_actor, "DeviceLstmActor",
+                        lambda ac, device, seed=1, step_counter=None, wide=False: asked.append(("actor", wide)) or types.SimpleNamespace(lib=None))
+    ac = ActorCriticRecurrent(48, 48, 12, [32, 32, 32], [32, 32, 32], rnn_type="gru", rnn_hidden_size=64)
+    f = recurrent_actor.RecurrentFusedActor(ac, "cuda:0", gru=True, wide=True)
+    assert f.gru is True and f.wide is False and f.cell_lib == "gru-lib" and asked == ["gru", "gru", ("actor", False)]
+    with pytest.raises(ValueError, match="no device LSTM cell for a GRU memory"):      # without gru: today's refusal
+        recurrent_actor.RecurrentFusedActor(ac, "cuda:0")
+    assert recurrent_actor.RecurrentFusedActor.gru is False
+
+
+def test_the_flag_reaches_the_runner_cfg(monkeypatch):
+    from legged_games_gym_amd.utils import get_args
+    assert get_args(["--task", "anymal_c_flat"]).device_gru is False
+    assert get_args(["--task", "anymal_c_flat", "--device_gru"]).device_gru is True
+    # the scripts set the runner key from the flag next to wide_memory
+    scripts = os.path.join(REPO, "legged_games_gym_amd", "scripts")
+    for name in ("train.py", "train_dec_game.py", "play_dec_game.py"):
+        text = open(os.path.join(scripts, name)).read()
+        assert re.search(r"runner\.device_gru = True", text), name
+    assert 'gru=getattr(args, "device_gru", False)' in open(os.path.join(scripts, "play_game.py")).read()
+    # train.py's way, on the registered cfg: the key reaches what OnPolicyRunner reads
+    from legged_games_gym_amd.envs import task_registry
+    from legged_games_gym_amd.utils.helpers import class_to_dict
+    _, train_cfg = task_registry.get_cfgs("anymal_c_flat")
+    assert "device_gru" not in class_to_dict(train_cfg)["runner"]
+    monkeypatch.setattr(train_cfg.runner, "device_gru", True, raising=False)
+    assert class_to_dict(train_cfg)["runner"]["device_gru"] is True

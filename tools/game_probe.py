@@ -33,7 +33,8 @@ state slots), alternating in one process:
   (f) the feed-forward three-launch step of the same env: lg_game_act, k_step, k_game_post;
 then, unless ``--train-iterations 0``, PPO training with ``ActorCriticRecurrent`` and the runner's ``device_rollout`` on and off: env-steps/s
 including the update, and the rollout's and the update's share of an iteration from synchronised stamps around every update.  With ``--trace``
-it replays (r) only.
+it replays (r) only.  With ``--gru`` a fourth variant joins the alternation, (g) the four-launch step with GRU memories (the key ``device_gru``):
+lg_gru_step, lg_game_lstm_act, k_step, k_game_post; no training then, and the file is profiles/game_recurrent_gru_step.json.
 
 The low-level policy is a seeded random-init checkpoint written to a temporary directory: the kernels' cost does not depend on the weights."""
 import argparse
@@ -280,17 +281,31 @@ def recurrent_main(args):
             finally:
                 del env._recurrent_launch
             three = env.make_graphed_policy_step(fused_high_level_actor(env), steps_per_replay=2)
-            for fn in (four, six, three):
+            gru_four = None
+            if args.gru:                               # the same step with GRU memories: lg_gru_step -> lg_game_lstm_act -> k_step -> post
+                torch.manual_seed(1)
+                gru_ac = ActorCriticRecurrent(env.num_obs, env.num_obs, env.num_actions, actor_hidden_dims=[512, 256, 128], critic_hidden_dims=[512, 256, 128],
+                                              rnn_type="gru", rnn_hidden_size=args.rnn_hidden).to("cuda:0").eval()
+                gru_actor = RecurrentFusedActor(gru_ac, "cuda:0", seed=7, step_counter=counter, num_envs=n, gru=True)
+                assert env.shared_actor_launch(gru_actor), "lg_game_lstm_act refused the probe's actor pair behind a GRU memory"
+                gru_four = env.make_graphed_policy_step(gru_actor, steps_per_replay=2)
+            for fn in (four, six, three) + ((gru_four,) if gru_four else ()):
                 timed(fn, 100)
-            r, s, f = [], [], []
+            r, s, f, g = [], [], [], []
             for _ in range(args.repeats):              # alternating: other work shares the machine
                 r.append(timed(four, args.replays // 2) / 2)
                 s.append(timed(six, args.replays // 2) / 2)
                 f.append(timed(three, args.replays // 2) / 2)
+                if gru_four:
+                    g.append(timed(gru_four, args.replays // 2) / 2)
             gain = [y - x for x, y in zip(r, s)]
             result["envs"][str(n)] = {"recurrent_four_launch_step": spread(r), "recurrent_separate_policy_launches": spread(s),
                                       "feed_forward_three_launch_step": spread(f), "separate_minus_one_launch": spread(gain),
                                       "env_steps_per_s_recurrent_four_launch_step": n / (statistics.median(r) * 1e-6)}
+            if gru_four:
+                result["envs"][str(n)]["gru_four_launch_step"] = spread(g)
+                result["envs"][str(n)]["gru_minus_lstm_four_launch_step"] = spread([y - x for x, y in zip(r, g)])
+                print(f"{n} envs, per step: GRU four launches {statistics.median(g):.1f} us ({min(g):.1f} .. {max(g):.1f})", flush=True)
             assert torch.isfinite(env.obs_buf).all() and torch.isfinite(env.ll_env.root_states).all()
             assert all(bool(torch.isfinite(t).all()) for pair in one.hidden_states() for t in pair)
             print(f"{n} envs, per step: four launches {statistics.median(r):.1f} us ({min(r):.1f} .. {max(r):.1f}), separate policy launches "
@@ -298,7 +313,7 @@ def recurrent_main(args):
                   f"{max(gain):+.2f}), feed-forward three launches {statistics.median(f):.1f} us ({min(f):.1f} .. {max(f):.1f})", flush=True)
         if args.trace:
             return
-        if args.train_iterations > 0:
+        if args.train_iterations > 0 and not args.gru:
             n = args.envs[0]
             for key, on in (("device_rollout_off", False), ("device_rollout_on", True)):
                 t = train_steps_per_s(n, args.mesh, tmp, on, args.train_iterations, rnn_hidden=args.rnn_hidden)
@@ -306,7 +321,7 @@ def recurrent_main(args):
                 print(f"training, recurrent policy, {n} envs, {key}: {t['env_steps_per_s']:.0f} env-steps/s; per iteration: rollout of 24 steps "
                       f"{t['rollout_ms']['median']:.2f} ms ({t['rollout_ms']['min']:.2f} .. {t['rollout_ms']['max']:.2f}), update "
                       f"{t['update_ms']['median']:.1f} ms ({t['update_ms']['min']:.1f} .. {t['update_ms']['max']:.1f})", flush=True)
-    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "game_recurrent_step.json")
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "game_recurrent_gru_step.json" if args.gru else "game_recurrent_step.json")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(result, fh, indent=1)
@@ -417,6 +432,8 @@ def main():
     ap.add_argument("--outcome", action="store_true", help="time the graphed policy step of both tasks with the outcome statistics off and on; writes profiles/game_outcome_step.json")
     ap.add_argument("--recurrent", action="store_true", help="time the recurrent policy's graphed step against separate policy launches and the feed-forward step; writes profiles/game_recurrent_step.json")
     ap.add_argument("--rnn-hidden", type=int, default=256, help="--recurrent: units per memory")
+    ap.add_argument("--gru", action="store_true", help="--recurrent: also time the four-launch step with GRU memories (the key device_gru) in the same alternation, "
+                    "no training; writes profiles/game_recurrent_gru_step.json")
     ap.add_argument("--trace", action="store_true", help="a short loop of graph replays only (for a kernel trace)")
     args = ap.parse_args()
     if not torch.cuda.is_available():

@@ -20,7 +20,11 @@ The kernel's own time, independent of the event timing above, comes from a profi
 
 ``--wide`` measures the wide library instead (include/legged_recurrent_wide.h, the runner key ``wide_memory``) -> profiles/recurrent_wide_step.json:
 the same three variants at 512 units (``lg_lstm_wide_step`` + ``lg_lstm_wide_actor_act`` against torch, the cell against its FLOP count), and at
-256 units ``lg_lstm_wide_step`` against ``lg_lstm_step`` on the same memories, all in one process."""
+256 units ``lg_lstm_wide_step`` against ``lg_lstm_step`` on the same memories, all in one process.
+
+``--gru`` measures the GRU library instead (include/legged_recurrent_gru.h, the runner key ``device_gru``) -> profiles/recurrent_gru_step.json:
+the three variants with ``rnn_type='gru'`` (``lg_gru_step`` + ``lg_lstm_actor_act`` against torch, the cell against its 3/4 FLOP count) and,
+in the same alternation, ``lstm``: the device stage of the LSTM policy of the same width."""
 import argparse
 import json
 import os
@@ -76,19 +80,28 @@ def alternate(variants, stages, replays, pairs, discard):
             for k, v in times.items()}
 
 
-def measure(n, hidden, args, wide=False):
+def measure(n, hidden, args, wide=False, gru=False):
     from legged_games_gym_amd.rl import ActorCriticRecurrent
-    from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor, lstm_step
+    from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor, gru_step, lstm_step
     torch.manual_seed(1)
-    ac = ActorCriticRecurrent(48, 48, 12, actor_hidden_dims=[128, 64, 32], critic_hidden_dims=[128, 64, 32], rnn_hidden_size=hidden).to(DEV)
-    rfa = RecurrentFusedActor(ac, DEV, seed=3, num_envs=n, wide=wide)
+    ac = ActorCriticRecurrent(48, 48, 12, actor_hidden_dims=[128, 64, 32], critic_hidden_dims=[128, 64, 32], rnn_hidden_size=hidden,
+                              rnn_type="gru" if gru else "lstm").to(DEV)
+    rfa = RecurrentFusedActor(ac, DEV, seed=3, num_envs=n, wide=wide, gru=gru)
     obs = torch.rand(n, 48, device=DEV) * 6.0 - 3.0
     reset = (torch.rand(n, device=DEV) < 0.02)
 
     def device():
         rfa.act_with_mean(obs, obs, reset=reset)
 
+    def gru_cell():
+        f = rfa._flip
+        gru_step(rfa.cell_lib, rfa.lstm_a, rfa.lstm_c, obs, obs, reset, rfa.state_a[f][0], rfa.state_a[1 - f][0], rfa.state_c[f][0], rfa.state_c[1 - f][0], n,
+                 torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
+        rfa._flip = 1 - f
+
     def cell():
+        if gru:
+            return gru_cell()
         f = rfa._flip
         lstm_step(rfa.cell_lib, rfa.lstm_a, rfa.lstm_c, obs, obs, reset, rfa.state_a[f], rfa.state_a[1 - f], rfa.state_c[f], rfa.state_c[1 - f], n,
                   torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
@@ -97,23 +110,29 @@ def measure(n, hidden, args, wide=False):
     # the torch memories' state in buffers that outlive every capture: Memory.forward leaves its state in a new tensor per step, and a graph
     # that read the warm-up's tensor would read freed memory once the allocator has released it (the next capture empties the cache)
     with torch.inference_mode():
-        held = {m: tuple(torch.zeros(1, n, hidden, device=DEV) for _ in range(2)) for m in (ac.memory_a, ac.memory_c)}
+        held = {m: tuple(torch.zeros(1, n, hidden, device=DEV) for _ in range(1 if gru else 2)) for m in (ac.memory_a, ac.memory_c)}
 
     def torch_stage():
         with torch.inference_mode():
             for m, buf in held.items():
-                m.hidden_states = buf
+                m.hidden_states = buf[0] if gru else buf
             ac.act(obs)
             ac.evaluate(obs)
             ac.reset(reset)
             for m, buf in held.items():                       # (four small copies the generic loop does not make)
-                for dst, src in zip(buf, m.hidden_states):
+                for dst, src in zip(buf, (m.hidden_states,) if gru else m.hidden_states):
                     dst.copy_(src)
 
     variants = {"device": (capture(device, args.graph_steps), device), "torch": (capture(torch_stage, args.graph_steps), torch_stage),
                 "cell": (capture(cell, args.graph_steps), cell)}
+    if gru:
+        torch.manual_seed(1)
+        lstm_ac = ActorCriticRecurrent(48, 48, 12, actor_hidden_dims=[128, 64, 32], critic_hidden_dims=[128, 64, 32], rnn_hidden_size=hidden).to(DEV)
+        lstm_rfa = RecurrentFusedActor(lstm_ac, DEV, seed=3, num_envs=n)
+        lstm = lambda: lstm_rfa.act_with_mean(obs, obs, reset=reset)
+        variants["lstm"] = (capture(lstm, args.graph_steps), lstm)
     r = alternate(variants, args.graph_steps, args.replays, args.pairs, args.discard)
-    flop = 2 * 2.0 * n * (48 + hidden) * 4 * hidden
+    flop = 2 * 2.0 * n * (48 + hidden) * (3 if gru else 4) * hidden
     r["cell"]["flop"] = flop
     r["cell"]["share_of_f32_mfma_peak"] = flop / (r["cell"]["median_us"] * 1e-6) / PEAK_F32_MFMA
     return r
@@ -187,12 +206,15 @@ def main():
     ap.add_argument("--cell-only", action="store_true", help="launch the cell 200 times and exit (for a rocprofv3 kernel trace)")
     ap.add_argument("--train-iterations", type=int, default=3)
     ap.add_argument("--wide", action="store_true", help="measure liblegged_lstm_wide.so: 512 units, and the wide cell against lg_lstm_step at 256")
+    ap.add_argument("--gru", action="store_true", help="measure liblegged_gru.so: GRU memories against torch and against the LSTM policy's device stage")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(REPO, "profiles", "recurrent_wide_step.json" if args.wide else "recurrent_step.json")
+        args.out = os.path.join(REPO, "profiles", "recurrent_wide_step.json" if args.wide else "recurrent_gru_step.json" if args.gru else "recurrent_step.json")
     if args.wide:
         args.hidden, args.train = [512], False
+    if args.gru:
+        args.train = False
     if args.cell_only:
         return cell_only(4096, 256, 200)
     prime = torch.cuda.CUDAGraph()                      # the generator's graph-safe state, created outside inference_mode (rl/ppo.py)
@@ -201,7 +223,7 @@ def main():
     out = {"device_name": torch.cuda.get_device_name(0), "graph_steps": args.graph_steps, "replays": args.replays, "pairs": args.pairs, "stage": {}}
     for n in args.envs:
         for h in args.hidden:
-            r = measure(n, h, args, wide=args.wide)
+            r = measure(n, h, args, wide=args.wide, gru=args.gru)
             out["stage"][f"{n}x{h}"] = r
             print(f"{n} envs, {h} units: " + "; ".join(f"{k} {v['median_us']:.1f} us [{v['min_us']:.1f} .. {v['max_us']:.1f}]" for k, v in r.items())
                   + f"; cell at {100 * r['cell']['share_of_f32_mfma_peak']:.1f} % of the f32-MFMA peak", flush=True)
