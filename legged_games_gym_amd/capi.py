@@ -1125,6 +1125,82 @@ def load_gru_library():
     return _gru_lib
 
 
+# ----------------------------------------------------------------------------------------------------------------- legged_dec_game_gru.h
+# The shared cell launch of GRU policies on dec_high_level_game, a ninth library (csrc/liblegged_dec_game_gru.so): outside ABI / ALL_SYMBOLS
+# / bind_all.  It reads the lg_gru handles liblegged_gru.so created.
+class lg_gru_handle(C.Structure):
+    """csrc/lg_gru.h: struct lg_gru (opaque to callers; here for the size check of ``bind_dec_game_gru``)."""
+    _fields_ = [("num_in", i32), ("hidden", i32), ("ksteps", i32), ("device", i32), ("d_wp", C.c_void_p), ("d_bp", C.c_void_p)]
+
+
+class lg_dec_gru_role(C.Structure):
+    """include/legged_dec_game_gru.h: lg_dec_gru_role (one memory of the cell launch: handle or None, device addresses)."""
+    _fields_ = [("l", C.c_void_p), ("x", C.c_void_p), ("h_in", C.c_void_p), ("h_out", C.c_void_p)]
+
+
+DEC_GAME_GRU_ABI = {
+    "lg_dec_gru_step": ([_P(lg_dec_gru_role), _vp, i32, _vp], _int),
+    "lg_dec_game_gru_last_error": ([], C.c_char_p),
+    "lg_dec_game_gru_sizeof": _SIZEOF,
+}
+DEC_GAME_GRU_SYMBOLS = list(DEC_GAME_GRU_ABI)
+DEC_GAME_GRU_STRUCTS = {0: lg_gru_handle, 1: lg_dec_gru_role}      # what lg_dec_game_gru_sizeof sizes by index
+_DEC_GAME_GRU_LIB_NAME = "liblegged_dec_game_gru.so"
+_dec_game_gru_lib = None
+
+
+def dec_game_gru_library_path() -> str:
+    """In-tree liblegged_dec_game_gru.so; LG_DEC_GAME_GRU_LIB selects another build of the same source."""
+    return os.environ.get("LG_DEC_GAME_GRU_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_GAME_GRU_LIB_NAME)
+
+
+def bind_dec_game_gru(lib):
+    for symbol, (argtypes, restype) in DEC_GAME_GRU_ABI.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    for which, st in DEC_GAME_GRU_STRUCTS.items():
+        size = lib.lg_dec_game_gru_sizeof(which)
+        if size != C.sizeof(st):
+            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def load_dec_game_gru_library():
+    """Load the shared GRU cell launch of dec_high_level_game or fail loudly -- never a CPU substitute."""
+    global _dec_game_gru_lib
+    if _dec_game_gru_lib is not None:
+        return _dec_game_gru_lib
+    path = dec_game_gru_library_path()
+    if not os.path.isfile(path):
+        raise RuntimeError(
+            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    _dec_game_gru_lib = bind_dec_game_gru(C.CDLL(path))
+    return _dec_game_gru_lib
+
+
+def dec_gru_roles(roles) -> "C.Array":
+    """``lg_dec_gru_role[4]`` from four entries in the order of ``DEC_LSTM_ROLES``: None (absent), or ``(handle, x, h_in, h_out)`` with
+    device addresses."""
+    if len(roles) != 4:
+        raise ValueError("lg_dec_gru_step takes four roles (None = absent)")
+    arr = (lg_dec_gru_role * 4)()
+    for slot, role in zip(arr, roles):
+        if role is not None:
+            slot.l, slot.x, slot.h_in, slot.h_out = (getattr(v, "value", v) for v in role)
+    return arr
+
+
+def dec_gru_step(roles, reset: Optional[int], num_envs: int, stream: int = 0) -> None:
+    """``lg_dec_gru_step``: up to four GRU memories advanced in one launch.  ``roles``: what ``dec_gru_roles`` takes, or its result (kept by
+    a caller that replays the same launch)."""
+    lib = load_dec_game_gru_library()
+    arr = roles if isinstance(roles, C.Array) else dec_gru_roles(roles)
+    rc = lib.lg_dec_gru_step(arr, reset, int(num_envs), stream)
+    if rc != 0:
+        raise RuntimeError(f"lg_dec_gru_step failed ({rc}): {lib.lg_dec_game_gru_last_error().decode()}")
+
+
 class Sim:
     """Owner of one ``lg_sim`` handle (one per GPU).  ``lib``/``prefix`` are
     parameters only so the tests can drive the CPU oracle through the same class."""

@@ -13,12 +13,8 @@
 #include "lg_recurrent.h"          // LG_LSTM_LD: the staged block and the lane maps
 #include "lg_lstm_cell_body.h"     // lstm_sigmoid, lstm_tanh
 #include "lg_gru_cell_body.h"
+#include "lg_gru.h"                // struct lg_gru
 #include "../../include/legged_recurrent_gru.h"
-
-struct lg_gru {
-    int32_t num_in, hidden, ksteps, device;
-    float  *d_wp, *d_bp;
-};
 
 namespace lg {
 

@@ -16,7 +16,9 @@ positions, four visibility flags) to its command ``(lin_vel_x, lin_vel_y, ang_ve
 
 With recurrent policies (two ``rl.RecurrentFusedActor``) it is four, ``lg_dec_lstm_step`` (the actor memories of both agents and the critic
 memories the caller asks for, one launch) and ``lg_dec_game_lstm_act`` (include/legged_dec_game_recurrent.h: the three actors on the actor
-memories' outputs, with the clips) taking ``lg_dec_game_act``'s place.
+memories' outputs, with the clips) taking ``lg_dec_game_act``'s place.  Two GRU policies (``RecurrentFusedActor(gru=True)``) take six separate
+launches for the policy stage; with ``shared_gru=True`` on both (the runner key ``dec_gru_shared``) the cell launch is ``lg_dec_gru_step``
+(include/legged_dec_game_gru.h) and the actor launch the same ``lg_dec_game_lstm_act``, which reads only ``h``.
 
 Outcome statistics (off by default; ``env.outcome_stats = True`` on the config object or ``enable_outcome_stats()``): the last launch of
 every step path becomes ``lg_dec_outcome_post`` (include/legged_dec_game_outcome.h), which writes what ``lg_dec_game_post`` writes, bit for
@@ -341,14 +343,49 @@ class DecHighLevelGame(GameBase):
     def _recurrent_launches(self, fused_pred, fused_prey, say=True, pooled=False):
         """``_recurrent_library`` for a pair of actors.  An actor with ``wide`` memories (``RecurrentFusedActor(wide=True)`` above 256 units) holds
         handles of liblegged_lstm_wide.so, which none of the shared launches reads: separate launches throughout, said once.  Likewise an
-        actor with ``gru`` memories (``RecurrentFusedActor(gru=True)``, handles of liblegged_gru.so): ``lg_dec_lstm_step`` reads ``lg_lstm`` handles."""
+        actor with ``gru`` memories (``RecurrentFusedActor(gru=True)``, handles of liblegged_gru.so): ``lg_dec_lstm_step`` reads ``lg_lstm`` handles.
+        Two ``gru`` actors that are both ``shared_gru`` (the runner key ``dec_gru_shared``) take ``_gru_shared_launches`` instead."""
         if getattr(fused_pred, "wide", False) or getattr(fused_prey, "wide", False):
             self._say_separate("wide memory", say, pooled)
             return None, False
+        if self._gru_shared_pair(fused_pred, fused_prey) and not pooled:
+            return self._gru_shared_launches(fused_pred, say=say)
         if getattr(fused_pred, "gru", False) or getattr(fused_prey, "gru", False):
             self._say_separate("GRU memory", say, pooled)
             return None, False
         return self._recurrent_library(fused_pred, say=say, pooled=pooled)
+
+    @staticmethod
+    def _gru_shared_pair(fused_pred, fused_prey):
+        """Whether both actors hold GRU memories and both ask for the shared launches (``RecurrentFusedActor(gru=True, shared_gru=True)``)."""
+        return all(getattr(f, "gru", False) and getattr(f, "shared_gru", False) for f in (fused_pred, fused_prey))
+
+    def _gru_log_prob_outputs(self, agent, out, fused):
+        """The optional outputs handed to ``lg_dec_game_lstm_act`` for a GRU pair on the shared launches: ``out`` itself when no log-prob is
+        asked for; otherwise ``out`` without its log-prob and with a sample tensor (the caller's, or one kept per agent so that a captured
+        graph finds it at the same address), from which ``_act_recurrent`` then fills the log-prob the way the separate launches do.  The
+        key ``dec_gru_shared`` so changes which launches run and not one bit of what a rollout stores."""
+        if out.get("log_prob") is None:
+            return out
+        sample = out.get("sample")
+        if sample is None:
+            kept = self.__dict__.setdefault("_gru_samples", {})
+            if agent not in kept or kept[agent].shape != (self.num_envs, fused.num_actions):
+                kept[agent] = torch.empty(self.num_envs, fused.num_actions, device=self.device)
+            sample = kept[agent]
+        return dict(out, sample=sample, log_prob=None)
+
+    def _gru_shared_launches(self, fused, say=True):
+        """``_recurrent_library`` for a GRU pair on the shared launches: ``(liblegged_dec_game_gru.so or None, whether lg_dec_game_lstm_act can
+        be used now)``.  The cell launch ``lg_dec_gru_step`` needs only the first; the actor MLP behind a GRU memory is an ``lg_lstm_actor`` on
+        ``h``, so the actor launch is the LSTM pair's, under its conditions.  Without the GRU library everything takes the separate launches
+        (a one-line message that names it); without liblegged_dec_game_recurrent.so or at wide precision 0 only the actors do."""
+        try:
+            lib = capi.load_dec_game_gru_library()
+        except (RuntimeError, OSError) as exc:
+            self._say_separate(f"{type(exc).__name__}: {exc}", say)
+            return None, False
+        return lib, self._recurrent_library(fused, say=say)[1]
 
     def _say_separate(self, why, say=True, pooled=False):
         said = self.__dict__.setdefault("_separate_said", set())
@@ -367,6 +404,7 @@ class DecHighLevelGame(GameBase):
         ``lg_dec_game_lstm_act`` on the two new ``h``.  The critic memories' outputs are left in ``self._critic_out`` (agent -> tensor, None
         when it did not move).  Separate launches (``lg_lstm_actor_act`` x 2 + ``lg_dec_game_pre`` + low-level ``lg_policy_act``) on rc -4, at wide
         precision 0 or without the library (then ``lg_lstm_step`` per agent as well).
+        Two GRU actors with ``shared_gru``: the cell launch is ``lg_dec_gru_step`` on the 1-tuple slots ``(h,)``, everything after it the same.
         ``pool_pred`` / ``pool_prey``: an ``rl.RecurrentOpponentPool`` whose live actor that agent's ``fused_*`` is.  The two launches are then
         ``lg_dec_pool_lstm_step`` / ``lg_dec_pool_lstm_act`` (include/legged_dec_pool_recurrent.h), which take that role's weights per 32-env
         block from the pool member its slot table names; the state is the live actor's.  Their separate launches are one ``lg_lstm_step`` /
@@ -382,6 +420,7 @@ class DecHighLevelGame(GameBase):
         pooled = pool_pred is not None or pool_prey is not None
         slots = {a: (pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None) for a, pool in pools.items()}
         lib, shared = self._recurrent_launches(fused_pred, fused_prey, pooled=pooled)
+        gru = lib is not None and self._gru_shared_pair(fused_pred, fused_prey)      # the cell launch is lg_dec_gru_step: the slots hold (h,)
         h, self._critic_out = {}, {}
         if lib is not None:
             roles = []
@@ -393,10 +432,17 @@ class DecHighLevelGame(GameBase):
                     if present and x.shape[-1] != lstm.num_in:
                         raise ValueError(f"the {a} agent's memory reads {lstm.num_in} inputs, its input here has {x.shape[-1]} (a critic memory reads "
                                          "the privileged observations where they are on)")
-                    roles.append((lstm.handle, x.data_ptr(), state[f][0].data_ptr(), state[f][1].data_ptr(), state[1 - f][0].data_ptr(),
-                                  state[1 - f][1].data_ptr()) if present else None)
+                    if not present:
+                        roles.append(None)
+                    elif gru:
+                        roles.append((lstm.handle, x.data_ptr(), state[f][0].data_ptr(), state[1 - f][0].data_ptr()))
+                    else:
+                        roles.append((lstm.handle, x.data_ptr(), state[f][0].data_ptr(), state[f][1].data_ptr(), state[1 - f][0].data_ptr(),
+                                      state[1 - f][1].data_ptr()))
                 h[a], self._critic_out[a] = fused.state_a[1 - f][0], (fused.state_c[1 - f][0] if critics[a] else None)
-            if pooled:
+            if gru:
+                capi.dec_gru_step(roles, self.reset_buf.data_ptr(), n, stream)
+            elif pooled:
                 capi.dec_pool_lstm_step(roles, *slots["pred"], *slots["prey"], self.reset_buf.data_ptr(), n, stream)
             else:
                 capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
@@ -418,9 +464,13 @@ class DecHighLevelGame(GameBase):
         want_prey_copy = out_prey.get("obs_copy") is not None
         if shared:
             step, ctr = fused_prey.peek_step()
+            # a GRU pair on the shared launches stores the log-prob the separate launches store (torch's, below): the launch leaves the
+            # unclipped sample for it, in the caller's tensor or in a buffer kept here, and writes no log-prob of its own
+            k_pred, k_prey = (self._gru_log_prob_outputs(a, out, fused) for a, out, fused in (("pred", out_pred, fused_pred), ("prey", out_prey, fused_prey))) \
+                if gru else (out_pred, out_prey)
             tail = (self._P, B, h["pred"].data_ptr(), h["prey"].data_ptr(), obs_pred_in.data_ptr(), obs_prey_in.data_ptr(), ll.obs_buf.data_ptr(),
                     ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, deterministic_pred,
-                    deterministic_prey, outputs(out_pred, None), outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
+                    deterministic_prey, outputs(k_pred, None), outputs(k_prey, obs_prey_out.data_ptr() if carry else None), stream)
             if pooled:
                 rc = capi.dec_pool_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *slots["pred"], *slots["prey"], *tail)
             else:
@@ -430,6 +480,10 @@ class DecHighLevelGame(GameBase):
                 fused_pred.next_step(); fused_prey.next_step()     # the launch used this step of both noise streams
                 if carry and want_prey_copy:
                     obs_prey_out.copy_(obs_prey_in)
+                if gru:
+                    for out, launched, mean, fused in ((out_pred, k_pred, mean_pred, fused_pred), (out_prey, k_prey, mean_prey, fused_prey)):
+                        if out.get("log_prob") is not None:      # _fill_optional_outputs' expression on the same sample, mean and std: the same bits
+                            out["log_prob"].view(n).copy_(torch.distributions.Normal(mean, fused.ac.std.detach()).log_prob(launched["sample"].view(n, -1)).sum(-1))
                 return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
             self._say_separate("no kernel for this actor pair", pooled=pooled)
         else:
@@ -472,12 +526,16 @@ class DecHighLevelGame(GameBase):
         lib, shared = self._recurrent_launches(fused_pred, fused_prey, say=False, pooled=pooled)
         if lib is None:
             return False
+        gru = self._gru_shared_pair(fused_pred, fused_prey)      # lg_dec_gru_step warms up k_dec_gru_cell the same way: the slots hold (h,)
         roles, h = [], []
         for fused, obs in ((fused_pred, self.obs_buf_pred), (fused_prey, self.obs_buf_prey)):
             if fused.num_envs != n:
                 fused._allocate(n)
             f, st = fused._flip, fused.state_a
-            roles += [(fused.lstm_a.handle, obs.data_ptr(), st[f][0].data_ptr(), st[f][1].data_ptr(), st[1 - f][0].data_ptr(), st[1 - f][1].data_ptr()), None]
+            if gru:
+                roles += [(fused.lstm_a.handle, obs.data_ptr(), st[f][0].data_ptr(), st[1 - f][0].data_ptr()), None]
+            else:
+                roles += [(fused.lstm_a.handle, obs.data_ptr(), st[f][0].data_ptr(), st[f][1].data_ptr(), st[1 - f][0].data_ptr(), st[1 - f][1].data_ptr()), None]
             h.append(st[f][0])
         tail = (self._P, B, h[0].data_ptr(), h[1].data_ptr(), None, None, self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
                 mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream)
@@ -485,7 +543,10 @@ class DecHighLevelGame(GameBase):
             slots = [a for pool in (pool_pred, pool_prey) for a in ((pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None))]
             capi.dec_pool_lstm_step(roles, *slots, self.reset_buf.data_ptr(), n, stream)
             return shared and capi.dec_pool_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *slots, *tail) == 0
-        capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
+        if gru:
+            capi.dec_gru_step(roles, self.reset_buf.data_ptr(), n, stream)
+        else:
+            capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
         return shared and capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *tail) == 0
 
     def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None, with_critic_memory=(),

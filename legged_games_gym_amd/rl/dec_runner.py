@@ -153,7 +153,10 @@ class DecGamePolicyRunner:
             raise ValueError(f"rnn_type must be 'lstm' or 'gru', got {kind!r}")
         probe = (nn.GRU if kind == "gru" else nn.LSTM)(input_size=3, hidden_size=int(policy.get("rnn_hidden_size", 256)),
                                                        num_layers=int(policy.get("rnn_num_layers", 1)))      # (the predator's memory; both have these units)
-        if kind == "gru" and bool(self.cfg.get("device_gru", False)):          # opt-in: GRU memories on liblegged_gru.so, separate launches
+        if bool(self.cfg.get("dec_gru_shared", False)) and not (kind == "gru" and bool(self.cfg.get("device_gru", False))):
+            raise ValueError("dec_gru_shared without GRU memories on the device: the key puts two GRU policies on lg_dec_gru_step -> lg_dec_game_lstm_act "
+                             "and needs rnn_type 'gru' (--rnn_type gru) together with the runner key device_gru (--device_gru)")
+        if kind == "gru" and bool(self.cfg.get("device_gru", False)):          # opt-in: GRU memories on liblegged_gru.so (separate launches without dec_gru_shared)
             if pool_recurrent:
                 raise ValueError("device_gru with opponent_pool_recurrent: the pooled launches (lg_dec_pool_lstm_step / lg_dec_pool_lstm_act) read "
                                  "lg_lstm handles; a recurrent opponent pool of GRU policies does not exist")

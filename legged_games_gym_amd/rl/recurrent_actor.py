@@ -250,15 +250,19 @@ class RecurrentFusedActor:
     ``gru`` (the runner key ``device_gru``): both memories are ``nn.GRU``; the cell handles are ``DeviceGru`` of liblegged_gru.so, the actor is
     the main library's and the attribute ``gru`` is True.  A GRU has one state tensor per memory: the slots hold 1-tuples ``(h,)`` where an
     LSTM's hold ``(h, c)``, and every method does for the one tensor what it does for the two.  ``dec_high_level_game`` then issues the
-    separate launches, because its cell launch reads ``lg_lstm`` handles.  Without ``gru`` a GRU memory is refused as before."""
+    separate launches, because its cell launch reads ``lg_lstm`` handles.  Without ``gru`` a GRU memory is refused as before.
+
+    ``shared_gru`` (the runner key ``dec_gru_shared``, on top of ``gru``): the attribute ``shared_gru`` is True only when ``gru`` is; two such
+    actors take ``lg_dec_gru_step`` (liblegged_dec_game_gru.so) -> ``lg_dec_game_lstm_act`` on ``dec_high_level_game``.  Nothing else reads it."""
 
     def __init__(self, actor_critic, device, seed: int = 1, step_counter: torch.Tensor = None, num_envs: int = None, wide: bool = False,
-                 gru: bool = False):
+                 gru: bool = False, shared_gru: bool = False):
         if not getattr(actor_critic, "is_recurrent", False):
             raise ValueError("RecurrentFusedActor wraps an ActorCriticRecurrent")
         self.ac, self.device = actor_critic, torch.device(device)
         rnns = (actor_critic.memory_a.rnn, actor_critic.memory_c.rnn)
         self.gru = bool(gru) and all(isinstance(r, nn.GRU) for r in rnns)
+        self.shared_gru = self.gru and bool(shared_gru)
         self.wide = not self.gru and bool(wide) and any(getattr(r, "hidden_size", 0) > capi.LG_LSTM_MAX_HIDDEN for r in rnns)
         if self.gru:
             self.lstm_a, self.lstm_c = DeviceGru(rnns[0], device), DeviceGru(rnns[1], device)
@@ -279,6 +283,7 @@ class RecurrentFusedActor:
     # ... and what HighLevelGame._act reads: the actor MLP's handle, buffers and step count; the marker selects lg_game_lstm_act there
     recurrent = True
     gru = False                                                 # (the instance's, set by __init__: liblegged_gru.so handles, one state tensor per memory)
+    shared_gru = False                                          # (likewise: the GRU pair of dec_high_level_game on the shared launches)
     handle = property(lambda self: self.fused.handle)
 
     def output_buffers(self, n):

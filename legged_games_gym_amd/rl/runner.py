@@ -168,7 +168,8 @@ class OnPolicyRunner:
             try:
                 fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
                                             step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs, wide=wide,
-                                            **({"gru": True} if gru else {}))
+                                            **({"gru": True} if gru else {}),
+                                            **({"shared_gru": True} if gru and self.cfg.get("dec_gru_shared", False) else {}))
                 env.shared_actor_launch(fused)                # raises the new kernel's LDS limit here, outside any capture; False = separate launches
                                                               # (an agent view has no opponent yet: DecGamePolicyRunner makes the call)
             except Exception as exc:

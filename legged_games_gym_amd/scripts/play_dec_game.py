@@ -124,6 +124,8 @@ class DecEvaluation:
                 train_cfg.runner.wide_memory = True
             if getattr(args, "device_gru", False):       # GRU memories on the device, as the run was trained
                 train_cfg.runner.device_gru = True
+            if getattr(args, "dec_gru_shared", False):   # ... on the two shared launches (on top of device_gru)
+                train_cfg.runner.dec_gru_shared = True
         runner, train_cfg = task_registry.make_dec_alg_runner(env=env, name=args.task, args=args, train_cfg=train_cfg, log_root=None)
         log_root = os.path.join(registry_module.LEGGED_GYM_ROOT_DIR, "logs", train_cfg.runner.experiment_name)
         self.checkpoint = get_load_path(log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)

@@ -16,7 +16,8 @@ trains two LSTM policies (four launches per step: ``lg_dec_lstm_step`` -> ``lg_d
 why.  ``--wide_memory`` runs memories of 288 .. 512 units (the reference's ``rnn_hidden_size = 512``) on the kernels of liblegged_lstm_wide.so with
 separate launches per step; not together with ``--opponent_pool_recurrent``.  ``--rnn_type gru --device_gru`` trains two GRU policies
 (one layer, up to 256 units) on the cell of liblegged_gru.so, with separate launches per step as well; not together with
-``--opponent_pool_recurrent`` either.  ``--opponent_pool K --opponent_pool_recurrent`` gives two recurrent policies their pools (``rl.RecurrentOpponentPool``: the launches are
+``--opponent_pool_recurrent`` either; ``--dec_gru_shared`` on top of it takes the two shared launches (``lg_dec_gru_step`` of
+liblegged_dec_game_gru.so -> ``lg_dec_game_lstm_act``).  ``--opponent_pool K --opponent_pool_recurrent`` gives two recurrent policies their pools (``rl.RecurrentOpponentPool``: the launches are
 ``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_lstm_act``, the weights of a block's actor memory and actor MLP its pool member's).
 ``--privileged_critic {prey,pred,both}`` gives that agent an asymmetric critic: it reads the true relative position, the prey's heading and
 the episode clock (the predator's: the prey's velocity and whether the prey sees it), written by one more launch per step,
@@ -42,6 +43,8 @@ def train(args):
         task_registry.get_cfgs(args.task)[1].runner.wide_memory = True
     if args.device_gru:                      # a runner key as well: GRU memories (--rnn_type gru; separate launches, liblegged_gru.so)
         task_registry.get_cfgs(args.task)[1].runner.device_gru = True
+    if args.dec_gru_shared:                  # a runner key on top of device_gru: the GRU pair on the two shared launches (liblegged_dec_game_gru.so)
+        task_registry.get_cfgs(args.task)[1].runner.dec_gru_shared = True
     if args.opponent_pool:                   # runner keys, read with .get() as well
         runner_cfg = task_registry.get_cfgs(args.task)[1].runner
         runner_cfg.opponent_pool_size, runner_cfg.opponent_latest_share = args.opponent_pool, args.opponent_latest_share

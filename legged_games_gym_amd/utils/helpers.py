@@ -215,7 +215,13 @@ def get_args(argv=None):
                         "and actor kernels of liblegged_lstm_wide.so; the game tasks then issue separate launches); off, such a memory falls back or is refused")
     p.add_argument("--device_gru", action="store_true", default=False,
                    help="ActorCriticRecurrent with --rnn_type gru on the GPU: run the GRU memories (one layer, up to 256 units) on the device rollout (runner key "
-                        "of the same name: the cell kernel of liblegged_gru.so; dec_high_level_game then issues separate launches); off, a GRU falls back or is refused")
+                        "of the same name: the cell kernel of liblegged_gru.so; dec_high_level_game then issues separate launches unless --dec_gru_shared is given "
+                        "as well); off, a GRU falls back or is refused")
+    p.add_argument("--dec_gru_shared", action="store_true", default=False,
+                   help="dec_high_level_game with --rnn_type gru --device_gru: advance the GRU memories of both agents in one launch (runner key of the same "
+                        "name: lg_dec_gru_step of liblegged_dec_game_gru.so) and run the three actors in lg_dec_game_lstm_act, two launches per policy step "
+                        "where --device_gru alone takes six (a training rollout adds torch's log-prob of the learner's sample, so that it stores what it stores "
+                        "without the flag, bit for bit); without --device_gru or with an LSTM the runner refuses it")
     p.add_argument("--outcome_stats", action="store_true", default=False,
                    help="the game tasks (dec_high_level_game: scripts/train_dec_game.py): count inside the post-step launch why episodes end (captured, left the arena, fell, "
                         "survived) and log the rates as Episode/outcome_*; the scripts set env.outcome_stats on the registration they use")

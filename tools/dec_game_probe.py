@@ -407,16 +407,17 @@ def member_outcome_main(args):
     print("wrote", out)
 
 
-def recurrent_pair(env, units, wide=False, gru=False):
+def recurrent_pair(env, units, wide=False, gru=False, shared_gru=False):
     """Two ``RecurrentFusedActor`` s of the task's default actor widths on the env's device step counter (seeded random-init policies: the
-    time does not depend on the weights).  ``wide``: the handles of liblegged_lstm_wide.so where ``units`` is above 256.  ``gru``: GRU memories on the handles of liblegged_gru.so."""
+    time does not depend on the weights).  ``wide``: the handles of liblegged_lstm_wide.so where ``units`` is above 256.  ``gru``: GRU memories on the handles of liblegged_gru.so;
+    ``shared_gru``: such a pair on the shared launches (the key dec_gru_shared)."""
     from legged_games_gym_amd.rl import ActorCriticRecurrent
     from legged_games_gym_amd.rl.recurrent_actor import RecurrentFusedActor
     ctr = env.ll_env._sim.buf["step_counter"]
     torch.manual_seed(1)
     return [RecurrentFusedActor(ActorCriticRecurrent(no, no, na, actor_hidden_dims=HIDDEN, critic_hidden_dims=HIDDEN, rnn_hidden_size=units,
                                                      rnn_type="gru" if gru else "lstm").to(DEV), DEV,
-                                seed=seed, step_counter=ctr, num_envs=env.num_envs, wide=wide, gru=gru) for no, na, seed in ((3, 2, 1 + 7919 + 104729), (16, 4, 1 + 7919))]
+                                seed=seed, step_counter=ctr, num_envs=env.num_envs, wide=wide, gru=gru, shared_gru=shared_gru) for no, na, seed in ((3, 2, 1 + 7919 + 104729), (16, 4, 1 + 7919))]
 
 
 def separate_recurrent_step(env, pred, prey):
@@ -598,6 +599,52 @@ def gru_main(args):
     print("wrote", out)
 
 
+def gru_shared_main(args):
+    """``gru_main`` with a third variant in front: the GRU pair with the key ``dec_gru_shared`` on top of ``device_gru`` -- the two-launch policy
+    stage ``lg_dec_gru_step`` -> ``lg_dec_game_lstm_act`` -- against the six-launch policy stage of ``device_gru`` alone (the yardstick: that path
+    is the one ``gru_main`` times) and the four-launch step of two LSTM policies (context); same process, same sizes, alternating repeats;
+    microseconds per STEP."""
+    S = 2
+    names = ("gru_shared_step", "gru_separate_launch_step", "lstm_four_launch_step")
+    variants = ((True, True), (True, False), (False, False))         # (gru, shared_gru)
+    result = {"device": torch.cuda.get_device_name(0), "mesh_type": args.mesh, "replays": args.step_replays, "repeats": args.repeats,
+              "rnn_hidden_size": args.rnn_hidden_size, "steps_per_replay": S, "learner": "pred (its critic memory moves)", "unit": "us per policy step", "envs": {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in args.envs:
+            envs, steps, actors = [], [], []
+            for gru, shared_gru in variants:
+                env = make_env(n, args.mesh, tmp)
+                pred, prey = recurrent_pair(env, args.rnn_hidden_size, gru=gru, shared_gru=shared_gru)
+                actors.append((pred, prey))
+                shared = env.shared_actor_launch(pred, prey)
+                if shared is not (shared_gru or not gru):            # only the GRU pair without the key takes the separate launches
+                    raise RuntimeError(f"shared_actor_launch returned {shared} for gru={gru}, shared_gru={shared_gru}")
+                steps.append(env.make_graphed_policy_step(pred, prey, steps_per_replay=S, with_critic_memory=("pred",)))
+                assert env.last_act_rc == (0 if shared else -4)
+                envs.append(env)
+            for fn in steps:
+                timed(fn, args.step_replays // (4 * S))          # warm every graph before the first timed window
+            t = [[] for _ in steps]
+            for _ in range(args.repeats):
+                for i, fn in enumerate(steps):
+                    t[i].append(timed(fn, args.step_replays // S) / S)
+            row = {name: spread(x) for name, x in zip(names, t)}
+            row["shared_minus_separate"] = spread([x - y for x, y in zip(t[0], t[1])])
+            row["shared_minus_lstm"] = spread([x - y for x, y in zip(t[0], t[2])])
+            for env in envs:
+                assert torch.isfinite(env.obs_buf_prey).all() and torch.isfinite(env.ll_env.root_states).all() and torch.isfinite(env.predator_pos).all()
+            result["envs"][str(n)] = row
+            print(f"{n} envs, per step of a two-step graph: " + "; ".join(f"{name} {statistics.median(x):.1f} us ({min(x):.1f} .. {max(x):.1f})" for name, x in zip(names, t)),
+                  flush=True)
+            torch.cuda.synchronize()
+            del steps, envs, actors
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "dec_recurrent_gru_shared_step.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh, indent=1)
+    print("wrote", out)
+
+
 def recurrent_pool_main(args):
     """Two-step graphs of the four-launch recurrent policy step: the plain launches (``lg_dec_lstm_step`` -> ``lg_dec_game_lstm_act``) against the
     pooled launches (``lg_dec_pool_lstm_step`` -> ``lg_dec_pool_lstm_act``) with --members members on the prey role, the blocks dealt round-robin;
@@ -675,6 +722,8 @@ def main():
                     "of liblegged_lstm_wide.so) against the four-launch step at 256 units; writes profiles/dec_recurrent_wide_step.json")
     ap.add_argument("--gru", action="store_true", help="time the graphed policy step with two GRU policies (the key device_gru: separate launches, "
                     "liblegged_gru.so) against the four-launch step of two LSTM policies at --rnn-hidden-size units; writes profiles/dec_recurrent_gru_step.json")
+    ap.add_argument("--gru-shared", action="store_true", help="--gru with the GRU pair on the shared launches as well (the key dec_gru_shared: lg_dec_gru_step -> "
+                    "lg_dec_game_lstm_act), the three variants alternating in one process; writes profiles/dec_recurrent_gru_shared_step.json")
     ap.add_argument("--wide-hidden-size", type=int, default=512, help="--wide: units of every memory of the wide pair")
     ap.add_argument("--trace", action="store_true", help="--recurrent: replay the four-launch graph only and write nothing (for a rocprofv3 kernel table)")
     ap.add_argument("--recurrent-pool", action="store_true", help="time the four-launch recurrent policy step with the plain launches against the pooled launches "
@@ -686,6 +735,8 @@ def main():
         return privileged_main(args)
     if args.wide:
         return wide_main(args)
+    if args.gru_shared:
+        return gru_shared_main(args)
     if args.gru:
         return gru_main(args)
     if args.recurrent_pool:
