@@ -15,6 +15,7 @@ not been built (``python -c "import __graft_entry__ as g; g.build()"``).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Dict, Optional
 
@@ -231,29 +232,81 @@ def struct_to_dict(s) -> Dict:
 
 
 # ----------------------------------------------------------------------------- library
-_LIB_NAME = "liblegged_hip.so"
-_lib = None
+class Library:
+    """One shared library of csrc/: its file, the environment variable that selects another build of the same sources, its entry points
+    (name -> (argtypes, restype)), the module attribute that caches the loaded handle (``handle`` reads and writes it), optionally the
+    ``sizeof`` entry point and the structs it sizes by index, and what loading it gives.  ``bind_hook`` / ``check`` replace the plain
+    binding / follow it (the main library's per-header tables and ABI version)."""
+
+    def __init__(self, file, env, abi, cache, sizeof=None, what="", bind_hook=None, check=None):
+        self.file, self.env, self.abi, self.sizeof, self.what, self.bind_hook, self.check = file, env, abi, sizeof, what, bind_hook, check
+        self.cache = cache                 # the module attribute that holds the loaded handle (``_gru_lib`` ...): callers that reset it still do
+        globals()[cache] = None
+
+    @property
+    def handle(self):
+        return globals()[self.cache]
+
+    @handle.setter
+    def handle(self, lib):
+        globals()[self.cache] = lib
+
+
+LIBRARIES: Dict[str, Library] = {}       # "main" and the eight side libraries, each registered where its ABI is declared
+
+
+def path(name: str) -> str:
+    """The library's in-tree file, or what its environment variable names (another build of the same sources)."""
+    rec = LIBRARIES[name]
+    return os.environ.get(rec.env) or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", rec.file)
+
+
+def bind(name: str, lib):
+    """Attach argtypes/restype for the library's entry points and check the layouts of the structs its ``sizeof`` sizes."""
+    rec = LIBRARIES[name]
+    if rec.bind_hook is not None:
+        return rec.bind_hook(lib)
+    for symbol, (argtypes, restype) in rec.abi.items():
+        fn = getattr(lib, symbol)
+        fn.argtypes, fn.restype = argtypes, restype
+    if rec.sizeof is not None:
+        sizeof, structs = rec.sizeof
+        for which, st in structs.items():
+            size = getattr(lib, sizeof)(which)
+            if size != C.sizeof(st):
+                raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
+    return lib
+
+
+def load(name: str, file: Optional[str] = None):
+    """Load the library (from ``file``, default ``path(name)``) or fail loudly -- never a CPU substitute."""
+    rec = LIBRARIES[name]
+    if rec.handle is not None:
+        return rec.handle
+    file = file or path(name)
+    if not os.path.isfile(file):
+        raise RuntimeError(
+            f"HIP extension {file} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
+    rec.handle = bind(name, C.CDLL(file))
+    if rec.check is not None:
+        rec.check(rec.handle)
+    return rec.handle
+
+
+def _library_names(name: str):
+    """The three public names of a library: ``*_library_path()``, ``bind_*(lib)``, ``load_*_library()``."""
+    return functools.partial(path, name), functools.partial(bind, name), functools.partial(load, name)
 
 
 def library_path() -> str:
     """In-tree liblegged_hip.so; LG_HIP_LIB selects another build of the same sources (tools/profile_sections.py)."""
-    return os.environ.get("LG_HIP_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _LIB_NAME)
+    return path("main")
 
 
 def load_library():
-    """Load the HIP extension or fail loudly -- never a CPU substitute."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    path = library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lib = bind_all(C.CDLL(path))
-    if _lib.lg_abi_version() != LG_ABI_VERSION:
-        raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
-    return _lib
+    """Load the HIP extension (from ``library_path()``) or fail loudly -- never a CPU substitute."""
+    return load("main", library_path())
 
 
 def _call(name, *args, ok=(0,)):
@@ -659,6 +712,15 @@ def bind_all(lib):
     return lib
 
 
+def _check_abi_version(lib):
+    if lib.lg_abi_version() != LG_ABI_VERSION:
+        raise RuntimeError("liblegged_hip.so ABI version mismatch; rebuild")
+
+
+LIBRARIES["main"] = Library("liblegged_hip.so", "LG_HIP_LIB", {symbol: sig for functions, _, _ in ABI.values() for symbol, sig in functions.items()},
+                            "_lib", what="the HIP extension", bind_hook=bind_all, check=_check_abi_version)
+
+
 # ---------------------------------------------------------------------------------------------------------------- legged_lstm_sequence.h
 # A library of its own (csrc/liblegged_lstm_seq.so, built by a second hipcc command): outside ABI / ALL_SYMBOLS / bind_all, which
 # describe liblegged_hip.so.
@@ -673,39 +735,13 @@ LSTM_SEQ_ABI = {
     "lg_lstm_seq_last_error": ([], C.c_char_p),
 }
 LSTM_SEQ_SYMBOLS = list(LSTM_SEQ_ABI)
-_LSTM_SEQ_LIB_NAME = "liblegged_lstm_seq.so"
-_lstm_seq_lib = None
+LIBRARIES["lstm_seq"] = Library("liblegged_lstm_seq.so", "LG_LSTM_SEQ_LIB", LSTM_SEQ_ABI, "_lstm_seq_lib", what="the LSTM sequence kernels")
+lstm_seq_library_path, bind_lstm_seq, load_lstm_seq_library = _library_names("lstm_seq")
 
 
 def lstm_seq_supported(num_in: int, hidden: int) -> bool:
     """The shapes ``lg_lstm_seq_create`` takes (the rollout cell's)."""
     return 1 <= num_in <= LG_LSTM_SEQ_MAX_IN and 32 <= hidden <= LG_LSTM_SEQ_MAX_HIDDEN and hidden % 32 == 0
-
-
-def lstm_seq_library_path() -> str:
-    """In-tree liblegged_lstm_seq.so; LG_LSTM_SEQ_LIB selects another build of the same source."""
-    return os.environ.get("LG_LSTM_SEQ_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _LSTM_SEQ_LIB_NAME)
-
-
-def bind_lstm_seq(lib):
-    for symbol, (argtypes, restype) in LSTM_SEQ_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
-
-
-def load_lstm_seq_library():
-    """Load the LSTM sequence kernels or fail loudly -- never a CPU substitute."""
-    global _lstm_seq_lib
-    if _lstm_seq_lib is not None:
-        return _lstm_seq_lib
-    path = lstm_seq_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lstm_seq_lib = bind_lstm_seq(C.CDLL(path))
-    return _lstm_seq_lib
 
 
 # ---------------------------------------------------------------------------------------------------------------- legged_game_recurrent.h
@@ -718,38 +754,8 @@ GAME_RECURRENT_ABI = {
 }
 GAME_RECURRENT_SYMBOLS = list(GAME_RECURRENT_ABI)
 GAME_RECURRENT_STRUCTS = (lg_game_params, lg_game_buffers)          # what lg_game_recurrent_sizeof sizes by index (2, 3: the two handles, opaque here)
-_GAME_RECURRENT_LIB_NAME = "liblegged_game_recurrent.so"
-_game_recurrent_lib = None
-
-
-def game_recurrent_library_path() -> str:
-    """In-tree liblegged_game_recurrent.so; LG_GAME_RECURRENT_LIB selects another build of the same source."""
-    return os.environ.get("LG_GAME_RECURRENT_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _GAME_RECURRENT_LIB_NAME)
-
-
-def bind_game_recurrent(lib):
-    for symbol, (argtypes, restype) in GAME_RECURRENT_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    for which, st in enumerate(GAME_RECURRENT_STRUCTS):
-        size = lib.lg_game_recurrent_sizeof(which)
-        if size != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
-    return lib
-
-
-def load_game_recurrent_library():
-    """Load the recurrent actor launch of the game tasks or fail loudly -- never a CPU substitute."""
-    global _game_recurrent_lib
-    if _game_recurrent_lib is not None:
-        return _game_recurrent_lib
-    path = game_recurrent_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _game_recurrent_lib = bind_game_recurrent(C.CDLL(path))
-    return _game_recurrent_lib
+LIBRARIES["game_recurrent"] = Library("liblegged_game_recurrent.so", "LG_GAME_RECURRENT_LIB", GAME_RECURRENT_ABI, "_game_recurrent_lib", sizeof=("lg_game_recurrent_sizeof", dict(enumerate(GAME_RECURRENT_STRUCTS))), what="the recurrent actor launch of the game tasks")
+game_recurrent_library_path, bind_game_recurrent, load_game_recurrent_library = _library_names("game_recurrent")
 
 
 def game_lstm_act(hl_actor, ll_policy, params: lg_game_params, buffers: lg_game_buffers, h: int, hl_obs: Optional[int], ll_obs: int, ll_actions: int,
@@ -784,38 +790,8 @@ DEC_GAME_RECURRENT_SYMBOLS = list(DEC_GAME_RECURRENT_ABI)
 # what lg_dec_game_recurrent_sizeof sizes by index (3, 4, 5: the three handles, opaque here)
 DEC_GAME_RECURRENT_STRUCTS = {0: lg_dec_game_params, 1: lg_dec_game_buffers, 2: lg_dec_act_outputs, 6: lg_dec_lstm_role}
 DEC_LSTM_ROLES = ("pred_actor", "pred_critic", "prey_actor", "prey_critic")      # the order of lg_dec_lstm_step's roles
-_DEC_GAME_RECURRENT_LIB_NAME = "liblegged_dec_game_recurrent.so"
-_dec_game_recurrent_lib = None
-
-
-def dec_game_recurrent_library_path() -> str:
-    """In-tree liblegged_dec_game_recurrent.so; LG_DEC_GAME_RECURRENT_LIB selects another build of the same source."""
-    return os.environ.get("LG_DEC_GAME_RECURRENT_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_GAME_RECURRENT_LIB_NAME)
-
-
-def bind_dec_game_recurrent(lib):
-    for symbol, (argtypes, restype) in DEC_GAME_RECURRENT_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    for which, st in DEC_GAME_RECURRENT_STRUCTS.items():
-        size = lib.lg_dec_game_recurrent_sizeof(which)
-        if size != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
-    return lib
-
-
-def load_dec_game_recurrent_library():
-    """Load the recurrent policy stage of dec_high_level_game or fail loudly -- never a CPU substitute."""
-    global _dec_game_recurrent_lib
-    if _dec_game_recurrent_lib is not None:
-        return _dec_game_recurrent_lib
-    path = dec_game_recurrent_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _dec_game_recurrent_lib = bind_dec_game_recurrent(C.CDLL(path))
-    return _dec_game_recurrent_lib
+LIBRARIES["dec_game_recurrent"] = Library("liblegged_dec_game_recurrent.so", "LG_DEC_GAME_RECURRENT_LIB", DEC_GAME_RECURRENT_ABI, "_dec_game_recurrent_lib", sizeof=("lg_dec_game_recurrent_sizeof", DEC_GAME_RECURRENT_STRUCTS), what="the recurrent policy stage of dec_high_level_game")
+dec_game_recurrent_library_path, bind_dec_game_recurrent, load_dec_game_recurrent_library = _library_names("dec_game_recurrent")
 
 
 def dec_lstm_roles(roles) -> "C.Array":
@@ -878,38 +854,8 @@ DEC_POOL_RECURRENT_ABI = {
 DEC_POOL_RECURRENT_SYMBOLS = list(DEC_POOL_RECURRENT_ABI)
 # what lg_dec_pool_recurrent_sizeof sizes by index (3, 4, 5: the three handles, opaque here)
 DEC_POOL_RECURRENT_STRUCTS = {0: lg_dec_game_params, 1: lg_dec_game_buffers, 2: lg_dec_act_outputs, 6: lg_dec_lstm_role, 7: lg_dec_rpool_info}
-_DEC_POOL_RECURRENT_LIB_NAME = "liblegged_dec_pool_recurrent.so"
-_dec_pool_recurrent_lib = None
-
-
-def dec_pool_recurrent_library_path() -> str:
-    """In-tree liblegged_dec_pool_recurrent.so; LG_DEC_POOL_RECURRENT_LIB selects another build of the same source."""
-    return os.environ.get("LG_DEC_POOL_RECURRENT_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_POOL_RECURRENT_LIB_NAME)
-
-
-def bind_dec_pool_recurrent(lib):
-    for symbol, (argtypes, restype) in DEC_POOL_RECURRENT_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    for which, st in DEC_POOL_RECURRENT_STRUCTS.items():
-        size = lib.lg_dec_pool_recurrent_sizeof(which)
-        if size != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
-    return lib
-
-
-def load_dec_pool_recurrent_library():
-    """Load the pooled recurrent policy stage of dec_high_level_game or fail loudly -- never a CPU substitute."""
-    global _dec_pool_recurrent_lib
-    if _dec_pool_recurrent_lib is not None:
-        return _dec_pool_recurrent_lib
-    path = dec_pool_recurrent_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _dec_pool_recurrent_lib = bind_dec_pool_recurrent(C.CDLL(path))
-    return _dec_pool_recurrent_lib
+LIBRARIES["dec_pool_recurrent"] = Library("liblegged_dec_pool_recurrent.so", "LG_DEC_POOL_RECURRENT_LIB", DEC_POOL_RECURRENT_ABI, "_dec_pool_recurrent_lib", sizeof=("lg_dec_pool_recurrent_sizeof", DEC_POOL_RECURRENT_STRUCTS), what="the pooled recurrent policy stage of dec_high_level_game")
+dec_pool_recurrent_library_path, bind_dec_pool_recurrent, load_dec_pool_recurrent_library = _library_names("dec_pool_recurrent")
 
 
 def _dec_pool_recurrent_call(name, *args, ok=(0,)):
@@ -983,38 +929,8 @@ DEC_GAME_PRIVILEGED_ABI = {
 }
 DEC_GAME_PRIVILEGED_SYMBOLS = list(DEC_GAME_PRIVILEGED_ABI)
 DEC_GAME_PRIVILEGED_STRUCTS = {0: lg_dec_game_params, 1: lg_dec_game_buffers}      # what lg_dec_game_privileged_sizeof sizes by index
-_DEC_GAME_PRIVILEGED_LIB_NAME = "liblegged_dec_game_privileged.so"
-_dec_game_privileged_lib = None
-
-
-def dec_game_privileged_library_path() -> str:
-    """In-tree liblegged_dec_game_privileged.so; LG_DEC_GAME_PRIVILEGED_LIB selects another build of the same source."""
-    return os.environ.get("LG_DEC_GAME_PRIVILEGED_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_GAME_PRIVILEGED_LIB_NAME)
-
-
-def bind_dec_game_privileged(lib):
-    for symbol, (argtypes, restype) in DEC_GAME_PRIVILEGED_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    for which, st in DEC_GAME_PRIVILEGED_STRUCTS.items():
-        size = lib.lg_dec_game_privileged_sizeof(which)
-        if size != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
-    return lib
-
-
-def load_dec_game_privileged_library():
-    """Load the privileged observations of dec_high_level_game or fail loudly -- never a CPU substitute."""
-    global _dec_game_privileged_lib
-    if _dec_game_privileged_lib is not None:
-        return _dec_game_privileged_lib
-    path = dec_game_privileged_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _dec_game_privileged_lib = bind_dec_game_privileged(C.CDLL(path))
-    return _dec_game_privileged_lib
+LIBRARIES["dec_game_privileged"] = Library("liblegged_dec_game_privileged.so", "LG_DEC_GAME_PRIVILEGED_LIB", DEC_GAME_PRIVILEGED_ABI, "_dec_game_privileged_lib", sizeof=("lg_dec_game_privileged_sizeof", DEC_GAME_PRIVILEGED_STRUCTS), what="the privileged observations of dec_high_level_game")
+dec_game_privileged_library_path, bind_dec_game_privileged, load_dec_game_privileged_library = _library_names("dec_game_privileged")
 
 
 def dec_game_privileged_obs(params: lg_dec_game_params, buffers: lg_dec_game_buffers, priv_pred: Optional[int], priv_prey: Optional[int],
@@ -1043,39 +959,13 @@ LSTM_WIDE_ABI = {
     "lg_lstm_wide_last_error": ([], C.c_char_p),
 }
 LSTM_WIDE_SYMBOLS = list(LSTM_WIDE_ABI)
-_LSTM_WIDE_LIB_NAME = "liblegged_lstm_wide.so"
-_lstm_wide_lib = None
+LIBRARIES["lstm_wide"] = Library("liblegged_lstm_wide.so", "LG_LSTM_WIDE_LIB", LSTM_WIDE_ABI, "_lstm_wide_lib", what="the wide LSTM cell and actor")
+lstm_wide_library_path, bind_lstm_wide, load_lstm_wide_library = _library_names("lstm_wide")
 
 
 def lstm_wide_supported(num_in: int, hidden: int) -> bool:
     """The shapes ``lg_lstm_wide_create`` takes."""
     return 1 <= num_in <= LG_LSTM_WIDE_MAX_IN and 32 <= hidden <= LG_LSTM_WIDE_MAX_HIDDEN and hidden % 32 == 0
-
-
-def lstm_wide_library_path() -> str:
-    """In-tree liblegged_lstm_wide.so; LG_LSTM_WIDE_LIB selects another build of the same source."""
-    return os.environ.get("LG_LSTM_WIDE_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _LSTM_WIDE_LIB_NAME)
-
-
-def bind_lstm_wide(lib):
-    for symbol, (argtypes, restype) in LSTM_WIDE_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
-
-
-def load_lstm_wide_library():
-    """Load the wide LSTM cell and actor or fail loudly -- never a CPU substitute."""
-    global _lstm_wide_lib
-    if _lstm_wide_lib is not None:
-        return _lstm_wide_lib
-    path = lstm_wide_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _lstm_wide_lib = bind_lstm_wide(C.CDLL(path))
-    return _lstm_wide_lib
 
 
 # ----------------------------------------------------------------------------------------------------------------- legged_recurrent_gru.h
@@ -1090,39 +980,13 @@ GRU_ABI = {
     "lg_gru_last_error": ([], C.c_char_p),
 }
 GRU_SYMBOLS = list(GRU_ABI)
-_GRU_LIB_NAME = "liblegged_gru.so"
-_gru_lib = None
+LIBRARIES["gru"] = Library("liblegged_gru.so", "LG_GRU_LIB", GRU_ABI, "_gru_lib", what="the GRU cell")
+gru_library_path, bind_gru, load_gru_library = _library_names("gru")
 
 
 def gru_supported(num_in: int, hidden: int) -> bool:
     """The shapes ``lg_gru_create`` takes."""
     return 1 <= num_in <= LG_GRU_MAX_IN and 32 <= hidden <= LG_GRU_MAX_HIDDEN and hidden % 32 == 0
-
-
-def gru_library_path() -> str:
-    """In-tree liblegged_gru.so; LG_GRU_LIB selects another build of the same source."""
-    return os.environ.get("LG_GRU_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _GRU_LIB_NAME)
-
-
-def bind_gru(lib):
-    for symbol, (argtypes, restype) in GRU_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    return lib
-
-
-def load_gru_library():
-    """Load the GRU cell or fail loudly -- never a CPU substitute."""
-    global _gru_lib
-    if _gru_lib is not None:
-        return _gru_lib
-    path = gru_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _gru_lib = bind_gru(C.CDLL(path))
-    return _gru_lib
 
 
 # ----------------------------------------------------------------------------------------------------------------- legged_dec_game_gru.h
@@ -1145,38 +1009,8 @@ DEC_GAME_GRU_ABI = {
 }
 DEC_GAME_GRU_SYMBOLS = list(DEC_GAME_GRU_ABI)
 DEC_GAME_GRU_STRUCTS = {0: lg_gru_handle, 1: lg_dec_gru_role}      # what lg_dec_game_gru_sizeof sizes by index
-_DEC_GAME_GRU_LIB_NAME = "liblegged_dec_game_gru.so"
-_dec_game_gru_lib = None
-
-
-def dec_game_gru_library_path() -> str:
-    """In-tree liblegged_dec_game_gru.so; LG_DEC_GAME_GRU_LIB selects another build of the same source."""
-    return os.environ.get("LG_DEC_GAME_GRU_LIB") or os.path.join(os.path.dirname(os.path.realpath(__file__)), "csrc", _DEC_GAME_GRU_LIB_NAME)
-
-
-def bind_dec_game_gru(lib):
-    for symbol, (argtypes, restype) in DEC_GAME_GRU_ABI.items():
-        fn = getattr(lib, symbol)
-        fn.argtypes, fn.restype = argtypes, restype
-    for which, st in DEC_GAME_GRU_STRUCTS.items():
-        size = lib.lg_dec_game_gru_sizeof(which)
-        if size != C.sizeof(st):
-            raise RuntimeError(f"struct layout mismatch for {st.__name__}: C {size} vs ctypes {C.sizeof(st)}")
-    return lib
-
-
-def load_dec_game_gru_library():
-    """Load the shared GRU cell launch of dec_high_level_game or fail loudly -- never a CPU substitute."""
-    global _dec_game_gru_lib
-    if _dec_game_gru_lib is not None:
-        return _dec_game_gru_lib
-    path = dec_game_gru_library_path()
-    if not os.path.isfile(path):
-        raise RuntimeError(
-            f"HIP extension {path} is not built; run `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the product path.")
-    _dec_game_gru_lib = bind_dec_game_gru(C.CDLL(path))
-    return _dec_game_gru_lib
+LIBRARIES["dec_game_gru"] = Library("liblegged_dec_game_gru.so", "LG_DEC_GAME_GRU_LIB", DEC_GAME_GRU_ABI, "_dec_game_gru_lib", sizeof=("lg_dec_game_gru_sizeof", DEC_GAME_GRU_STRUCTS), what="the shared GRU cell launch of dec_high_level_game")
+dec_game_gru_library_path, bind_dec_game_gru, load_dec_game_gru_library = _library_names("dec_game_gru")
 
 
 def dec_gru_roles(roles) -> "C.Array":

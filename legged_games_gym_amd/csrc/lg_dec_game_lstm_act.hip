@@ -11,9 +11,7 @@
 // handles the main library created (lg_policy, lg_lstm_actor, lg_lstm) come from the headers both are compiled from; the kernel arguments
 // are filled here (fill_policy_args / fill_wide_operands / fail of lg_host.h live in other units and are not called).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #define LG_POLICY_BLOCKS_ONLY      // lg_policy.h without its two non-template pack kernels
 #include "lg_device.h"
@@ -24,6 +22,8 @@
 #include "lg_recurrent.h"          // struct lg_lstm, lg_lstm_actor, LstmRole, LstmActorArgs, LG_LSTM_LD
 #include "lg_lstm_cell_body.h"
 #include "lg_lstm_actor_body.h"
+#include "lg_lib_error.h"            // g_error, refuse, raise_lds_limit, HIP_TRY_WHO
+#include "lg_memory_host.h"          // cell_lds_bytes, fill_lstm_role, fill_lstm_actor_args
 #include "lg_dec_lstm_act.h"         // DecLstmArgs, DecGameLstmActArgs, dec_lstm_actor_role<PREY>, the host code that sizes and fills them
 #include "../../include/legged_dec_game_recurrent.h"
 
@@ -55,19 +55,7 @@ __global__ void __launch_bounds__(64 * LG_PW_WAVES) k_dec_game_lstm_act(const De
     }
 }
 
-static thread_local char g_error[512] = "";
-static int refuse(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 }  // namespace lg
-
-#undef HIP_TRY                     // lg_host.h's reports through the main library's lg::fail
-#define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return lg::refuse(-10, "%s: HIP error: %s", who, hipGetErrorString(_e)); } while (0)
 
 extern "C" {
 
@@ -94,8 +82,7 @@ int lg_dec_lstm_step(const lg_dec_lstm_role roles[4], const uint8_t *reset, int3
         if (slot && R.l->device != device) return lg::refuse(-2, "%s: the memories live on different devices", who);
         device = R.l->device;
         lg::LstmRole &K = A.role[r];
-        K.x = R.x; K.h_in = R.h_in; K.c_in = R.c_in; K.h_out = R.h_out; K.c_out = R.c_out;
-        K.wp = R.l->d_wp; K.bp = R.l->d_bp; K.num_in = R.l->num_in; K.hidden = R.l->hidden; K.ksteps = R.l->ksteps;
+        lg::fill_lstm_role(K, R.l, R.x, R.h_in, R.c_in, R.h_out, R.c_out);
         if (K.hidden > hidden) hidden = K.hidden;
         if (K.ksteps > ksteps) ksteps = K.ksteps;
         A.order |= (uint32_t)r << (2 * slot++);
@@ -103,12 +90,12 @@ int lg_dec_lstm_step(const lg_dec_lstm_role roles[4], const uint8_t *reset, int3
     if (hidden < 32 || hidden > LG_LSTM_MAX_HIDDEN || hidden % 32 || ksteps < 1 || ksteps > lg::LSTM_MAX_KSTEPS)
         return lg::refuse(-2, "%s: a handle's shape is outside what lg_lstm_create makes", who);
     static bool raised[64] = {};
-    HIP_TRY(lg::raise_lds_limit((const void *)lg::k_dec_lstm_cell, lg::cell_lds_bytes(lg::LSTM_MAX_KSTEPS), raised));
+    HIP_TRY_WHO(lg::raise_lds_limit((const void *)lg::k_dec_lstm_cell, lg::cell_lds_bytes(lg::LSTM_MAX_KSTEPS), raised));
     A.reset = reset;
     A.num_envs = num_envs;
     A.blocks = (num_envs + LG_LSTM_BLOCK_ENVS - 1) / LG_LSTM_BLOCK_ENVS;
     hipLaunchKernelGGL(lg::k_dec_lstm_cell, dim3(present * A.blocks), dim3(2 * hidden), lg::cell_lds_bytes(ksteps), (hipStream_t)stream, A);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_WHO(hipGetLastError());
     return 0;
 }
 
@@ -133,7 +120,7 @@ int lg_dec_game_lstm_act(const lg_lstm_actor *pred, const lg_lstm_actor *prey, l
     if (seed_pred == seed_prey) return lg::refuse(-2, "%s: seed_pred and seed_prey must differ (the sampled roles share their noise purposes)", who);
 
     static bool raised[64] = {};
-    HIP_TRY(lg::raise_lds_limit((const void *)lg::k_dec_game_lstm_act, lg::dec_game_lstm_lds_bytes(512), raised));
+    HIP_TRY_WHO(lg::raise_lds_limit((const void *)lg::k_dec_game_lstm_act, lg::dec_game_lstm_lds_bytes(512), raised));
 
     lg::DecGameLstmActArgs g = {};
     lg::fill_ll_role_args(g.ll, ll, ll_obs, ll_actions, P->num_envs, seed_prey, step, step_counter);
@@ -146,7 +133,7 @@ int lg_dec_game_lstm_act(const lg_lstm_actor *pred, const lg_lstm_actor *prey, l
     g.blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;
     const int width = pred->max_width > prey->max_width ? pred->max_width : prey->max_width;
     hipLaunchKernelGGL(lg::k_dec_game_lstm_act, dim3(3 * g.blocks), dim3(64 * LG_PW_WAVES), lg::dec_game_lstm_lds_bytes(width), (hipStream_t)stream, g);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_WHO(hipGetLastError());
     return 0;
 }
 

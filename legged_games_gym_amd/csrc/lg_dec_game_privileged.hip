@@ -8,14 +8,13 @@
 // clock (game_quotient: correctly rounded) are bit-comparable with the NumPy twin (tests/dec_privileged_twin.py); fx, fy sit behind
 // sqrtf and the fast division (1 ulp and 2.5 ulp on this build).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #define LG_POLICY_BLOCKS_ONLY      // lg_policy.h (which lg_game_common.h needs) without its two non-template pack kernels
 #include "lg_device.h"
 #include "lg_policy.h"
 #include "lg_dec_game_post.h"      // LG_DEC_BLOCK, dec_grid; game_quotient (lg_game_post.h)
+#include "lg_lib_error.h"          // g_error, refuse, HIP_TRY_WHO
 #include "../../include/legged_dec_game_privileged.h"
 
 namespace lg {
@@ -62,15 +61,6 @@ __global__ __launch_bounds__(LG_DEC_BLOCK) void k_privileged_obs(const Privilege
     }
 }
 
-static thread_local char g_error[512] = "";
-static int refuse(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 }  // namespace lg
 
 extern "C" {
@@ -86,8 +76,7 @@ int lg_dec_game_privileged_obs(const lg_dec_game_params *P, const lg_dec_game_bu
     const lg::PrivilegedArgs A = {B->predator_pos, B->ll_root_states, B->obs_prey, B->obs_pred, B->episode_length_buf, priv_pred, priv_prey,
                                   P->num_envs, P->max_episode_length};
     hipLaunchKernelGGL(lg::k_privileged_obs, lg::dec_grid(*P), dim3(LG_DEC_BLOCK), 0, (hipStream_t)stream, A);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return lg::refuse(-10, "%s: HIP error: %s", who, hipGetErrorString(err));
+    HIP_TRY_WHO(hipGetLastError());
     return 0;
 }
 

@@ -5,15 +5,14 @@
 // The only translation unit of liblegged_dec_game_gru.so: it links against nothing of the other libraries.  The layout of the handles
 // liblegged_gru.so created comes from lg_gru.h, which both are compiled from.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "lg_device.h"             // f32x16
 #include "lg_recurrent.h"          // LG_LSTM_LD: the staged block and the lane maps
-#include "lg_lstm_cell_body.h"     // lstm_sigmoid, lstm_tanh
+#include "lg_lstm_cell_body.h"     // stage_xh, lstm_sigmoid, lstm_tanh
 #include "lg_gru_cell_body.h"
 #include "lg_gru.h"                // struct lg_gru
+#include "lg_lib_error.h"          // g_error, refuse, raise_lds_limit, HIP_TRY_WHO
 #include "../../include/legged_dec_game_gru.h"
 
 namespace lg {
@@ -39,31 +38,7 @@ __global__ void __launch_bounds__(2 * LG_GRU_MAX_HIDDEN) k_dec_gru_cell(const De
 static size_t gru_lds_bytes(const int ksteps) { return (size_t)2 * ksteps * LG_LSTM_LD * sizeof(float); }
 static const int GRU_MAX_KSTEPS = (LG_GRU_MAX_IN + LG_GRU_MAX_HIDDEN) / 2;
 
-static thread_local char g_error[512] = "";
-static int refuse(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// hipFuncSetAttribute once per device for this process (not capture-safe: the first call happens in a warm-up)
-static hipError_t raise_lds_limit(const void *kernel, const size_t bytes, bool (&raised)[64]) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !raised[dev]) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) raised[dev] = true;
-    }
-    return hipSuccess;
-}
-
 }  // namespace lg
-
-#define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return lg::refuse(-10, "%s: HIP error: %s", who, hipGetErrorString(_e)); } while (0)
 
 extern "C" {
 
@@ -104,12 +79,12 @@ int lg_dec_gru_step(const lg_dec_gru_role roles[4], const uint8_t *reset, int32_
             return lg::refuse(-2, "%s: the shape of the %s memory's handle is outside what lg_gru_create makes", who, names[r]);
     }
     static bool raised[64] = {};
-    HIP_TRY(lg::raise_lds_limit((const void *)lg::k_dec_gru_cell, lg::gru_lds_bytes(lg::GRU_MAX_KSTEPS), raised));
+    HIP_TRY_WHO(lg::raise_lds_limit((const void *)lg::k_dec_gru_cell, lg::gru_lds_bytes(lg::GRU_MAX_KSTEPS), raised));
     A.reset = reset;
     A.num_envs = num_envs;
     A.blocks = (num_envs + LG_GRU_BLOCK_ENVS - 1) / LG_GRU_BLOCK_ENVS;
     hipLaunchKernelGGL(lg::k_dec_gru_cell, dim3(present * A.blocks), dim3(2 * hidden), lg::gru_lds_bytes(ksteps), (hipStream_t)stream, A);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_WHO(hipGetLastError());
     return 0;
 }
 

@@ -3,7 +3,8 @@
 // (liblegged_dec_game_recurrent.so: k_dec_lstm_cell, k_dec_game_lstm_act) and lg_dec_pool_lstm_act.hip (liblegged_dec_pool_recurrent.so:
 // k_dec_pool_lstm_cell, k_dec_pool_lstm_act) are each ONE translation unit that includes it; nothing here is exported.
 // Needs lg_device.h, lg_policy.h, lg_host.h (struct lg_policy), lg_dec_game_common.h (DecActAgent), lg_dec_game_act.h
-// (dec_command_epilogue), lg_recurrent.h, lg_lstm_actor_body.h and <hip/hip_runtime.h>.
+// (dec_command_epilogue), lg_recurrent.h, lg_lstm_actor_body.h and <hip/hip_runtime.h>.  The units' host code also reads lg_lib_error.h
+// (raise_lds_limit) and lg_memory_host.h (cell_lds_bytes, fill_lstm_role, fill_lstm_actor_args).
 #pragma once
 #include "../../include/legged_recurrent.h"      // LG_LSTM_MAX_IN, LG_LSTM_MAX_HIDDEN
 
@@ -17,7 +18,6 @@ struct DecLstmArgs {
     uint32_t order, _pad;          // two bits per slot: the role of workgroups slot * blocks .. (slot + 1) * blocks - 1
 };
 
-static size_t cell_lds_bytes(const int ksteps) { return (size_t)2 * ksteps * LG_LSTM_LD * sizeof(float); }
 static const int LSTM_MAX_KSTEPS = (LG_LSTM_MAX_IN + LG_LSTM_MAX_HIDDEN) / 2;
 
 // ------------------------------------------------------------------ the actor launch
@@ -68,27 +68,6 @@ LG_DEV void dec_lstm_actor_role(const LstmActorArgs &A, const DecActAgent &O, co
 static size_t dec_game_lstm_lds_bytes(const int max_width) {
     const size_t hl = ((size_t)2 * max_width * LG_LSTM_LD + 32 * 16 + 32 * 16) * sizeof(float), ll = 98304;
     return hl > ll ? hl : ll;
-}
-
-// above the 64 KB a kernel gets without asking: raised once per device, at the first call (outside any capture)
-static hipError_t raise_lds_limit(const void *kernel, const size_t bytes, bool (&raised)[64]) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !raised[dev]) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) raised[dev] = true;
-    }
-    return hipSuccess;
-}
-
-static void fill_lstm_actor_args(LstmActorArgs &A, const lg_lstm_actor *a, const float *h, float *sample, float *mean, const int num_envs,
-                                 const uint64_t seed, const int64_t step, const int64_t *step_counter, const int deterministic) {   // as lg_lstm_actor_act
-    A.h = h; A.p = a->d_p; A.std = a->d_std; A.actions = sample; A.mean = mean; A.step_counter = step_counter;
-    A.seed = seed; A.step = step; A.num_envs = num_envs; A.deterministic = deterministic; A.max_width = a->max_width;
-    for (int i = 0; i < 5; i++) { A.dims[i] = a->dims[i]; A.pad[i] = a->pad[i]; }
-    for (int i = 0; i < 4; i++) { A.w_off[i] = (uint32_t)a->w_off[i]; A.b_off[i] = (uint32_t)a->b_off[i]; }
 }
 
 // the low-level role: what fill_policy_args / fill_wide_operands do for lg_policy_act(ll, deterministic = 1)

@@ -11,9 +11,7 @@
 // handles the main library created (lg_policy, lg_lstm_actor, lg_lstm) come from the headers both are compiled from.
 #include <hip/hip_runtime.h>
 #include <new>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #define LG_POLICY_BLOCKS_ONLY      // lg_policy.h without its two non-template pack kernels
@@ -25,6 +23,8 @@
 #include "lg_recurrent.h"          // struct lg_lstm, lg_lstm_actor, LstmRole, LstmActorArgs, LG_LSTM_LD
 #include "lg_lstm_cell_body.h"
 #include "lg_lstm_actor_body.h"
+#include "lg_lib_error.h"          // g_error, refuse, raise_lds_limit, HIP_TRY_WHO
+#include "lg_memory_host.h"        // cell_lds_bytes, fill_lstm_role, fill_lstm_actor_args
 #include "lg_dec_lstm_act.h"       // DecLstmArgs, DecGameLstmActArgs, dec_lstm_actor_role<PREY>, the host code that sizes and fills them
 #include "../../include/legged_dec_pool_recurrent.h"
 
@@ -114,15 +114,6 @@ __global__ void __launch_bounds__(64 * LG_PW_WAVES) k_dec_pool_lstm_act(const De
     }
 }
 
-static thread_local char g_error[512] = "";
-static int refuse(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 static int role_inputs(int role) { return role == 1 ? LG_DEC_NUM_OBS_PREY : LG_DEC_NUM_OBS_PRED; }
 static int role_actions(int role) { return role == 1 ? LG_DEC_NUM_ACTIONS_PREY : LG_DEC_NUM_ACTIONS_PRED; }
 
@@ -138,9 +129,6 @@ static DecRPoolRole pool_role(const lg_dec_rpool *pool, const int32_t *block_slo
 }
 
 }  // namespace lg
-
-#undef HIP_TRY                     // lg_host.h's reports through the main library's lg::fail
-#define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return lg::refuse(-10, "%s: HIP error: %s", who, hipGetErrorString(_e)); } while (0)
 
 extern "C" {
 
@@ -165,7 +153,7 @@ int lg_dec_rpool_create(const lg_lstm *const *lstm_members, const lg_lstm_actor 
         const int m = i < count ? i : 0;
         rows[i] = {lstm_members[m]->d_wp, lstm_members[m]->d_bp, actor_members[m]->d_p, actor_members[m]->d_std};
     }
-    HIP_TRY(hipSetDevice(device));
+    HIP_TRY_WHO(hipSetDevice(device));
     lg_dec_rpool *pool = new (std::nothrow) lg_dec_rpool();
     if (!pool) return lg::refuse(-5, "%s: out of host memory", who);
     pool->d_table = nullptr; pool->count = count; pool->role = role; pool->device = device;
@@ -230,8 +218,7 @@ int lg_dec_pool_lstm_step(const lg_dec_lstm_role roles[4], const lg_dec_rpool *p
         if (slot && dev != device) return lg::refuse(-2, "%s: the memories and pools live on different devices", who);
         device = dev;
         lg::LstmRole &K = A.role[r];
-        K.x = R.x; K.h_in = R.h_in; K.c_in = R.c_in; K.h_out = R.h_out; K.c_out = R.c_out;
-        K.wp = l->d_wp; K.bp = l->d_bp; K.num_in = l->num_in; K.hidden = l->hidden; K.ksteps = l->ksteps;      // (null for a pooled role: the kernel takes the member's)
+        lg::fill_lstm_role(K, l, R.x, R.h_in, R.c_in, R.h_out, R.c_out);             // (wp, bp null for a pooled role: the kernel takes the member's)
         if (K.hidden > hidden) hidden = K.hidden;
         if (K.ksteps > ksteps) ksteps = K.ksteps;
         A.order |= (uint32_t)r << (2 * slot++);
@@ -239,14 +226,14 @@ int lg_dec_pool_lstm_step(const lg_dec_lstm_role roles[4], const lg_dec_rpool *p
     if (hidden < 32 || hidden > LG_LSTM_MAX_HIDDEN || hidden % 32 || ksteps < 1 || ksteps > lg::LSTM_MAX_KSTEPS)
         return lg::refuse(-2, "%s: a handle's shape is outside what lg_lstm_create makes", who);
     static bool raised[64] = {};
-    HIP_TRY(lg::raise_lds_limit((const void *)lg::k_dec_pool_lstm_cell, lg::cell_lds_bytes(lg::LSTM_MAX_KSTEPS), raised));
+    HIP_TRY_WHO(lg::raise_lds_limit((const void *)lg::k_dec_pool_lstm_cell, lg::cell_lds_bytes(lg::LSTM_MAX_KSTEPS), raised));
     A.reset = reset;
     A.num_envs = num_envs;
     A.blocks = (num_envs + LG_LSTM_BLOCK_ENVS - 1) / LG_LSTM_BLOCK_ENVS;
     G.pred = lg::pool_role(pool_pred, block_slot_pred);
     G.prey = lg::pool_role(pool_prey, block_slot_prey);
     hipLaunchKernelGGL(lg::k_dec_pool_lstm_cell, dim3(present * A.blocks), dim3(2 * hidden), lg::cell_lds_bytes(ksteps), (hipStream_t)stream, G);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_WHO(hipGetLastError());
     return 0;
 }
 
@@ -276,7 +263,7 @@ int lg_dec_pool_lstm_act(const lg_lstm_actor *pred, const lg_lstm_actor *prey, l
     if (seed_pred == seed_prey) return lg::refuse(-2, "%s: seed_pred and seed_prey must differ (the sampled roles share their noise purposes)", who);
 
     static bool raised[64] = {};
-    HIP_TRY(lg::raise_lds_limit((const void *)lg::k_dec_pool_lstm_act, lg::dec_game_lstm_lds_bytes(512), raised));
+    HIP_TRY_WHO(lg::raise_lds_limit((const void *)lg::k_dec_pool_lstm_act, lg::dec_game_lstm_lds_bytes(512), raised));
 
     lg::DecPoolLstmActArgs q = {};
     lg::DecGameLstmActArgs &g = q.act;
@@ -292,7 +279,7 @@ int lg_dec_pool_lstm_act(const lg_lstm_actor *pred, const lg_lstm_actor *prey, l
     q.pred = lg::pool_role(pool_pred, block_slot_pred);
     const int width = pd->max_width > py->max_width ? pd->max_width : py->max_width;
     hipLaunchKernelGGL(lg::k_dec_pool_lstm_act, dim3(3 * g.blocks), dim3(64 * LG_PW_WAVES), lg::dec_game_lstm_lds_bytes(width), (hipStream_t)stream, q);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_WHO(hipGetLastError());
     return 0;
 }
 

@@ -8,9 +8,7 @@
 // that library created (lg_policy, lg_lstm_actor) come from the headers both are compiled from; the kernel arguments are filled here
 // (fill_policy_args / fill_wide_operands / fail of lg_host.h live in other units and are not called).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #define LG_POLICY_BLOCKS_ONLY      // lg_policy.h without its two non-template pack kernels
 #include "lg_device.h"
@@ -19,6 +17,8 @@
 #include "lg_game_common.h"        // game_clip, game_wrap_to_pi; include/legged_game.h
 #include "lg_recurrent.h"          // struct lg_lstm_actor, LstmActorArgs, LG_LSTM_LD
 #include "lg_lstm_actor_body.h"
+#include "lg_lib_error.h"          // g_error, refuse, raise_lds_limit, HIP_TRY_WHO
+#include "lg_memory_host.h"        // fill_lstm_actor_args
 #include "../../include/legged_game_recurrent.h"
 
 namespace lg {
@@ -102,25 +102,14 @@ static size_t game_lstm_lds_bytes(const int max_width) {
     return hl > ll ? hl : ll;
 }
 
-static thread_local char g_error[512] = "";
-static int refuse(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 }  // namespace lg
-
-#undef HIP_TRY                     // lg_host.h's reports through the main library's lg::fail
-#define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return lg::refuse(-10, "lg_game_lstm_act: HIP error: %s", hipGetErrorString(_e)); } while (0)
 
 extern "C" {
 
 int lg_game_lstm_act(const lg_lstm_actor *hl, lg_policy *ll, const lg_game_params *P, const lg_game_buffers *B, const float *h, const float *hl_obs,
                      const float *ll_obs, float *ll_actions, float *mean, uint64_t seed, int64_t step, const int64_t *step_counter,
                      int32_t deterministic, float *sample, float *sigma, float *log_prob, float *obs_copy, void *stream) {
+    static const char *const who = "lg_game_lstm_act";
     if (!hl || !ll || !P || !B || !h || !ll_obs || !ll_actions || !mean) return lg::refuse(-1, "lg_game_lstm_act: null argument");
     if (!B->command || !B->ll_commands) return lg::refuse(-1, "lg_game_lstm_act: null command or ll_commands in the buffers");
     if (obs_copy && !hl_obs) return lg::refuse(-1, "lg_game_lstm_act: null hl_obs with obs_copy given");
@@ -130,14 +119,8 @@ int lg_game_lstm_act(const lg_lstm_actor *hl, lg_policy *ll, const lg_game_param
                               "use lg_lstm_actor_act + lg_game_pre + lg_policy_act");
     if (hl->max_width < 32 || hl->max_width > 512) return lg::refuse(-4, "lg_game_lstm_act: layer widths of the recurrent actor must be 32 .. 512");
 
-    // above the 64 KB a kernel gets without asking: raised once per device, at the first call (outside any capture)
     static bool raised[64] = {};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !raised[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void *)lg::k_game_lstm_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lg::game_lstm_lds_bytes(512)));
-        if (dev >= 0 && dev < 64) raised[dev] = true;
-    }
+    HIP_TRY_WHO(lg::raise_lds_limit((const void *)lg::k_game_lstm_act, lg::game_lstm_lds_bytes(512), raised));
 
     lg::GameLstmActArgs g = {};
     lg::PolicyArgs &a = g.ll.base;                                 // what fill_policy_args / fill_wide_operands do for lg_policy_act(ll, deterministic = 1)
@@ -147,17 +130,13 @@ int lg_game_lstm_act(const lg_lstm_actor *hl, lg_policy *ll, const lg_game_param
         a.w[i] = ll->d_w[i]; a.b[i] = ll->d_b[i];
         g.ll.wb[i] = reinterpret_cast<const lg::bf16x8g *>(ll->d_wb[i]); g.ll.bb[i] = ll->d_bb[i];
     }
-    lg::LstmActorArgs &A = g.hl;                                   // as lg_lstm_actor_act
-    A.h = h; A.p = hl->d_p; A.std = hl->d_std; A.actions = sample; A.mean = mean; A.step_counter = step_counter;
-    A.seed = seed; A.step = step; A.num_envs = P->num_envs; A.deterministic = deterministic; A.max_width = hl->max_width;
-    for (int i = 0; i < 5; i++) { A.dims[i] = hl->dims[i]; A.pad[i] = hl->pad[i]; }
-    for (int i = 0; i < 4; i++) { A.w_off[i] = (uint32_t)hl->w_off[i]; A.b_off[i] = (uint32_t)hl->b_off[i]; }
+    lg::fill_lstm_actor_args(g.hl, hl, h, sample, mean, P->num_envs, seed, step, step_counter, deterministic);
     g.P = *P; g.hl_obs = hl_obs; g.command = B->command; g.ll_commands = B->ll_commands;
     g.sigma = sigma; g.log_prob = log_prob; g.obs_copy = obs_copy;
     const int blocks = (P->num_envs + LG_PW_ENVS - 1) / LG_PW_ENVS;
     g.ll_blocks = blocks;
     hipLaunchKernelGGL(lg::k_game_lstm_act, dim3(2 * blocks), dim3(64 * LG_PW_WAVES), lg::game_lstm_lds_bytes(hl->max_width), (hipStream_t)stream, g);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_WHO(hipGetLastError());
     return 0;
 }
 

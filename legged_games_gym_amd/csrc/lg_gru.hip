@@ -5,15 +5,15 @@
 // The launch, the staged [x | h_in] block, the lane maps and the k-loop are k_lstm_cell's (lg_recurrent.h); the pack kernel and the
 // epilogue are the GRU's (lg_gru_cell_body.h).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "lg_device.h"             // f32x16
 #include "lg_recurrent.h"          // LG_LSTM_LD: the staged block and the lane maps
-#include "lg_lstm_cell_body.h"     // lstm_sigmoid, lstm_tanh
+#include "lg_lstm_cell_body.h"     // stage_xh, lstm_sigmoid, lstm_tanh
 #include "lg_gru_cell_body.h"
 #include "lg_gru.h"                // struct lg_gru
+#include "lg_lib_error.h"          // g_error, refuse, HIP_TRY
+#include "lg_memory_host.h"        // create / load_device / destroy of the handle, written once for the three cell libraries
 #include "../../include/legged_recurrent_gru.h"
 
 namespace lg {
@@ -61,31 +61,15 @@ __global__ void __launch_bounds__(2 * LG_GRU_MAX_HIDDEN) k_gru_cell(const GruArg
     else gru_cell_role(A.role[1], A.reset, A.num_envs, blk, xs);
 }
 
-static size_t gru_lds_bytes(const int ksteps) { return (size_t)2 * ksteps * LG_LSTM_LD * sizeof(float); }
-static const int GRU_MAX_KSTEPS = (LG_GRU_MAX_IN + LG_GRU_MAX_HIDDEN) / 2;
-
-static thread_local char g_error[512] = "";
-static int refuse(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-}  // namespace lg
-
-#define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return lg::refuse(-10, "HIP error: %s", hipGetErrorString(_e)); } while (0)
-
-namespace lg {
-
-static int gru_pack(lg_gru *l, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, hipStream_t stream) {
-    const int total = (l->hidden / 32) * l->ksteps * 64 + l->hidden;
-    hipLaunchKernelGGL(k_gru_pack, dim3((total + 255) / 256), dim3(256), 0, stream, w_ih, w_hh, b_ih, b_hh, (float4 *)l->d_wp, (float4 *)l->d_bp,
-                       l->num_in, l->hidden, l->ksteps);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
+struct GruMemory {                 // lg_memory_host.h: the traits of lg_gru
+    using Handle = lg_gru;
+    static constexpr int GATES = 3, MAX_IN = LG_GRU_MAX_IN, MAX_HIDDEN = LG_GRU_MAX_HIDDEN;
+    static const char *name() { return "lg_gru"; }
+    static const char *hidden_note() { return " (one layer)"; }
+    static const void *cell_kernel() { return (const void *)k_gru_cell; }               // 67 584 B of staged [x | h] at the largest shape
+    template <class... Args> static void pack(const dim3 grid, hipStream_t stream, Args... args) { hipLaunchKernelGGL(k_gru_pack, grid, dim3(256), 0, stream, args...); }
+    static int error(const int code, const char *msg) { return refuse(code, "%s", msg); }
+};
 
 }  // namespace lg
 
@@ -93,57 +77,14 @@ extern "C" {
 
 int lg_gru_create(int32_t num_in, int32_t hidden, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh,
                   int32_t device_id, lg_gru **out) {
-    if (!out || !w_ih || !w_hh || !b_ih || !b_hh) return lg::refuse(-1, "lg_gru_create: null argument");
-    *out = nullptr;
-    if (num_in < 1 || num_in > LG_GRU_MAX_IN)
-        return lg::refuse(-4, "lg_gru_create: num_in must be 1 .. 256");
-    if (hidden < 32 || hidden > LG_GRU_MAX_HIDDEN || hidden % 32)
-        return lg::refuse(-4, "lg_gru_create: hidden must be a multiple of 32 in 32 .. 256 (one layer)");
-    HIP_TRY(hipSetDevice(device_id));
-    // the staged [x | h] block of the largest shape (67 584 B) is above the 64 KB a kernel gets without asking
-    HIP_TRY(hipFuncSetAttribute((const void *)lg::k_gru_cell, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lg::gru_lds_bytes(lg::GRU_MAX_KSTEPS)));
-    lg_gru *l = new lg_gru();
-    l->num_in = num_in; l->hidden = hidden; l->ksteps = (num_in + hidden + 1) / 2; l->device = device_id;
-    l->d_wp = l->d_bp = nullptr;
-    const size_t n_ih = (size_t)3 * hidden * num_in, n_hh = (size_t)3 * hidden * hidden, n_b = (size_t)3 * hidden;
-    float *raw = nullptr;
-    auto body = [&]() -> int {
-        HIP_TRY(hipMalloc(&l->d_wp, (size_t)(hidden / 32) * l->ksteps * 64 * 4 * sizeof(float)));
-        HIP_TRY(hipMalloc(&l->d_bp, (size_t)4 * hidden * sizeof(float)));
-        HIP_TRY(hipMalloc(&raw, (n_ih + n_hh + 2 * n_b) * sizeof(float)));
-        HIP_TRY(hipMemcpy(raw, w_ih, n_ih * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(raw + n_ih, w_hh, n_hh * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(raw + n_ih + n_hh, b_ih, n_b * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(raw + n_ih + n_hh + n_b, b_hh, n_b * sizeof(float), hipMemcpyHostToDevice));
-        const int prc = lg::gru_pack(l, raw, raw + n_ih, raw + n_ih + n_hh, raw + n_ih + n_hh + n_b, nullptr);
-        if (prc) return prc;
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        return 0;
-    };
-    const int rc = body();
-    if (raw) (void)hipFree(raw);
-    if (rc) {
-        if (l->d_wp) (void)hipFree(l->d_wp);
-        if (l->d_bp) (void)hipFree(l->d_bp);
-        delete l;
-        return rc;
-    }
-    *out = l;
-    return 0;
+    return lg::memory_create<lg::GruMemory>(num_in, hidden, w_ih, w_hh, b_ih, b_hh, device_id, out);
 }
 
 int lg_gru_load_device(lg_gru *l, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, void *stream) {
-    if (!l || !w_ih || !w_hh || !b_ih || !b_hh) return lg::refuse(-1, "lg_gru_load_device: null argument");
-    return lg::gru_pack(l, w_ih, w_hh, b_ih, b_hh, (hipStream_t)stream);
+    return lg::memory_load_device<lg::GruMemory>(l, w_ih, w_hh, b_ih, b_hh, stream);
 }
 
-int lg_gru_destroy(lg_gru *l) {
-    if (!l) return lg::refuse(-1, "lg_gru_destroy: null handle");
-    (void)hipFree(l->d_wp);
-    (void)hipFree(l->d_bp);
-    delete l;
-    return 0;
-}
+int lg_gru_destroy(lg_gru *l) { return lg::memory_destroy<lg::GruMemory>(l); }
 
 int lg_gru_step(const lg_gru *l_a, const lg_gru *l_c, const float *x_a, const float *x_c, const uint8_t *reset,
                 const float *h_in_a, float *h_out_a, const float *h_in_c, float *h_out_c, int32_t num_envs, void *stream) {
@@ -167,7 +108,7 @@ int lg_gru_step(const lg_gru *l_a, const lg_gru *l_c, const float *x_a, const fl
     A.first_role = l_a ? 0 : 1;
     const int roles = (l_a ? 1 : 0) + (l_c ? 1 : 0);
     const int hidden = max(l_a ? l_a->hidden : 0, l_c ? l_c->hidden : 0), ksteps = max(l_a ? l_a->ksteps : 0, l_c ? l_c->ksteps : 0);
-    hipLaunchKernelGGL(lg::k_gru_cell, dim3(roles * A.blocks), dim3(2 * hidden), lg::gru_lds_bytes(ksteps), (hipStream_t)stream, A);
+    hipLaunchKernelGGL(lg::k_gru_cell, dim3(roles * A.blocks), dim3(2 * hidden), lg::cell_lds_bytes(ksteps), (hipStream_t)stream, A);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -1,5 +1,6 @@
 // lg_gru_cell_body.h -- the GRU cell of a recurrent policy's memory (k_gru_cell, lg_gru.hip, lg_gru_step).  Needs lg_device.h (f32x16),
-// lg_recurrent.h (LG_LSTM_LD: the staged block and the lane maps are the LSTM cell's) and lg_lstm_cell_body.h (lstm_sigmoid, lstm_tanh).
+// lg_recurrent.h (LG_LSTM_LD: the staged block and the lane maps are the LSTM cell's) and lg_lstm_cell_body.h (stage_xh: the one copy of the
+// staging; lstm_sigmoid, lstm_tanh).
 //
 // torch's GRU keeps the x part and the h part of the n gate apart (b_hn sits inside the product with r), so a wave's four accumulators
 // over the staged [x | h_in] block are (r, z, n_x, n_h): the packed weight of n_x is zero for k >= num_in, that of n_h for k < num_in.
@@ -41,22 +42,10 @@ __device__ __forceinline__ void gru_chain(const float4 *__restrict__ wp, const f
 // One role's workgroup: env rows 32 blk .. 32 blk + 31, all hidden units (hidden / 32 waves).
 __device__ __forceinline__ void gru_cell_role(const GruRole &R, const uint8_t *__restrict__ reset, const int num_envs, const int blk, float *xs) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int I = R.num_in, H = R.hidden, K = I + H, nthreads = 2 * H;            // 64 threads per 32 hidden units
-    const bool active = wave < H / 32;                                            // (the launch is sized for the wider role: the
-    const int env0 = 32 * blk;
-    if (active) {                                                                 //  narrower one's surplus waves only meet the barrier)
-        // stage [x | h_in] of the 32 rows as xs[k][row]; rows past num_envs and the pad row k = K are zeros, a reset row's h is zero
-        for (int e = tid; e < 32 * I; e += nthreads) {
-            const int row = e / I, k = e - row * I, env = env0 + row;
-            xs[k * LG_LSTM_LD + row] = env < num_envs ? R.x[(size_t)env * I + k] : 0.0f;
-        }
-        for (int e = tid; e < 32 * H; e += nthreads) {
-            const int row = e / H, k = e - row * H, env = env0 + row;
-            const bool live = env < num_envs && !(reset && reset[env]);
-            xs[(I + k) * LG_LSTM_LD + row] = live ? R.h_in[(size_t)env * H + k] : 0.0f;
-        }
-        if ((K & 1) && tid < 32) xs[K * LG_LSTM_LD + tid] = 0.0f;                     // the pad row of an odd K (the buffer holds 2 ksteps = K + 1 rows then)
-    }
+    const int I = R.num_in, H = R.hidden;
+    const bool active = wave < H / 32;                                            // (the launch is sized for the wider role: the narrower
+    const int env0 = 32 * blk;                                                    //  one's surplus waves only meet the barrier)
+    if (active) stage_xh(R.x, R.h_in, I, H, reset, num_envs, env0, tid, 2 * H, xs);        // lg_lstm_cell_body.h: 64 threads per 32 hidden units
     __syncthreads();
     if (!active) return;
 

@@ -98,4 +98,20 @@ LG_DEV void lstm_actor_body(const LstmActorArgs &A, const int blk, float *xa, fl
     }
 }
 
+// One layer of the actor MLP into the packed layout (lg_recurrent.h); one thread per packed weight, then the padded bias: the body of
+// k_lstm_actor_pack (lg_recurrent.hip) and k_lstm_wide_actor_pack (lg_lstm_wide.hip).
+__device__ __forceinline__ void lstm_actor_pack_body(const float *__restrict__ w, const float *__restrict__ b, float *__restrict__ wp,
+                                                     float *__restrict__ bp, const int in, const int out, const int out_pad) {
+    const int n_w = out_pad * in;
+    const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (idx < n_w) {
+        const int lane = idx & 63, ks = in / 2, s = (idx >> 6) % ks, o = (idx >> 6) / ks;
+        const int unit = 32 * o + (lane & 31), k = 2 * s + (lane >> 5);
+        wp[idx] = unit < out ? w[(size_t)unit * in + k] : 0.0f;
+    } else if (idx < n_w + out_pad) {
+        const int unit = idx - n_w;
+        bp[unit] = unit < out ? b[unit] : 0.0f;
+    }
+}
+
 }  // namespace lg

@@ -50,39 +50,49 @@ def wide_memory_would_help(rnn):
     return lstm_unsupported_reason(rnn) is not None and lstm_unsupported_reason(rnn, wide=True) is None
 
 
-class DeviceLstm:
-    """One ``lg_lstm`` handle over a one-layer ``nn.LSTM``; with ``wide`` one ``lg_lstm_wide`` handle of liblegged_lstm_wide.so (up to 512
-    units), whose entry points have the same signatures."""
+# kind of a cell memory -> (its record in capi.LIBRARIES, the prefix of its entry points, the library's last-error entry point, its name in messages)
+MEMORY_KINDS = {
+    "lstm": ("main", "lg_lstm", "lg_last_error", "LSTM"),
+    "lstm_wide": ("lstm_wide", "lg_lstm_wide", "lg_lstm_wide_last_error", "LSTM"),       # up to 512 units; the signatures of lg_lstm_*
+    "gru": ("gru", "lg_gru", "lg_gru_last_error", "GRU"),                                # one state tensor: lg_gru_step has its own signature
+}
 
-    def __init__(self, rnn, device, wide=False):
-        why = lstm_unsupported_reason(rnn, wide)
+
+class DeviceMemory:
+    """One cell-memory handle (``lg_lstm``, ``lg_lstm_wide`` or ``lg_gru``, by ``kind``) over a one-layer ``nn.LSTM`` / ``nn.GRU``: create from
+    the host copies of the parameters, repack from the CUDA parameters, destroy.  The three libraries' entry points have the same
+    signatures but for ``*_step``."""
+
+    def __init__(self, rnn, device, kind):
+        record, self._pre, last_error, cell = MEMORY_KINDS[kind]
+        why = gru_unsupported_reason(rnn) if kind == "gru" else lstm_unsupported_reason(rnn, kind == "lstm_wide")
         if why is not None:
-            raise ValueError(f"no device LSTM cell for a {why}")
-        self.wide = bool(wide)
-        self.lib, self.rnn, self.device = (capi.load_lstm_wide_library() if wide else capi.load_library()), rnn, torch.device(device)
-        self._pre = "lg_lstm_wide" if wide else "lg_lstm"
-        self._last_error = self.lib.lg_lstm_wide_last_error if wide else self.lib.lg_last_error
+            raise ValueError(f"no device {cell} cell for a {why}")
+        self.kind, self.wide, self.gru = kind, kind == "lstm_wide", kind == "gru"
+        self.lib, self.rnn, self.device = capi.load(record), rnn, torch.device(device)
+        self._last_error = getattr(self.lib, last_error)
         self.num_in, self.hidden = rnn.input_size, rnn.hidden_size
         self.handle = C.c_void_p()
         host = [np.ascontiguousarray(p.detach().float().cpu().numpy()) for p in self._params()]
-        rc = getattr(self.lib, self._pre + "_create")(self.num_in, self.hidden, *[a.ctypes.data for a in host], self.device.index or 0,
-                                                      C.byref(self.handle))
+        self._call("_create", self.num_in, self.hidden, *[a.ctypes.data for a in host], self.device.index or 0, C.byref(self.handle))
+
+    def _call(self, entry, *args, lib=None):
+        """Entry point ``<prefix><entry>`` of ``lib`` (default: the handle's library); a RuntimeError with the library's message on failure."""
+        rc = getattr(lib or self.lib, self._pre + entry)(*args)
         if rc != 0:
-            raise RuntimeError(f"{self._pre}_create failed ({rc}): {self._last_error().decode()}")
+            raise RuntimeError(f"{self._pre}{entry} failed ({rc}): {self._last_error().decode()}")
 
     def _params(self):
         r = self.rnn
         return r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0
 
     def load_device(self):
-        """Repack from the module's CUDA parameters (``lg_lstm_load_device``): one launch on the current stream, no host copy."""
+        """Repack from the module's CUDA parameters (``*_load_device``): one launch on the current stream, no host copy."""
         ps = self._params()
         for p in ps:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise ValueError("DeviceLstm.load_device needs contiguous float32 CUDA parameters")
-        rc = getattr(self.lib, self._pre + "_load_device")(self.handle, *[p.data_ptr() for p in ps], torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"{self._pre}_load_device failed ({rc}): {self._last_error().decode()}")
+                raise ValueError(f"{type(self).__name__}.load_device needs contiguous float32 CUDA parameters")
+        self._call("_load_device", self.handle, *[p.data_ptr() for p in ps], torch.cuda.current_stream(self.device).cuda_stream)
 
     def __del__(self):
         try:
@@ -93,72 +103,40 @@ class DeviceLstm:
             pass
 
 
-class DeviceGru:
-    """One ``lg_gru`` handle of liblegged_gru.so over a one-layer ``nn.GRU``: ``DeviceLstm``'s twin."""
+class DeviceLstm(DeviceMemory):
+    """One ``lg_lstm`` handle over a one-layer ``nn.LSTM``; with ``wide`` one ``lg_lstm_wide`` handle of liblegged_lstm_wide.so (up to 512 units)."""
 
-    wide, gru = False, True
+    def __init__(self, rnn, device, wide=False):
+        super().__init__(rnn, device, "lstm_wide" if wide else "lstm")
+
+
+class DeviceGru(DeviceMemory):
+    """One ``lg_gru`` handle of liblegged_gru.so over a one-layer ``nn.GRU``."""
 
     def __init__(self, rnn, device):
-        why = gru_unsupported_reason(rnn)
-        if why is not None:
-            raise ValueError(f"no device GRU cell for a {why}")
-        self.lib, self.rnn, self.device = capi.load_gru_library(), rnn, torch.device(device)
-        self.num_in, self.hidden = rnn.input_size, rnn.hidden_size
-        self.handle = C.c_void_p()
-        host = [np.ascontiguousarray(p.detach().float().cpu().numpy()) for p in self._params()]
-        rc = self.lib.lg_gru_create(self.num_in, self.hidden, *[a.ctypes.data for a in host], self.device.index or 0, C.byref(self.handle))
-        if rc != 0:
-            raise RuntimeError(f"lg_gru_create failed ({rc}): {self.lib.lg_gru_last_error().decode()}")
-
-    def _params(self):
-        r = self.rnn
-        return r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0
-
-    def load_device(self):
-        """Repack from the module's CUDA parameters (``lg_gru_load_device``): one launch on the current stream, no host copy."""
-        ps = self._params()
-        for p in ps:
-            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                raise ValueError("DeviceGru.load_device needs contiguous float32 CUDA parameters")
-        rc = self.lib.lg_gru_load_device(self.handle, *[p.data_ptr() for p in ps], torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"lg_gru_load_device failed ({rc}): {self.lib.lg_gru_last_error().decode()}")
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self.lib.lg_gru_destroy(self.handle)
-                self.handle = C.c_void_p()
-        except Exception:
-            pass
+        super().__init__(rnn, device, "gru")
 
 
 def gru_step(lib, gru_a, gru_c, x_a, x_c, reset, h_in_a, h_out_a, h_in_c, h_out_c, num_envs, stream):
     """``lg_gru_step`` on tensors; a role is absent when its ``DeviceGru`` is None.  ``lib`` is liblegged_gru.so."""
     p = lambda t, present: None if (t is None or not present) else t.data_ptr()
     a, c = gru_a is not None, gru_c is not None
-    rc = lib.lg_gru_step(gru_a.handle if a else None, gru_c.handle if c else None, p(x_a, a), p(x_c, c), p(reset, True),
-                         p(h_in_a, a), p(h_out_a, a), p(h_in_c, c), p(h_out_c, c), int(num_envs), stream)
-    if rc != 0:
-        raise RuntimeError(f"lg_gru_step failed ({rc}): {lib.lg_gru_last_error().decode()}")
+    (gru_a if a else gru_c)._call("_step", gru_a.handle if a else None, gru_c.handle if c else None, p(x_a, a), p(x_c, c), p(reset, True),
+                                  p(h_in_a, a), p(h_out_a, a), p(h_in_c, c), p(h_out_c, c), int(num_envs), stream, lib=lib)
 
 
 def lstm_step(lib, lstm_a, lstm_c, x_a, x_c, reset, state_in_a, state_out_a, state_in_c, state_out_c, num_envs, stream):
     """``lg_lstm_step`` on tensors; a role is absent when its ``DeviceLstm`` is None.  ``state_*`` are ``(h, c)`` pairs.  ``lib`` is the
-    library of the handles: with ``wide`` memories (liblegged_lstm_wide.so) the launch is ``lg_lstm_wide_step``."""
-    wide = getattr(lstm_a if lstm_a is not None else lstm_c, "wide", False)
-    step, last_error, name = ((lib.lg_lstm_wide_step, lib.lg_lstm_wide_last_error, "lg_lstm_wide_step") if wide
-                              else (lib.lg_lstm_step, lib.lg_last_error, "lg_lstm_step"))
+    library of the handles: with ``wide`` memories (liblegged_lstm_wide.so) the launch is ``lg_lstm_wide_step``, by the handles' kind."""
     p = lambda t: None if t is None else t.data_ptr()
     ha, ca = state_in_a if lstm_a is not None else (None, None)
     hoa, coa = state_out_a if lstm_a is not None else (None, None)
     hc, cc = state_in_c if lstm_c is not None else (None, None)
     hoc, coc = state_out_c if lstm_c is not None else (None, None)
-    rc = step(lstm_a.handle if lstm_a is not None else None, lstm_c.handle if lstm_c is not None else None,
-              p(x_a) if lstm_a is not None else None, p(x_c) if lstm_c is not None else None, p(reset),
-              p(ha), p(ca), p(hoa), p(coa), p(hc), p(cc), p(hoc), p(coc), int(num_envs), stream)
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {last_error().decode()}")
+    (lstm_a if lstm_a is not None else lstm_c)._call(
+        "_step", lstm_a.handle if lstm_a is not None else None, lstm_c.handle if lstm_c is not None else None,
+        p(x_a) if lstm_a is not None else None, p(x_c) if lstm_c is not None else None, p(reset),
+        p(ha), p(ca), p(hoa), p(coa), p(hc), p(cc), p(hoc), p(coc), int(num_envs), stream, lib=lib)
 
 
 class DeviceLstmActor:

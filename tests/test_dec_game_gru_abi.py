@@ -80,8 +80,14 @@ def test_build_lists_name_the_source_the_headers_and_the_resources_file():
     assert not any(os.path.basename(h) in ("lg_gru.h", HEADER) for h in entry.HIP_HEADERS)      # the main library is not stale when they change
     assert "lg_gru.h" in entry.GRU_HEADERS and '#include "lg_gru.h"' in open(os.path.join(CSRC, entry.GRU_SOURCE)).read()
     assert "struct lg_gru {" not in open(os.path.join(CSRC, entry.GRU_SOURCE)).read()
+    # build() writes that resources file, looks those symbols up and reports that library: through the library's row of the table
+    spec = next(s for s in entry.LIBS if s.key == "dec_game_gru")
+    assert (spec.resources, spec.symbols, spec.target) == (entry.DEC_GAME_GRU_RESOURCES, "DEC_GAME_GRU_SYMBOLS", entry.DEC_GAME_GRU_LIB)
+    assert set(spec.checks) == {"no_spill", "two_waves"}
     source = inspect.getsource(entry.build)
-    assert "DEC_GAME_GRU_RESOURCES" in source and "capi.DEC_GAME_GRU_SYMBOLS" in source and re.search(r"\[build\] ok:.*DEC_GAME_GRU_LIB", source)
+    assert source.count("for spec in LIBS:") == 2 and "_check_resources(spec" in source and "getattr(capi, spec.symbols)" in source
+    assert re.search(r"\[build\] ok:.*spec\.target for spec in LIBS", source)
+    assert "_write_resources(table, spec.resources)" in inspect.getsource(entry._check_resources)
 
 
 @pytest.fixture(scope="module")
@@ -101,7 +107,7 @@ def test_the_library_exports_the_symbols_sizes_its_structs_and_fails_loudly_when
     assert (lib.lg_dec_game_gru_sizeof(0), lib.lg_dec_game_gru_sizeof(1), lib.lg_dec_game_gru_sizeof(2), lib.lg_dec_game_gru_sizeof(-1)) == (32, 32, -1, -1)
     monkeypatch.setenv("LG_DEC_GAME_GRU_LIB", "/nonexistent/liblegged_dec_game_gru.so")
     assert capi.dec_game_gru_library_path() == "/nonexistent/liblegged_dec_game_gru.so"
-    monkeypatch.setattr(capi, "_dec_game_gru_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_game_gru"], "handle", None)
     with pytest.raises(RuntimeError, match="not built; run"):
         capi.load_dec_game_gru_library()
     with pytest.raises(RuntimeError, match="not built; run"):
@@ -315,7 +321,7 @@ def test_recurrent_launches_without_the_key_and_for_a_mixed_pair_are_todays(caps
 
 def test_recurrent_launches_of_a_shared_pair(lib, monkeypatch, capsys):
     pair = (_stub(shared=True), _stub(shared=True))
-    monkeypatch.setattr(capi, "_dec_game_gru_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_game_gru"], "handle", None)
     env = _env()
     if not os.path.isfile(capi.dec_game_recurrent_library_path()):
         import __graft_entry__ as entry
@@ -328,14 +334,14 @@ def test_recurrent_launches_of_a_shared_pair(lib, monkeypatch, capsys):
     assert got is capi.load_dec_game_gru_library() and shared is False
     assert capsys.readouterr().out == f"[{env.TASK}] recurrent actor launch unavailable (wide precision 0); {SEPARATE}\n"
     # without liblegged_dec_game_recurrent.so: likewise
-    monkeypatch.setattr(capi, "_dec_game_recurrent_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_game_recurrent"], "handle", None)
     monkeypatch.setenv("LG_DEC_GAME_RECURRENT_LIB", "/nonexistent/liblegged_dec_game_recurrent.so")
     env = _env()
     got, shared = env._recurrent_launches(*pair)
     out = capsys.readouterr().out
     assert got is capi.load_dec_game_gru_library() and shared is False and out.count("\n") == 1 and "liblegged_dec_game_recurrent.so" in out and SEPARATE in out
     # without the new library: everything separate, one line that names it
-    monkeypatch.setattr(capi, "_dec_game_gru_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_game_gru"], "handle", None)
     monkeypatch.setenv("LG_DEC_GAME_GRU_LIB", "/nonexistent/liblegged_dec_game_gru.so")
     env = _env()
     assert env._recurrent_launches(*pair) == (None, False)

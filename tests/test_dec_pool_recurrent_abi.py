@@ -65,7 +65,7 @@ def test_the_fifth_library_exports_the_symbols_and_the_other_libraries_do_not(li
     assert "dec_lstm_actor_role(const LstmActorArgs" not in text and "dec_lstm_actor_role(const LstmActorArgs" not in open(os.path.join(CSRC, entry.DEC_GAME_REC_SOURCE)).read()
     monkeypatch.setenv("LG_DEC_POOL_RECURRENT_LIB", "/nonexistent/liblegged_dec_pool_recurrent.so")
     assert capi.dec_pool_recurrent_library_path() == "/nonexistent/liblegged_dec_pool_recurrent.so"
-    monkeypatch.setattr(capi, "_dec_pool_recurrent_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_pool_recurrent"], "handle", None)
     with pytest.raises(RuntimeError, match="not built"):
         capi.load_dec_pool_recurrent_library()
 

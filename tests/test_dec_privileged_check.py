@@ -147,7 +147,7 @@ def test_the_library_exports_the_symbols_and_is_built_from_its_own_source(libs, 
     assert {"lg_dec_game_post.h", HEADER} <= included
     monkeypatch.setenv("LG_DEC_GAME_PRIVILEGED_LIB", "/nonexistent/liblegged_dec_game_privileged.so")
     assert capi.dec_game_privileged_library_path() == "/nonexistent/liblegged_dec_game_privileged.so"
-    monkeypatch.setattr(capi, "_dec_game_privileged_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_game_privileged"], "handle", None)
     with pytest.raises(RuntimeError, match=r"is not built; run .*build\(\)"):
         capi.load_dec_game_privileged_library()
 

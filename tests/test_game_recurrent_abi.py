@@ -70,7 +70,7 @@ def test_the_new_library_exports_the_symbols_and_the_main_library_does_not(libs,
     source = open(os.path.join(CSRC, "lg_recurrent.hip")).read()
     assert '#include "lg_lstm_actor_body.h"' in source
     # ... and the new library's reads every shared header its source includes
-    want = {"lg_policy.h", "lg_device.h", "lg_game_common.h", "lg_recurrent.h", "lg_host.h", "lg_lstm_actor_body.h"}
+    want = {"lg_policy.h", "lg_device.h", "lg_game_common.h", "lg_recurrent.h", "lg_host.h", "lg_lstm_actor_body.h", "lg_lib_error.h", "lg_memory_host.h"}
     assert want <= set(entry.GAME_REC_HEADERS)
     assert {os.path.basename(h) for h in entry.GAME_REC_HEADERS if os.path.isabs(h)} >= {"legged_game.h", "legged_game_recurrent.h"}
     included = set(re.findall(r'#include\s+"([^"]+)"', open(os.path.join(CSRC, entry.GAME_REC_SOURCE)).read()))

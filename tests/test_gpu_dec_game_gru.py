@@ -368,7 +368,7 @@ def test_env_takes_the_separate_launches_without_the_library(tmp_path, monkeypat
     from legged_games_gym_amd import capi
     A, B = _two_envs(tmp_path)
     actors_a, actors_b = _pair(True), _pair(False)
-    monkeypatch.setattr(capi, "_dec_game_gru_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_game_gru"], "handle", None)
     monkeypatch.setenv("LG_DEC_GAME_GRU_LIB", str(tmp_path / "liblegged_dec_game_gru_absent.so"))
     cell, act = _counted(monkeypatch)
     said = ""

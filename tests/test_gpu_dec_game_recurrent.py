@@ -554,7 +554,7 @@ def test_env_takes_the_separate_launches_at_precision_0_on_rc_minus_4_and_withou
     monkeypatch.setattr(capi, "dec_game_lstm_act", real)
 
     # without the library: lg_lstm_step per agent as well
-    monkeypatch.setattr(capi, "_dec_game_recurrent_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["dec_game_recurrent"], "handle", None)
     monkeypatch.setenv("LG_DEC_GAME_RECURRENT_LIB", str(tmp_path / "absent.so"))
     got = act()
     out = capsys.readouterr().out

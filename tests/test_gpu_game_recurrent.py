@@ -326,7 +326,7 @@ def test_env_takes_the_separate_launches_at_precision_0_on_rc_minus_4_and_withou
     monkeypatch.setattr(capi, "game_lstm_act", real)
 
     # without the library
-    monkeypatch.setattr(capi, "_game_recurrent_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["game_recurrent"], "handle", None)
     monkeypatch.setenv("LG_GAME_RECURRENT_LIB", str(tmp_path / "absent.so"))
     got = act()
     out = capsys.readouterr().out

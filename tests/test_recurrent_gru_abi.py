@@ -67,7 +67,7 @@ def test_the_new_library_exports_the_symbols_and_the_main_library_does_not(libs,
     assert {os.path.basename(h) for h in entry.GRU_OWN_HEADERS} == {"lg_gru_cell_body.h", HEADER}
     monkeypatch.setenv("LG_GRU_LIB", "/nonexistent/liblegged_gru.so")
     assert capi.gru_library_path() == "/nonexistent/liblegged_gru.so"
-    monkeypatch.setattr(capi, "_gru_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["gru"], "handle", None)
     with pytest.raises(RuntimeError, match="not built; run"):
         capi.load_gru_library()
 

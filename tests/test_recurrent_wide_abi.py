@@ -64,7 +64,7 @@ def test_the_new_library_exports_the_symbols_and_the_main_library_does_not(libs,
     assert {os.path.basename(i) for i in included} == {os.path.basename(h) for h in entry.LSTM_WIDE_HEADERS}, included
     monkeypatch.setenv("LG_LSTM_WIDE_LIB", "/nonexistent/liblegged_lstm_wide.so")
     assert capi.lstm_wide_library_path() == "/nonexistent/liblegged_lstm_wide.so"
-    monkeypatch.setattr(capi, "_lstm_wide_lib", None)
+    monkeypatch.setattr(capi.LIBRARIES["lstm_wide"], "handle", None)
     with pytest.raises(RuntimeError, match="not built; run"):
         capi.load_lstm_wide_library()
 
