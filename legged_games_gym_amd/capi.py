@@ -794,11 +794,11 @@ LIBRARIES["dec_game_recurrent"] = Library("liblegged_dec_game_recurrent.so", "LG
 dec_game_recurrent_library_path, bind_dec_game_recurrent, load_dec_game_recurrent_library = _library_names("dec_game_recurrent")
 
 
-def dec_lstm_roles(roles) -> "C.Array":
+def dec_lstm_roles(roles, entry: str = "lg_dec_lstm_step") -> "C.Array":
     """``lg_dec_lstm_role[4]`` from four entries in the order of ``DEC_LSTM_ROLES``: None (absent), or
-    ``(handle, x, h_in, c_in, h_out, c_out)`` with device addresses."""
+    ``(handle, x, h_in, c_in, h_out, c_out)`` with device addresses.  ``entry``: the entry point a wrong count is reported for."""
     if len(roles) != 4:
-        raise ValueError("lg_dec_lstm_step takes four roles (None = absent)")
+        raise ValueError(f"{entry} takes four roles (None = absent)")
     arr = (lg_dec_lstm_role * 4)()
     for slot, role in zip(arr, roles):
         if role is not None:
@@ -893,15 +893,8 @@ def dec_pool_lstm_step(roles, pool_pred, block_slot_pred: Optional[int], pool_pr
     """``lg_dec_pool_lstm_step``: ``lg_dec_lstm_step`` with the weights of a pooled ACTOR memory chosen per 32-env block.  ``roles`` as for
     ``dec_lstm_step`` (a pooled role's handle may be None: give its five buffers); ``pool_*``: an ``lg_dec_rpool`` handle or None,
     ``block_slot_*``: the device address of its int32 slot table."""
-    if not isinstance(roles, C.Array):
-        if len(roles) != 4:
-            raise ValueError("lg_dec_pool_lstm_step takes four roles (None = absent)")
-        arr = (lg_dec_lstm_role * 4)()
-        for slot, role in zip(arr, roles):
-            if role is not None:
-                slot.l, slot.x, slot.h_in, slot.c_in, slot.h_out, slot.c_out = (getattr(v, "value", v) for v in role)
-        roles = arr
-    _dec_pool_recurrent_call("lg_dec_pool_lstm_step", roles, pool_pred, block_slot_pred, pool_prey, block_slot_prey, reset, int(num_envs), stream)
+    arr = roles if isinstance(roles, C.Array) else dec_lstm_roles(roles, "lg_dec_pool_lstm_step")
+    _dec_pool_recurrent_call("lg_dec_pool_lstm_step", arr, pool_pred, block_slot_pred, pool_prey, block_slot_prey, reset, int(num_envs), stream)
 
 
 def dec_pool_lstm_act(pred_actor, prey_actor, ll_policy, pool_pred, block_slot_pred: Optional[int], pool_prey, block_slot_prey: Optional[int],

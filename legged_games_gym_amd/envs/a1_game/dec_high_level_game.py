@@ -228,89 +228,140 @@ class DecHighLevelGame(GameBase):
         return replay
 
     # ------------------------------------------------------------------ hot path with both actors on the device
+    def _who_acts(self, fused_pred, fused_prey):
+        """The pair of a policy step, resolved once: ``(live, pools, recurrent)``, the first two by agent.  ``fused_*`` may each be an
+        ``rl.OpponentPool`` (``rl.RecurrentOpponentPool``) instead of an actor: ``pools`` then holds it (else None) and ``live`` its live actor,
+        which supplies seed, step source, output buffers and, recurrent, the state.  ``recurrent``: ``_recurrent_pair``, with its refusals."""
+        pools = {a: f if getattr(f, "is_opponent_pool", False) else None for a, f in zip(AGENTS, (fused_pred, fused_prey))}
+        live = {"pred": _live(fused_pred), "prey": _live(fused_prey)}
+        return live, pools, self._recurrent_pair(live["pred"], live["prey"], pools["pred"], pools["prey"])
+
+    @staticmethod
+    def _slot_args(pools, n):
+        """What a pooled launch takes per agent, predator first: ``pool handle, address of its slot table`` (read per call), or ``None, None``."""
+        return [a for pool in (pools["pred"], pools["prey"]) for a in ((pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None))]
+
+    def _cell_launch(self, roles, gru, slots, stream):
+        """The shared cell launch on four role entries (``RecurrentFusedActor.cell_roles`` of the predator, then of the prey):
+        ``lg_dec_gru_step`` for a GRU pair (the entries hold one state tensor each way), ``lg_dec_pool_lstm_step`` given ``slots``
+        (``_slot_args``: the weights of a pooled actor memory per 32-env block), else ``lg_dec_lstm_step``.  Rows that ``reset_buf`` of the
+        previous step marks start from a zero state."""
+        if gru:
+            capi.dec_gru_step(roles, self.reset_buf.data_ptr(), self.num_envs, stream)
+        elif slots is not None:
+            capi.dec_pool_lstm_step(roles, *slots, self.reset_buf.data_ptr(), self.num_envs, stream)
+        else:
+            capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), self.num_envs, stream)
+
+    def _actor_launch(self, live, slots, B, ll_actions, mean, h, obs, det, outputs, stream):
+        """The shared actor launch, the three actors and both clips: ``lg_dec_game_act`` on the observations, with ``h`` (the two actor
+        memories' outputs) ``lg_dec_game_lstm_act`` on those; given ``slots`` (``_slot_args``) the pooled ``lg_dec_pool_act`` /
+        ``lg_dec_pool_lstm_act``, which take a pooled role's weights, biases and std per 32-env block from the member its slot table names.
+        ``live``, ``mean``, ``h``, ``obs``, ``det`` (deterministic), ``outputs`` are by agent; an observation tensor may be None in the recurrent
+        warm-up, ``outputs`` are ``capi.lg_dec_act_outputs`` or None.  Returns rc: 0, or -4 when the actor triple or the wide precision has
+        no shared kernel and nothing was launched; no noise stream is advanced here."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        pred, prey = live["pred"], live["prey"]
+        step, ctr = prey.peek_step()
+        front = (pred.handle, prey.handle, self._ll_fused.handle, *(slots or ()), self._P, B)
+        tail = (ptr(obs["pred"]), ptr(obs["prey"]), self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean["pred"].data_ptr(), mean["prey"].data_ptr(),
+                pred.seed, prey.seed, step, ctr, det["pred"], det["prey"], outputs["pred"], outputs["prey"], stream)
+        if h is None:
+            return (capi.dec_game_act if slots is None else capi.dec_pool_act)(*front, *tail)
+        return (capi.dec_game_lstm_act if slots is None else capi.dec_pool_lstm_act)(*front, h["pred"].data_ptr(), h["prey"].data_ptr(), *tail)
+
     def _act(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_pred_out, obs_prey_out, deterministic_pred, deterministic_prey, out_pred=None, out_prey=None,
              with_critic_memory=(), critic_obs=None):
         """``lg_dec_game_act``: both commands = clip(actor(obs) + noise), the prey's into the low-level commands, the low-level actions, and
         the prey's observations copied to ``obs_prey_out`` (where ``lg_dec_game_post`` then shifts the history in place) -- one launch.
-        Separate launches when the actor triple or the wide precision has no shared kernel (rc -4).  ``out_*``: dicts of optional float32
-        outputs ``sample`` / ``sigma`` / ``log_prob`` / ``obs_copy`` (the rollout storage's copy of the observations read).
-        ``fused_pred`` / ``fused_prey`` may each be an ``rl.OpponentPool`` instead of a ``FusedActor``: the launch is then ``lg_dec_pool_act``
-        (include/legged_dec_game_pool.h), which takes that role's weights, biases and std per 32-env block from the pool member its slot table
-        names; the pool's ``live`` actor supplies seed, step source and output buffers.  Its rc -4 path is one ``lg_policy_act`` on all envs
-        per member in use, rows selected by block.
-        Two ``RecurrentFusedActor`` s take ``_act_recurrent`` (``with_critic_memory``: the agents whose critic memory moves too;
-        ``critic_obs``: agent -> what that memory reads, None = the agent's observations).
+        Separate launches when the actor triple or the wide precision has no shared kernel (rc -4, decided per call:
+        ``lg_mlp_wide_set_precision`` may change between calls): ``lg_policy_act`` x 3 + ``lg_dec_game_pre``.  ``out_*``: dicts of optional
+        float32 outputs ``sample`` / ``sigma`` / ``log_prob`` / ``obs_copy`` (the rollout storage's copy of the observations read).
+        ``fused_pred`` / ``fused_prey`` may each be an ``rl.OpponentPool`` instead of a ``FusedActor`` (``_who_acts``): the launch is then
+        ``lg_dec_pool_act`` (include/legged_dec_game_pool.h).  Its rc -4 path is one ``lg_policy_act`` on all envs per member in use, rows
+        selected by block.
+        Two ``RecurrentFusedActor`` s: the memory stage first (``_step_memories``; ``with_critic_memory``: the agents whose critic memory
+        moves too; ``critic_obs``: agent -> what that memory reads, None = the agent's observations), then ``lg_dec_game_lstm_act`` on the
+        two new ``h`` -- ``lg_dec_pool_lstm_act`` given an ``rl.RecurrentOpponentPool`` (include/legged_dec_pool_recurrent.h).  Separate
+        launches (``lg_lstm_actor_act`` x 2, per member in use and rows selected by block for a pooled role, + ``lg_dec_game_pre`` +
+        low-level ``lg_policy_act``) on rc -4, at wide precision 0 or without the library.
+        ``self.last_act_rc``: 0 when the shared actor launch ran, else -4.
         Returns ``(command_pred, mean_pred), (command_prey, mean_prey), ll_actions, buffers``."""
         ll, n = self.ll_env, self.num_envs
-        pool_pred, pool_prey = (f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey))
-        fused_pred, fused_prey = _live(fused_pred), _live(fused_prey)
-        recurrent = self._recurrent_pair(fused_pred, fused_prey, pool_pred, pool_prey)
+        live, pools, recurrent = self._who_acts(fused_pred, fused_prey)
+        obs, det = {"pred": obs_pred_in, "prey": obs_prey_in}, {"pred": deterministic_pred, "prey": deterministic_prey}
         for name, t, width in (("predator", obs_pred_in, self.num_obs_pred), ("prey", obs_prey_in, self.num_obs_prey)):
             if t.shape != (n, width) or t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError(f"{name} observations must be a contiguous float32 [{n},{width}] tensor")
-        out_pred, out_prey = dict(out_pred or {}), dict(out_prey or {})
-        for out, na, no in ((out_pred, self.num_actions_pred, self.num_obs_pred), (out_prey, self.num_actions_prey, self.num_obs_prey)):
-            unknown = set(out) - {"sample", "sigma", "log_prob", "obs_copy"}
+        out = {"pred": dict(out_pred or {}), "prey": dict(out_prey or {})}
+        for o, na, no in ((out["pred"], self.num_actions_pred, self.num_obs_pred), (out["prey"], self.num_actions_prey, self.num_obs_prey)):
+            unknown = set(o) - {"sample", "sigma", "log_prob", "obs_copy"}
             if unknown:
                 raise ValueError(f"unknown optional outputs {sorted(unknown)}")
-            self._check_output("sample", out.get("sample"), n * na)
-            self._check_output("sigma", out.get("sigma"), n * na)
-            self._check_output("log_prob", out.get("log_prob"), n)
-            self._check_output("obs_copy", out.get("obs_copy"), n * no)
-        command_pred, mean_pred = fused_pred.output_buffers(n)
-        command_prey, mean_prey = fused_prey.output_buffers(n)
+            self._check_output("sample", o.get("sample"), n * na)
+            self._check_output("sigma", o.get("sigma"), n * na)
+            self._check_output("log_prob", o.get("log_prob"), n)
+            self._check_output("obs_copy", o.get("obs_copy"), n * no)
+        command, mean = {}, {}
+        for a in AGENTS:
+            command[a], mean[a] = live[a].output_buffers(n)
+        result = (command["pred"], mean["pred"]), (command["prey"], mean["prey"])
         ll_actions = self._ll_fused.output_buffers(n)[0]
-        B = self._bind(command_pred, command_prey, obs_pred_out, obs_prey_out)
+        B = self._bind(command["pred"], command["prey"], obs_pred_out, obs_prey_out)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         ptr = lambda t: None if t is None else t.data_ptr()
         carry = obs_prey_out is not obs_prey_in
 
-        def outputs(out, extra_copy):
-            o = capi.lg_dec_act_outputs()
-            o.sample, o.sigma, o.log_prob = ptr(out.get("sample")), ptr(out.get("sigma")), ptr(out.get("log_prob"))
-            o.obs_copy = ptr(out.get("obs_copy")) if out.get("obs_copy") is not None else extra_copy
-            return o
+        def outputs(o, extra_copy):
+            s = capi.lg_dec_act_outputs()
+            s.sample, s.sigma, s.log_prob = ptr(o.get("sample")), ptr(o.get("sigma")), ptr(o.get("log_prob"))
+            s.obs_copy = ptr(o.get("obs_copy")) if o.get("obs_copy") is not None else extra_copy
+            return s
         # the kernel has one observation copy per agent: the prey's goes to the other ping-pong buffer (history carry) unless the caller asks
         # for its own copy, in which case the carry is a separate copy below
-        want_prey_copy = out_prey.get("obs_copy") is not None
-        (step_y, ctr_y), (step_p, ctr_p) = fused_prey.peek_step(), fused_pred.peek_step()
-        if (step_y, ctr_y) != (step_p, ctr_p):
+        want_prey_copy = out["prey"].get("obs_copy") is not None
+        if live["prey"].peek_step() != live["pred"].peek_step():
             raise ValueError("the two FusedActors must count their noise steps alike (both on the low-level sim's device step counter, or both on the host)")
-        if fused_pred.seed == fused_prey.seed:
+        if live["pred"].seed == live["prey"].seed:
             raise ValueError("the two FusedActors need different seeds: they draw their noise under the same purposes")
+        pooled = pools["pred"] is not None or pools["prey"] is not None
+        slots = self._slot_args(pools, n) if pooled else None
+        h, shared, gru = None, True, False
         if recurrent:
-            return self._act_recurrent(fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
-                                       outputs, B, with_critic_memory, pool_pred, pool_prey, critic_obs)
-        if pool_pred is None and pool_prey is None:
-            rc = capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, obs_pred_in.data_ptr(), obs_prey_in.data_ptr(),
-                                   ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed,
-                                   step_y, ctr_y, deterministic_pred, deterministic_prey, outputs(out_pred, None),
-                                   outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
-        else:
-            pool_args = [a for pool in (pool_pred, pool_prey) for a in ((pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None))]
-            rc = capi.dec_pool_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *pool_args, self._P, B, obs_pred_in.data_ptr(),
-                                   obs_prey_in.data_ptr(), ll.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(),
-                                   fused_pred.seed, fused_prey.seed, step_y, ctr_y, deterministic_pred, deterministic_prey, outputs(out_pred, None),
-                                   outputs(out_prey, obs_prey_out.data_ptr() if carry else None), stream)
-        self.last_act_rc = rc                                  # 0: the shared launch ran; -4: the separate launches below
+            h, shared, gru = self._step_memories(live, pools, slots, obs, with_critic_memory, critic_obs, stream)
+        rc = -4                                                # 0: the shared launch ran; -4: the separate launches below
+        if shared:
+            # a GRU pair on the shared launches stores the log-prob the separate launches store (torch's, below): the launch leaves the
+            # unclipped sample for it, in the caller's tensor or in a buffer kept here, and writes no log-prob of its own
+            launched = {a: self._gru_log_prob_outputs(a, out[a], live[a]) if gru else out[a] for a in AGENTS}
+            structs = {"pred": outputs(launched["pred"], None), "prey": outputs(launched["prey"], obs_prey_out.data_ptr() if carry else None)}
+            rc = self._actor_launch(live, slots, B, ll_actions, mean, h, obs, det, structs, stream)
+            if rc != 0 and recurrent:
+                self._say_separate("no kernel for this actor pair", pooled=pooled)
+        self.last_act_rc = rc
         if rc == 0:
-            fused_pred.next_step(); fused_prey.next_step()     # the launch used this step of both noise streams
+            live["pred"].next_step(); live["prey"].next_step()     # the launch used this step of both noise streams
             if carry and want_prey_copy:
                 obs_prey_out.copy_(obs_prey_in)
-            return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
-        # rc -4, nothing was launched: lg_policy_act x 3 + lg_dec_game_pre (decided per call: lg_mlp_wide_set_precision may change between calls)
-        for fused, pool, obs_in, det, out in ((fused_pred, pool_pred, obs_pred_in, deterministic_pred, out_pred),
-                                              (fused_prey, pool_prey, obs_prey_in, deterministic_prey, out_prey)):
-            if pool is None:
-                command, mean = fused.act_with_mean(obs_in, det)
+            if gru:
+                for a in AGENTS:
+                    if out[a].get("log_prob") is not None:       # _fill_optional_outputs' expression on the same sample, mean and std: the same bits
+                        out[a]["log_prob"].view(n).copy_(torch.distributions.Normal(mean[a], live[a].ac.std.detach()).log_prob(launched[a]["sample"].view(n, -1)).sum(-1))
+            return *result, ll_actions, B
+        # nothing was launched: each agent's actor on what it reads (the observations; behind a memory, its output) -- of a pool per member in
+        # use, rows by block, std [n, actions] of the rows' members -- then the clips and the low-level actor
+        for a in AGENTS:
+            x = h[a] if recurrent else obs[a]
+            if pools[a] is None:
+                (sample, mu), std = (live[a].fused if recurrent else live[a]).act_with_mean(x, det[a]), live[a].ac.std.detach()
             else:
-                command, mean, std = pool.act_separate(obs_in, det)          # per member in use, rows by block; std [n, actions] of the rows' members
-            self._fill_optional_outputs(out, n, command, mean, std if pool is not None else fused.ac.std.detach(), obs_in)
+                sample, mu, std = pools[a].act_separate(x, det[a])
+            self._fill_optional_outputs(out[a], n, sample, mu, std, obs[a])
         if carry:
             obs_prey_out.copy_(obs_prey_in)
         capi.dec_game_pre(self._P, B, stream)
         ll_actions = self.ll_policy(ll.obs_buf)
-        return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
+        return *result, ll_actions, B
 
     # ------------------------------------------------------------------ recurrent policies
     @staticmethod
@@ -330,15 +381,11 @@ class DecHighLevelGame(GameBase):
         0 takes the separate actor launches, and a build without the library takes separate launches throughout (a one-line message the
         first time for each reason).  Decided per call: ``lg_mlp_wide_set_precision`` may change between calls.  ``pooled``: the library of
         the pooled launches (``lg_dec_pool_lstm_step`` / ``lg_dec_pool_lstm_act``) instead."""
-        try:
-            lib = capi.load_dec_pool_recurrent_library() if pooled else capi.load_dec_game_recurrent_library()
-        except (RuntimeError, OSError) as exc:
-            self._say_separate(f"{type(exc).__name__}: {exc}", say, pooled)
-            return None, False
-        if fused.lib.lg_mlp_wide_set_precision(-1) != 1:              # (an invalid mode changes nothing and returns the current one)
+        lib = self._load_or_say(capi.load_dec_pool_recurrent_library if pooled else capi.load_dec_game_recurrent_library, say, pooled)
+        if lib is not None and self._wide_precision_0(fused):
             self._say_separate("wide precision 0", say, pooled)
             return lib, False
-        return lib, True
+        return lib, lib is not None
 
     def _recurrent_launches(self, fused_pred, fused_prey, say=True, pooled=False):
         """``_recurrent_library`` for a pair of actors.  An actor with ``wide`` memories (``RecurrentFusedActor(wide=True)`` above 256 units) holds
@@ -363,7 +410,7 @@ class DecHighLevelGame(GameBase):
     def _gru_log_prob_outputs(self, agent, out, fused):
         """The optional outputs handed to ``lg_dec_game_lstm_act`` for a GRU pair on the shared launches: ``out`` itself when no log-prob is
         asked for; otherwise ``out`` without its log-prob and with a sample tensor (the caller's, or one kept per agent so that a captured
-        graph finds it at the same address), from which ``_act_recurrent`` then fills the log-prob the way the separate launches do.  The
+        graph finds it at the same address), from which ``_act`` then fills the log-prob the way the separate launches do.  The
         key ``dec_gru_shared`` so changes which launches run and not one bit of what a rollout stores."""
         if out.get("log_prob") is None:
             return out
@@ -380,174 +427,76 @@ class DecHighLevelGame(GameBase):
         be used now)``.  The cell launch ``lg_dec_gru_step`` needs only the first; the actor MLP behind a GRU memory is an ``lg_lstm_actor`` on
         ``h``, so the actor launch is the LSTM pair's, under its conditions.  Without the GRU library everything takes the separate launches
         (a one-line message that names it); without liblegged_dec_game_recurrent.so or at wide precision 0 only the actors do."""
-        try:
-            lib = capi.load_dec_game_gru_library()
-        except (RuntimeError, OSError) as exc:
-            self._say_separate(f"{type(exc).__name__}: {exc}", say)
-            return None, False
-        return lib, self._recurrent_library(fused, say=say)[1]
+        lib = self._load_or_say(capi.load_dec_game_gru_library, say)
+        return lib, lib is not None and self._recurrent_library(fused, say=say)[1]
 
     def _say_separate(self, why, say=True, pooled=False):
-        said = self.__dict__.setdefault("_separate_said", set())
-        if say and (why, pooled) not in said:
-            said.add((why, pooled))
-            if pooled:
-                print(f"[{self.TASK}] pooled recurrent actor launch unavailable ({why}); lg_lstm_actor_act per member + lg_dec_game_pre + lg_policy_act")
-            else:
-                print(f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act x 2 + lg_dec_game_pre + lg_policy_act")
+        if pooled:
+            line = f"[{self.TASK}] pooled recurrent actor launch unavailable ({why}); lg_lstm_actor_act per member + lg_dec_game_pre + lg_policy_act"
+        else:
+            line = f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act x 2 + lg_dec_game_pre + lg_policy_act"
+        self._say_once((why, pooled), say, line)
 
-    def _act_recurrent(self, fused_pred, fused_prey, obs_pred_in, obs_prey_in, obs_prey_out, deterministic_pred, deterministic_prey, out_pred, out_prey,
-                       outputs, B, with_critic_memory, pool_pred=None, pool_prey=None, critic_obs=None):
-        """``_act`` for two ``RecurrentFusedActor`` s (arguments already checked there).  ``lg_dec_lstm_step``: both actor memories on the
-        observations they read, and the critic memory of every agent in ``with_critic_memory``, in one launch on the actors' own ``(h, c)``
-        slots (read ``[flip]``, write ``[1 - flip]``); rows that ``reset_buf`` of the previous step marks start from a zero state.  Then
-        ``lg_dec_game_lstm_act`` on the two new ``h``.  The critic memories' outputs are left in ``self._critic_out`` (agent -> tensor, None
-        when it did not move).  Separate launches (``lg_lstm_actor_act`` x 2 + ``lg_dec_game_pre`` + low-level ``lg_policy_act``) on rc -4, at wide
-        precision 0 or without the library (then ``lg_lstm_step`` per agent as well).
-        Two GRU actors with ``shared_gru``: the cell launch is ``lg_dec_gru_step`` on the 1-tuple slots ``(h,)``, everything after it the same.
-        ``pool_pred`` / ``pool_prey``: an ``rl.RecurrentOpponentPool`` whose live actor that agent's ``fused_*`` is.  The two launches are then
-        ``lg_dec_pool_lstm_step`` / ``lg_dec_pool_lstm_act`` (include/legged_dec_pool_recurrent.h), which take that role's weights per 32-env
-        block from the pool member its slot table names; the state is the live actor's.  Their separate launches are one ``lg_lstm_step`` /
-        ``lg_lstm_actor_act`` per member in use on all envs, rows selected by block (``step_memory_separate`` / ``act_separate``).
-        ``critic_obs``: agent -> the input of its critic memory (the privileged observations that belong to the observations read), None or
-        absent = the observations themselves."""
-        ll, n = self.ll_env, self.num_envs
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        agents = (("pred", fused_pred, obs_pred_in), ("prey", fused_prey, obs_prey_in))
-        cobs = {a: obs if (critic_obs or {}).get(a) is None else critic_obs[a] for a, _, obs in agents}
-        critics = {a: a in with_critic_memory for a in AGENTS}
-        pools = {"pred": pool_pred, "prey": pool_prey}
-        pooled = pool_pred is not None or pool_prey is not None
-        slots = {a: (pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None) for a, pool in pools.items()}
-        lib, shared = self._recurrent_launches(fused_pred, fused_prey, pooled=pooled)
-        gru = lib is not None and self._gru_shared_pair(fused_pred, fused_prey)      # the cell launch is lg_dec_gru_step: the slots hold (h,)
-        h, self._critic_out = {}, {}
+    def _step_memories(self, live, pools, slots, obs, with_critic_memory, critic_obs, stream):
+        """The memory stage of ``_act`` for two ``RecurrentFusedActor`` s (arguments already checked there): both actor memories on the
+        observations they read, and the critic memory of every agent in ``with_critic_memory``, in one launch (``_cell_launch``) on the
+        actors' own slots (``RecurrentFusedActor.cell_roles``).  ``critic_obs``: agent -> the input of its critic memory (the privileged
+        observations that belong to the observations read), None or absent = the observations themselves.  The critic memories' outputs are
+        left in ``self._critic_out`` (agent -> tensor, None when it did not move).  Given pools (``slots``) the state is the live actor's
+        and the critic memory is never pooled.  Without a library of the shared launches (``_recurrent_launches``) ``lg_lstm_step`` per agent
+        instead (a GRU's ``lg_gru_step``), of a pooled role one per member in use on all envs, rows selected by block
+        (``step_memory_separate``).  Returns ``(h by agent, whether the shared actor launch can follow, whether the pair is a GRU pair on the
+        shared launches)``."""
+        n = self.num_envs
+        cobs = {a: None if a not in with_critic_memory else obs[a] if (critic_obs or {}).get(a) is None else critic_obs[a] for a in AGENTS}
+        lib, shared = self._recurrent_launches(live["pred"], live["prey"], pooled=slots is not None)
+        gru = lib is not None and self._gru_shared_pair(live["pred"], live["prey"])
+        roles, h, self._critic_out = [], {}, {}
+        for a in AGENTS:
+            if lib is not None:
+                entries, h[a], self._critic_out[a] = live[a].cell_roles(n, obs[a], cobs[a], a)
+                roles += entries
+            elif pools[a] is None:
+                h[a], self._critic_out[a] = live[a].step_memories(obs[a], cobs[a], reset=self.reset_buf)
+            else:
+                h[a] = pools[a].step_memory_separate(obs[a], reset=self.reset_buf)
+                self._critic_out[a] = None if cobs[a] is None else live[a].step_critic_memory(cobs[a], reset=self.reset_buf)
+                live[a].advance_slots(cobs[a] is not None)
         if lib is not None:
-            roles = []
-            for a, fused, obs in agents:
-                if fused.num_envs != n:
-                    fused._allocate(n)
-                f = fused._flip
-                for lstm, state, present, x in ((fused.lstm_a, fused.state_a, True, obs), (fused.lstm_c, fused.state_c, critics[a], cobs[a])):
-                    if present and x.shape[-1] != lstm.num_in:
-                        raise ValueError(f"the {a} agent's memory reads {lstm.num_in} inputs, its input here has {x.shape[-1]} (a critic memory reads "
-                                         "the privileged observations where they are on)")
-                    if not present:
-                        roles.append(None)
-                    elif gru:
-                        roles.append((lstm.handle, x.data_ptr(), state[f][0].data_ptr(), state[1 - f][0].data_ptr()))
-                    else:
-                        roles.append((lstm.handle, x.data_ptr(), state[f][0].data_ptr(), state[f][1].data_ptr(), state[1 - f][0].data_ptr(),
-                                      state[1 - f][1].data_ptr()))
-                h[a], self._critic_out[a] = fused.state_a[1 - f][0], (fused.state_c[1 - f][0] if critics[a] else None)
-            if gru:
-                capi.dec_gru_step(roles, self.reset_buf.data_ptr(), n, stream)
-            elif pooled:
-                capi.dec_pool_lstm_step(roles, *slots["pred"], *slots["prey"], self.reset_buf.data_ptr(), n, stream)
-            else:
-                capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
-            for a, fused, _ in agents:
-                fused.advance_slots(critics[a])
-        else:
-            for a, fused, obs in agents:
-                if pools[a] is None:
-                    h[a], self._critic_out[a] = fused.step_memories(obs, cobs[a] if critics[a] else None, reset=self.reset_buf)
-                    continue
-                h[a], self._critic_out[a] = pools[a].step_memory_separate(obs, reset=self.reset_buf), None
-                if critics[a]:                                   # the critic memory is never pooled: the live actor's, alone
-                    self._critic_out[a] = fused.step_critic_memory(cobs[a], reset=self.reset_buf)
-                fused.advance_slots(critics[a])
-        command_pred, mean_pred = fused_pred.output_buffers(n)
-        command_prey, mean_prey = fused_prey.output_buffers(n)
-        ll_actions = self._ll_fused.output_buffers(n)[0]
-        carry = obs_prey_out is not obs_prey_in
-        want_prey_copy = out_prey.get("obs_copy") is not None
-        if shared:
-            step, ctr = fused_prey.peek_step()
-            # a GRU pair on the shared launches stores the log-prob the separate launches store (torch's, below): the launch leaves the
-            # unclipped sample for it, in the caller's tensor or in a buffer kept here, and writes no log-prob of its own
-            k_pred, k_prey = (self._gru_log_prob_outputs(a, out, fused) for a, out, fused in (("pred", out_pred, fused_pred), ("prey", out_prey, fused_prey))) \
-                if gru else (out_pred, out_prey)
-            tail = (self._P, B, h["pred"].data_ptr(), h["prey"].data_ptr(), obs_pred_in.data_ptr(), obs_prey_in.data_ptr(), ll.obs_buf.data_ptr(),
-                    ll_actions.data_ptr(), mean_pred.data_ptr(), mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, deterministic_pred,
-                    deterministic_prey, outputs(k_pred, None), outputs(k_prey, obs_prey_out.data_ptr() if carry else None), stream)
-            if pooled:
-                rc = capi.dec_pool_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *slots["pred"], *slots["prey"], *tail)
-            else:
-                rc = capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *tail)
-            self.last_act_rc = rc
-            if rc == 0:
-                fused_pred.next_step(); fused_prey.next_step()     # the launch used this step of both noise streams
-                if carry and want_prey_copy:
-                    obs_prey_out.copy_(obs_prey_in)
-                if gru:
-                    for out, launched, mean, fused in ((out_pred, k_pred, mean_pred, fused_pred), (out_prey, k_prey, mean_prey, fused_prey)):
-                        if out.get("log_prob") is not None:      # _fill_optional_outputs' expression on the same sample, mean and std: the same bits
-                            out["log_prob"].view(n).copy_(torch.distributions.Normal(mean, fused.ac.std.detach()).log_prob(launched["sample"].view(n, -1)).sum(-1))
-                return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
-            self._say_separate("no kernel for this actor pair", pooled=pooled)
-        else:
-            self.last_act_rc = -4
-        for a, fused, obs, det, out in (("pred", fused_pred, obs_pred_in, deterministic_pred, out_pred), ("prey", fused_prey, obs_prey_in, deterministic_prey, out_prey)):
-            if pools[a] is None:
-                (command, mean), std = fused.fused.act_with_mean(h[a], det), fused.ac.std.detach()
-            else:
-                command, mean, std = pools[a].act_separate(h[a], det)        # per member in use, rows by block; std [n, actions] of the rows' members
-            self._fill_optional_outputs(out, n, command, mean, std, obs)
-        if carry:
-            obs_prey_out.copy_(obs_prey_in)
-        capi.dec_game_pre(self._P, B, stream)
-        ll_actions = self.ll_policy(ll.obs_buf)
-        return (command_pred, mean_pred), (command_prey, mean_prey), ll_actions, B
+            self._cell_launch(roles, gru, slots, stream)
+            for a in AGENTS:
+                live[a].advance_slots(cobs[a] is not None)
+        return h, shared, gru
 
     def shared_actor_launch(self, fused_pred, fused_prey):
         """Whether the actor launch of a step has a kernel for this pair next to the low-level actor at the current wide precision (rc 0, not
         -4).  Issues it once, deterministically, on the current observations when it has: commands, means, low-level commands and actions
-        are overwritten (every step path rewrites them before reading them), no noise stream is advanced and no memory moves.  With two
-        ``RecurrentFusedActor`` s the warm-up call that raises the LDS limits of both kernels of liblegged_dec_game_recurrent.so outside
-        any capture: one ``lg_dec_lstm_step`` of the two actor memories into the slots the next step overwrites, then
-        ``lg_dec_game_lstm_act`` on the actor memories' current outputs.  Given an ``rl.RecurrentOpponentPool`` for an agent, the pooled
-        kernels of liblegged_dec_pool_recurrent.so are warmed up the same way (``lg_dec_pool_lstm_step``, ``lg_dec_pool_lstm_act``)."""
+        are overwritten (every step path rewrites them before reading them), no noise stream is advanced and no memory moves.  A
+        feed-forward pair: ``lg_dec_game_act`` on the live actors, also when a pool is given.  With two ``RecurrentFusedActor`` s the
+        warm-up call that raises the LDS limits of both kernels of liblegged_dec_game_recurrent.so outside any capture: one cell launch
+        (``_cell_launch``: ``lg_dec_lstm_step``; ``lg_dec_gru_step`` warms up k_dec_gru_cell the same way) of the two actor memories into the
+        slots the next step overwrites, then ``lg_dec_game_lstm_act`` on the actor memories' current outputs.  Given an
+        ``rl.RecurrentOpponentPool`` for an agent, the pooled kernels of liblegged_dec_pool_recurrent.so are warmed up the same way
+        (``lg_dec_pool_lstm_step``, ``lg_dec_pool_lstm_act``)."""
         n = self.num_envs
-        pool_pred, pool_prey = (f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey))
-        fused_pred, fused_prey = _live(fused_pred), _live(fused_prey)
-        recurrent = self._recurrent_pair(fused_pred, fused_prey, pool_pred, pool_prey)
-        command_pred, mean_pred = fused_pred.output_buffers(n)
-        command_prey, mean_prey = fused_prey.output_buffers(n)
+        live, pools, recurrent = self._who_acts(fused_pred, fused_prey)
+        command, mean = {}, {}
+        for a in AGENTS:
+            command[a], mean[a] = live[a].output_buffers(n)
         ll_actions = self._ll_fused.output_buffers(n)[0]
-        B = self._bind(command_pred, command_prey, self.obs_buf_pred, self.obs_buf_prey)
+        B = self._bind(command["pred"], command["prey"], self.obs_buf_pred, self.obs_buf_prey)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        step, ctr = fused_prey.peek_step()
-        if not recurrent:
-            return capi.dec_game_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, self._P, B, self.obs_buf_pred.data_ptr(),
-                                     self.obs_buf_prey.data_ptr(), self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
-                                     mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream) == 0
-        pooled = pool_pred is not None or pool_prey is not None
-        lib, shared = self._recurrent_launches(fused_pred, fused_prey, say=False, pooled=pooled)
-        if lib is None:
-            return False
-        gru = self._gru_shared_pair(fused_pred, fused_prey)      # lg_dec_gru_step warms up k_dec_gru_cell the same way: the slots hold (h,)
-        roles, h = [], []
-        for fused, obs in ((fused_pred, self.obs_buf_pred), (fused_prey, self.obs_buf_prey)):
-            if fused.num_envs != n:
-                fused._allocate(n)
-            f, st = fused._flip, fused.state_a
-            if gru:
-                roles += [(fused.lstm_a.handle, obs.data_ptr(), st[f][0].data_ptr(), st[1 - f][0].data_ptr()), None]
-            else:
-                roles += [(fused.lstm_a.handle, obs.data_ptr(), st[f][0].data_ptr(), st[f][1].data_ptr(), st[1 - f][0].data_ptr(), st[1 - f][1].data_ptr()), None]
-            h.append(st[f][0])
-        tail = (self._P, B, h[0].data_ptr(), h[1].data_ptr(), None, None, self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean_pred.data_ptr(),
-                mean_prey.data_ptr(), fused_pred.seed, fused_prey.seed, step, ctr, True, True, None, None, stream)
-        if pooled:
-            slots = [a for pool in (pool_pred, pool_prey) for a in ((pool.handle, pool.slot_table(n).data_ptr()) if pool is not None else (None, None))]
-            capi.dec_pool_lstm_step(roles, *slots, self.reset_buf.data_ptr(), n, stream)
-            return shared and capi.dec_pool_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *slots, *tail) == 0
-        if gru:
-            capi.dec_gru_step(roles, self.reset_buf.data_ptr(), n, stream)
-        else:
-            capi.dec_lstm_step(roles, self.reset_buf.data_ptr(), n, stream)
-        return shared and capi.dec_game_lstm_act(fused_pred.handle, fused_prey.handle, self._ll_fused.handle, *tail) == 0
+        obs, slots, h, shared = {"pred": self.obs_buf_pred, "prey": self.obs_buf_prey}, None, None, True
+        if recurrent:
+            pooled = pools["pred"] is not None or pools["prey"] is not None
+            lib, shared = self._recurrent_launches(live["pred"], live["prey"], say=False, pooled=pooled)
+            if lib is None:
+                return False
+            roles = [entry for a in AGENTS for entry in live[a].cell_roles(n, obs[a], agent=a)[0]]
+            h, obs = {a: live[a].hidden_states()[0][0][0] for a in AGENTS}, dict.fromkeys(AGENTS)
+            slots = self._slot_args(pools, n) if pooled else None
+            self._cell_launch(roles, self._gru_shared_pair(live["pred"], live["prey"]), slots, stream)
+        return shared and self._actor_launch(live, slots, B, ll_actions, mean, h, obs, dict.fromkeys(AGENTS, True), dict.fromkeys(AGENTS), stream) == 0
 
     def step_policy(self, fused_pred, fused_prey, deterministic_pred=False, deterministic_prey=False, out_pred=None, out_prey=None, with_critic_memory=(),
                     privileged_out=None):
@@ -616,8 +565,8 @@ class DecHighLevelGame(GameBase):
         for fused in (_live(fused_pred), _live(fused_prey)):
             self._require_device_step_counter(fused)
         self._own_privileged()
-        pools = [f if getattr(f, "is_opponent_pool", False) else None for f in (fused_pred, fused_prey)]
-        hold = self._recurrent_pair(_live(fused_pred), _live(fused_prey), *pools) and steps_per_replay % 2 == 1
+        live, _, recurrent = self._who_acts(fused_pred, fused_prey)
+        hold = recurrent and steps_per_replay % 2 == 1
         with_critic_memory = (with_critic_memory,) if isinstance(with_critic_memory, str) else tuple(with_critic_memory or ())
 
         def device_step():
@@ -625,7 +574,7 @@ class DecHighLevelGame(GameBase):
                                             deterministic_prey, with_critic_memory=with_critic_memory,
                                             critic_obs={a: getattr(self, f"privileged_obs_buf_{a}") for a in AGENTS})
             if hold:
-                _live(fused_pred).hold_slot(); _live(fused_prey).hold_slot()      # (a pool's state is its live actor's)
+                live["pred"].hold_slot(); live["prey"].hold_slot()      # (a pool's state is its live actor's)
             sim.step(ll_actions, -1)
             self._post(B, -1, torch.cuda.current_stream(self.device).cuda_stream)
         self._policy_step_graph, replay = self._capture(device_step, warmup, steps_per_replay, self._step_result)

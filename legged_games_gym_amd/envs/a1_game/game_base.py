@@ -151,6 +151,28 @@ class GameBase:
         if out.get("obs_copy") is not None:
             out["obs_copy"].view(n, -1).copy_(obs_in)
 
+    # ------------------------------------------------------------------ whether a shared recurrent launch is available
+    # What both envs' deciders are made of; each env keeps the order of its checks and the text of its message (``_say_separate``).
+    def _load_or_say(self, load, say, *said_for):
+        """``load()``, a ``capi.load_*_library``; None, with the env's one-line message, for a build without the library."""
+        try:
+            return load()
+        except (RuntimeError, OSError) as exc:
+            self._say_separate(f"{type(exc).__name__}: {exc}", say, *said_for)
+            return None
+
+    @staticmethod
+    def _wide_precision_0(fused):
+        """The low-level role of a shared recurrent launch is the split-bf16 kernel: wide precision 0 takes the separate actor launches.
+        Asked per call: ``lg_mlp_wide_set_precision`` may change between calls (an invalid mode changes nothing and returns the current one)."""
+        return fused.lib.lg_mlp_wide_set_precision(-1) != 1
+
+    def _say_once(self, key, say, line):
+        said = self.__dict__.setdefault("_separate_said", set())
+        if say and key not in said:
+            said.add(key)
+            print(line)
+
     # ------------------------------------------------------------------ outcome statistics
     def enable_outcome_stats(self, on=True):
         """Switch the outcome statistics on or off.  On: ``_post`` issues the outcome entry point of the task on every step path and

@@ -110,34 +110,52 @@ class HighLevelGame(GameBase):
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
     # ------------------------------------------------------------------ hot path with the actor on the device
+    def _actor_launch(self, fused_actor, B, ll_actions, mean, h, obs, deterministic, outputs, stream):
+        """The shared actor launch: ``lg_game_act`` on ``obs``, or with ``h`` (a ``RecurrentFusedActor``'s actor memory output)
+        ``lg_game_lstm_act`` on it.  ``obs`` may be None in the recurrent warm-up; ``outputs``: the optional ``(sample, sigma, log_prob,
+        obs_copy)`` tensors or None each.  Returns rc: 0, or -4 when nothing was launched; the noise stream is not advanced here."""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        step, ctr = fused_actor.peek_step()
+        tail = (ptr(obs), self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step, ctr, deterministic,
+                *(ptr(t) for t in outputs), stream)
+        if h is None:
+            return capi.game_act(fused_actor.handle, self._ll_fused.handle, self._P, B, *tail)
+        return capi.game_lstm_act(fused_actor.handle, self._ll_fused.handle, self._P, B, h.data_ptr(), *tail)
+
     def _act(self, fused_actor, obs_in, obs_out, deterministic, sample=None, sigma=None, log_prob=None):
         """``lg_game_act``: command = clip(actor(obs_in) + noise) into the low-level commands, the low-level actions, and ``obs_in`` copied
         to ``obs_out`` (where ``lg_game_post`` then shifts the history in place) -- one launch.  Separate launches when the actor pair or
-        the wide precision has no shared kernel (rc -4).  Returns ``command, mean, ll_actions, buffers``."""
+        the wide precision has no shared kernel (rc -4): ``lg_policy_act`` x 2 + ``lg_game_pre``, each actor into its own ``FusedActor``'s
+        buffers (decided per call: ``lg_mlp_wide_set_precision`` may change between calls).
+        A ``RecurrentFusedActor``: first ``lg_lstm_step`` on ``obs_in`` (both memories; a deterministic evaluation advances only the actor
+        memory), rows that ``reset_buf`` of the previous step marks starting from a zero state, then ``lg_game_lstm_act`` on the new ``h``.
+        The critic memory's output of the step is left in ``self._critic_out`` (None when it did not move).  Separate launches
+        (``lg_lstm_actor_act`` + ``lg_game_pre`` + low-level ``lg_policy_act``) on rc -4, at wide precision 0 or without the library.
+        Returns ``command, mean, ll_actions, buffers``."""
         ll, n = self.ll_env, self.num_envs
         if obs_in.shape != (n, self.num_obs) or obs_in.dtype != torch.float32 or not obs_in.is_contiguous():
             raise ValueError(f"observations must be a contiguous float32 [{n},{self.num_obs}] tensor")
         self._check_output("sample", sample, n * self.num_actions)
         self._check_output("sigma", sigma, n * self.num_actions)
         self._check_output("log_prob", log_prob, n)
-        if getattr(fused_actor, "recurrent", False):
-            return self._act_recurrent(fused_actor, obs_in, obs_out, deterministic, sample, sigma, log_prob)
+        recurrent = getattr(fused_actor, "recurrent", False)
         command, mean = fused_actor.output_buffers(n)
         ll_actions = self._ll_fused.output_buffers(n)[0]
         B = self._bind_command(command, obs_out)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        ptr = lambda t: None if t is None else t.data_ptr()
         copy = obs_out is not obs_in
-        step, ctr = fused_actor.peek_step()
-        rc = capi.game_act(fused_actor.handle, self._ll_fused.handle, self._P, B, obs_in.data_ptr(), ll.obs_buf.data_ptr(), ll_actions.data_ptr(),
-                           mean.data_ptr(), fused_actor.seed, step, ctr, deterministic, ptr(sample), ptr(sigma), ptr(log_prob),
-                           obs_out.data_ptr() if copy else None, stream)
-        if rc == 0:
-            fused_actor.next_step()                            # the launch used this step of the actor's noise stream
-            return command, mean, ll_actions, B
-        # rc -4, nothing was launched: lg_policy_act x 2 + lg_game_pre (decided per call: lg_mlp_wide_set_precision may change between
-        # calls), each actor into its own FusedActor's buffers as above
-        command, mean = fused_actor.act_with_mean(obs_in, deterministic)
+        h, shared = None, True
+        if recurrent:
+            shared = self._recurrent_launch(fused_actor) is not None
+            h, self._critic_out = fused_actor.step_memories(obs_in, None if deterministic else obs_in, reset=self.reset_buf)
+        if shared:
+            if self._actor_launch(fused_actor, B, ll_actions, mean, h, obs_in, deterministic, (sample, sigma, log_prob, obs_out if copy else None), stream) == 0:
+                fused_actor.next_step()                        # the launch used this step of the actor's noise stream
+                return command, mean, ll_actions, B
+            if recurrent:
+                self._say_separate("no kernel for this actor pair")
+        # nothing was launched: the actor on what it reads (the observations; behind a memory, its output), then the clip and the low-level actor
+        command, mean = fused_actor.fused.act_with_mean(h, deterministic) if recurrent else fused_actor.act_with_mean(obs_in, deterministic)
         self._fill_optional_outputs({"sample": sample, "sigma": sigma, "log_prob": log_prob, "obs_copy": obs_out if copy else None}, n, command, mean,
                                     fused_actor.ac.std.detach(), obs_in)
         capi.game_pre(self._P, B, stream)
@@ -146,56 +164,19 @@ class HighLevelGame(GameBase):
 
     def _recurrent_launch(self, fused_actor, say=True):
         """The bound ``lg_game_lstm_act`` library when the recurrent actor launch can be used now, else None (with a one-line message the
-        first time for each reason): the low-level role is the split-bf16 kernel, so wide precision 0 takes the separate launches, and so
-        does a build without the library.  Decided per call: ``lg_mlp_wide_set_precision`` may change between calls."""
-        why = None
-        if getattr(fused_actor, "wide", False):                       # handles of liblegged_lstm_wide.so: lg_game_lstm_act reads main-library ones
+        first time for each reason): a ``wide`` memory holds handles of liblegged_lstm_wide.so where ``lg_game_lstm_act`` reads main-library
+        ones, wide precision 0 takes the separate launches (``GameBase._wide_precision_0``), and so does a build without the library."""
+        if getattr(fused_actor, "wide", False):
             why = "wide memory"
-        elif fused_actor.lib.lg_mlp_wide_set_precision(-1) != 1:      # (an invalid mode changes nothing and returns the current one)
+        elif self._wide_precision_0(fused_actor):
             why = "wide precision 0"
         else:
-            try:
-                return capi.load_game_recurrent_library()
-            except (RuntimeError, OSError) as exc:
-                why = f"{type(exc).__name__}: {exc}"
+            return self._load_or_say(capi.load_game_recurrent_library, say)
         self._say_separate(why, say)
         return None
 
     def _say_separate(self, why, say=True):
-        said = self.__dict__.setdefault("_separate_said", set())
-        if say and why not in said:
-            said.add(why)
-            print(f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act + lg_game_pre + lg_policy_act")
-
-    def _act_recurrent(self, fused_actor, obs_in, obs_out, deterministic, sample, sigma, log_prob):
-        """``_act`` for a ``RecurrentFusedActor``: ``lg_lstm_step`` on ``obs_in`` (both memories; a deterministic evaluation advances only
-        the actor memory), rows that ``reset_buf`` of the previous step marks starting from a zero state, then ``lg_game_lstm_act`` on the
-        new ``h``.  The critic memory's output of the step is left in ``self._critic_out`` (None when it did not move).  Separate launches
-        (``lg_lstm_actor_act`` + ``lg_game_pre`` + low-level ``lg_policy_act``) on rc -4, at wide precision 0 or without the library."""
-        ll, n = self.ll_env, self.num_envs
-        command, mean = fused_actor.output_buffers(n)
-        ll_actions = self._ll_fused.output_buffers(n)[0]
-        B = self._bind_command(command, obs_out)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        ptr = lambda t: None if t is None else t.data_ptr()
-        copy = obs_out is not obs_in
-        lib = self._recurrent_launch(fused_actor)
-        h_a, self._critic_out = fused_actor.step_memories(obs_in, None if deterministic else obs_in, reset=self.reset_buf)
-        if lib is not None:
-            step, ctr = fused_actor.peek_step()
-            rc = capi.game_lstm_act(fused_actor.handle, self._ll_fused.handle, self._P, B, h_a.data_ptr(), obs_in.data_ptr(), ll.obs_buf.data_ptr(),
-                                    ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step, ctr, deterministic, ptr(sample), ptr(sigma),
-                                    ptr(log_prob), obs_out.data_ptr() if copy else None, stream)
-            if rc == 0:
-                fused_actor.next_step()                        # the launch used this step of the actor's noise stream
-                return command, mean, ll_actions, B
-            self._say_separate("no kernel for this actor pair")
-        command, mean = fused_actor.fused.act_with_mean(h_a, deterministic)
-        self._fill_optional_outputs({"sample": sample, "sigma": sigma, "log_prob": log_prob, "obs_copy": obs_out if copy else None}, n, command, mean,
-                                    fused_actor.ac.std.detach(), obs_in)
-        capi.game_pre(self._P, B, stream)
-        ll_actions = self.ll_policy(ll.obs_buf)
-        return command, mean, ll_actions, B
+        self._say_once(why, say, f"[{self.TASK}] recurrent actor launch unavailable ({why}); lg_lstm_actor_act + lg_game_pre + lg_policy_act")
 
     def step_policy(self, fused_actor, deterministic=False, sample=None, sigma=None, log_prob=None, with_critic_memory=False):
         """Rollout step with the high-level actor on the device: ``lg_game_act`` -> ``lg_step`` -> ``lg_game_post``, three launches.
@@ -225,24 +206,21 @@ class HighLevelGame(GameBase):
     def shared_actor_launch(self, fused_actor):
         """Whether ``lg_game_act`` has a kernel for ``fused_actor`` next to the low-level actor at the current wide precision (rc 0, not -4).
         Issues that launch once, deterministically, on the current observations when it has: command, mean, low-level commands and actions
-        are overwritten (every step path rewrites them before reading them) and the actor's noise stream is not advanced."""
+        are overwritten (every step path rewrites them before reading them) and the actor's noise stream is not advanced.  A
+        ``RecurrentFusedActor``: ``lg_game_lstm_act`` on the actor memory's current output; the memories do not move."""
         n = self.num_envs
         command, mean = fused_actor.output_buffers(n)
         ll_actions = self._ll_fused.output_buffers(n)[0]
         B = self._bind_command(command, self.obs_buf)
-        step, ctr = fused_actor.peek_step()
+        h, obs = None, self.obs_buf
         if getattr(fused_actor, "recurrent", False):
-            # lg_game_lstm_act on the actor memory's current output: the memories do not move
-            lib = self._recurrent_launch(fused_actor, say=False)
+            available = self._recurrent_launch(fused_actor, say=False) is not None
             if fused_actor.num_envs != n:
                 fused_actor._allocate(n)
-            h = fused_actor.hidden_states()[0][0][0]
-            return lib is not None and capi.game_lstm_act(fused_actor.handle, self._ll_fused.handle, self._P, B, h.data_ptr(), None,
-                                                          self.ll_env.obs_buf.data_ptr(), ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step,
-                                                          ctr, True, None, None, None, None, torch.cuda.current_stream(self.device).cuda_stream) == 0
-        return capi.game_act(fused_actor.handle, self._ll_fused.handle, self._P, B, self.obs_buf.data_ptr(), self.ll_env.obs_buf.data_ptr(),
-                             ll_actions.data_ptr(), mean.data_ptr(), fused_actor.seed, step, ctr, True, None, None, None, None,
-                             torch.cuda.current_stream(self.device).cuda_stream) == 0
+            if not available:
+                return False
+            h, obs = fused_actor.hidden_states()[0][0][0], None
+        return self._actor_launch(fused_actor, B, ll_actions, mean, h, obs, True, (None,) * 4, torch.cuda.current_stream(self.device).cuda_stream) == 0
 
     def make_graphed_policy_step(self, fused_actor, warmup=3, steps_per_replay=1, deterministic=False):
         """``make_graphed_step`` with the actor on the device: the graph is ``lg_game_act`` -> ``lg_step`` -> ``lg_game_post`` per step, the

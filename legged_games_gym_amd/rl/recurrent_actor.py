@@ -347,9 +347,25 @@ class RecurrentFusedActor:
                         critic_obs.shape[0])
         return self.state_c[1 - f][0]
 
+    def cell_roles(self, n, x, critic_x=None, agent=""):
+        """This actor's two role entries of a shared cell launch (``lg_dec_lstm_step`` / ``lg_dec_pool_lstm_step``, a GRU's ``lg_dec_gru_step``) on
+        its own slots for ``n`` envs (allocated first when ``num_envs`` differs): the actor memory on ``x``, the critic memory on ``critic_x``
+        or None.  An entry reads ``[flip]`` and writes ``[1 - flip]``: ``(handle, x, h_in, c_in, h_out, c_out)``, a GRU's
+        ``(handle, x, h_in, h_out)``.  Returns ``(entries, h, critic output or None)``, the tensors the outputs land in; the caller issues the
+        launch and then calls ``advance_slots`` (a warm-up call does not: the next step overwrites what it wrote)."""
+        if self.num_envs != n:
+            self._allocate(n)
+        f, entries = self._flip, []
+        for cell, state, inp in ((self.lstm_a, self.state_a, x), (self.lstm_c, self.state_c, critic_x)):
+            if inp is not None and inp.shape[-1] != cell.num_in:
+                raise ValueError(f"the {agent} agent's memory reads {cell.num_in} inputs, its input here has {inp.shape[-1]} (a critic memory reads "
+                                 "the privileged observations where they are on)")
+            entries.append(None if inp is None else (cell.handle, inp.data_ptr(), *(t.data_ptr() for t in state[f]), *(t.data_ptr() for t in state[1 - f])))
+        return entries, self.state_a[1 - f][0], (None if critic_x is None else self.state_c[1 - f][0])
+
     def advance_slots(self, with_critic):
-        """What ``step_memories`` does after its launch, for a caller that issued the launch itself on this actor's slots (``lg_dec_lstm_step``
-        of ``dec_high_level_game``: read ``[flip]``, write ``[1 - flip]``).  A critic memory that did not move needs both of its slots
+        """What ``step_memories`` does after its launch, for a caller that issued the launch itself on this actor's slots (``cell_roles``:
+        read ``[flip]``, write ``[1 - flip]``).  A critic memory that did not move needs both of its slots
         current; they are copied only when the last step that moved it left them different, so a memory that never moves costs no copy."""
         f = self._flip
         if with_critic:
