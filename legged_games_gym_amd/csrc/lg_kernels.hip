@@ -413,8 +413,34 @@ LG_DEV void contact_assemble(const Contact &c, const lg_params &P, float kn, AI 
     }
 }
 // more: another pass follows (wave-uniform) -- only that pass reads the corrector's results
-template <bool HF>
-LG_DEV void contact_evaluate(Contact &c, const lg_params &P, float kn, float mu, S6 acc, bool more = true) {
+// SEL (plane quadruped builds): the plane form as straight-line code.  The nested `if`s of the text below it -- in contact, leaving,
+// beyond the cone, re-aim -- are data-dependent per lane: each costs the lone rigid-body wave a saveexec / branch / restore and the
+// copies that merge its two sides, executed whichever side its lanes take.  Here every value is formed with the same operations and
+// rounded the same way, and selects keep what the branches kept; a quotient of a lane that does not use it is dropped by its select.
+// skip: one scalar branch around the point -- nothing is evaluated for a point that no lane of the wave has in contact.  The thigh,
+// shank and base points take it; a foot, which some lane of nearly every wave stands on, is evaluated without asking (measured:
+// DESIGN.md section 10, profiles/r10_contact_selects_ab.txt).
+template <bool HF, bool SEL = false>
+LG_DEV void contact_evaluate(Contact &c, const lg_params &P, float kn, float mu, S6 acc, bool more = true, bool skip = true) {
+    if constexpr (!HF && SEL) {
+        if (!skip || __builtin_amdgcn_ballot_w64(c.on) != 0) {
+            const V3 v1 = c.vc + (acc.v + cross(acc.w, c.r)) * P.sim_dt;
+            const float fn = plane_normal_force(P, kn, c.depth, v1.z);
+            const V3 f = plane_force(c, v1, fn);
+            const bool on1 = c.on && !(fn <= 0.0f);                    // c.f is zero already wherever c.on is false (contact_setup, or left earlier)
+            c.f = v3(on1 ? f.x : 0.0f, on1 ? f.y : 0.0f, on1 ? f.z : 0.0f);
+            if (more) {
+                const float vtm = plane_slip_speed(v1), cone = mu * fn;
+                const bool slide = on1 && c.bt * vtm > cone;
+                const float s = -cone / vtm, aim = fminf(P.friction_damping, cone / fmaxf(vtm, P.stick_velocity));
+                c.fs = v3(slide ? v1.x * s : c.fs.x, slide ? v1.y * s : c.fs.y, slide ? 0.0f : c.fs.z);
+                const float bt_in = c.bt > 0.0f ? aim : c.bt;
+                c.bt = !on1 ? c.bt : slide ? 0.0f : bt_in;
+            }
+            c.on = on1;
+        }
+        return;
+    }
     if constexpr (!HF) {
         if (c.on) {
             V3 v1 = c.vc + (acc.v + cross(acc.w, c.r)) * P.sim_dt;
@@ -998,6 +1024,7 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
     float Dinv[L], uu[L], vl[L];      // vl: 0, or +-1 = joint speed limit active in that direction (set by the previous pass)
 #pragma unroll
     for (int j = 0; j < L; j++) vl[j] = 0.0f;
+    bool vl_lane = false, vl_wave = false;      // HELD: a joint of this lane / of any lane of the wave is on its speed limit
 #pragma unroll 1
     for (int pass = 0; pass < LG_PASSES; pass++) {
         const bool more = !LAST_LEAN || pass < LG_PASSES - 1;       // wave-uniform: a scalar branch on the loop counter
@@ -1048,10 +1075,13 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
                         u = u + lim_u[j];
                     }
                 }
-                if (vl[j] != 0.0f) {  // implicit damper towards +-v_lim (100x the joint's articulated inertia), reaction on the parent
-                    float Bv = 100.0f * D / dt;
-                    u = __builtin_fmaf(-__builtin_fmaf(-vl[j], jvlim[j], qd[j]), Bv, u);
-                    D = __builtin_fmaf(dt, Bv, D);
+                if (vl_wave) {        // wave-uniform, one flag for all joints like lim_wave: the division is not issued where no lane of the wave is on a speed limit
+                    // implicit damper towards +-v_lim (100x the joint's articulated inertia), reaction on the parent
+                    const bool damped = vl[j] != 0.0f;
+                    const float Bv = 100.0f * D / dt;
+                    const float ud = __builtin_fmaf(-__builtin_fmaf(-vl[j], jvlim[j], qd[j]), Bv, u), Dd = __builtin_fmaf(dt, Bv, D);
+                    u = damped ? ud : u;
+                    D = damped ? Dd : D;
                 }
             } else {
             float damp = tj[J_DAMP];
@@ -1105,9 +1135,12 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
         ai_add(IAb, Ia); pAb = pAb + pa;
         float rhs[6] = {-pAb.w.x, -pAb.w.y, -pAb.w.z, -pAb.v.x, -pAb.v.y, -pAb.v.z}, a0[6];
         bool ok = solve6(IAb, rhs, a0);
-        if (!ok) { a0[0] = a0[1] = a0[2] = a0[3] = a0[4] = a0[5] = 0.0f; }
+        if constexpr (HELD) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) a0[i] = ok ? a0[i] : 0.0f;
+        } else if (!ok) { a0[0] = a0[1] = a0[2] = a0[3] = a0[4] = a0[5] = 0.0f; }
         acc0.w = v3(a0[0], a0[1], a0[2]); acc0.v = v3(a0[3], a0[4], a0[5]);
-        contact_evaluate<HF>(cb, P, kn, mu, acc0, more);
+        contact_evaluate<HF, HELD>(cb, P, kn, mu, acc0, more);
         LG_PROF(PF_BASE);
         S6 a = acc0;
 #pragma unroll
@@ -1121,11 +1154,16 @@ LG_DEV void physics_substep(const KArgs &A, const float *tab, int lane_k, float 
             uu[j] = qdd;
             if (more) {
                 float lim = HELD ? jvlim[j] : tab[j * LG_JS + J_VLIM], qn = qd[j] + dt * qdd;
-                if (lim > 0.0f && vl[j] == 0.0f && fabsf(qn) > lim) vl[j] = qn > 0.0f ? 1.0f : -1.0f;
+                if constexpr (HELD) {
+                    const bool arm = lim > 0.0f && vl[j] == 0.0f && fabsf(qn) > lim;
+                    vl[j] = arm ? (qn > 0.0f ? 1.0f : -1.0f) : vl[j];
+                    vl_lane |= arm;
+                } else if (lim > 0.0f && vl[j] == 0.0f && fabsf(qn) > lim) vl[j] = qn > 0.0f ? 1.0f : -1.0f;
             }
 #pragma unroll
-            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) contact_evaluate<HF>(cl[i], P, kn, mu, a, more);
+            for (int i = 0; i < NPT; i++) if (T::pt_joint(i) == j) contact_evaluate<HF, HELD>(cl[i], P, kn, mu, a, more, T::pt_rep(i) != T::NREP - 1);
         }
+        if constexpr (HELD) if (more) vl_wave = __builtin_amdgcn_ballot_w64(vl_lane) != 0;
         LG_PROF(PF_OUTWARD);
     }
 
