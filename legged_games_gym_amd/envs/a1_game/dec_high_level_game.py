@@ -117,15 +117,17 @@ class DecHighLevelGame(GameBase):
         new tensors every step, :377, :391): alternate between two buffers per agent, carrying the prey's history over when ``carry``."""
         prev = self.obs_buf_prey
         self._obs_flip ^= 1
-        self.obs_buf_prey = self._obs_pair_prey[self._obs_flip]
-        self.obs_buf_pred = self._obs_pair_pred[self._obs_flip]
-        self._select_privileged()
+        self._select_observations()
         if carry:
             self.obs_buf_prey.copy_(prev)
         return prev
 
     def _unflip_observations(self):
         self._obs_flip ^= 1
+        self._select_observations()
+
+    def _select_observations(self):
+        """Both agents' buffers and the privileged ones on the current side of their pairs."""
         self.obs_buf_prey = self._obs_pair_prey[self._obs_flip]
         self.obs_buf_pred = self._obs_pair_pred[self._obs_flip]
         self._select_privileged()
@@ -756,30 +758,8 @@ class AgentView:
     extras = property(lambda self: self.env.extras)
     episode_length_buf = property(lambda self: self.env.episode_length_buf)
     dt = property(lambda self: self.env.dt)
-    _obs_pair = property(lambda self: getattr(self.env, f"_obs_pair_{self.agent}"))
-
-    @property
-    def _obs_flip(self):
-        return self.env._obs_flip
-
-    @_obs_flip.setter
-    def _obs_flip(self, value):          # (the runner puts the ping-pong back after a capture that failed part-way)
-        self.env._obs_flip = value
-        self.env.obs_buf_prey, self.env.obs_buf_pred = self.env._obs_pair_prey[value], self.env._obs_pair_pred[value]
-        self.env._select_privileged()
-
-    @obs_buf.setter
-    def obs_buf(self, value):            # (same path, after the _obs_flip setter: only the current buffer of the pair can be "assigned")
-        if value is not self.obs_buf:
-            raise ValueError("an agent view's obs_buf is the env's current buffer of its observation pair; set _obs_flip to choose it")
-
-    @property
-    def _capturing(self):
-        return self.env._capturing
-
-    @_capturing.setter
-    def _capturing(self, value):
-        self.env._capturing = value
+    _obs_flip = property(lambda self: self.env._obs_flip)
+    _capturing = property(lambda self: self.env._capturing)
 
     @property
     def common_step_counter(self):
@@ -797,6 +777,12 @@ class AgentView:
 
     def end_graph_capture(self, steps_captured):
         self.env.end_graph_capture(steps_captured)
+
+    def capture_state(self):
+        return self.env.capture_state()
+
+    def abort_graph_capture(self, state):
+        self.env.abort_graph_capture(state)
 
     def reset(self):
         obs_pred, obs_prey, priv_pred, priv_prey = self.env.reset()

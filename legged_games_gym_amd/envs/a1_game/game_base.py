@@ -261,10 +261,6 @@ class GameBase:
     def _capturing(self):
         return self.ll_env._capturing
 
-    @_capturing.setter
-    def _capturing(self, value):
-        self.ll_env._capturing = value
-
     @property
     def common_step_counter(self):
         return self.ll_env.common_step_counter
@@ -282,6 +278,17 @@ class GameBase:
 
     def end_graph_capture(self, steps_captured: int):
         self.ll_env.end_graph_capture(steps_captured)
+
+    def capture_state(self):
+        """``LeggedRobot.capture_state`` of the game: its own observation ping-pong and the low-level env's state (flip and counter)."""
+        return self._obs_flip, self.ll_env.capture_state()
+
+    def abort_graph_capture(self, state):
+        """``LeggedRobot.abort_graph_capture`` of the game: the env's own buffers back on ``state``'s side of their pairs; the low-level env
+        leaves capture mode and restores its flip, the sim's output binding and the counter."""
+        self._obs_flip, ll_state = state
+        self._select_observations()
+        self.ll_env.abort_graph_capture(ll_state)
 
     def render(self, sync_frame_time=True):
         return None     # headless

@@ -71,7 +71,7 @@ class HighLevelGame(GameBase):
         # builds a new tensor every step, :405): alternate between two buffers, carrying the history over
         prev = self.obs_buf
         self._obs_flip ^= 1
-        self.obs_buf = self._obs_pair[self._obs_flip]
+        self._select_observations()
         self.obs_buf.copy_(prev)
         B = self._bind_command(command, self.obs_buf)
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -108,6 +108,9 @@ class HighLevelGame(GameBase):
 
     def _step_result(self):
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
+
+    def _select_observations(self):
+        self.obs_buf = self._obs_pair[self._obs_flip]
 
     # ------------------------------------------------------------------ hot path with the actor on the device
     def _actor_launch(self, fused_actor, B, ll_actions, mean, h, obs, deterministic, outputs, stream):
@@ -191,7 +194,7 @@ class HighLevelGame(GameBase):
         ll = self.ll_env
         prev = self.obs_buf
         self._obs_flip ^= 1
-        self.obs_buf = self._obs_pair[self._obs_flip]
+        self._select_observations()
         try:
             command, mean, ll_actions, B = self._act(fused_actor, prev, self.obs_buf, deterministic, sample, sigma, log_prob)
         except Exception:

@@ -145,11 +145,26 @@ class LeggedRobot(BaseTask):
         self._sim.set_deferred_extras(False)               # ... eager steps publish them before they return, as the reference does
         self.common_step_counter -= steps_captured      # capture does not execute; replays are accounted by the caller
 
-    def make_graphed_step(self, policy_act, warmup=3, steps_per_replay=1):
-        """Capture ``actions = policy_act(obs_buf); step(actions)`` into one HIP graph and return a
-        zero-argument callable that replays it (launch-bound inner loop -> one hipGraphLaunch).
-        The step counter lives on the device while replaying (``lg_step(..., -1)``), the host copy is
-        advanced alongside.  ``policy_act`` must be capturable (no host syncs) and read ``self.obs_buf``."""
+    def capture_state(self):
+        """What a graph capture that fails can leave moved on the host, as a value to compare and to hand to ``abort_graph_capture``: the
+        observation ping-pong and the step counter (push / resample / RNG phase)."""
+        return self._obs_flip, self.common_step_counter
+
+    def abort_graph_capture(self, state):
+        """Undo a capture that failed, whether or not ``begin_graph_capture`` was reached: leave capture mode, and put the ping-pong, the
+        sim's observation output and the counter back to ``state`` (``capture_state()`` before the capture) -- the steps issued while
+        capturing were counted but never executed."""
+        self._capturing = False
+        self._sim.set_deferred_extras(False)
+        paired = self.obs_buf is self._obs_pair[self._obs_flip]      # (not behind rollout_policy: its obs[T] stays the current observations)
+        self._obs_flip, self.common_step_counter = state
+        if paired:
+            self.obs_buf = self._obs_pair[self._obs_flip]
+        self._sim.set_obs_output(self.obs_buf)
+
+    def _capture_steps(self, device_step, warmup, steps_per_replay):
+        """Warm up on a side stream, capture ``steps_per_replay`` x ``device_step`` and the flush of the deferred extras into one HIP graph,
+        return the graph and the callable that replays it (the shape of ``GameBase._capture``)."""
         self._expose_device_command_range()
         sim = self._sim
         sim.set_obs_output(self.obs_buf)                  # single fixed buffer while replaying (the policy reads it inside the graph)
@@ -158,7 +173,7 @@ class LeggedRobot(BaseTask):
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                sim.step(policy_act(self.obs_buf), -1)
+                device_step()
                 self.common_step_counter += 1
         torch.cuda.current_stream(self.device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
@@ -166,49 +181,30 @@ class LeggedRobot(BaseTask):
         try:
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 for _ in range(steps_per_replay):                # several policy steps per hipGraphLaunch: no host in between
-                    sim.step(policy_act(self.obs_buf), -1)
+                    device_step()
                 if _DEFER_EXTRAS:
                     sim.flush_extras(-1)                         # extras["episode"] of the replay's last step
         finally:
             sim.set_deferred_extras(False)
-        self._step_graph = graph
 
         def replay():
             graph.replay()
             self.common_step_counter += steps_per_replay
             return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
+        return graph, replay
+
+    def make_graphed_step(self, policy_act, warmup=3, steps_per_replay=1):
+        """Capture ``actions = policy_act(obs_buf); step(actions)`` into one HIP graph and return a
+        zero-argument callable that replays it (launch-bound inner loop -> one hipGraphLaunch).
+        The step counter lives on the device while replaying (``lg_step(..., -1)``), the host copy is
+        advanced alongside.  ``policy_act`` must be capturable (no host syncs) and read ``self.obs_buf``."""
+        self._step_graph, replay = self._capture_steps(lambda: self._sim.step(policy_act(self.obs_buf), -1), warmup, steps_per_replay)
         return replay
 
     def make_graphed_policy_step(self, fused_actor, warmup=3, steps_per_replay=1):
         """Like ``make_graphed_step`` with the actor fused into the step kernel: the graph is ONE ``lg_step_policy`` launch
         (obs_buf -> actions -> next obs_buf, in place).  Raises RuntimeError when the sim / actor pair has no fused kernel."""
-        self._expose_device_command_range()
-        sim = self._sim
-        sim.set_obs_output(self.obs_buf)
-        sim.buf["step_counter"].fill_(self.common_step_counter)
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                sim.step_policy(fused_actor, self.obs_buf, -1)
-                self.common_step_counter += 1
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        sim.set_deferred_extras(_DEFER_EXTRAS)
-        try:
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                for _ in range(steps_per_replay):
-                    sim.step_policy(fused_actor, self.obs_buf, -1)
-                if _DEFER_EXTRAS:
-                    sim.flush_extras(-1)
-        finally:
-            sim.set_deferred_extras(False)
-        self._step_graph = graph
-
-        def replay():
-            graph.replay()
-            self.common_step_counter += steps_per_replay
-            return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
+        self._step_graph, replay = self._capture_steps(lambda: self._sim.step_policy(fused_actor, self.obs_buf, -1), warmup, steps_per_replay)
         return replay
 
     def rollout_policy(self, fused_actor, steps, storage=None, deterministic=False):

@@ -83,7 +83,7 @@ class DecGamePolicyRunner:
             if device_path:
                 self.views[a].opponent = fused[other]
             else:                                         # generic path for both: a view cannot mix a device learner with a torch opponent
-                self.runners[a]._fused, self.runners[a]._game_rollout = None, False
+                self.runners[a].use_generic_loop()
                 self.views[a].opponent = self._sampling_policy(other)
         if self.recurrent and not device_path:                # (an actor shape the kernels refuse: the per-agent runner has said which)
             raise NotImplementedError("ActorCriticRecurrent on dec_high_level_game runs on the device rollout only and it is unavailable (see the "

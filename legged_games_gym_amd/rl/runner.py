@@ -33,6 +33,8 @@ def check_critic_width(actor_critic, state_dict, agent=None):
 
 
 class OnPolicyRunner:
+    _csv = _csv_cols = None                 # progress.csv and its columns, opened with the writer (_log_scalars)
+
     def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
         self.cfg, self.alg_cfg, self.policy_cfg = train_cfg["runner"], train_cfg["algorithm"], train_cfg["policy"]
         self.device, self.env = device, env
@@ -55,74 +57,111 @@ class OnPolicyRunner:
         _, _ = self.env.reset()
         self._fused = self._make_fused_actor()
 
+    def _init_rollout_state(self):
+        """Everything the rollouts keep between calls, with its "not yet" value: the generic loop, no device actor."""
+        self._fused = None                  # the device actor: a FusedActor or a RecurrentFusedActor
+        self._game_rollout = False          # the device rollout goes through env.step_policy of a game task (else: a locomotion env)
+        self._recurrent_rollout = False     # ... with the memories of a recurrent policy on the device
+        self._fused_step = None             # locomotion: lg_step_policy (True) or actor kernel + lg_step (False); None until the first rollout decides
+        self._rolled = None                 # ... or the whole rollout in one launch (lg_rollout_policy), decided likewise
+        self._roll = None                   # the storage lg_rollout_policy writes
+        self._time_outs = None              # [T, N, 1] time-out floats of the rollout (locomotion, an agent view of dec_high_level_game)
+        self._critic_features = None        # [T, N, H] the critic memory's output of every step (recurrent)
+        self._priv_carry = None             # [N, P] the privileged rows behind the rollout's last step (an agent view with privileged observations)
+        self._critic_fwd = None             # _critic_values: the learner kernels' forward of the critic (False: torch)
+        self._critic_chunks = self._critic_out = None     # ... in row chunks, and where their values are gathered
+
+    def use_generic_loop(self):
+        """Drop the device actor and its mode: the rollouts take the generic VecEnv loop."""
+        self._init_rollout_state()
+
     def _make_fused_actor(self):
         """Rollouts with the MFMA actor (and, for the flat task, the actor fused into the step kernel) instead of torch ops;
-        the critic, log-probs and the time-out bootstrap are then evaluated once per rollout on all T x N transitions."""
-        env = self.env
-        self._game_rollout = False
-        self._recurrent_rollout = False
-        alg = getattr(self, "alg", None)              # (tests/test_game_policy_abi.py calls this on a bare runner that has no learner yet)
-        if alg is not None and alg.actor_critic.is_recurrent:
-            return self._make_recurrent_fused_actor()
-        if (self.cfg.get("device_rollout", False) and str(self.device).startswith("cuda") and hasattr(env, "ll_env")
-                and hasattr(env, "step_policy") and (env.num_privileged_obs is None or getattr(env, "dec_agent_view", False))):
-            # high_level_game, opt-in (an agent view of dec_high_level_game may have privileged observations: _rollout_steps_game): the high-level actor on the noise stream of the low-level sim's device step counter
-            from .fused_actor import FusedActor
-            try:
-                fused = FusedActor(self.alg.actor_critic, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
-                                   step_counter=env.ll_env._sim.buf["step_counter"])      # (an agent view of dec_high_level_game names its agent's offset)
-                fused.act_inference(env.get_observations())   # a shape lg_policy_act refuses (rc -4) shows here, not in the first rollout
-            except Exception as exc:
-                print(f"[runner] device rollout unavailable ({type(exc).__name__}: {exc}); generic VecEnv loop")
-                return None
-            self._game_rollout = True
-            return fused
-        if not (str(self.device).startswith("cuda") and self.cfg.get("fused_rollout", True) and hasattr(env, "_sim")
-                and env.num_privileged_obs is None):
-            return None
-        try:
-            from .fused_actor import FusedActor
-            fused = FusedActor(self.alg.actor_critic, self.device, seed=int(getattr(env.cfg, "seed", 1)) + 7919,
-                               step_counter=env._sim.buf["step_counter"])
-        except Exception as exc:                              # unsupported actor shape: torch rollouts
-            print(f"[runner] MFMA actor unavailable ({type(exc).__name__}: {exc}); torch policy in the rollout")
-            return None
-        self._time_outs = torch.zeros(self.num_steps_per_env, env.num_envs, 1, device=self.device)
-        self._fused_step = None                               # decided at the first rollout: lg_step_policy or actor kernel + lg_step
-        self._rolled = None                                   # ... or the whole rollout in one launch (lg_rollout_policy)
-        return fused
+        the critic, log-probs and the time-out bootstrap are then evaluated once per rollout on all T x N transitions.  Decides the mode:
+        the generic loop (None), the device rollout of a locomotion env or of a game task (``device_rollout``, opt-in: ``high_level_game``,
+        ``scripted_predator_game``, an agent view of ``dec_high_level_game``), each feed-forward or recurrent.
 
-    def _make_recurrent_fused_actor(self):
-        """Recurrent policy: both memories in one ``lg_lstm_step`` launch, then the MFMA actor on the actor memory's output, per step
+        Recurrent policy: both memories in one ``lg_lstm_step`` launch, then the MFMA actor on the actor memory's output, per step
         (``RecurrentFusedActor``); the critic MLP once per rollout on the critic memory's outputs of all T steps.  A memory the device cell
-        does not cover (a GRU without the key ``device_gru``, several layers, more than 256 units) or privileged observations take the torch loop.  The single-policy game
-        tasks with ``device_rollout``: the same actor through ``env.step_policy`` (lg_lstm_step -> lg_game_lstm_act -> lg_step -> post)."""
-        env, ac = self.env, self.alg.actor_critic
-        if hasattr(env, "ll_env"):
-            if not self.cfg.get("device_rollout", False):
+        does not cover (a GRU without the key ``device_gru``, several layers, more than 256 units without ``wide_memory``) takes the torch
+        loop.  On a game task the same actor goes through ``env.step_policy`` (lg_lstm_step -> lg_game_lstm_act -> lg_step -> post)."""
+        self._init_rollout_state()
+        env, cfg = self.env, self.cfg
+        alg = getattr(self, "alg", None)              # (tests/test_game_policy_abi.py calls this on a bare runner that has no learner yet)
+        ac = alg.actor_critic if alg is not None else None
+        rec = ac is not None and ac.is_recurrent
+        cuda, game = str(self.device).startswith("cuda"), hasattr(env, "ll_env")
+        view = getattr(env, "dec_agent_view", False)  # (its critic may read privileged observations, and it sends time-outs)
+        priv = env.num_privileged_obs is not None
+        unserved = priv and not view                  # privileged observations the device rollouts have no critic path for
+        why, hint, more = None, "", {}
+        if game:
+            if not cfg.get("device_rollout", False):
                 return None
-            return self._make_recurrent_game_actor()
-        if not (str(self.device).startswith("cuda") and self.cfg.get("fused_rollout", True) and hasattr(env, "_sim")):
+            if not cuda:
+                why = f"the policy is on {self.device}, the game actor kernels run on a GPU"
+            elif not hasattr(env, "step_policy"):
+                why = "the game actor kernels have no recurrent policy for this task"
+            elif unserved:
+                why = "privileged observations"
+            if why is not None and not rec:               # (a feed-forward policy never said why)
+                return None
+        elif not (cuda and cfg.get("fused_rollout", True) and hasattr(env, "_sim")) or (unserved and not rec):
             return None
-        from .recurrent_actor import RecurrentFusedActor
-        wide = bool(self.cfg.get("wide_memory", False))       # opt-in: memories of up to 512 units on liblegged_lstm_wide.so
-        gru, cell_why, hint = self._recurrent_cell_reason(ac, wide)       # opt-in: GRU memories on liblegged_gru.so (the key device_gru)
-        why = "privileged observations" if env.num_privileged_obs is not None else cell_why
-        if why is not None:
-            print(f"[runner] device {'GRU' if gru else 'LSTM'} cell unavailable ({why}); torch policy in the rollout{hint}")
-            return None
-        try:
-            fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + 7919, step_counter=env._sim.buf["step_counter"],
-                                        num_envs=env.num_envs, wide=wide, **({"gru": True} if gru else {}))
-        except Exception as exc:                              # unsupported actor shape: torch rollouts
-            print(f"[runner] MFMA actor unavailable ({type(exc).__name__}: {exc}); torch policy in the rollout")
+        if rec and why is None:
+            wide = bool(cfg.get("wide_memory", False))    # opt-in: memories of up to 512 units on liblegged_lstm_wide.so
+            gru, cell_why, hint = self._recurrent_cell_reason(ac, wide)       # opt-in: GRU memories on liblegged_gru.so (the key device_gru)
+            if not game and (unserved or cell_why is not None):
+                print(f"[runner] device {'GRU' if gru else 'LSTM'} cell unavailable ({'privileged observations' if unserved else cell_why}); "
+                      f"torch policy in the rollout{hint}")
+                return None
+            if cell_why is not None:
+                why = f"no device {'GRU' if gru else 'LSTM'} cell for a {cell_why}"
+            else:
+                hint = ""
+            more = dict({"gru": True} if gru else {}, num_envs=env.num_envs, wide=wide)
+            if game and gru and cfg.get("dec_gru_shared", False):
+                more["shared_gru"] = True
+        fused = self._build_actor(ac, game, rec, why, hint, more)
+        if fused is None:
             return None
         T, N = self.num_steps_per_env, env.num_envs
-        self._time_outs = torch.zeros(T, N, 1, device=self.device)
-        self._critic_features = torch.zeros(T, N, ac.memory_c.rnn.hidden_size, device=self.device)     # the critic memory's output of every step
-        self._fused_step, self._rolled = False, False         # neither lg_step_policy nor lg_rollout_policy has a recurrent kernel
-        self._recurrent_rollout = True
+        if not game or view:
+            self._time_outs = torch.zeros(T, N, 1, device=self.device)
+        if rec:
+            self._critic_features = torch.zeros(T, N, ac.memory_c.rnn.hidden_size, device=self.device)
+            self._fused_step, self._rolled = False, False         # neither lg_step_policy nor lg_rollout_policy has a recurrent kernel
+        if view and priv:
+            self._priv_carry = torch.zeros(N, env.num_privileged_obs, device=self.device)
+        self._game_rollout, self._recurrent_rollout = game, rec
         return fused
+
+    def _build_actor(self, ac, game, rec, why, hint, more):
+        """The one place a device actor is made: on the noise stream of the sim's device step counter (a game task: the low-level sim's;
+        an agent view of dec_high_level_game names its agent's seed offset).  None, with the path's fall-back message, when ``why`` says so
+        already or the actor's shape has no kernel -- on a game task that shows in a first launch here, not in the first rollout."""
+        env = self.env
+        if why is None:
+            try:
+                if rec:
+                    from .recurrent_actor import RecurrentFusedActor as make
+                else:
+                    from .fused_actor import FusedActor as make
+                fused = make(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
+                             step_counter=(env.ll_env if game else env)._sim.buf["step_counter"], **more)
+                if game and rec:
+                    env.shared_actor_launch(fused)            # raises the new kernel's LDS limit here, outside any capture; False = separate launches
+                                                              # (an agent view has no opponent yet: DecGamePolicyRunner makes the call)
+                elif game:
+                    fused.act_inference(env.get_observations())   # a shape lg_policy_act refuses (rc -4)
+                return fused
+            except Exception as exc:
+                why = f"{type(exc).__name__}: {exc}"
+        if game:
+            print(f"[runner] device rollout unavailable ({why}); generic VecEnv loop{hint}")
+        else:                                                 # unsupported actor shape: torch rollouts
+            print(f"[runner] MFMA actor unavailable ({why}); torch policy in the rollout")
+        return None
 
     @staticmethod
     def _wide_memory_hint(ac, wide):
@@ -146,41 +185,6 @@ class OnPolicyRunner:
         if why is not None and all(device_gru_would_help(r) for r in rnns):
             hint += " (the runner key device_gru / --device_gru runs GRU memories on the device)"
         return False, why, hint
-
-    def _make_recurrent_game_actor(self):
-        """``device_rollout`` of ``high_level_game`` / ``scripted_predator_game`` / an agent view of ``dec_high_level_game`` with a recurrent
-        policy; None (and why) where it cannot run."""
-        env, ac = self.env, self.alg.actor_critic
-        from .recurrent_actor import RecurrentFusedActor
-        why, hint, gru = None, "", False
-        wide = bool(self.cfg.get("wide_memory", False))
-        if not str(self.device).startswith("cuda"):
-            why = f"the policy is on {self.device}, the game actor kernels run on a GPU"
-        elif not hasattr(env, "step_policy"):
-            why = "the game actor kernels have no recurrent policy for this task"
-        elif env.num_privileged_obs is not None and not getattr(env, "dec_agent_view", False):
-            why = "privileged observations"
-        else:                                                     # (an agent view: the critic memory reads the privileged buffer)
-            gru, why, hint = self._recurrent_cell_reason(ac, wide)
-            why = why and f"no device {'GRU' if gru else 'LSTM'} cell for a {why}"
-            hint = hint if why else ""
-        if why is None:
-            try:
-                fused = RecurrentFusedActor(ac, self.device, seed=int(getattr(env.cfg, "seed", 1)) + getattr(env, "fused_seed_offset", 7919),
-                                            step_counter=env.ll_env._sim.buf["step_counter"], num_envs=env.num_envs, wide=wide,
-                                            **({"gru": True} if gru else {}),
-                                            **({"shared_gru": True} if gru and self.cfg.get("dec_gru_shared", False) else {}))
-                env.shared_actor_launch(fused)                # raises the new kernel's LDS limit here, outside any capture; False = separate launches
-                                                              # (an agent view has no opponent yet: DecGamePolicyRunner makes the call)
-            except Exception as exc:
-                why = f"{type(exc).__name__}: {exc}"
-        if why is not None:
-            print(f"[runner] device rollout unavailable ({why}); generic VecEnv loop{hint}")
-            return None
-        T, N = self.num_steps_per_env, env.num_envs
-        self._critic_features = torch.zeros(T, N, ac.memory_c.rnn.hidden_size, device=self.device)     # the critic memory's output of every step
-        self._game_rollout = self._recurrent_rollout = True
-        return fused
 
     def _recurrent_last_values(self, critic_obs):
         """The value behind the rollout's last step from one critic-only ``lg_lstm_step`` into scratch outputs: the carried state stays."""
@@ -207,8 +211,8 @@ class OnPolicyRunner:
         """critic(obs) for all stored transitions: lg_mlp_forward / lg_mlp_wide_forward when the critic has one of the learner kernels' shapes, torch otherwise."""
         ac = self.alg.actor_critic
         cobs = (st.privileged_observations if st.privileged_observations is not None else st.observations).flatten(0, 1)
-        tr = getattr(self, "_critic_fwd", None)
-        if tr is None or (tr is not False and (tr.inputs[0].data_ptr() != cobs.data_ptr() or tr.mb * len(getattr(self, "_critic_chunks", None) or [0]) != cobs.shape[0])):
+        tr = self._critic_fwd
+        if tr is None or (tr is not False and (tr.inputs[0].data_ptr() != cobs.data_ptr() or tr.mb * len(self._critic_chunks or [0]) != cobs.shape[0])):
             from .mlp_kernels import MlpTrainer, WideMlpTrainer
             tr = False
             self._critic_chunks = None
@@ -226,7 +230,7 @@ class OnPolicyRunner:
             self._critic_fwd = tr
         if tr is not False and tr.supported:
             tr.refresh()                              # parameter addresses (stable; the values follow the optimiser)
-            if getattr(self, "_critic_chunks", None):
+            if self._critic_chunks:
                 n = self._critic_chunks[0].numel()
                 for i, rows in enumerate(self._critic_chunks):
                     self._critic_out[i * n:(i + 1) * n].copy_(tr.forward(rows)[0])
@@ -241,7 +245,7 @@ class OnPolicyRunner:
         env, alg, fused = self.env, self.alg, self._fused
         st, T = alg.storage, self.num_steps_per_env
         N, A, dev = env.num_envs, st.actions.shape[-1], self.device
-        roll = getattr(self, "_roll", None)
+        roll = self._roll
         fresh = roll is None or roll["obs"].shape[0] != T + 1 or st.observations.data_ptr() != roll["obs"].data_ptr()
         if fresh:
             with torch.inference_mode(False):         # (rollouts run under inference_mode; env.obs_buf becomes a view of this buffer and callers feed it to autograd modules)
@@ -272,23 +276,59 @@ class OnPolicyRunner:
         obs = env.obs_buf
         return obs, obs
 
-    def _rollout_steps_fused(self, stats):
+    def _step_locomotion(self, t, obs):
+        """Step ``t`` of the device rollout on a locomotion env: ``actions, mean, step result``."""
+        env, fused = self.env, self._fused
+        if not self._recurrent_rollout:
+            return self._fused_env_step(obs)
+        actions, mean, h_c = fused.act_with_mean(obs, obs, reset=env.reset_buf)       # lstm -> actor -> lg_step
+        self._critic_features[t].copy_(h_c)
+        return actions, mean, env.step(actions)
+
+    def _step_game(self, t, obs):
+        """Step ``t`` of the device rollout on a game task: ``env.step_policy`` (lg_game_act -> lg_step -> lg_game_post; recurrent:
+        lg_lstm_step -> lg_game_lstm_act -> lg_step -> post), whose actor launch writes ``sigma[t]`` and ``actions_log_prob[t]`` of the
+        unclipped sample straight into the storage.  With privileged observations (an agent view) the env's privileged launch of step
+        ``t`` writes slot ``t + 1`` of the storage itself, the last step the carry buffer -- no copy launch per step."""
+        st, T = self.alg.storage, self.num_steps_per_env
+        more = {"with_critic_memory": True} if self._recurrent_rollout else {}
+        if self._priv_carry is not None:
+            more["privileged_out"] = st.privileged_observations[t + 1] if t < T - 1 else self._priv_carry
+        head, out = self.env.step_policy(self._fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t], **more)
+        if self._recurrent_rollout:
+            self._critic_features[t].copy_(head[2])
+        return head[0], head[1], out
+
+    def _rollout_steps_device(self, stats):
+        """The device rollout: per step the path's launches (``_step_locomotion`` / ``_step_game``) and one ``lg_rollout_record`` (storage
+        writes and episode statistics of the transition); the critic once per rollout.  A locomotion env tries the one-launch rollout
+        first.  What differs by path:
+        - ``sigma`` / ``log_prob``: ``lg_rollout_record`` stores them on a locomotion env; on a game task the actor launch has (the
+          reference clips the command in the caller's tensor after ``PPO.act`` took the log-prob, so ``actions[t]`` is the clipped command
+          while those two belong to the unclipped sample).
+        - time-outs: a locomotion env and an agent view of ``dec_high_level_game`` record them per step and bootstrap on them;
+          ``high_level_game`` sends none, and a view with ``env.send_timeouts = False`` records none.
+        - the critic observations of an agent view with privileged observations are ``st.privileged_observations``: one copy of the carried
+          rows into slot 0, the rest by ``_step_game``.
+        Returns ``(obs, critic obs)`` behind the last step."""
         env, alg, fused = self.env, self.alg, self._fused
         st, T = alg.storage, self.num_steps_per_env
-        if self._rolled is not False and "_sums" in stats and self.cfg.get("rolled_rollout", True):
+        game, rec, priv = self._game_rollout, self._recurrent_rollout, self._priv_carry is not None
+        bootstrap = self._time_outs is not None
+        if not game and self._rolled is not False and "_sums" in stats and self.cfg.get("rolled_rollout", True):
             out = self._rollout_steps_rolled(stats)
             self._rolled = out is not None
             if out is not None:
                 return out
+        if priv:
+            st.privileged_observations[0].copy_(env.get_privileged_observations())      # (the carry of the last rollout, or the env's own after a reset / the other agent's steps)
         obs = env.get_observations()
         lib, step = fused.lib, capi.lg_rollout_step()
         p = lambda x: x.data_ptr()
         step.num_envs, step.num_obs, step.num_actions = env.num_envs, st.observations.shape[-1], st.actions.shape[-1]
         step.cur_return, step.cur_length, step.sums = p(stats["cur_rew"]), p(stats["cur_len"]), p(stats["_sums"])
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        ac = alg.actor_critic
-        step.std = p(ac.std)                          # log-prob and sigma of the transition are stored by the same launch
-        rec = self._recurrent_rollout
+        step.std = None if game else p(alg.actor_critic.std)
         if rec:
             # the state this rollout starts from, once (part of the captured work); an env whose last step ended an episode starts from
             # zeros: the cell reads the env's persistent reset_buf of the previous step instead of zeroing the buffers
@@ -296,86 +336,19 @@ class OnPolicyRunner:
             keep = (env.reset_buf == 0).view(1, -1, 1)
             for hid in st.initial_hidden_a + st.initial_hidden_c:
                 hid.mul_(keep)
-        for t in range(T):
-            prev_obs = obs
-            if rec:                                   # lstm -> actor -> lg_step
-                actions, mean, h_c = fused.act_with_mean(obs, obs, reset=env.reset_buf)
-                self._critic_features[t].copy_(h_c)
-                obs, _, rewards, dones, infos = env.step(actions)
-            else:
-                actions, mean, (obs, _, rewards, dones, infos) = self._fused_env_step(obs)
-            # storage writes + episode statistics of this transition: one launch (lg_rollout_record)
-            touts = infos.get("time_outs")
-            step.obs, step.actions, step.mean, step.rewards, step.dones = p(prev_obs), p(actions), p(mean), p(rewards), p(dones)
-            step.time_outs = p(touts) if touts is not None else None
-            step.storage_obs, step.storage_actions, step.storage_mu = p(st.observations[t]), p(st.actions[t]), p(st.mu[t])
-            step.storage_rewards, step.storage_dones, step.storage_time_outs = p(st.rewards[t]), p(st.dones[t]), p(self._time_outs[t])
-            step.storage_sigma, step.storage_log_prob = p(st.sigma[t]), p(st.actions_log_prob[t])
-            assert dones.element_size() == 1 and (touts is None or touts.element_size() == 1) and rewards.is_contiguous()   # bool / uint8 flags
-            rc = lib.lg_rollout_record(step, stream)
-            if rc != 0:
-                raise RuntimeError(f"lg_rollout_record failed ({rc}): {lib.lg_last_error().decode()}")
-        st.step = T
-        if rec:
-            st.values.copy_(ac.critic(self._critic_features.flatten(0, 1)).view(T, -1, 1))      # critic MLP once on the memory's outputs of all steps
-            fused.publish_states(env.reset_buf)                                                # the torch memories follow the device state
-        else:
-            st.values.copy_(self._critic_values(st).view(T, -1, 1))                            # critic once on all transitions
-        st.rewards.add_(alg.gamma * st.values * self._time_outs)                               # bootstrap on time-outs (PPO.process_env_step)
-        return obs, obs
-
-    def _rollout_steps_game(self, stats):
-        """Device rollout of ``high_level_game``: per step ``env.step_policy`` (lg_game_act -> lg_step -> lg_game_post) and one
-        ``lg_rollout_record``; the critic once per rollout.  Storage semantics of the generic path: the reference clips the command in the
-        caller's tensor after ``PPO.act`` took the log-prob, so ``actions[t]`` is the clipped command while ``actions_log_prob[t]`` (and
-        ``sigma[t]``, both written by the actor launch straight into the storage) belong to the unclipped sample.  The game sends no
-        time-outs: nothing is bootstrapped.  An agent view of ``dec_high_level_game`` does send them (``dec_agent_view``): they are recorded
-        per step and bootstrapped as ``_rollout_steps_fused`` does.  With privileged observations on that view the critic observations of
-        step ``t`` are ``st.privileged_observations[t]``: one copy of the carried rows into slot 0, then the env's privileged launch of step
-        ``t`` writes slot ``t + 1`` itself (the last step a carry buffer) -- no copy launch per step.  Returns ``(obs, critic obs)`` behind
-        the last step."""
-        env, alg, fused = self.env, self.alg, self._fused
-        st, T = alg.storage, self.num_steps_per_env
-        dec = getattr(env, "dec_agent_view", False)
-        priv = dec and env.num_privileged_obs is not None
-        if priv:
-            if getattr(self, "_priv_carry", None) is None:
-                self._priv_carry = torch.zeros(env.num_envs, env.num_privileged_obs, device=self.device)
-            st.privileged_observations[0].copy_(env.get_privileged_observations())      # (the carry of the last rollout, or the env's own after a reset / the other agent's steps)
-        if dec and getattr(self, "_time_outs", None) is None:
-            self._time_outs = torch.zeros(T, env.num_envs, 1, device=self.device)
-        obs = env.get_observations()
-        lib, step = fused.lib, capi.lg_rollout_step()
-        p = lambda x: x.data_ptr()
-        step.num_envs, step.num_obs, step.num_actions = env.num_envs, st.observations.shape[-1], st.actions.shape[-1]
-        step.cur_return, step.cur_length, step.sums = p(stats["cur_rew"]), p(stats["cur_len"]), p(stats["_sums"])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        step.std, step.time_outs, step.storage_time_outs = None, None, None
-        rec = self._recurrent_rollout
-        if rec:
-            # as _rollout_steps_fused: the state this rollout starts from, once; rows whose episode ended in the last step start from zeros
-            st.save_initial_hidden_states(fused.hidden_states())
-            keep = (env.reset_buf == 0).view(1, -1, 1)
-            for hid in st.initial_hidden_a + st.initial_hidden_c:
-                hid.mul_(keep)
+        take_step = self._step_game if game else self._step_locomotion
         cobs = None
         for t in range(T):
             prev_obs = obs
-            more = {"privileged_out": st.privileged_observations[t + 1] if t < T - 1 else self._priv_carry} if priv else {}
-            if rec:                                               # lg_lstm_step -> lg_game_lstm_act -> lg_step -> post
-                (command, mean, h_c), (obs, cobs, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t],
-                                                                                           with_critic_memory=True, **more)
-                self._critic_features[t].copy_(h_c)
-            else:
-                (command, mean), (obs, cobs, rewards, dones, infos) = env.step_policy(fused, sigma=st.sigma[t], log_prob=st.actions_log_prob[t], **more)
-            step.obs, step.actions, step.mean, step.rewards, step.dones = p(prev_obs), p(command), p(mean), p(rewards), p(dones)
-            touts = infos.get("time_outs") if dec else None
-            if touts is not None:                                 # (absent with env.send_timeouts = False: nothing is bootstrapped then)
-                step.time_outs, step.storage_time_outs = p(touts), p(self._time_outs[t])
+            actions, mean, (obs, cobs, rewards, dones, infos) = take_step(t, obs)
+            touts = infos.get("time_outs") if bootstrap else None
+            step.obs, step.actions, step.mean, step.rewards, step.dones = p(prev_obs), p(actions), p(mean), p(rewards), p(dones)
+            step.time_outs = p(touts) if touts is not None else None
+            step.storage_time_outs = p(self._time_outs[t]) if not game or touts is not None else None
             step.storage_obs, step.storage_actions, step.storage_mu = p(st.observations[t]), p(st.actions[t]), p(st.mu[t])
             step.storage_rewards, step.storage_dones = p(st.rewards[t]), p(st.dones[t])
-            step.storage_sigma, step.storage_log_prob = None, None
-            assert dones.element_size() == 1 and rewards.is_contiguous()
+            step.storage_sigma, step.storage_log_prob = (None, None) if game else (p(st.sigma[t]), p(st.actions_log_prob[t]))
+            assert dones.element_size() == 1 and (touts is None or touts.element_size() == 1) and rewards.is_contiguous()   # bool / uint8 flags
             rc = lib.lg_rollout_record(step, stream)
             if rc != 0:
                 raise RuntimeError(f"lg_rollout_record failed ({rc}): {lib.lg_last_error().decode()}")
@@ -384,18 +357,16 @@ class OnPolicyRunner:
             st.values.copy_(alg.actor_critic.critic(self._critic_features.flatten(0, 1)).view(T, -1, 1))      # critic MLP once on the memory's outputs of all steps
             fused.publish_states(env.reset_buf)                                                              # the torch memories follow the device state
         else:
-            st.values.copy_(self._critic_values(st).view(T, -1, 1))
-        if dec:
+            st.values.copy_(self._critic_values(st).view(T, -1, 1))                            # critic once on all transitions
+        if bootstrap:
             st.rewards.add_(alg.gamma * st.values * self._time_outs)                           # bootstrap on time-outs (PPO.process_env_step)
         return obs, (cobs if priv else obs)
 
     # ------------------------------------------------------------------ graphed rollout
     def _rollout_steps(self, stats):
         """num_steps_per_env x (act -> env.step -> store); episode statistics as tensor ops (no host sync)."""
-        if self._fused is not None and self._game_rollout:
-            return self._rollout_steps_game(stats)
         if self._fused is not None:
-            return self._rollout_steps_fused(stats)
+            return self._rollout_steps_device(stats)
         env, alg = self.env, self.alg
         obs = env.get_observations()
         pobs = env.get_privileged_observations()
@@ -421,70 +392,56 @@ class OnPolicyRunner:
         and an even number of steps so the observation buffers line up between replays."""
         env = self.env
         ok = (str(self.device).startswith("cuda") and hasattr(env, "begin_graph_capture") and self.num_steps_per_env % 2 == 0
-              and self.cfg.get("graphed_rollout", True) and (hasattr(env, "_sim") or getattr(self, "_game_rollout", False)))
+              and self.cfg.get("graphed_rollout", True) and (hasattr(env, "_sim") or self._game_rollout))
         if not ok:
             return None
         if self.alg.actor_critic.is_recurrent and not self._recurrent_rollout:
             # torch memories in the generic loop: Memory.forward leaves its state in a new tensor every step, so a replay would start every
             # rollout from the state the warm-up left at the captured address, not from the one the previous rollout ended in
             return None
-        flip0, counter0 = getattr(env, "_obs_flip", 0), env.common_step_counter
-        ll_flip0 = getattr(getattr(env, "ll_env", None), "_obs_flip", 0)
-        captured = False
-        mem_flip0 = getattr(self._fused, "_flip", None)       # (recurrent policy: the (h, c) ping-pong of its memories)
+        snapshot = None
         opponent = getattr(env, "opponent", None)             # (an agent view of dec_high_level_game: the other agent's memories move in every step too)
-        opp_flip0 = getattr(opponent, "_flip", None)
         try:
-            N, dev = env.num_envs, self.device
-            sums = torch.zeros(3, device=dev)             # {sum of finished-episode returns, of their lengths, their count}
-            stats = {"cur_rew": torch.zeros(N, device=dev), "cur_len": torch.zeros(N, device=dev),
-                     "sum_rew": sums[0], "sum_len": sums[1], "count": sums[2], "_sums": sums}
+            stats = self._new_stats()
             with torch.inference_mode():
                 self._rollout_steps(stats)              # one eager warm-up rollout (allocators, lazy init); discarded
                 self.alg.storage.clear()
                 for v in stats.values():
                     v.zero_()
                 torch.cuda.synchronize()
-                flip0, counter0 = env._obs_flip, env.common_step_counter
-                ll_flip0 = getattr(getattr(env, "ll_env", None), "_obs_flip", 0)
-                mem_flip0 = getattr(self._fused, "_flip", None)
+                snapshot = env.capture_state()
+                mem_flip0 = getattr(self._fused, "_flip", None)       # (recurrent policy: the (h, c) ping-pong of its memories)
                 opp_flip0 = getattr(opponent, "_flip", None)
                 env.begin_graph_capture()
-                captured = True
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                     obs, cobs = self._rollout_steps(stats)
                     if hasattr(env, "capture_extras_flush"):
                         env.capture_extras_flush()          # extras["episode"] of the rollout's last step (its steps defer them)
                 env.end_graph_capture(self.num_steps_per_env)
-                captured = False
-                assert env._obs_flip == flip0 and env.common_step_counter == counter0
+                assert env.capture_state() == snapshot
             self.alg.storage.clear()
             return graph, stats, obs, cobs
         except Exception as exc:                          # fall back to eager launches
             print(f"[runner] graphed rollout unavailable ({type(exc).__name__}: {exc}); using eager steps")
-            if hasattr(env, "_capturing"):
-                env._capturing = False
-                getattr(env, "ll_env", env)._sim.set_deferred_extras(False)
-            if captured:
-                # steps issued during a capture that failed part-way were counted but never executed: put the observation
-                # ping-pong and the step counter (push / resample / RNG phase) back where they were
-                env._obs_flip = flip0
-                env.obs_buf = env._obs_pair[flip0]
-                if hasattr(env, "_sim"):
-                    env._sim.set_obs_output(env.obs_buf)
-                else:                                     # the game: its low-level env stepped (and flipped) along with it
-                    ll = env.ll_env
-                    ll._obs_flip = ll_flip0
-                    ll.obs_buf = ll._obs_pair[ll_flip0]
-                    ll._sim.set_obs_output(ll.obs_buf)
-                env.common_step_counter = counter0
+            if snapshot is not None:
+                # steps issued during a capture that failed part-way were counted but never executed: the env puts its observation
+                # ping-pong and step counter (push / resample / RNG phase) back where they were, the memories go back here
+                env.abort_graph_capture(snapshot)
                 if mem_flip0 is not None:
                     self._fused._flip = mem_flip0
                 if opp_flip0 is not None:
                     opponent._flip = opp_flip0
             self.alg.storage.clear()
             return None
+
+    def _new_stats(self, cur_rew=None, cur_len=None):
+        """The episode statistics a rollout keeps on the device: running return and length per env (the caller's, or new ones), and
+        ``_sums`` = {sum of finished-episode returns, of their lengths, their count} with a 0-dim view of each."""
+        N, dev = self.env.num_envs, self.device
+        sums = torch.zeros(3, device=dev)
+        return {"cur_rew": torch.zeros(N, device=dev) if cur_rew is None else cur_rew, "cur_len": torch.zeros(N, device=dev) if cur_len is None else cur_len,
+                "sum_rew": sums[0], "sum_len": sums[1], "count": sums[2], "_sums": sums}
 
     def learn(self, num_learning_iterations, init_at_random_ep_len=False):
         if init_at_random_ep_len:
@@ -502,8 +459,7 @@ class OnPolicyRunner:
         graphed = self._try_build_graphed_rollout()
         if graphed is None and self._fused is not None and (self._game_rollout or self._recurrent_rollout):
             # the game's device rollout without a graph (graphed_rollout = False, odd step count, failed capture): the same launches, eagerly
-            sums = torch.zeros(3, device=self.device)
-            graphed = (None, {"cur_rew": cur_rew, "cur_len": cur_len, "sum_rew": sums[0], "sum_len": sums[1], "count": sums[2], "_sums": sums}, obs, cobs)
+            graphed = (None, self._new_stats(cur_rew, cur_len), obs, cobs)
         last = self.current_learning_iteration + num_learning_iterations
         for it in range(self.current_learning_iteration, last):
             t0 = time.time()
@@ -611,7 +567,7 @@ class OnPolicyRunner:
             self.alg.optimizer.load_state_dict(d["optimizer_state_dict"])
             if hasattr(self.alg, "after_optimizer_load"):
                 self.alg.after_optimizer_load()               # re-link the device learning rate, drop the captured update graph
-        if getattr(self, "_fused", None) is not None:
+        if self._fused is not None:
             self._fused.sync_device()
         self.current_learning_iteration = d["iter"]
         return d["infos"]
